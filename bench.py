@@ -243,6 +243,28 @@ def verify_timed_region(eng, cfg, snap, action_of_step, K, read_step, surviving_
                     "steps whose slots survive in the storage the timed launch wrote + the final persistent state (ints / dones / RNG counters exact)"}
 
 
+DUMP_BYTES = 64 * 10 ** 6        # --dump-outputs writes at most this much
+
+
+def dump_outputs(out_dir, outputs, seed=0):
+    """Writes one step's outputs (dict name -> tensor [N, ...]) as out_dir/<name>.npy: float64 where the output is fp64, float32 otherwise (agent ids and
+    dones are exact in float32). When the N envs' outputs exceed DUMP_BYTES, every file holds the same envs: a sorted sample drawn with `seed`, so two runs
+    with the same arguments dump the same rows. Returns what was written."""
+    import numpy as np
+    import torch
+    dtypes = {k: np.float64 if t.dtype == torch.float64 else np.float32 for k, t in outputs.items()}
+    n_envs = next(iter(outputs.values())).shape[0]
+    per_env = sum(t[0].numel() * np.dtype(dtypes[k]).itemsize for k, t in outputs.items())
+    n = min(n_envs, DUMP_BYTES // per_env)
+    envs = np.arange(n_envs) if n == n_envs else np.sort(np.random.RandomState(seed).choice(n_envs, n, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, t in outputs.items():
+        rows = t.index_select(0, torch.as_tensor(envs, device=t.device))          # sample on the device: the full outputs can be many GB
+        np.save(os.path.join(out_dir, k + ".npy"), rows.cpu().numpy().astype(dtypes[k]))
+    return {"dir": out_dir, "files": sorted(k + ".npy" for k in outputs), "envs": int(n), "of_envs": int(n_envs), "bytes": int(n * per_env),
+            "sample": "all envs" if n == n_envs else "sorted(RandomState(%d).choice(%d, %d, replace=False))" % (seed, n_envs, n)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -264,6 +286,9 @@ def main():
     ap.add_argument("--gather", action="store_true", help="also time step + RCCL gather of the compact rollout slab to rank 0")
     ap.add_argument("--no-verify", action="store_true", help="skip the post-region oracle check of the timed launch's outputs (`verified`)")
     ap.add_argument("--diag", action="store_true", help="allow GMPE_LIB / GMPE_ABLATE (diagnostic A/B runs; recorded in the line, never a result)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (rank 0's envs) as DIR/<output>.npy, at most 64 MB in all: a fixed seeded sample "
+                         "of the envs when they are larger")
     args = ap.parse_args()
 
     env_knobs = {k: os.environ[k] for k in PERF_KNOBS + DIAG_KNOBS if k in os.environ}
@@ -404,6 +429,11 @@ def main():
             snap = eng.get_state()                                   # between two timed regions (both bracketed by synchronize): the state the last repetition starts from
         reps.append(timed(run_k_steps, K))
     eng.check_errors()
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # before the side measurements below, which overwrite the engine's own buffers; slot storage: step k -> slot k % n_slots
+        last = {k: v[(K - 1) % n_slots] for k, v in slots.items()} if slots is not None else {k: getattr(eng.out, k) for k in out_keys}
+        dumped = dump_outputs(args.dump_outputs, last)
     verified = None
     if do_verify:
         # ---- outside every timed region: what did the last timed repetition write? (the number sits on a launch nothing else compares at this size)
@@ -625,6 +655,8 @@ def main():
             out["closed_loop"] = closed
         if verified is not None:
             out["verified"] = verified
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if gather is not None:
             out["with_gather"] = gather
         if world == 1 and not args.no_boundary:

@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -55,6 +56,26 @@ def test_launch_loop_and_compact_lines_price_their_own_bytes():
     c = _bench("--no-cpu-baseline", "--no-boundary", "--adj-compact", "--reps", "1")
     A, E, F, D = 10, 20, 8, 13
     assert c["roofline"]["algorithmic_bytes_per_env_step"] == 4 * (E * E + A * (E * F + D + 2)) + A + 4 * A + 2 * A * 48
+
+
+def test_dump_outputs_of_the_last_timed_step(tmp_path):
+    """--dump-outputs writes the last timed step's outputs. The rollout launch (slot-per-step storage) and one launch per step are bit-identical
+    (tests/test_gpu_rollout_kernel.py), so two processes timing the two shapes on the same seeded inputs must dump the same arrays."""
+    flags = ("--no-cpu-baseline", "--no-boundary", "--no-closed-loop", "--reps", "2", "--dump-outputs")
+    r = _bench(*flags, str(tmp_path / "rollout"))
+    s = _bench(*flags, str(tmp_path / "steps"), "--launch-loop")
+    assert r["launch_shape"] == "rollout_into_26_slots" and s["launch_shape"] == "one_launch_per_step" and r["steps"] == s["steps"] == 20
+    names = ["adj.npy", "agent_id.npy", "done.npy", "info.npy", "node_obs.npy", "obs.npy", "reward.npy"]
+    assert r["dump_outputs"]["files"] == s["dump_outputs"]["files"] == names and r["dump_outputs"]["of_envs"] == 4096
+    assert r["dump_outputs"]["envs"] == s["dump_outputs"]["envs"] < 4096 and r["dump_outputs"]["sample"] == s["dump_outputs"]["sample"]
+    total = 0
+    for f in names:
+        a, b = np.load(tmp_path / "rollout" / f), np.load(tmp_path / "steps" / f)
+        assert a.dtype == np.float32 and a.shape[0] == r["dump_outputs"]["envs"], f
+        np.testing.assert_array_equal(a, b, err_msg=f)
+        total += a.nbytes
+    assert total <= 64 * 10 ** 6
+    assert np.isin(np.load(tmp_path / "rollout" / "done.npy"), (0.0, 1.0)).all()
 
 
 def test_diagnostic_knobs_are_refused_and_perf_knobs_recorded():

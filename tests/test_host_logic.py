@@ -583,6 +583,34 @@ def test_bench_cpu_baseline_runs_at_host_scale():
         assert cb["value"] > 1.5 * cb["single_thread"]          # the C call releases the GIL: threads really run in parallel
 
 
+def test_bench_dump_outputs_is_bounded_typed_and_reproducible(tmp_path):
+    """bench.py --dump-outputs: the c2 step outputs (98 MB) are cut to the same seeded env sample in every file, under 64 MB in all; fp64 outputs stay
+    float64, the rest become float32 with ints / flags exact; a second dump of the same outputs is identical. Small outputs are written whole."""
+    import torch
+    import bench
+    N, A, E, F, D = 4096, 10, 20, 8, 13
+    g = torch.Generator().manual_seed(0)
+    outs = {"obs": torch.rand((N, A, D), generator=g), "agent_id": torch.randint(0, A, (N, A, 1), generator=g, dtype=torch.int32),
+            "node_obs": torch.rand((N, A, E, F), generator=g), "adj": torch.rand((N, A, E, E), generator=g), "reward": torch.rand((N, A), generator=g),
+            "done": torch.randint(0, 2, (N, A), generator=g, dtype=torch.uint8), "info": torch.rand((N, A, 18), generator=g),
+            "entity_table": torch.rand((N, 40), generator=g, dtype=torch.float64)}
+    d1 = bench.dump_outputs(str(tmp_path / "a"), outs)
+    d2 = bench.dump_outputs(str(tmp_path / "b"), outs)
+    assert 0 < d1["envs"] < N and d1 == dict(d2, dir=d1["dir"])
+    envs = np.sort(np.random.RandomState(0).choice(N, d1["envs"], replace=False))
+    total = 0
+    for k, t in outs.items():
+        a, b = np.load(tmp_path / "a" / (k + ".npy")), np.load(tmp_path / "b" / (k + ".npy"))
+        assert a.dtype == (np.float64 if k == "entity_table" else np.float32), k
+        np.testing.assert_array_equal(a, b, err_msg=k)
+        np.testing.assert_array_equal(a, t.numpy()[envs].astype(a.dtype), err_msg=k)
+        total += a.nbytes
+    assert total == d1["bytes"] <= 64 * 10 ** 6
+    small = bench.dump_outputs(str(tmp_path / "c"), {k: t[:64] for k, t in outs.items()})
+    assert small["envs"] == small["of_envs"] == 64 and small["sample"] == "all envs"
+    np.testing.assert_array_equal(np.load(tmp_path / "c" / "done.npy"), outs["done"][:64].numpy().astype(np.float32))
+
+
 def test_plain_c_consumer_of_the_abi_compiles_and_links(tmp_path):
     """examples/c_abi_consumer.c — a consumer that is neither Python nor torch — builds with gcc -std=c11 -Wall -Werror against include/gmpe.h and links against
     libgmpe.so + the HIP runtime (it RUNS in tests/test_gpu_c_consumer.py)."""
