@@ -1703,9 +1703,14 @@ __global__ __launch_bounds__(BLOCK, (SC == SC_NAV_WALLS ? GMPE_MIN_WAVES : (FL =
 }
 
 
-// Host entry points of one scenario variant; defined and explicitly instantiated in gmpe_sc.hip (-DGMPE_SC=k).
-template <int SC> void launch_env(int block, int ap, int fl, dim3 grid, size_t lds, hipStream_t st, const KParams& p);
-template <int SC> hipError_t set_max_lds(int lds);
-template <int SC> int max_tiles_per_cu(int block, int ap, size_t lds, int roll, int g = 0);   // of the steady-state (FL = 1) instantiation where one exists; roll: of the rollout (FL = 2) one; g: envs per tile (selects the compile-time-G instantiation where one exists)
+// One k_env instantiation as the host launches it: the kernel, its BLOCK, and whether it carves the separate pair-force buffer.
+struct EnvKernel {
+    const void* fn;
+    int threads;
+    bool fuse;
+};
+// The instantiation of scenario variant SC that runs for a tile of `block` threads, exact-size instantiation `ap` (0: run-time sizes),
+// FL = fl (0: general, 1: steady-state step, 2: rollout) and G envs per tile; defined and explicitly instantiated in gmpe_sc.hip (-DGMPE_SC=k).
+template <int SC> EnvKernel env_kernel(int block, int ap, int fl, int G);
 
 }  // namespace gmpe

@@ -16,9 +16,18 @@
 // launch of the rollout instantiation (FL 2) for K steps, state carried in LDS / registers; handles on the split big-E path run
 // k_env -> compact [N,E,E] scratch -> k_adj_expand -> [N,A,E,E], chunk-pipelined on side streams.
 //
+// Host side: gmpe_create validates the config, allocates the state slab, reads every GMPE_* knob once (read_knobs) and makes the
+// handle's tuning plan (make_plan: tile shapes, store flavour, split / rollout paths and the split path's chunking), which
+// gmpe_get_tuning reports. Which k_env instantiation runs is decided in one place, env_kernel in gmpe_sc.hip: launch_env launches
+// what it returns, the tile-shape search asks the runtime for the residency of what it returns, and the LDS opt-in covers all of it.
+// make_params builds every launch's KParams.
+//
 // HBM-bound by construction: per env-step the kernel reads ~1 KB of state and writes 4·A·(E² + F·E + D + 2) bytes of fp32
 // observations; no MFMA (there is no contraction here). All geometry is fp64 with contraction OFF so thresholds see the
 // reference's roundings; values are rounded to fp32 once, on store, like GraphReplayBuffer's float32 copy (graph_buffer.py:226).
+#include <algorithm>
+#include <optional>
+
 #include "gmpe_kernel.h"
 
 namespace gmpe {
@@ -211,45 +220,38 @@ __global__ __launch_bounds__(256) void k_adj_expand1(const float* __restrict__ s
 // =================================================================== host side / C ABI
 using namespace gmpe;
 
+// What gmpe_create decided for a handle: the gmpe_tuning that gmpe_get_tuning reports, plus the decisions that stay inside the library.
+struct Plan : gmpe_tuning {
+    int nfuse;      // doubles per env of the separate pair-force buffer (fused rollouts of exact-size navigation_graph tiles), 0: none
+    int rowpairs;   // rollouts of the exact-size instantiations visit agent-row pairs only (distance_force_pass)
+    int rollnt;     // GMPE_ROLLNT (-1: nontemporal rollout stores by slot volume, gmpe_rollout_steps)
+    int ramp;       // GMPE_RAMP (-1: the default rule of split_pipeline)
+    int ablate;     // GMPE_ABLATE: diagnostic build only (timing ablations, wrong results)
+};
+
 struct gmpe_handle {
     gmpe_config c;
     int device;
     DevState s;
     int A, L, O, E, D, F;
+    Plan plan{};
     std::vector<void*> allocs;
     bool timing = false;
     std::vector<hipEvent_t> ev;      // pairs
     size_t ev_used = 0;
     double t_total_ms = 0;
     int64_t t_launches = 0;
-    int block = 0;
-    int G = 1;                       // envs per workgroup
-    int ablate = 0;
-    int nt = 0;
-    int spec = 0;
-    int ap = 0;                      // exact-size instantiation in use (0: run-time sizes)
     const double* ovr = nullptr;     // safety-filter hook slot (gmpe_set_control_override)
     const uint8_t* ovr_use = nullptr;
-    int split = 0;                   // big-E path: k_env -> compact scratch -> k_adj_expand
-    int roll = 1;                    // gmpe_step_many runs the persistent rollout kernel
-    int G_roll = 1, block_roll = 256;   // tile shape of the rollout kernel (its own register budget -> its own residency)
     float* adj_scratch = nullptr;    // [N,E,E] (split path only)
     // split path: chunks of envs flow through two kernels on side streams — k_env(chunk c) on env_st[c & 1], k_adj_expand(chunk c)
     // on exp_st after it — so the HBM-bound expansion of one chunk overlaps the latency-bound fused kernel of the next
-    int chunks = 1;
     hipStream_t env_st[2] = {nullptr, nullptr}, exp_st = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
     std::vector<hipEvent_t> ev_chunk;
     hipStream_t part_st[4] = {nullptr, nullptr, nullptr, nullptr};   // gmpe_step_many_envs: one side stream per env range (created on first use)
     hipEvent_t part_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     std::vector<hipEvent_t> ev_exp;      // expansion of chunk c finished (back-pressure on the k_env streams)
-    int ahead = 0;                       // k_env may run at most this many chunks ahead of the expansion (0: unbounded)
-    int xstep = 0;                       // gmpe_step_many on the split path: chain the steps' pipelines (no join between steps)
-    int chunks_x = 1, ahead_x = 0;       // chunking / run-ahead bound of the chained pipeline
-    int rowpairs = 0;                    // rollouts of the exact-size instantiations visit agent-row pairs only (distance_force_pass)
-    int nfuse = 0;                       // doubles per env of the separate pair-force buffer (fused rollouts of exact-size navigation_graph tiles), 0: none
-    int ramp = -1;                       // GMPE_RAMP, read once by gmpe_create (-1: the default rule of split_pipeline)
-    int rollnt = -1;                     // GMPE_ROLLNT, read once by gmpe_create (-1: nontemporal rollout stores by slot volume)
     unsigned long long* stamps = nullptr;
     hipEvent_t region_ev[2] = {nullptr, nullptr};
     int32_t* edge_ws = nullptr;      // [cap_graphs] counts | [cap_graphs] offsets | [cap_graphs/1024+2] chunk sums
@@ -276,10 +278,6 @@ static void slab_take(char* base, size_t& off, T** p, size_t n, int fill_byte, s
     fills.push_back({off, {bytes, fill_byte}});
     off = (off + bytes + 255) / 256 * 256;
 }
-// The separate pair-force buffer (F2, 2*A*A doubles per env) exists only in launches that can run the fused distance + next-step-force pass: the rollout
-// instantiation k_env<256, 10, SC_NAV, 2> (FUSE_OK in gmpe_kernel.h). Every other launch — step kernels, run-time-size or single-wave rollouts — carves no
-// F2 and is not charged its LDS (the c2 step tile at G = 6 sat 100 bytes under the 48 KiB cut-off because of it).
-static int nfuse_of(const gmpe_handle* h, int block, int ap, int fl) { return (fl == 2 && block > 64 && ap == 10) ? h->nfuse : 0; }
 // scenario variant of a validated config (gmpe_kernel.h)
 static int sc_of(const gmpe_config& c) {
     switch (c.scenario) {
@@ -290,25 +288,251 @@ static int sc_of(const gmpe_config& c) {
         default: return c.num_walls > 0 ? SC_NAV_WALLS : SC_NAV;
     }
 }
-static int sc_dispatch_occ(int sc, int block, int ap, size_t lds, int roll = 0, int g = 0) {
+// gmpe_sc.hip's instantiation selector of scenario variant sc
+static EnvKernel select_env(int sc, int block, int ap, int fl, int G) {
     switch (sc) {
-        case SC_NAV: return max_tiles_per_cu<SC_NAV>(block, ap, lds, roll, g);
-        case SC_NAV_WALLS: return max_tiles_per_cu<SC_NAV_WALLS>(block, ap, lds, roll, g);
-        case SC_JULY: return max_tiles_per_cu<SC_JULY>(block, ap, lds, roll, g);
-        case SC_ROT: return max_tiles_per_cu<SC_ROT>(block, ap, lds, roll, g);
-        case SC_TWO: return max_tiles_per_cu<SC_TWO>(block, ap, lds, roll, g);
-        default: return max_tiles_per_cu<SC_THREE>(block, ap, lds, roll, g);
+        case SC_NAV: return env_kernel<SC_NAV>(block, ap, fl, G);
+        case SC_NAV_WALLS: return env_kernel<SC_NAV_WALLS>(block, ap, fl, G);
+        case SC_JULY: return env_kernel<SC_JULY>(block, ap, fl, G);
+        case SC_ROT: return env_kernel<SC_ROT>(block, ap, fl, G);
+        case SC_TWO: return env_kernel<SC_TWO>(block, ap, fl, G);
+        default: return env_kernel<SC_THREE>(block, ap, fl, G);
     }
 }
-static hipError_t sc_dispatch_lds(int sc, int lds) {
-    switch (sc) {
-        case SC_NAV: return set_max_lds<SC_NAV>(lds);
-        case SC_NAV_WALLS: return set_max_lds<SC_NAV_WALLS>(lds);
-        case SC_JULY: return set_max_lds<SC_JULY>(lds);
-        case SC_ROT: return set_max_lds<SC_ROT>(lds);
-        case SC_TWO: return set_max_lds<SC_TWO>(lds);
-        default: return set_max_lds<SC_THREE>(lds);
+// The separate pair-force buffer (F2, 2*A*A doubles per env) exists only in launches that can run the fused distance + next-step-force pass (EnvKernel::fuse).
+// Every other launch — step kernels, run-time-size or single-wave rollouts — carves no F2 and is not charged its LDS (the c2 step tile at G = 6
+// sat 100 bytes under the 48 KiB cut-off because of it).
+static int nfuse_of(const gmpe_handle* h, const EnvKernel& k) { return k.fuse ? h->plan.nfuse : 0; }
+// dynamic LDS of a tile of G envs on instantiation k
+static size_t tile_lds(const gmpe_handle* h, const EnvKernel& k, int G) { return lds_bytes(G, h->A, h->E, h->D, h->c.num_walls, nfuse_of(h, k)); }
+// resident workgroups per CU (registers + LDS) of the instantiation that runs tiles of G envs and `block` threads, 0 on error
+static int tiles_per_cu(const gmpe_handle* h, int block, int fl, int G) {
+    const EnvKernel k = select_env(sc_of(h->c), block, h->plan.ap, fl, G);
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k.fn, k.threads, tile_lds(h, k, G)) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    return nb;
+}
+// opt every instantiation the selector can return for scenario variant sc in to `lds` bytes of dynamic LDS (> 64 KiB: gfx950 has 160 KiB per CU);
+// G = 1 stands for every tile size without a compile-time-G instantiation
+static hipError_t set_max_lds(int sc, int lds) {
+    for (int block : {64, 128, 256})
+        for (int ap : {0, 3, 10})
+            for (int fl : {0, 1, 2})
+                for (int G : {1, 4, 6}) {
+                    const hipError_t e = hipFuncSetAttribute(select_env(sc, block, ap, fl, G).fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+                    if (e != hipSuccess) return e;
+                }
+    return hipSuccess;
+}
+// recorded rollouts bake the kernel parameters (state, tape and override pointers) into their nodes
+static void drop_graphs(gmpe_handle* h) {
+    for (auto& g : h->graphs) { (void)hipGraphExecDestroy(g.exec); (void)hipGraphDestroy(g.graph); }
+    h->graphs.clear();
+}
+
+// ---------------------------------------------------------------- gmpe_create, job by job
+static int validate_config(const gmpe_config* cfg) {
+    if (cfg->abi_version != GMPE_ABI_VERSION) return fail(GMPE_ERR_INVALID_ARG, "gmpe_config.abi_version mismatch");
+    const int E = gmpe_num_entities(cfg);
+    if (cfg->num_envs < 1 || cfg->num_agents < 1 || cfg->num_agents > GMPE_MAX_AGENTS || cfg->num_landmarks < cfg->num_agents ||
+        cfg->num_obstacles < 0 || cfg->num_walls < 0 || cfg->num_walls > GMPE_MAX_WALLS || E > GMPE_MAX_ENTITIES)
+        return fail(GMPE_ERR_INVALID_ARG, "config out of range (agents<=64, entities<=160, walls<=8, landmarks>=agents)");
+    if (cfg->scenario < GMPE_SCENARIO_NAVIGATION_GRAPH || cfg->scenario > GMPE_SCENARIO_THREE_PHASE)
+        return fail(GMPE_ERR_UNSUPPORTED, "unknown scenario");
+    if ((cfg->scenario != GMPE_SCENARIO_NAVIGATION_GRAPH) == (cfg->dynamics == GMPE_DYN_DOUBLE_INTEGRATOR))
+        return fail(GMPE_ERR_UNSUPPORTED, "the tube scenarios are kinematic; navigation_graph is double_integrator");
+    if (cfg->graph_feat_type < 0 || cfg->graph_feat_type > 1) return fail(GMPE_ERR_UNSUPPORTED, "graph_feat_type: 0 (relative) or 1 (global)");
+    if (cfg->formation_type < GMPE_FORMATION_POINT || cfg->formation_type > GMPE_FORMATION_CIRCLE)
+        return fail(GMPE_ERR_UNSUPPORTED, "formation_type: 0 (point), 1 (line) or 2 (circle)");
+    if (cfg->contact_family < 0 || cfg->contact_family > 1 || (cfg->contact_family == 1 && (cfg->scenario != GMPE_SCENARIO_NAVIGATION_GRAPH || !(cfg->agent_mass > 0))))
+        return fail(GMPE_ERR_UNSUPPORTED, "contact_family 1 (classic MPE) applies to navigation_graph and needs agent_mass > 0");
+    if (cfg->dynamics == GMPE_DYN_DOUBLE_INTEGRATOR ? (cfg->n_actions != 5 && cfg->n_actions != 9) : cfg->n_actions != 25)
+        return fail(GMPE_ERR_INVALID_ARG, "n_actions does not match the dynamics");
+    return GMPE_OK;
+}
+
+static int alloc_state(gmpe_handle* h) {
+    const size_t N = h->c.num_envs, NA = N * h->A;
+    DevState& s = h->s;
+    std::vector<std::pair<size_t, std::pair<size_t, int>>> fills;
+    char* slab = nullptr;
+    for (int pass = 0; pass < 2; ++pass) {                  // pass 0 sizes the slab, pass 1 hands out the pointers
+        size_t off = 0;
+        fills.clear();
+#define AL(p, n, fill) slab_take(slab, off, &(p), (n), (fill), fills);
+        AL(s.x, NA, 0) AL(s.y, NA, 0) AL(s.s2, NA, 0) AL(s.s3, NA, 0) AL(s.p_dist, NA, 0) AL(s.time, NA, 0)
+        AL(s.status, NA, 0) AL(s.prev_phase, NA, 0) AL(s.phase_reached, NA, 0) AL(s.cooldown, NA, 0)
+        AL(s.goal_tracker, NA, 0xFF) AL(s.current_step, N, 0) AL(s.rng_ctr, N, 0)
+        AL(s.tube, N * GMPE_TUBE_STRIDE, 0) AL(s.landmarks, N * h->L * 2, 0) AL(s.obstacles, N * h->O * 2, 0)
+        AL(s.times_required, NA, 0xFF) AL(s.dists_to_goal, NA, 0xFF) AL(s.dist_left, NA, 0xFF) AL(s.goal_reached, NA, 0xFF)
+        AL(s.n_agent_coll, NA, 0) AL(s.n_obst_coll, NA, 0) AL(s.spacing_viol, NA, 0) AL(s.steps_in_corr, NA, 0)
+        AL(s.conformance, NA, 0) AL(s.goal_min_time, NA, 0) AL(s.delta_spacing, N, 0) AL(s.error_flags, N, 0) AL(s.prev_proj, NA, 0)
+#undef AL
+        if (pass == 0) {
+            void* q = nullptr;
+            hipError_t e = hipMalloc(&q, off);
+            if (e != hipSuccess) return fail(GMPE_ERR_HIP, std::string("hipMalloc(state slab): ") + hipGetErrorString(e));
+            h->allocs.push_back(q);
+            slab = static_cast<char*>(q);
+        }
     }
+    for (auto& f : fills) {
+        hipError_t e = hipMemset(slab + f.first, f.second.second, f.second.first);
+        if (e != hipSuccess) return fail(GMPE_ERR_HIP, std::string("hipMemset: ") + hipGetErrorString(e));
+    }
+    s.tape = nullptr; s.tape_len = 0;
+    return GMPE_OK;
+}
+
+// Every GMPE_* knob (bench.py PERF_KNOBS, plus GMPE_ABLATE), read once by gmpe_create: a knob that is not set is empty. They override
+// the heuristics of make_plan (tuning, tests); nothing on the step path reads the environment.
+struct Knobs {
+    std::optional<int> G, block, G_roll, ap, fuse, nt, split, roll, rollnt, spec, xstep, ramp, chunks, ahead, ablate;
+};
+static Knobs read_knobs() {
+    auto knob = [](const char* name) { const char* v = getenv(name); return v ? std::optional<int>(atoi(v)) : std::nullopt; };
+    Knobs k;
+    k.G = knob("GMPE_G"); k.block = knob("GMPE_BLOCK"); k.G_roll = knob("GMPE_GROLL"); k.ap = knob("GMPE_AP"); k.fuse = knob("GMPE_FUSE");
+    k.nt = knob("GMPE_NT"); k.split = knob("GMPE_SPLIT"); k.roll = knob("GMPE_ROLL"); k.rollnt = knob("GMPE_ROLLNT"); k.spec = knob("GMPE_SPEC");
+    k.xstep = knob("GMPE_XSTEP"); k.ramp = knob("GMPE_RAMP"); k.chunks = knob("GMPE_CHUNKS"); k.ahead = knob("GMPE_AHEAD");
+#if defined(GMPE_DIAG) || defined(GMPE_NTORDER_KNOB)
+    k.ablate = knob("GMPE_ABLATE");
+#endif
+    return k;
+}
+
+// Tile shape (measured on MI355X, profiles/README.md "tile shapes"): every tile should be RESIDENT at once (a second round of
+// tiles repeats the whole latency chain), with about four tiles per CU — one wave-0 chain per SIMD — and as many waves per
+// tile as still fit: C2/C3 pick G = 4, BLOCK = 256 (1024 tiles = 4 per CU x 4 waves at <= 128 VGPRs). Residency is asked
+// from the runtime (registers + LDS of the instantiation that will run). Returns the smallest G from N / (4 CUs) up to Gmax
+// whose tiles are all resident, 0 when the batch cannot be resident at all (C4/C5, N >> 4096).
+static int resident_G(const gmpe_handle* h, int block, int fl, int Gmax, int cus) {
+    const size_t N = h->c.num_envs;
+    int G0 = (int)((N + 4 * (size_t)cus - 1) / (4 * (size_t)cus));
+    if (G0 < 1) G0 = 1;
+    for (int g = G0; g <= Gmax; ++g) {
+        const int per_cu = tiles_per_cu(h, block, fl, g);
+        if (per_cu > 0 && (N + g - 1) / g <= (size_t)per_cu * cus) return g;
+    }
+    return 0;
+}
+
+static int make_plan(gmpe_handle* h, const Knobs& k) {
+    Plan& t = h->plan;
+    const size_t N = h->c.num_envs;
+    const int A = h->A, E = h->E;
+    int cus = 256;
+    { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, h->device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount; }
+    // exact-size instantiations of the common cases (A = L, no obstacles); GMPE_AP=0: run-time sizes
+    t.ap = (A == h->L && h->O == 0 && (A == 10 || A == 3) && k.ap != 0) ? A : 0;
+    // Rollouts of the exact-size navigation_graph instantiation (A = L = 10, no obstacles, no walls) compute the next step's contact forces inside the distance
+    // pass (distance_force_pass): the forces then need a buffer of their own, 2*A*A doubles per env (1.6 KB). GMPE_FUSE=0: the classic force pass, all rows.
+    t.nfuse = (sc_of(h->c) == SC_NAV && t.ap == 10 && k.fuse != 0) ? 2 * A * A : 0;
+    t.rowpairs = k.fuse != 0;
+    t.ablate = k.ablate.value_or(0);
+#ifdef GMPE_DIAG
+    t.diag_build = 1;
+#endif
+    // G envs per workgroup so that the sequential-semantics passes fill wave 0 (G*A <= 64) while the per-tile LDS stays small enough for
+    // several workgroups per CU; one cap for both tile shapes (the rollout tile carries the F2 buffer)
+    int Gmax = 64 / A; if (Gmax < 1) Gmax = 1; if (Gmax > (int)N) Gmax = (int)N;
+    while (Gmax > 1 && lds_bytes(Gmax, A, E, h->D, h->c.num_walls, t.nfuse) > 48 * 1024) --Gmax;
+    {   // exact magic division (fdiv) needs q*d < 2^32 for every (range, divisor) pair the kernel uses
+        const uint64_t S = (uint64_t)h->L + h->O;
+        uint64_t d = (uint64_t)A * E;
+        if ((uint64_t)A * (E * E / 4) * (E * E / 4) >= (1ull << 32)) return fail(GMPE_ERR_UNSUPPORTED, "adjacency block too large for the index arithmetic");
+        const uint64_t cand[] = {(uint64_t)E * E, S * S, (uint64_t)A * (A + h->O), (uint64_t)A * h->D, 2ull * E};
+        for (uint64_t x : cand) if (x > d) d = x;
+        if ((uint64_t)Gmax * d * d >= (1ull << 32)) return fail(GMPE_ERR_UNSUPPORTED, "tile too large for the index arithmetic");
+    }
+    // step tile: BLOCK 256 first, then 128, 64; a batch that cannot be resident packs as many envs as wave 0 holds and the stores decide
+    int block = 0;                                                  // BLOCK of the resident step tile (0: none, or GMPE_G / GMPE_BLOCK set)
+    if (!k.G && !k.block)
+        for (int b : {256, 128, 64})
+            if ((t.G = resident_G(h, b, 1, Gmax, cus))) { block = b; break; }
+    if (!t.G) t.G = k.G.value_or(Gmax);
+    if (t.G < 1) t.G = 1;
+    if (t.G > Gmax) t.G = Gmax;
+    const size_t stream_f4 = (size_t)t.G * A * ((size_t)E * E / 4 + 2 * (size_t)E);
+    t.block = k.block.value_or(block ? block : (stream_f4 <= 2048 ? 64 : (stream_f4 <= 6144 ? 128 : 256)));
+    if (t.block != 64 && t.block != 128 && t.block != 256) t.block = 256;
+    // rollout tile: same rule with ITS registers; BLOCK 256 unless the step kernel runs single-wave tiles
+    t.block_roll = k.block.value_or(block) == 64 ? 64 : 256;
+    if (!k.G && !k.G_roll) t.G_roll = resident_G(h, t.block_roll, 2, Gmax, cus);
+    if (!t.G_roll) t.G_roll = k.G_roll.value_or(k.G ? t.G : Gmax);
+    if (t.G_roll < 1) t.G_roll = 1;
+    if (t.G_roll > Gmax) t.G_roll = Gmax;
+    t.lds_bytes = (int32_t)tile_lds(h, select_env(sc_of(h->c), t.block, t.ap, 1, t.G), t.G);
+    t.lds_bytes_roll = (int32_t)tile_lds(h, select_env(sc_of(h->c), t.block_roll, t.ap, 2, t.G_roll), t.G_roll);
+    // Graph outputs per launch vs the 256 MiB Infinity Cache: small launches (C2/C3: 92 MB) are absorbed by it and run
+    // faster with ordinary stores (37.0 vs 40.4 us measured); big ones (C4 6 GB, C5 9 GB) stream past it and gain ~10 %
+    // from nontemporal stores (C4 1417 -> 1285 us, C5 2005 -> 1852 us).
+    const bool past_cache = (double)N * A * ((double)E * E + 8.0 * E) * 4.0 > 192.0 * 1024 * 1024;
+    t.nt = k.nt.value_or(past_cache ? 1 : 0);
+    // Multi-wave tiles specialise (wave 0: reward / info / write-back, waves 1..: graph stores). Measured with the final register
+    // budgets: C2 30.2 vs 33.2 us, C4 1286 vs 1297 us, C5 shard 1901 vs 1970 us — on everywhere (GMPE_SPEC=0 turns it off).
+    t.spec = k.spec.value_or(1);
+    t.roll = k.roll.value_or(1);
+    t.rollnt = k.rollnt ? (*k.rollnt != 0) : -1;
+    t.ramp = k.ramp ? (*k.ramp != 0) : -1;
+    // Split path (fused kernel -> compact matrix, k_adj_expand -> A copies, chunk-pipelined; see split_pipeline): pays where the
+    // adjacency is >= ~95 % of the bytes (A >= 48): c5 shapes (64 agents) 2048 envs 1515 us split vs 1731 fused, 4096: 2994 vs 3455,
+    // 8192: 6043 vs 6565, 16384: 11618 vs 12981 (with the run-ahead bound below); c4 (A = 32) 1260 vs 1132: stays fused
+    // (profiles/r02_notes.md). Everything else runs the fused kernel.
+    t.split = k.split.value_or(past_cache && A >= 48 ? 1 : 0);
+    if ((uint64_t)N * E * E >= (1ull << 32)) t.split = 0;            // k_adj_expand indexes the compact matrix with 32 bits
+    if ((uint64_t)A * E * E / 4 * (E * E / 4 + 1) >= (1ull << 32)) t.split = 0;   // k_adj_expand's exact magic division
+    if (!t.split) return GMPE_OK;
+    const size_t tiles_resident = (size_t)cus * std::max(1, tiles_per_cu(h, block ? block : 256, 1, t.G)), tiles_total = (N + t.G - 1) / t.G;
+    // Back-pressure: the fused kernel is the faster stage, and left alone it runs many chunks ahead; by the time k_adj_expand reads a
+    // chunk's matrices they have left the 256 MiB Infinity Cache, and its A re-reads per matrix (one per ego copy, spread over the
+    // XCDs' L2s) come from HBM: 220 us per 256-env chunk instead of 150 (rocprofv3 trace, profiles/r02_notes.md). With k_env(c)
+    // waiting for expand(c - 2) the live part of the scratch stays cache-resident: c5 shapes 4096 envs 3640 -> 2994 us, 8192
+    // 7744 -> 6043, 16384 16003 -> 11618. A scratch that fits the cache as a whole (the 2048-env shard: 134 MB) needs no bound.
+    t.ahead = k.ahead.value_or((double)N * E * E * sizeof(float) > 192.0 * 1024 * 1024 ? 2 : 0);
+    if (t.ahead < 0) t.ahead = 0;
+    // one chunk = one full round of resident tiles (c5 shard of 2048 envs: 8 chunks of 256 envs; 2 / 4 / 6 / 8 / 12 / 16 chunks: 1802 / 1602 /
+    // 1560 / 1522 / 1548 / 1539 us), two rounds when the run-ahead is bounded (long pipelines: fewer launch gaps on the expansion
+    // stream; 512- vs 256-env chunks: 4096 envs 2944-3029 vs 3104 us, 8192: 5729 vs 5828, 16384: 11223 vs 11521)
+    const size_t per_chunk = tiles_resident * (t.ahead > 0 ? 2 : 1);
+    t.chunks = (int)((tiles_total + per_chunk - 1) / per_chunk);
+    if (t.chunks < 4) t.chunks = 4;
+    if (t.chunks > 128) t.chunks = 128;
+    if (k.chunks) t.chunks = *k.chunks;
+    if (t.chunks < 1) t.chunks = 1;
+    if ((size_t)t.chunks > N) t.chunks = (int)N;
+    // gmpe_step_many (open-loop steps): the steps' pipelines are chained — k_env(step s+1, chunk c) waits for expand(step s, chunk c), not for
+    // the whole step s — which hides the pipeline's fill: c5 shard 1486-1524 -> 1383 us per step, 16384 envs 11.26 -> 10.94 ms. The chained
+    // pipeline is long at any batch size, so it always uses two rounds of tiles per chunk and the run-ahead bound of 2 (shard: 8 chunks
+    // unbounded 1416, 4 chunks D = 2 1383, 3 / 5 / 6 chunks 1409 / 1410 / 1434; D = 1 1982, D = 3 1407). GMPE_CHUNKS / GMPE_AHEAD set both pipelines.
+    t.xstep = k.xstep.value_or(1);
+    t.chunks_x = (int)((tiles_total + 2 * tiles_resident - 1) / (2 * tiles_resident));
+    if (t.chunks_x < 2) t.chunks_x = 2;
+    if (t.chunks_x > 128) t.chunks_x = 128;
+    if ((size_t)t.chunks_x > N) t.chunks_x = (int)N;
+    if (k.chunks) t.chunks_x = t.chunks;
+    t.ahead_x = k.ahead ? t.ahead : 2;
+    return GMPE_OK;
+}
+
+// split path: the compact adjacency scratch, the side streams and the chunk events (enough for the longer of the two pipelines)
+static int create_split_path(gmpe_handle* h) {
+    void* q = nullptr;
+    hipError_t e = hipMalloc(&q, (size_t)h->c.num_envs * h->E * h->E * sizeof(float));
+    if (e != hipSuccess) return fail(GMPE_ERR_HIP, std::string("hipMalloc(adjacency scratch): ") + hipGetErrorString(e));
+    h->allocs.push_back(q);
+    h->adj_scratch = static_cast<float*>(q);
+    bool ok = true;
+    for (int q2 = 0; q2 < 2 && ok; ++q2) ok = hipStreamCreateWithFlags(&h->env_st[q2], hipStreamNonBlocking) == hipSuccess;
+    ok = ok && hipStreamCreateWithFlags(&h->exp_st, hipStreamNonBlocking) == hipSuccess;
+    ok = ok && hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) == hipSuccess;
+    for (int q2 = 0; q2 < 3 && ok; ++q2) ok = hipEventCreateWithFlags(&h->ev_join[q2], hipEventDisableTiming) == hipSuccess;
+    h->ev_chunk.resize((size_t)std::max(h->plan.chunks, h->plan.chunks_x) + 2, nullptr);
+    for (size_t q2 = 0; q2 < h->ev_chunk.size() && ok; ++q2) ok = hipEventCreateWithFlags(&h->ev_chunk[q2], hipEventDisableTiming) == hipSuccess;
+    h->ev_exp.resize(h->ev_chunk.size(), nullptr);
+    for (size_t q2 = 0; q2 < h->ev_exp.size() && ok; ++q2) ok = hipEventCreateWithFlags(&h->ev_exp[q2], hipEventDisableTiming) == hipSuccess;
+    if (!ok) return fail(GMPE_ERR_HIP, "split path: could not create the side streams / events");
+    return GMPE_OK;
 }
 
 // ---------------------------------------------------------------- learner side: node_obs rows from entity tables (gmpe_expand_node_obs)
@@ -500,212 +724,25 @@ static int field_info(const gmpe_handle* h, int f, void** ptr, size_t* bytes) {
 
 int gmpe_create(const gmpe_config* cfg, int device, gmpe_handle** out) {
     if (!cfg || !out) return fail(GMPE_ERR_INVALID_ARG, "null argument");
-    if (cfg->abi_version != GMPE_ABI_VERSION) return fail(GMPE_ERR_INVALID_ARG, "gmpe_config.abi_version mismatch");
-    const int E = gmpe_num_entities(cfg);
-    if (cfg->num_envs < 1 || cfg->num_agents < 1 || cfg->num_agents > GMPE_MAX_AGENTS || cfg->num_landmarks < cfg->num_agents ||
-        cfg->num_obstacles < 0 || cfg->num_walls < 0 || cfg->num_walls > GMPE_MAX_WALLS || E > GMPE_MAX_ENTITIES)
-        return fail(GMPE_ERR_INVALID_ARG, "config out of range (agents<=64, entities<=160, walls<=8, landmarks>=agents)");
-    if (cfg->scenario < GMPE_SCENARIO_NAVIGATION_GRAPH || cfg->scenario > GMPE_SCENARIO_THREE_PHASE)
-        return fail(GMPE_ERR_UNSUPPORTED, "unknown scenario");
-    if ((cfg->scenario != GMPE_SCENARIO_NAVIGATION_GRAPH) == (cfg->dynamics == GMPE_DYN_DOUBLE_INTEGRATOR))
-        return fail(GMPE_ERR_UNSUPPORTED, "the tube scenarios are kinematic; navigation_graph is double_integrator");
-    if (cfg->graph_feat_type < 0 || cfg->graph_feat_type > 1) return fail(GMPE_ERR_UNSUPPORTED, "graph_feat_type: 0 (relative) or 1 (global)");
-    if (cfg->formation_type < GMPE_FORMATION_POINT || cfg->formation_type > GMPE_FORMATION_CIRCLE)
-        return fail(GMPE_ERR_UNSUPPORTED, "formation_type: 0 (point), 1 (line) or 2 (circle)");
-    if (cfg->contact_family < 0 || cfg->contact_family > 1 || (cfg->contact_family == 1 && (cfg->scenario != GMPE_SCENARIO_NAVIGATION_GRAPH || !(cfg->agent_mass > 0))))
-        return fail(GMPE_ERR_UNSUPPORTED, "contact_family 1 (classic MPE) applies to navigation_graph and needs agent_mass > 0");
-    if (cfg->dynamics == GMPE_DYN_DOUBLE_INTEGRATOR ? (cfg->n_actions != 5 && cfg->n_actions != 9) : cfg->n_actions != 25)
-        return fail(GMPE_ERR_INVALID_ARG, "n_actions does not match the dynamics");
+    int rc = validate_config(cfg);
+    if (rc) return rc;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(GMPE_ERR_NO_DEVICE, "no HIP device visible: the engine has no CPU fallback");
     if (device < 0 || device >= ndev) return fail(GMPE_ERR_INVALID_ARG, "bad device index");
     HIPCHK(hipSetDevice(device));
     gmpe_handle* h = new gmpe_handle();
     h->c = *cfg; h->device = device;
-    h->A = cfg->num_agents; h->L = cfg->num_landmarks; h->O = cfg->num_obstacles; h->E = E; h->D = gmpe_obs_dim(cfg); h->F = gmpe_node_feats(cfg);
-    const size_t N = cfg->num_envs, NA = N * h->A;
-    DevState& s = h->s;
-    std::vector<std::pair<size_t, std::pair<size_t, int>>> fills;
-    char* slab = nullptr;
-    for (int pass = 0; pass < 2; ++pass) {                  // pass 0 sizes the slab, pass 1 hands out the pointers
-        size_t off = 0;
-        fills.clear();
-#define AL(p, n, fill) slab_take(slab, off, &(p), (n), (fill), fills);
-        AL(s.x, NA, 0) AL(s.y, NA, 0) AL(s.s2, NA, 0) AL(s.s3, NA, 0) AL(s.p_dist, NA, 0) AL(s.time, NA, 0)
-        AL(s.status, NA, 0) AL(s.prev_phase, NA, 0) AL(s.phase_reached, NA, 0) AL(s.cooldown, NA, 0)
-        AL(s.goal_tracker, NA, 0xFF) AL(s.current_step, N, 0) AL(s.rng_ctr, N, 0)
-        AL(s.tube, N * GMPE_TUBE_STRIDE, 0) AL(s.landmarks, N * h->L * 2, 0) AL(s.obstacles, N * h->O * 2, 0)
-        AL(s.times_required, NA, 0xFF) AL(s.dists_to_goal, NA, 0xFF) AL(s.dist_left, NA, 0xFF) AL(s.goal_reached, NA, 0xFF)
-        AL(s.n_agent_coll, NA, 0) AL(s.n_obst_coll, NA, 0) AL(s.spacing_viol, NA, 0) AL(s.steps_in_corr, NA, 0)
-        AL(s.conformance, NA, 0) AL(s.goal_min_time, NA, 0) AL(s.delta_spacing, N, 0) AL(s.error_flags, N, 0) AL(s.prev_proj, NA, 0)
-#undef AL
-        if (pass == 0) {
-            void* q = nullptr;
-            hipError_t e = hipMalloc(&q, off);
-            if (e != hipSuccess) { gmpe_destroy(h); return fail(GMPE_ERR_HIP, std::string("hipMalloc(state slab): ") + hipGetErrorString(e)); }
-            h->allocs.push_back(q);
-            slab = static_cast<char*>(q);
-        }
-    }
-    for (auto& f : fills) {
-        hipError_t e = hipMemset(slab + f.first, f.second.second, f.second.first);
-        if (e != hipSuccess) { gmpe_destroy(h); return fail(GMPE_ERR_HIP, std::string("hipMemset: ") + hipGetErrorString(e)); }
-    }
-    s.tape = nullptr; s.tape_len = 0;
-    // Tile shape. G envs per workgroup so that the sequential-semantics passes fill wave 0 (G*A <= 64)
-    // while the per-tile LDS stays small enough for several workgroups per CU; BLOCK threads share the
-    // distance pass and the stores. GMPE_G / GMPE_BLOCK override the heuristic (tuning, tests).
-    const char* env_g = getenv("GMPE_G");
-    const char* env_block = getenv("GMPE_BLOCK");
-    // Heuristic (measured on MI355X, profiles/README.md "tile shapes"): every tile should be RESIDENT at once (a second round of
-    // tiles repeats the whole latency chain), with about four tiles per CU — one wave-0 chain per SIMD — and as many waves per
-    // tile as still fit: C2/C3 pick G = 4, BLOCK = 256 (1024 tiles = 4 per CU x 4 waves at <= 128 VGPRs). Residency is asked
-    // from the runtime (registers + LDS of the instantiation that will run). When the batch cannot be resident at all
-    // (C4/C5, N >> 4096) a tile packs as many envs as wave 0 holds (G*A <= 64) and the stores decide.
-    int dev_cus = 256;
-    { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) dev_cus = prop.multiProcessorCount; }
-    // Rollouts of the exact-size navigation_graph instantiation (A = L = 10, no obstacles, no walls) compute the next step's contact forces inside the distance
-    // pass (distance_force_pass): the forces then need a buffer of their own, 2*A*A doubles per env (1.6 KB). GMPE_FUSE=0: the classic force pass.
-    h->nfuse = (sc_of(h->c) == SC_NAV && h->A == h->L && h->O == 0 && h->A == 10 && !(getenv("GMPE_AP") && atoi(getenv("GMPE_AP")) == 0)) ? 2 * h->A * h->A : 0;
-    if (getenv("GMPE_FUSE") && atoi(getenv("GMPE_FUSE")) == 0) h->nfuse = 0;
-    h->rowpairs = (getenv("GMPE_FUSE") && atoi(getenv("GMPE_FUSE")) == 0) ? 0 : 1;
-    int Gmax = 64 / h->A; if (Gmax < 1) Gmax = 1; if (Gmax > (int)N) Gmax = (int)N;
-    while (Gmax > 1 && lds_bytes(Gmax, h->A, E, h->D, cfg->num_walls, h->nfuse) > 48 * 1024) --Gmax;   // one cap for both tile shapes (the rollout tile carries the F2 buffer)
-    int ap_sel = (h->A == h->L && h->O == 0 && (h->A == 10 || h->A == 3)) ? h->A : 0;   // exact-size instantiations of the common cases (A = L, no obstacles)
-    if (getenv("GMPE_AP") && atoi(getenv("GMPE_AP")) == 0) ap_sel = 0;                    // tuning: run-time sizes
-    h->ap = ap_sel;
-    int G = 0, block_sel = 0;
-    if (!env_g && !env_block) {
-        int G0 = (int)((N + 4 * (size_t)dev_cus - 1) / (4 * (size_t)dev_cus));
-        if (G0 < 1) G0 = 1;
-        const int blocks[3] = {256, 128, 64};
-        for (int bi = 0; bi < 3 && !G; ++bi)
-            for (int g = G0; g <= Gmax; ++g) {
-                const size_t tiles = (N + g - 1) / g;
-                const int per_cu = sc_dispatch_occ(sc_of(h->c), blocks[bi], ap_sel, lds_bytes(g, h->A, E, h->D, cfg->num_walls, 0), 0, g);
-                if (per_cu > 0 && tiles <= (size_t)per_cu * dev_cus) { G = g; block_sel = blocks[bi]; break; }
-            }
-    }
-    if (!G) {
-        G = env_g ? atoi(env_g) : Gmax;
-        if (G < 1) G = 1;
-        if (G > Gmax) G = Gmax;
-    }
-    {   // exact magic division (fdiv) needs q*d < 2^32 for every (range, divisor) pair the kernel uses
-        const uint64_t S = (uint64_t)h->L + h->O;
-        uint64_t d = (uint64_t)h->A * E;
-        if ((uint64_t)h->A * (E * E / 4) * (E * E / 4) >= (1ull << 32)) { gmpe_destroy(h); return fail(GMPE_ERR_UNSUPPORTED, "adjacency block too large for the index arithmetic"); }
-        const uint64_t cand[] = {(uint64_t)E * E, S * S, (uint64_t)h->A * (h->A + h->O), (uint64_t)h->A * h->D, 2ull * E};
-        for (uint64_t x : cand) if (x > d) d = x;
-        if ((uint64_t)Gmax * d * d >= (1ull << 32)) { gmpe_destroy(h); return fail(GMPE_ERR_UNSUPPORTED, "tile too large for the index arithmetic"); }
-    }
-    h->G = G;
-    {   // rollout kernel: same rule (every tile resident, from four tiles per CU upward) with ITS registers; BLOCK 256 unless the step kernel runs single-wave tiles
-        const char* env_gr = getenv("GMPE_GROLL");
-        h->block_roll = ((env_block ? atoi(env_block) : block_sel) == 64) ? 64 : 256;
-        int Gr = 0;
-        if (!env_g && !env_gr) {
-            int G0 = (int)((N + 4 * (size_t)dev_cus - 1) / (4 * (size_t)dev_cus));
-            if (G0 < 1) G0 = 1;
-            for (int g = G0; g <= Gmax && !Gr; ++g) {
-                const size_t tiles = (N + g - 1) / g;
-                const int per_cu = sc_dispatch_occ(sc_of(h->c), h->block_roll, ap_sel, lds_bytes(g, h->A, E, h->D, cfg->num_walls, nfuse_of(h, h->block_roll, ap_sel, 2)), 1, g);
-                if (per_cu > 0 && tiles <= (size_t)per_cu * dev_cus) Gr = g;
-            }
-        }
-        if (!Gr) Gr = env_gr ? atoi(env_gr) : (env_g ? G : Gmax);
-        if (Gr < 1) Gr = 1;
-        if (Gr > Gmax) Gr = Gmax;
-        h->G_roll = Gr;
-    }
-#if defined(GMPE_DIAG) || defined(GMPE_NTORDER_KNOB)
-    h->ablate = getenv("GMPE_ABLATE") ? atoi(getenv("GMPE_ABLATE")) : 0;   // diagnostic build only: timing ablations (wrong results)
-#else
-    h->ablate = 0;
-#endif
-    // Graph outputs per launch vs the 256 MiB Infinity Cache: small launches (C2/C3: 92 MB) are absorbed by it and run
-    // faster with ordinary stores (37.0 vs 40.4 us measured); big ones (C4 6 GB, C5 9 GB) stream past it and gain ~10 %
-    // from nontemporal stores (C4 1417 -> 1285 us, C5 2005 -> 1852 us).
-    {
-        const double out_bytes = (double)N * h->A * ((double)E * E + 8.0 * E) * 4.0;
-        h->nt = getenv("GMPE_NT") ? atoi(getenv("GMPE_NT")) : (out_bytes > 192.0 * 1024 * 1024 ? 1 : 0);
-        // Split path (fused kernel -> compact matrix, k_adj_expand -> A copies, chunk-pipelined; see split_pipeline): pays where the
-        // adjacency is >= ~95 % of the bytes (A >= 48): c5 shapes (64 agents) 2048 envs 1515 us split vs 1731 fused, 4096: 2994 vs 3455,
-        // 8192: 6043 vs 6565, 16384: 11618 vs 12981 (with the run-ahead bound below); c4 (A = 32) 1260 vs 1132: stays fused
-        // (profiles/r02_notes.md). Everything else runs the fused kernel.
-        const size_t tiles_resident = (size_t)dev_cus * (size_t)[&] { const int q = sc_dispatch_occ(sc_of(h->c), block_sel ? block_sel : 256, ap_sel, lds_bytes(G, h->A, E, h->D, cfg->num_walls, 0), 0, G); return q > 0 ? q : 1; }();
-        const size_t tiles_total = (N + G - 1) / G;
-        h->split = getenv("GMPE_SPLIT") ? atoi(getenv("GMPE_SPLIT"))
-                                        : (out_bytes > 192.0 * 1024 * 1024 && h->A >= 48 ? 1 : 0);
-        if ((uint64_t)N * E * E >= (1ull << 32)) h->split = 0;            // k_adj_expand indexes the compact matrix with 32 bits
-        h->roll = getenv("GMPE_ROLL") ? atoi(getenv("GMPE_ROLL")) : 1;
-        h->rollnt = getenv("GMPE_ROLLNT") ? (atoi(getenv("GMPE_ROLLNT")) != 0) : -1;
-        if ((uint64_t)h->A * E * E / 4 * (E * E / 4 + 1) >= (1ull << 32)) h->split = 0;   // k_adj_expand's exact magic division
-        if (h->split) {
-            void* q = nullptr;
-            hipError_t e = hipMalloc(&q, (size_t)N * E * E * sizeof(float));
-            if (e != hipSuccess) { gmpe_destroy(h); return fail(GMPE_ERR_HIP, std::string("hipMalloc(adjacency scratch): ") + hipGetErrorString(e)); }
-            h->allocs.push_back(q);
-            h->adj_scratch = static_cast<float*>(q);
-            // Back-pressure: the fused kernel is the faster stage, and left alone it runs many chunks ahead; by the time k_adj_expand reads a
-            // chunk's matrices they have left the 256 MiB Infinity Cache, and its A re-reads per matrix (one per ego copy, spread over the
-            // XCDs' L2s) come from HBM: 220 us per 256-env chunk instead of 150 (rocprofv3 trace, profiles/r02_notes.md). With k_env(c)
-            // waiting for expand(c - 2) the live part of the scratch stays cache-resident: c5 shapes 4096 envs 3640 -> 2994 us, 8192
-            // 7744 -> 6043, 16384 16003 -> 11618. A scratch that fits the cache as a whole (the 2048-env shard: 134 MB) needs no bound.
-            h->ahead = (double)N * E * E * sizeof(float) > 192.0 * 1024 * 1024 ? 2 : 0;
-            if (getenv("GMPE_AHEAD")) h->ahead = atoi(getenv("GMPE_AHEAD"));
-            if (h->ahead < 0) h->ahead = 0;
-            // gmpe_step_many (open-loop steps): the steps' pipelines are chained — k_env(step s+1, chunk c) waits for expand(step s, chunk c), not for
-            // the whole step s — which hides the pipeline's fill: c5 shard 1486-1524 -> 1383 us per step, 16384 envs 11.26 -> 10.94 ms. The chained
-            // pipeline is long at any batch size, so it always uses two rounds of tiles per chunk and the run-ahead bound of 2 (shard: 8 chunks
-            // unbounded 1416, 4 chunks D = 2 1383, 3 / 5 / 6 chunks 1409 / 1410 / 1434; D = 1 1982, D = 3 1407).
-            h->xstep = getenv("GMPE_XSTEP") ? atoi(getenv("GMPE_XSTEP")) : 1;
-            h->ramp = getenv("GMPE_RAMP") ? (atoi(getenv("GMPE_RAMP")) != 0) : -1;
-            h->chunks_x = (int)((tiles_total + 2 * tiles_resident - 1) / (2 * tiles_resident));
-            if (h->chunks_x < 2) h->chunks_x = 2;
-            if (h->chunks_x > 128) h->chunks_x = 128;
-            h->ahead_x = 2;
-            // one chunk = one full round of resident tiles (c5 shard of 2048 envs: 8 chunks of 256 envs; 2 / 4 / 6 / 8 / 12 / 16 chunks: 1802 / 1602 /
-            // 1560 / 1522 / 1548 / 1539 us), two rounds when the run-ahead is bounded (long pipelines: fewer launch gaps on the expansion
-            // stream; 512- vs 256-env chunks: 4096 envs 2944-3029 vs 3104 us, 8192: 5729 vs 5828, 16384: 11223 vs 11521)
-            const size_t per_chunk = tiles_resident * (h->ahead > 0 ? 2 : 1);
-            h->chunks = (int)((tiles_total + per_chunk - 1) / per_chunk);
-            if (h->chunks < 4) h->chunks = 4;
-            if (h->chunks > 128) h->chunks = 128;
-            if (getenv("GMPE_CHUNKS")) h->chunks = atoi(getenv("GMPE_CHUNKS"));
-            if (h->chunks < 1) h->chunks = 1;
-            if ((size_t)h->chunks > N) h->chunks = (int)N;
-            if (getenv("GMPE_CHUNKS")) h->chunks_x = h->chunks;            // the knobs set both pipelines
-            if (getenv("GMPE_AHEAD")) h->ahead_x = h->ahead;
-            if ((size_t)h->chunks_x > N) h->chunks_x = (int)N;
-            bool ok = true;
-            for (int q2 = 0; q2 < 2 && ok; ++q2) ok = hipStreamCreateWithFlags(&h->env_st[q2], hipStreamNonBlocking) == hipSuccess;
-            ok = ok && hipStreamCreateWithFlags(&h->exp_st, hipStreamNonBlocking) == hipSuccess;
-            ok = ok && hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) == hipSuccess;
-            for (int q2 = 0; q2 < 3 && ok; ++q2) ok = hipEventCreateWithFlags(&h->ev_join[q2], hipEventDisableTiming) == hipSuccess;
-            h->ev_chunk.resize((size_t)(h->chunks > h->chunks_x ? h->chunks : h->chunks_x) + 2, nullptr);
-            for (size_t q2 = 0; q2 < h->ev_chunk.size() && ok; ++q2) ok = hipEventCreateWithFlags(&h->ev_chunk[q2], hipEventDisableTiming) == hipSuccess;
-            h->ev_exp.resize(h->ev_chunk.size(), nullptr);
-            for (size_t q2 = 0; q2 < h->ev_exp.size() && ok; ++q2) ok = hipEventCreateWithFlags(&h->ev_exp[q2], hipEventDisableTiming) == hipSuccess;
-            if (!ok) { gmpe_destroy(h); return fail(GMPE_ERR_HIP, "split path: could not create the side streams / events"); }
-        }
-    }
-    const size_t stream_f4 = (size_t)G * h->A * ((size_t)E * E / 4 + 2 * (size_t)E);
-    h->block = env_block ? atoi(env_block) : (block_sel ? block_sel : (stream_f4 <= 2048 ? 64 : (stream_f4 <= 6144 ? 128 : 256)));
-    if (h->block != 64 && h->block != 128 && h->block != 256) h->block = 256;
-    // Multi-wave tiles specialise (wave 0: reward / info / write-back, waves 1..: graph stores). Measured with the final register
-    // budgets: C2 30.2 vs 33.2 us, C4 1286 vs 1297 us, C5 shard 1901 vs 1970 us — on everywhere (GMPE_SPEC=0 turns it off).
-    h->spec = getenv("GMPE_SPEC") ? atoi(getenv("GMPE_SPEC")) : 1;
-    const size_t lds_step = lds_bytes(h->G, h->A, E, h->D, cfg->num_walls, 0), lds_roll = lds_bytes(h->G_roll, h->A, E, h->D, cfg->num_walls, nfuse_of(h, h->block_roll, h->ap, 2));
-    const size_t lds = lds_step > lds_roll ? lds_step : lds_roll;
+    h->A = cfg->num_agents; h->L = cfg->num_landmarks; h->O = cfg->num_obstacles; h->E = gmpe_num_entities(cfg); h->D = gmpe_obs_dim(cfg); h->F = gmpe_node_feats(cfg);
+    if ((rc = alloc_state(h)) || (rc = make_plan(h, read_knobs())) || (h->plan.split && (rc = create_split_path(h)))) { gmpe_destroy(h); return rc; }
+    const size_t lds = (size_t)std::max(h->plan.lds_bytes, h->plan.lds_bytes_roll);
     if (lds > 160 * 1024) { gmpe_destroy(h); return fail(GMPE_ERR_UNSUPPORTED, "per-tile LDS exceeds 160 KiB"); }
-    if (lds > 48 * 1024) {                                   // opt in to >64 KiB dynamic LDS (gfx950: 160 KiB per CU)
-        const hipError_t e = sc_dispatch_lds(sc_of(h->c), (int)lds);
+    if (lds > 48 * 1024) {
+        const hipError_t e = set_max_lds(sc_of(h->c), (int)lds);
         if (e != hipSuccess) { gmpe_destroy(h); return fail(GMPE_ERR_HIP, std::string("hipFuncSetAttribute: ") + hipGetErrorString(e)); }
     }
 #ifdef GMPE_STAMPS
     {
-        const size_t grid = (N + G - 1) / G;
+        const size_t grid = (h->c.num_envs + h->plan.G - 1) / h->plan.G;
         void* q = nullptr;
         if (hipMalloc(&q, grid * GMPE_NSTAMPS * 8) == hipSuccess) { (void)hipMemset(q, 0, grid * GMPE_NSTAMPS * 8); h->allocs.push_back(q); h->stamps = static_cast<unsigned long long*>(q); }
     }
@@ -717,7 +754,7 @@ int gmpe_create(const gmpe_config* cfg, int device, gmpe_handle** out) {
 #ifdef GMPE_STAMPS
 // diagnostic build only: copy the per-workgroup phase stamps of the LAST launch to the host
 int gmpe_debug_stamps(gmpe_handle* h, unsigned long long* host_dst, int64_t max_blocks) {
-    const int64_t grid = (h->c.num_envs + h->G - 1) / h->G;
+    const int64_t grid = (h->c.num_envs + h->plan.G - 1) / h->plan.G;
     const int64_t nb = grid < max_blocks ? grid : max_blocks;
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(host_dst, h->stamps, (size_t)nb * GMPE_NSTAMPS * 8, hipMemcpyDeviceToHost));
@@ -726,19 +763,16 @@ int gmpe_debug_stamps(gmpe_handle* h, unsigned long long* host_dst, int64_t max_
 #endif
 
 int gmpe_destroy(gmpe_handle* h) {
-    if (h) (void)hipSetDevice(h->device);                             // streams / events / allocations below belong to the handle's device
-    if (h) { for (auto& g : h->graphs) { (void)hipGraphExecDestroy(g.exec); (void)hipGraphDestroy(g.graph); } h->graphs.clear(); if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream); h->cap_stream = nullptr; }
-    if (h) {
-        for (hipStream_t s : {h->env_st[0], h->env_st[1], h->exp_st}) if (s) (void)hipStreamDestroy(s);
-        for (hipEvent_t e : {h->ev_fork, h->ev_join[0], h->ev_join[1], h->ev_join[2]}) if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : h->ev_chunk) if (e) (void)hipEventDestroy(e);
-        for (hipStream_t& s : h->part_st) if (s) { (void)hipStreamDestroy(s); s = nullptr; }
-        for (hipEvent_t& e : h->part_ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-        for (hipEvent_t e : h->ev_exp) if (e) (void)hipEventDestroy(e);
-        h->ev_exp.clear();
-        h->ev_chunk.clear();
-    }
     if (!h) return GMPE_OK;
+    (void)hipSetDevice(h->device);                             // streams / events / allocations below belong to the handle's device
+    drop_graphs(h);
+    if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream);
+    for (hipStream_t s : {h->env_st[0], h->env_st[1], h->exp_st}) if (s) (void)hipStreamDestroy(s);
+    for (hipEvent_t e : {h->ev_fork, h->ev_join[0], h->ev_join[1], h->ev_join[2]}) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : h->ev_chunk) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : h->ev_exp) if (e) (void)hipEventDestroy(e);
+    for (hipStream_t s : h->part_st) if (s) (void)hipStreamDestroy(s);
+    for (hipEvent_t e : h->part_ev) if (e) (void)hipEventDestroy(e);
     for (void* q : h->allocs) (void)hipFree(q);
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
     if (h->edge_ws) (void)hipFree(h->edge_ws);
@@ -751,18 +785,14 @@ int gmpe_destroy(gmpe_handle* h) {
 int gmpe_set_rng_tape(gmpe_handle* h, const double* tape_dev, int64_t len_per_env) {
     if (!h) return fail(GMPE_ERR_INVALID_ARG, "null handle");
     h->s.tape = tape_dev; h->s.tape_len = tape_dev ? len_per_env : 0;
-    // recorded rollouts bake the kernel parameters (tape pointer included) into their nodes: drop them
-    for (auto& g : h->graphs) { (void)hipGraphExecDestroy(g.exec); (void)hipGraphDestroy(g.graph); }
-    h->graphs.clear();
+    drop_graphs(h);
     return GMPE_OK;
 }
 
 int gmpe_set_control_override(gmpe_handle* h, const double* ctrl_dev, const uint8_t* use_dev) {
     if (!h) return fail(GMPE_ERR_INVALID_ARG, "null handle");
     h->ovr = ctrl_dev; h->ovr_use = ctrl_dev ? use_dev : nullptr;
-    // recorded rollouts bake the kernel parameters into their nodes: drop them
-    for (auto& g : h->graphs) { (void)hipGraphExecDestroy(g.exec); (void)hipGraphDestroy(g.graph); }
-    h->graphs.clear();
+    drop_graphs(h);
     return GMPE_OK;
 }
 int gmpe_field_device_ptr(gmpe_handle* h, int field, void** ptr_out) {
@@ -793,14 +823,19 @@ int gmpe_set_field(gmpe_handle* h, int field, const void* host_src, size_t bytes
     return GMPE_OK;
 }
 
-static void fill_params(const gmpe_handle* h, KParams& p, int G) {
+// The kernel parameters of one launch over the whole batch: the handle's sizes, state and plan, and the launch's inputs and outputs.
+// roll: the rollout tile (G_roll envs); the caller adds the rollout fields.
+static KParams make_params(const gmpe_handle* h, int mode, const int32_t* act, const float* onehot, const uint8_t* mask, const gmpe_outputs* out, bool roll) {
+    KParams p;
     memset(&p, 0, sizeof p);
     p.c = h->c; p.s = h->s;
-    p.A = h->A; p.L = h->L; p.O = h->O; p.E = h->E; p.D = h->D; p.F = h->F; p.G = G;
-    p.ablate = h->ablate;
-    p.nt = h->nt;
-    p.nfuse = 0; p.rowpairs = h->rowpairs;                                // nfuse: set per launch by dispatch_env
-    p.spec = h->spec;
+    if (out) p.o = *out;
+    p.act = act; p.onehot = onehot; p.mask = mask; p.mode = mode;
+    p.A = h->A; p.L = h->L; p.O = h->O; p.E = h->E; p.D = h->D; p.F = h->F; p.G = roll ? h->plan.G_roll : h->plan.G;
+    p.ablate = h->plan.ablate;
+    p.nt = h->plan.nt;
+    p.rowpairs = h->plan.rowpairs;                                     // nfuse: set per launch by launch_env
+    p.spec = h->plan.spec;
     p.stamps = h->stamps;
     p.K = 1; p.S = 1; p.num_slots = 1;
     p.env_lo = 0; p.env_hi = h->c.num_envs;
@@ -813,20 +848,18 @@ static void fill_params(const gmpe_handle* h, KParams& p, int G) {
     p.m_W = magic_of(p.E * (p.E - 1) / 2); p.m_Sx = magic_of((p.E & 1) ? (p.E - 1) / 2 : p.E - 1);      // distance_pass: pairs per env, inner divisor
     p.m_FW = magic_of(p.A * (p.A - 1) / 2 + p.A * p.O);
     p.TW = gmpe_entity_table_width(&h->c); p.m_TW = magic_of(p.TW);
+    return p;
 }
-static int ap_of(const gmpe_handle* h) { return h->ap; }
-static void dispatch_env(const gmpe_handle* h, int block, int ap, int fl, hipStream_t st, KParams& p) {
-    p.nfuse = nfuse_of(h, block, ap, fl);
-    const size_t lds = lds_bytes(p.G, h->A, h->E, h->D, h->c.num_walls, p.nfuse);
-    const dim3 grid((p.env_hi - p.env_lo + p.G - 1) / p.G);
-    switch (sc_of(h->c)) {
-        case SC_NAV: launch_env<SC_NAV>(block, ap, fl, grid, lds, st, p); break;
-        case SC_NAV_WALLS: launch_env<SC_NAV_WALLS>(block, ap, fl, grid, lds, st, p); break;
-        case SC_JULY: launch_env<SC_JULY>(block, ap, fl, grid, lds, st, p); break;
-        case SC_ROT: launch_env<SC_ROT>(block, ap, fl, grid, lds, st, p); break;
-        case SC_TWO: launch_env<SC_TWO>(block, ap, fl, grid, lds, st, p); break;
-        default: launch_env<SC_THREE>(block, ap, fl, grid, lds, st, p); break;
-    }
+// One launch of the fused kernel over p's env range: the rollout instantiation (FL = 2) for a rollout; for a step, the steady-state
+// instantiation (FL = 1, its run-time flags folded) when those flags hold — step mode, ordinary stores, wave specialisation, no ablation —
+// and the general one (FL = 0) for everything else, explicit resets included.
+static void launch_env(const gmpe_handle* h, bool roll, hipStream_t st, KParams& p) {
+    const Plan& t = h->plan;
+    const int fl = roll ? 2 : (p.mode == MODE_STEP && !t.nt && !t.ablate && t.spec) ? 1 : 0;
+    const EnvKernel k = select_env(sc_of(h->c), roll ? t.block_roll : t.block, t.ap, fl, p.G);
+    p.nfuse = nfuse_of(h, k);
+    void* args[] = {&p};
+    (void)hipLaunchKernel(k.fn, dim3((p.env_hi - p.env_lo + p.G - 1) / p.G), dim3(k.threads), args, tile_lds(h, k, p.G), st);
 }
 
 // Split big-E path: one step as a software pipeline over env chunks —
@@ -839,12 +872,12 @@ static void dispatch_env(const gmpe_handle* h, int block, int ap, int fl, hipStr
 // `first` / `last`: gmpe_step_many_launches chains the pipelines of consecutive open-loop steps without joining in between (fork before the first step,
 // join after the last): k_env(step s+1, chunk c) then waits for expand(step s, chunk c) — the reader of the scratch rows it overwrites — instead of for
 // the whole step s. (A first version with TWO scratch buffers and no bound was slower than joining per step: its live scratch did not fit the cache.)
-static int split_pipeline(gmpe_handle* h, int mode, KParams& p, float* adj_full, hipStream_t st, bool first = true, bool last = true) {
+static int split_pipeline(gmpe_handle* h, KParams& p, hipStream_t st, bool first = true, bool last = true) {
     const bool chained = !(first && last);
     const uint32_t EE = (uint32_t)h->E * h->E;
-    const int N = h->c.num_envs, C = chained ? h->chunks_x : h->chunks, ahead = chained ? h->ahead_x : h->ahead;
-    const int per = ((N + C - 1) / C + h->G - 1) / h->G * h->G;              // envs per chunk, a whole number of tiles
-    const int fl = (mode == MODE_STEP && !h->nt && !h->ablate && h->spec) ? 1 : 0;
+    const int N = h->c.num_envs, G = h->plan.G, C = chained ? h->plan.chunks_x : h->plan.chunks, ahead = chained ? h->plan.ahead_x : h->plan.ahead;
+    const int per = ((N + C - 1) / C + G - 1) / G * G;                    // envs per chunk, a whole number of tiles
+    float* const adj_full = p.o.adj;
     p.o.adj = h->adj_scratch; p.o.adj_compact = 1;
     if (first) {
         HIPCHK(hipEventRecord(h->ev_fork, st));
@@ -855,9 +888,9 @@ static int split_pipeline(gmpe_handle* h, int mode, KParams& p, float* adj_full,
     // step with / without: 1024 envs 729 / 697, 2048: 1375-1431 / 1350, 4096: 2750 / 2790, 8192: 5818 / 6000, 16384: 10941-11219 / 11327-11368)
     int bounds[134]; int nb = 0;                                            // <= 128 chunks + the two ramp chunks + the end marker
     {
-        const bool ramp = (h->ramp >= 0 ? h->ramp != 0 : (!chained || C >= 6)) && per >= 4 * h->G;   // GMPE_RAMP=0: equal chunks
+        const bool ramp = (h->plan.ramp >= 0 ? h->plan.ramp != 0 : (!chained || C >= 6)) && per >= 4 * G;   // GMPE_RAMP=0: equal chunks
         int lo = 0;
-        if (ramp) { const int q = (per / 4 + h->G - 1) / h->G * h->G; bounds[nb++] = lo; lo += q; bounds[nb++] = lo; lo += 2 * q; }
+        if (ramp) { const int q = (per / 4 + G - 1) / G * G; bounds[nb++] = lo; lo += q; bounds[nb++] = lo; lo += 2 * q; }
         while (lo < N && nb < 132) { bounds[nb++] = lo; lo += per; }
         bounds[nb] = N;
         for (int q = 0; q < nb; ++q) if (bounds[q] > N) bounds[q] = N;
@@ -873,7 +906,7 @@ static int split_pipeline(gmpe_handle* h, int mode, KParams& p, float* adj_full,
         p.env_lo = lo; p.env_hi = hi;
         if (ahead > 0 && c >= ahead) HIPCHK(hipStreamWaitEvent(se, h->ev_exp[c - ahead], 0));
         if (chained && !first) HIPCHK(hipStreamWaitEvent(se, h->ev_exp[c], 0));   // the previous step's expansion of this chunk has read the scratch rows
-        dispatch_env(h, h->block, ap_of(h), fl, se, p);
+        launch_env(h, false, se, p);
         HIPCHK(hipEventRecord(h->ev_chunk[c], se));
         HIPCHK(hipStreamWaitEvent(h->exp_st, h->ev_chunk[c], 0));
         const int gy = hi - lo < 1024 ? hi - lo : 1024;
@@ -893,10 +926,7 @@ static int split_pipeline(gmpe_handle* h, int mode, KParams& p, float* adj_full,
 static int launch(gmpe_handle* h, int mode, const int32_t* act, const float* onehot, const uint8_t* mask,
                   const gmpe_outputs* out, void* stream, int env_lo = 0, int env_hi = -1) {
     if (!h) return fail(GMPE_ERR_INVALID_ARG, "null handle");
-    KParams p;
-    fill_params(h, p, h->G);
-    if (out) p.o = *out;
-    p.act = act; p.onehot = onehot; p.mask = mask; p.mode = mode;
+    KParams p = make_params(h, mode, act, onehot, mask, out, false);
     if (env_hi >= 0) { p.env_lo = env_lo; p.env_hi = env_hi; }           // gmpe_step_envs: a contiguous env range (pointers stay whole-batch)
     HIPCHK(hipSetDevice(h->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -908,14 +938,12 @@ static int launch(gmpe_handle* h, int mode, const int32_t* act, const float* one
         e0 = h->ev[h->ev_used]; e1 = h->ev[h->ev_used + 1];
         HIPCHK(hipEventRecord(e0, st));
     }
-    if (h->split && p.o.adj && !p.o.adj_compact) {
+    if (h->plan.split && p.o.adj && !p.o.adj_compact) {
         // the fused kernel writes the env's single matrix into the scratch, k_adj_expand makes the A copies (chunk pipeline)
-        float* adj_full = p.o.adj;
-        const int rc = split_pipeline(h, mode, p, adj_full, st);
+        const int rc = split_pipeline(h, p, st);
         if (rc) return rc;
     } else {
-        const int fl = (mode == MODE_STEP && !h->nt && !h->ablate && h->spec) ? 1 : 0;   // steady-state instantiation (flags folded)
-        dispatch_env(h, h->block, ap_of(h), fl, st, p);
+        launch_env(h, false, st, p);
     }
     HIPCHK(hipGetLastError());
     if (h->timing && !h->capturing) { HIPCHK(hipEventRecord(e1, st)); h->ev_used += 2; }
@@ -926,38 +954,26 @@ int gmpe_rollout_steps(gmpe_handle* h, const int32_t* actions_dev, const gmpe_ro
     if (!h || !actions_dev || !r) return fail(GMPE_ERR_INVALID_ARG, "gmpe_rollout_steps: null argument");
     if (r->num_steps < 1 || r->num_action_sets < 1 || r->num_slots < 1 || r->first_slot < 0 || r->first_slot >= r->num_slots)
         return fail(GMPE_ERR_INVALID_ARG, "gmpe_rollout_steps: bad step / slot counts");
-    if (h->split) return fail(GMPE_ERR_UNSUPPORTED, "gmpe_rollout_steps: this handle runs the split big-E path (use gmpe_step_many)");
+    if (h->plan.split) return fail(GMPE_ERR_UNSUPPORTED, "gmpe_rollout_steps: this handle runs the split big-E path (use gmpe_step_many)");
 
-    KParams p;
-    fill_params(h, p, h->G_roll);
-    if (slot0) p.o = *slot0;
-    p.act = actions_dev; p.mode = MODE_STEP;
+    KParams p = make_params(h, MODE_STEP, actions_dev, nullptr, nullptr, slot0, true);
     p.K = r->num_steps; p.S = r->num_action_sets; p.num_slots = r->num_slots; p.first_slot = r->first_slot;
     p.st_obs = r->stride_obs; p.st_id = r->stride_agent_id; p.st_node = r->stride_node_obs; p.st_adj = r->stride_adj;
     p.st_rew = r->stride_reward; p.st_done = r->stride_done; p.st_info = r->stride_info; p.st_mask = r->stride_masks; p.st_tab = r->stride_entity_table;
     p.masks = r->masks; p.active = r->active_masks;
     {   // a rollout that fills more slots than the 256 MiB Infinity Cache holds streams past it: nontemporal graph stores (like the big launches)
         const double step_bytes = (double)h->c.num_envs * h->A * ((double)h->E * h->E * (p.o.adj_compact ? 1.0 / h->A : 1.0) + (double)h->F * h->E) * 4.0;
-        p.nt = h->rollnt >= 0 ? h->rollnt : (step_bytes * r->num_slots > 192.0 * 1024 * 1024 ? 1 : 0);      // GMPE_ROLLNT was read by gmpe_create: no getenv on the collect path
+        p.nt = h->plan.rollnt >= 0 ? h->plan.rollnt : (step_bytes * r->num_slots > 192.0 * 1024 * 1024 ? 1 : 0);      // GMPE_ROLLNT was read by gmpe_create: no getenv on the collect path
     }
     HIPCHK(hipSetDevice(h->device));
-    dispatch_env(h, h->block_roll, ap_of(h), 2, static_cast<hipStream_t>(stream), p);
+    launch_env(h, true, static_cast<hipStream_t>(stream), p);
     HIPCHK(hipGetLastError());
     return GMPE_OK;
 }
 
 int gmpe_get_tuning(const gmpe_handle* h, gmpe_tuning* t) {
     if (!h || !t) return fail(GMPE_ERR_INVALID_ARG, "gmpe_get_tuning: null argument");
-    memset(t, 0, sizeof *t);
-    t->G = h->G; t->block = h->block; t->nt = h->nt; t->spec = h->spec; t->split = h->split; t->roll = h->roll; t->ap = ap_of(h);
-    t->lds_bytes = (int32_t)lds_bytes(h->G, h->A, h->E, h->D, h->c.num_walls, 0);
-    t->lds_bytes_roll = (int32_t)lds_bytes(h->G_roll, h->A, h->E, h->D, h->c.num_walls, nfuse_of(h, h->block_roll, h->ap, 2));
-    t->G_roll = h->G_roll; t->block_roll = h->block_roll;
-    t->chunks = h->split ? h->chunks : 0; t->ahead = h->split ? h->ahead : 0;
-    t->xstep = h->split ? h->xstep : 0; t->chunks_x = h->split ? h->chunks_x : 0; t->ahead_x = h->split ? h->ahead_x : 0;
-#ifdef GMPE_DIAG
-    t->diag_build = 1;
-#endif
+    *t = h->plan;
     return GMPE_OK;
 }
 
@@ -971,14 +987,14 @@ int gmpe_step(gmpe_handle* h, const int32_t* action_idx_dev, const gmpe_outputs*
 int gmpe_step_envs(gmpe_handle* h, const int32_t* action_idx_dev, const gmpe_outputs* out, int32_t env_lo, int32_t env_hi, void* stream) {
     if (!h || !action_idx_dev) return fail(GMPE_ERR_INVALID_ARG, "gmpe_step_envs: null argument");
     if (env_lo < 0 || env_hi > h->c.num_envs || env_lo >= env_hi) return fail(GMPE_ERR_INVALID_ARG, "gmpe_step_envs: bad env range");
-    if (h->split && out && out->adj && !out->adj_compact) return fail(GMPE_ERR_UNSUPPORTED, "gmpe_step_envs: this handle runs the split big-E path (whole-batch steps only)");
+    if (h->plan.split && out && out->adj && !out->adj_compact) return fail(GMPE_ERR_UNSUPPORTED, "gmpe_step_envs: this handle runs the split big-E path (whole-batch steps only)");
     return launch(h, MODE_STEP, action_idx_dev, nullptr, nullptr, out, stream, env_lo, env_hi);
 }
 int gmpe_step_many_envs(gmpe_handle* h, const int32_t* actions_dev, int32_t num_steps, int32_t num_action_sets, const gmpe_outputs* out,
                         int32_t parts, void* stream) {
     if (!h || !actions_dev || num_steps < 0 || num_action_sets < 1) return fail(GMPE_ERR_INVALID_ARG, "gmpe_step_many_envs: bad arguments");
     if (parts < 1 || parts > 4 || parts > h->c.num_envs) return fail(GMPE_ERR_INVALID_ARG, "gmpe_step_many_envs: 1..4 env ranges");
-    if (h->split && out && out->adj && !out->adj_compact) return fail(GMPE_ERR_UNSUPPORTED, "gmpe_step_many_envs: split big-E path");
+    if (h->plan.split && out && out->adj && !out->adj_compact) return fail(GMPE_ERR_UNSUPPORTED, "gmpe_step_many_envs: split big-E path");
     if (num_steps == 0) return GMPE_OK;
     HIPCHK(hipSetDevice(h->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -991,7 +1007,7 @@ int gmpe_step_many_envs(gmpe_handle* h, const int32_t* actions_dev, int32_t num_
     for (int32_t k = 0; k < num_steps; ++k)
         for (int q = 0; q < parts; ++q) {
             // range q's step k depends only on range q's step k-1 (same side stream): its latency chain runs under the other ranges' store drains
-            const int lo = (int)((long long)N * q / parts / h->G * h->G), hi = q + 1 == parts ? N : (int)((long long)N * (q + 1) / parts / h->G * h->G);
+            const int G = h->plan.G, lo = (int)((long long)N * q / parts / G * G), hi = q + 1 == parts ? N : (int)((long long)N * (q + 1) / parts / G * G);
             if (lo >= hi) continue;
             const int rc = launch(h, MODE_STEP, actions_dev + (size_t)(k % num_action_sets) * stride, nullptr, nullptr, out, h->part_st[q], lo, hi);
             if (rc) {                                                   // join what is already enqueued, so the caller's stream stays ordered after it
@@ -1018,7 +1034,7 @@ int gmpe_step_many_prepare(gmpe_handle* h, const int32_t* actions_dev, int32_t n
     if (!h || !actions_dev || num_steps < 1 || num_action_sets < 1) return fail(GMPE_ERR_INVALID_ARG, "gmpe_step_many_prepare: bad arguments");
     gmpe_outputs o; memset(&o, 0, sizeof o); if (out) o = *out;
     if (find_graph(h, actions_dev, num_steps, num_action_sets, o) >= 0) return GMPE_OK;
-    if (h->split) return GMPE_OK;                                 // the split path forks onto side streams per step: not recorded, gmpe_step_many loops
+    if (h->plan.split) return GMPE_OK;                            // the split path forks onto side streams per step: not recorded, gmpe_step_many loops
     HIPCHK(hipSetDevice(h->device));
     if (!h->cap_stream) HIPCHK(hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking));
     if (h->graphs.size() >= 4) {                                  // small cache: drop the oldest
@@ -1045,7 +1061,7 @@ int gmpe_step_many(gmpe_handle* h, const int32_t* actions_dev, int32_t num_steps
                    const gmpe_outputs* out, void* stream) {
     if (!h || !actions_dev || num_steps < 0 || num_action_sets < 1) return fail(GMPE_ERR_INVALID_ARG, "gmpe_step_many: bad arguments");
     if (num_steps == 0) return GMPE_OK;
-    if (h->roll && !h->split && !h->timing && !h->ablate) {                  // one launch: the persistent rollout kernel (same results as the launch loop)
+    if (h->plan.roll && !h->plan.split && !h->timing && !h->plan.ablate) {   // one launch: the persistent rollout kernel (same results as the launch loop)
         gmpe_rollout r; memset(&r, 0, sizeof r);
         r.num_steps = num_steps; r.num_action_sets = num_action_sets; r.num_slots = 1;
         return gmpe_rollout_steps(h, actions_dev, &r, out, stream);
@@ -1066,14 +1082,12 @@ int gmpe_step_many_launches(gmpe_handle* h, const int32_t* actions_dev, int32_t 
         }
     }
     const size_t stride = (size_t)h->c.num_envs * h->A;
-    if (h->split && h->xstep && !h->timing && num_steps > 1 && out && out->adj && !out->adj_compact) {
+    if (h->plan.split && h->plan.xstep && !h->timing && num_steps > 1 && out && out->adj && !out->adj_compact) {
         // open-loop steps on the split path: one chunk pipeline over all the steps (no join between steps)
         HIPCHK(hipSetDevice(h->device));
         for (int32_t k = 0; k < num_steps; ++k) {
-            KParams p;
-            fill_params(h, p, h->G);
-            p.o = *out; p.act = actions_dev + (size_t)(k % num_action_sets) * stride; p.mode = MODE_STEP;
-            const int rc = split_pipeline(h, MODE_STEP, p, out->adj, static_cast<hipStream_t>(stream), k == 0, k == num_steps - 1);
+            KParams p = make_params(h, MODE_STEP, actions_dev + (size_t)(k % num_action_sets) * stride, nullptr, nullptr, out, false);
+            const int rc = split_pipeline(h, p, static_cast<hipStream_t>(stream), k == 0, k == num_steps - 1);
             if (rc) return rc;
         }
         return GMPE_OK;
