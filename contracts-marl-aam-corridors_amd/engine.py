@@ -71,15 +71,23 @@ class GmpeEngine(object):
 
     def rebind(self, outputs):
         """Point the engine at other caller-owned output tensors (same shapes/dtypes, same device)."""
-        ref = self.out
-        for k in StepOutputs.__slots__:
-            a, b = getattr(ref, k), getattr(outputs, k)
-            if (a is None) != (b is None):
-                raise ValueError("output %r: presence differs" % k)
-            if a is not None and (tuple(a.shape) != tuple(b.shape) or a.dtype != b.dtype or b.device != self.device or not b.is_contiguous()):
-                raise ValueError("output %r must be a contiguous %s tensor of shape %s on %s" % (k, a.dtype, tuple(a.shape), self.device))
+        self._check_outputs(outputs)
         self.out = outputs
         self._o = self._pack(outputs)
+
+    def _check_outputs(self, o, partial=False, num_slots=1, strides=None):
+        """`o` against the engine's own outputs: same shape and dtype, on this device, contiguous. Presence must match, except that with partial=True an absent
+        output is allowed (it is not written). With num_slots > 1 the storage behind every output must also hold num_slots slots at its entry in `strides`."""
+        for k in StepOutputs.__slots__:
+            a, b = getattr(self.out, k), getattr(o, k)
+            if b is None and (a is None or partial):
+                continue
+            if a is None or b is None:
+                raise ValueError("output %r: presence differs" % k)
+            if tuple(a.shape) != tuple(b.shape) or a.dtype != b.dtype or b.device != self.device or not b.is_contiguous():
+                raise ValueError("output %r must be a contiguous %s tensor of shape %s on %s" % (k, a.dtype, tuple(a.shape), self.device))
+            if num_slots > 1:
+                _check_slots(k, b, b.numel(), num_slots, int((strides or {}).get(k, 0)))
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -104,22 +112,25 @@ class GmpeEngine(object):
                                        self._stream()), "gmpe_reset")
         return self.out
 
+    def _actions(self, a, dtype, numel, convert, msg):
+        """`a` as a contiguous `dtype` tensor on this device with `numel` elements: converted when `convert`, refused (ValueError `msg`) otherwise."""
+        if a.dtype != dtype or not a.is_contiguous() or a.device != self.device:
+            a = a.to(device=self.device, dtype=dtype).contiguous() if convert else None
+        if a is None or a.numel() != numel:
+            raise ValueError(msg)
+        return a
+
     def step(self, action_idx):
         """action_idx: int32 device tensor [N,A]."""
-        a = action_idx
-        if a.dtype != torch.int32 or not a.is_contiguous() or a.device != self.device:
-            a = a.to(device=self.device, dtype=torch.int32).contiguous()
-        if a.numel() != self.N * self.A:
-            raise ValueError("action_idx must have N*A = %d elements" % (self.N * self.A))
+        a = self._actions(action_idx, torch.int32, self.N * self.A, True, "action_idx must have N*A = %d elements" % (self.N * self.A))
         _lib.check(self.lib.gmpe_step(self.h, a.data_ptr(), C.byref(self._o), self._stream()), "gmpe_step")
         return self.out
 
     def step_envs(self, action_idx, env_lo, env_hi, stream=None):
         """Step the envs [env_lo, env_hi) only (whole-batch `action_idx` [N,A] and outputs; rows outside the range untouched), on `stream`
         (a torch.cuda.Stream; default: the current one). Ranges are independent: a runner can double-buffer halves of the batch."""
-        a = action_idx
-        if a.dtype != torch.int32 or not a.is_contiguous() or a.device != self.device or a.numel() != self.N * self.A:
-            raise ValueError("action_idx must be a contiguous int32 device tensor with N*A = %d elements" % (self.N * self.A))
+        a = self._actions(action_idx, torch.int32, self.N * self.A, False,
+                          "action_idx must be a contiguous int32 device tensor with N*A = %d elements" % (self.N * self.A))
         st = C.c_void_p(stream.cuda_stream) if stream is not None else self._stream()
         _lib.check(self.lib.gmpe_step_envs(self.h, a.data_ptr(), C.byref(self._o), int(env_lo), int(env_hi), st), "gmpe_step_envs")
         return self.out
@@ -165,17 +176,27 @@ class GmpeEngine(object):
     def prepare_rollout(self, action_sets, num_steps, slot0=None, num_slots=1, first_slot=0, strides=None, masks=None, active_masks=None):
         """The launch of rollout(...) with these arguments as a callable: the argument structs (gmpe_rollout, gmpe_outputs) are built once, a call is ONE C call
         (gmpe_rollout_steps on the current stream). For collect loops that launch the same rollout every episode — building slot views and structs in Python costs
-        ~30 us per launch, 7 % of a 20-step rollout at c2. The tensors are referenced, not copied: their contents are read / written at launch time."""
+        ~30 us per launch, 7 % of a 20-step rollout at c2. The tensors are referenced, not copied: their contents are read / written at launch time.
+        Every argument is checked here, before anything is launched: `slot0` like rebind's outputs (an absent output is not written), and the storage behind every
+        output and mask must hold `num_slots` slots at its stride. With slot0=None the callable writes the outputs the engine is bound to NOW and keeps them alive:
+        a later rebind points the engine elsewhere but does not free them under it."""
         a = action_sets
         self._check_action_sets(a)
-        o = self._o if slot0 is None else self._pack(slot0)
         st = strides or {}
+        outs = self.out if slot0 is None else slot0
+        self._check_outputs(outs, partial=True, num_slots=int(num_slots), strides=st)
+        for k, m in (("masks", masks), ("active_masks", active_masks)):
+            if m is not None:
+                if m.dtype != torch.float32 or m.device != self.device or not m.is_contiguous():
+                    raise ValueError("%s must be a contiguous float32 tensor on %s" % (k, self.device))
+                _check_slots(k, m, self.N * self.A, int(num_slots), int(st.get("masks", 0)))
+        o = self._pack(outs)
         r = _lib.GmpeRollout(int(num_steps), int(a.shape[0]), int(num_slots), int(first_slot),
                              int(st.get("obs", 0)), int(st.get("agent_id", 0)), int(st.get("node_obs", 0)), int(st.get("adj", 0)),
                              int(st.get("reward", 0)), int(st.get("done", 0)), int(st.get("info", 0)), int(st.get("masks", 0)),
                              None if masks is None else masks.data_ptr(), None if active_masks is None else active_masks.data_ptr(),
                              int(st.get("entity_table", 0)))
-        keep = (a, slot0, masks, active_masks)                           # the tensors behind the raw pointers stay alive with the callable
+        keep = (a, masks, active_masks) + tuple(getattr(outs, k) for k in StepOutputs.__slots__)   # the tensors behind the raw pointers stay alive with the callable
         eng, fn, ap, rp, op, stream, check = self, self.lib.gmpe_rollout_steps, a.data_ptr(), C.byref(r), C.byref(o), self._stream, _lib.check
 
         def launch(_keep=keep, _r=r, _o=o):
@@ -201,11 +222,7 @@ class GmpeEngine(object):
 
     def step_onehot(self, onehot):
         """onehot: float32 device tensor [N,A,n_actions] (argmax fused into the kernel)."""
-        a = onehot
-        if a.dtype != torch.float32 or not a.is_contiguous() or a.device != self.device:
-            a = a.to(device=self.device, dtype=torch.float32).contiguous()
-        if a.numel() != self.N * self.A * self.cfg.n_actions:
-            raise ValueError("onehot must be [N,A,%d]" % self.cfg.n_actions)
+        a = self._actions(onehot, torch.float32, self.N * self.A * self.cfg.n_actions, True, "onehot must be [N,A,%d]" % self.cfg.n_actions)
         _lib.check(self.lib.gmpe_step_onehot(self.h, a.data_ptr(), C.byref(self._o), self._stream()),
                    "gmpe_step_onehot")
         return self.out
@@ -365,45 +382,41 @@ class GmpeEngine(object):
         return algorithmic_bytes_per_env_step(self.cfg)
 
 
-def expand_node_obs(cfg, table, out=None, out_envs=None, env_offset=0):
-    """Learner side of the compact gather: float64 entity tables [..., n, W] (device tensor, contiguous; leading dims = blocks such as the T+1 slots of a rollout) ->
-    node_obs float32 [..., out_envs, A, E, F], rows of the table's n envs written at env_offset .. env_offset + n of every block (default: out_envs = n). The rows are
-    bit-identical to the engine's own node_obs (same arithmetic, gmpe_step.hip k_node_expand). No handle needed: the learner rank may own no envs."""
+def _check_slots(name, t, numel, num_slots, stride):
+    """The storage behind `t` holds num_slots slots of `numel` elements, `stride` elements apart, from t's first element on: what a rollout writes through it."""
+    if stride < 0 or (t.storage_offset() + stride * (num_slots - 1) + numel) * t.element_size() > t.untyped_storage().nbytes():
+        raise ValueError("%s: its storage does not hold %d slots of %d elements %d apart" % (name, num_slots, numel, stride))
+
+
+def _expand(fn, cfg, table, out, out_envs, env_offset, row_shape, *extra):
+    """What expand_node_obs and expand_adj share: check the tables, allocate or check `out` [..., out_envs, *row_shape], one launch of `fn` on the current stream."""
     lib = _lib.load()
     if table.dtype != torch.float64 or not table.is_contiguous() or not table.is_cuda or table.dim() < 2 or table.shape[-1] != cfg.entity_table_width:
         raise ValueError("table must be a contiguous float64 device tensor [..., n, %d]" % cfg.entity_table_width)
     n = int(table.shape[-2])
     blocks = int(table.numel() // (n * table.shape[-1])) if n else 0
     out_envs = n if out_envs is None else int(out_envs)
-    A, E, F = cfg.num_agents, cfg.num_entities, cfg.node_feats
-    shape = tuple(table.shape[:-2]) + (out_envs, A, E, F)
+    shape = tuple(table.shape[:-2]) + (out_envs,) + tuple(row_shape)
     if out is None:
         out = torch.empty(shape, dtype=torch.float32, device=table.device)
     elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != table.device:
         raise ValueError("out must be a contiguous float32 tensor of shape %s on %s" % (shape, table.device))
     if blocks and n:
-        _lib.check(lib.gmpe_expand_node_obs(C.byref(cfg), table.device.index, table.data_ptr(), blocks, n, out.data_ptr(), out_envs, int(env_offset),
-                                            C.c_void_p(torch.cuda.current_stream(table.device).cuda_stream)), "gmpe_expand_node_obs")
+        _lib.check(getattr(lib, fn)(C.byref(cfg), table.device.index, table.data_ptr(), blocks, n, out.data_ptr(), out_envs, int(env_offset), *extra,
+                                    C.c_void_p(torch.cuda.current_stream(table.device).cuda_stream)), fn)
     return out
+
+
+def expand_node_obs(cfg, table, out=None, out_envs=None, env_offset=0):
+    """Learner side of the compact gather: float64 entity tables [..., n, W] (device tensor, contiguous; leading dims = blocks such as the T+1 slots of a rollout) ->
+    node_obs float32 [..., out_envs, A, E, F], rows of the table's n envs written at env_offset .. env_offset + n of every block (default: out_envs = n). The rows are
+    bit-identical to the engine's own node_obs (same arithmetic, gmpe_step.hip k_node_expand). No handle needed: the learner rank may own no envs."""
+    return _expand("gmpe_expand_node_obs", cfg, table, out, out_envs, env_offset, (cfg.num_agents, cfg.num_entities, cfg.node_feats))
 
 
 def expand_adj(cfg, table, copies=1, out=None, out_envs=None, env_offset=0):
     """float64 entity tables [..., n, W] -> adjacency float32 [..., out_envs, E, E] (copies = 1) or [..., out_envs, copies, E, E] (copies = A: the materialised
     per-agent form), rows of the table's n envs written at env_offset .. env_offset + n of every block. f32(sqrt(dx^2 + dy^2)) with the engine's own expression and
     this step's mask words: bit-identical to the adjacency the engine writes (gmpe_step.hip k_adj_from_table). No handle needed."""
-    lib = _lib.load()
-    if table.dtype != torch.float64 or not table.is_contiguous() or not table.is_cuda or table.dim() < 2 or table.shape[-1] != cfg.entity_table_width:
-        raise ValueError("table must be a contiguous float64 device tensor [..., n, %d]" % cfg.entity_table_width)
-    n = int(table.shape[-2])
-    blocks = int(table.numel() // (n * table.shape[-1])) if n else 0
-    out_envs = n if out_envs is None else int(out_envs)
     E = cfg.num_entities
-    shape = tuple(table.shape[:-2]) + ((out_envs, E, E) if copies == 1 else (out_envs, int(copies), E, E))
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=table.device)
-    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != table.device:
-        raise ValueError("out must be a contiguous float32 tensor of shape %s on %s" % (shape, table.device))
-    if blocks and n:
-        _lib.check(lib.gmpe_expand_adj(C.byref(cfg), table.device.index, table.data_ptr(), blocks, n, out.data_ptr(), out_envs, int(env_offset), int(copies),
-                                       C.c_void_p(torch.cuda.current_stream(table.device).cuda_stream)), "gmpe_expand_adj")
-    return out
+    return _expand("gmpe_expand_adj", cfg, table, out, out_envs, env_offset, (E, E) if copies == 1 else (int(copies), E, E), int(copies))

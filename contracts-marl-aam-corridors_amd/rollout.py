@@ -43,9 +43,8 @@ class DeviceRolloutBuffer(object):
         self.T = int(episode_length)
         self.use_centralized_V = bool(use_centralized_V)
         c, dev = engine.cfg, engine.device
-        self.node_form = getattr(engine, "node_form", "rows")
+        self.node_form, self.adj_form = engine.node_form, engine.adj_form
         storage = dict(storage or {})
-        self.adj_form = getattr(engine, "adj_form", "compact" if engine.adj_compact else "full")
         self._adj = None
         for name, (dt, shape) in storage_spec(c, self.T, engine.adj_compact, self.node_form, with_adj=self.adj_form != "none").items():
             t = storage.pop(name, None)
@@ -64,6 +63,8 @@ class DeviceRolloutBuffer(object):
             self.entity_table = None
         self.info = torch.zeros_like(engine.out.info) if engine.out.info is not None else None
         self.step = 0
+        tu = engine.tuning()                                     # fixed by gmpe_create
+        self._one_launch = bool(tu["roll"]) and not tu["split"]
         self._prepared = {}
 
     @property
@@ -104,24 +105,31 @@ class DeviceRolloutBuffer(object):
         return self.agent_id.reshape(T1, N, 1, A).expand(T1, N, A, A)
 
     # ------------------------------------------------------------------ filling
-    def _bind(self, slot, reward_slot):
+    def _slot(self, t):
+        """Slot t of the arrays as engine outputs — reward / done of slot t - 1, the step that writes slot t; the engine's own buffers at t = 0, where a reset
+        writes none — and the elements between consecutive slots of every array (the rollout kernel's strides; info is one buffer every step overwrites)."""
         e = self.engine
-        o = StepOutputs(obs=self.obs[slot], agent_id=self.agent_id[slot], node_obs=None if self._node_obs is None else self._node_obs[slot],
-                        entity_table=None if self.entity_table is None else self.entity_table[slot], adj=None if self._adj is None else self._adj[slot],
-                        reward=self.rewards[reward_slot].view(e.N, e.A) if reward_slot is not None else e.out.reward,
-                        done=self.dones[reward_slot] if reward_slot is not None else e.out.done, info=self.info)
-        e.rebind(o)
+        arrays = dict(obs=self.obs, agent_id=self.agent_id, node_obs=self._node_obs, entity_table=self.entity_table, adj=self._adj)
+        lagged = dict(reward=self.rewards.view(self.T, e.N, e.A), done=self.dones)
+        o = {k: None if v is None else v[t] for k, v in arrays.items()}
+        o.update({k: v[t - 1] for k, v in lagged.items()} if t else dict(reward=e.out.reward, done=e.out.done))
+        strides = {k: v.numel() // v.shape[0] for k, v in dict(arrays, **lagged).items() if v is not None}
+        strides["masks"] = e.N * e.A
+        return StepOutputs(info=self.info, **o), strides
+
+    def _bind(self, t):
+        self.engine.rebind(self._slot(t)[0])
 
     def warmup(self):
         """GMPERunner.warmup (graph_mpe_runner.py:213-238): reset outputs go to slot 0."""
-        self._bind(0, None)
+        self._bind(0)
         self.engine.reset()
         self.step = 0
 
     def insert_step(self, action_idx):
         """One env step written straight into slot step+1 (+ masks), GraphReplayBuffer.insert semantics."""
         t = self.step
-        self._bind(t + 1, t)
+        self._bind(t + 1)
         self.engine.step(action_idx)
         # masks[dones] = 0; active_masks[dones] = 0 except where the whole env is done — one small kernel instead of eight torch ops
         self.engine.masks_from_dones(self.dones[t], self.masks[t + 1], self.active_masks[t + 1])
@@ -155,39 +163,25 @@ class DeviceRolloutBuffer(object):
         step+k+1 of every array in place, masks / active_masks included (gmpe_rollout_steps). Same results as `num_steps`
         insert_step calls. Falls back to that loop on the split big-E path."""
         K = self.T - self.step if num_steps is None else int(num_steps)
-        e = self.engine
-        if e.tuning()["split"] or not e.tuning()["roll"]:
+        e, a = self.engine, action_sets
+        if not self._one_launch:
             for k in range(K):
-                self.insert_step(action_sets[k % action_sets.shape[0]])
+                self.insert_step(a[k % a.shape[0]])
             return e.out
-        NA = e.N * e.A
-        key = (action_sets.data_ptr(), int(action_sets.shape[0]), K, self.step)
-        launch = self._prepared.get(key) if hasattr(e, "prepare_rollout") else None
-        if launch is not None:                                   # the same rollout as an earlier call: one C call, no views / structs rebuilt (engine.prepare_rollout)
-            launch[0]()
-            last = (self.step + K - 1) % self.T
-            self._bind(last + 1, last)
-            self.step = (self.step + K) % self.T
-            return e.out
-        slot0 = StepOutputs(obs=self.obs[1], agent_id=self.agent_id[1], node_obs=None if self._node_obs is None else self._node_obs[1],
-                            entity_table=None if self.entity_table is None else self.entity_table[1], adj=None if self._adj is None else self._adj[1],
-                            reward=self.rewards[0].view(e.N, e.A), done=self.dones[0], info=self.info)
-        strides = dict(obs=self.obs[0].numel(), agent_id=NA, node_obs=0 if self._node_obs is None else self._node_obs[0].numel(),
-                       entity_table=0 if self.entity_table is None else self.entity_table[0].numel(), adj=0 if self._adj is None else self._adj[0].numel(),
-                       reward=NA, done=NA, info=0, masks=NA)
-        if hasattr(e, "prepare_rollout"):
-            launch = e.prepare_rollout(action_sets, K, slot0=slot0, num_slots=self.T, first_slot=self.step, strides=strides,
+        # the same rollout as an earlier call: one C call, no views / structs rebuilt (engine.prepare_rollout). Another view of the same address is another key,
+        # prepared (and checked) again.
+        key = (a.data_ptr(), a.device, a.dtype, a.shape, a.stride(), K, self.step)
+        hit = self._prepared.get(key)
+        if hit is None:
+            slot0, strides = self._slot(1)
+            launch = e.prepare_rollout(a, K, slot0=slot0, num_slots=self.T, first_slot=self.step, strides=strides,
                                        masks=self.masks[1], active_masks=self.active_masks[1])
             if len(self._prepared) >= 8:
                 self._prepared.clear()
-            self._prepared[key] = (launch, action_sets)         # keeps the action tensor alive: its address is part of the key
-            launch()
-        else:
-            e.rollout(action_sets, K, slot0=slot0, num_slots=self.T, first_slot=self.step, strides=strides,
-                      masks=self.masks[1], active_masks=self.active_masks[1])
+            hit = self._prepared[key] = (launch, a)             # keeps the action tensor alive: its address is part of the key
+        hit[0]()
         # the engine's "current outputs" are the last slot written, as after insert_step
-        last = (self.step + K - 1) % self.T
-        self._bind(last + 1, last)
+        self._bind((self.step + K - 1) % self.T + 1)
         self.step = (self.step + K) % self.T
         return e.out
 

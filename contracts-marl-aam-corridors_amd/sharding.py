@@ -15,6 +15,7 @@ Two slabs alternate so that the gather of step k runs on RCCL's stream while ste
 """
 import torch
 
+from . import engine as _engine
 from .engine import StepOutputs
 
 
@@ -61,33 +62,63 @@ def unpack_gathered(gathered, world, n_envs, A, E, D, F):
     return out
 
 
-class RolloutGather(object):
+class _TwoSlabs(object):
+    """What RolloutGather and ShardedRolloutCollector share: the same number of envs on every rank (all_gather_into_tensor / gather need one slab size), two byte
+    slabs that alternate — the collective of one runs on RCCL's stream while the other is filled — and the gather of a slab to the rank `dst`. `gathered[b]`
+    (uint8 [world, slab_bytes]) exists on the ranks that receive: `dst`, or every rank when `everyone`."""
+
+    def __init__(self, engine, world, rank, group, dst, slab_bytes, everyone=False):
+        import torch.distributed as dist
+        self.dist, self.group, self.dst = dist, group, int(dst)
+        self.engine, self.world = engine, int(world)
+        self.rank = dist.get_rank(group) if rank is None else int(rank)
+        dev = engine.device
+        n = torch.tensor([engine.cfg.num_envs], dtype=torch.int64, device=dev if dist.get_backend(group) == "nccl" else "cpu")
+        lo, hi = n.clone(), n.clone()
+        dist.all_reduce(lo, op=dist.ReduceOp.MIN, group=group); dist.all_reduce(hi, op=dist.ReduceOp.MAX, group=group)
+        if int(lo.item()) != int(hi.item()):
+            raise ValueError("%s: every rank must hold the same number of envs (got %d..%d)" % (type(self).__name__, int(lo.item()), int(hi.item())))
+        self.slab_bytes = slab_bytes
+        self.slabs = [torch.zeros(slab_bytes, dtype=torch.uint8, device=dev) for _ in range(2)]
+        root = everyone or self.rank == self.dst
+        self.gathered = [torch.zeros((self.world, slab_bytes), dtype=torch.uint8, device=dev) if root else None for _ in range(2)]
+        self._flip = 0
+        self._work = [None, None]
+
+    def _next(self):
+        """Index of the slab to fill next, once the collective still in flight on it has finished."""
+        b = self._flip
+        self._flip ^= 1
+        self.wait(b)
+        return b
+
+    def _issue(self, b):
+        d, g = self.dist, self.group
+        dst_global = self.dst if g is None else d.get_global_rank(g, self.dst)
+        lst = list(self.gathered[b].unbind(0)) if self.rank == self.dst else None
+        return d.gather(self.slabs[b], lst, dst=dst_global, group=g, async_op=True)
+
+    def wait(self, b):
+        if self._work[b] is not None:
+            self._work[b].wait(); self._work[b] = None
+        return self.gathered[b]
+
+
+class RolloutGather(_TwoSlabs):
     """step + gather of the compact slab to the learner rank `dst` (mode="gather", default) or to every rank
     (mode="all_gather"). Every rank must hold the same number of envs (checked at construction). The engine must write the
     compact adjacency (`GmpeEngine(..., adj_compact=True)`): the [N,A,E,E] form is a broadcast view the learner makes for free."""
 
     def __init__(self, engine, world, rank=None, group=None, dst=0, mode="gather"):
-        import torch.distributed as dist
         if mode not in ("gather", "all_gather"):
             raise ValueError("mode must be 'gather' or 'all_gather'")
         if not engine.adj_compact:
             raise ValueError("RolloutGather needs an engine created with adj_compact=True (one ExE matrix per env is shipped)")
-        self.dist, self.group, self.mode, self.dst = dist, group, mode, int(dst)
-        self.engine, self.world = engine, int(world)
-        self.rank = dist.get_rank(group) if rank is None else int(rank)
+        self.mode = mode
         c = engine.cfg
         self.dims = (c.num_envs, c.num_agents, c.num_entities, c.obs_dim, c.node_feats)
-        self.layout, self.slab_bytes = slab_layout(*self.dims)
-        dev = engine.device
-        # equal shard sizes: all_gather_into_tensor / gather need one slab size
-        n = torch.tensor([c.num_envs], dtype=torch.int64, device=dev if dist.get_backend(group) == "nccl" else "cpu")
-        lo, hi = n.clone(), n.clone()
-        dist.all_reduce(lo, op=dist.ReduceOp.MIN, group=group); dist.all_reduce(hi, op=dist.ReduceOp.MAX, group=group)
-        if int(lo.item()) != int(hi.item()):
-            raise ValueError("RolloutGather: every rank must hold the same number of envs (got %d..%d)" % (int(lo.item()), int(hi.item())))
-        self.slabs = [torch.zeros(self.slab_bytes, dtype=torch.uint8, device=dev) for _ in range(2)]
-        root = self.mode == "all_gather" or self.rank == self.dst
-        self.gathered = [torch.zeros((self.world, self.slab_bytes), dtype=torch.uint8, device=dev) if root else None for _ in range(2)]
+        self.layout, slab_bytes = slab_layout(*self.dims)
+        _TwoSlabs.__init__(self, engine, world, rank, group, dst, slab_bytes, everyone=mode == "all_gather")
         self._outs = []
         for s in self.slabs:
             v = slab_views(s, self.layout, *self.dims)
@@ -96,35 +127,23 @@ class RolloutGather(object):
             for k in _F32 + ("done",):
                 assert getattr(o, k).numel() == getattr(engine.out, k).numel(), k      # layout vs the engine's real shapes
             self._outs.append(o)
-        self._flip = 0
-        self._work = [None, None]
 
     def _issue(self, b):
         d, g = self.dist, self.group
-        if self.mode == "all_gather":
-            if d.get_backend(g) == "nccl":                       # RCCL over xGMI on the GPU node
-                return d.all_gather_into_tensor(self.gathered[b].view(-1), self.slabs[b], group=g, async_op=True)
-            return d.all_gather(list(self.gathered[b].unbind(0)), self.slabs[b], group=g, async_op=True)   # gloo (CPU rehearsal / tests)
-        dst_global = self.dst if g is None else d.get_global_rank(g, self.dst)
-        lst = list(self.gathered[b].unbind(0)) if self.rank == self.dst else None
-        return d.gather(self.slabs[b], lst, dst=dst_global, group=g, async_op=True)
+        if self.mode == "gather":
+            return _TwoSlabs._issue(self, b)
+        if d.get_backend(g) == "nccl":                           # RCCL over xGMI on the GPU node
+            return d.all_gather_into_tensor(self.gathered[b].view(-1), self.slabs[b], group=g, async_op=True)
+        return d.all_gather(list(self.gathered[b].unbind(0)), self.slabs[b], group=g, async_op=True)   # gloo (CPU rehearsal / tests)
 
     def step_and_gather_async(self, action_idx):
         """Step into the next slab and start its gather; returns the buffer index. The previous gather on that slab is waited for
         first (depth-2 pipeline: the gather of step k overlaps the computation of step k+1)."""
-        b = self._flip
-        self._flip ^= 1
-        if self._work[b] is not None:
-            self._work[b].wait(); self._work[b] = None
+        b = self._next()
         self.engine.rebind(self._outs[b])
         self.engine.step(action_idx)
         self._work[b] = self._issue(b)
         return b
-
-    def wait(self, b):
-        if self._work[b] is not None:
-            self._work[b].wait(); self._work[b] = None
-        return self.gathered[b]
 
     def step_and_gather(self, action_idx):
         """Blocking form: -> gathered uint8 [world, slab_bytes] on the learner rank (None elsewhere in mode="gather")."""
@@ -183,7 +202,7 @@ def rollout_bytes_per_env_step(cfg, episode_length=25, form="compact"):
     return (4 * A * D + 8 * W + (4 * E * E if form == "compact" else 0) + 8 * A) * (T + 1) / T + 4 * A + A
 
 
-class ShardedRolloutCollector(object):
+class ShardedRolloutCollector(_TwoSlabs):
     """The runner's collect loop (graph_mpe_runner.py:57-103) on every rank's env shard + ONE collective per T-step rollout that moves the rank's rollout slab to
     the learner rank — what replaces GraphSubprocVecEnv.step_wait's per-step `remote.recv()` loop (env_wrappers.py:996-1004) for a GraphReplayBuffer-shaped consumer
     (graph_buffer.py:168-251).
@@ -197,48 +216,26 @@ class ShardedRolloutCollector(object):
     Every rank must hold the same number of envs. The engine must be created with adj_compact=True, node_form="table"."""
 
     def __init__(self, engine, episode_length, world, rank=None, group=None, dst=0, expand=None, expand_adj=None):
-        import torch.distributed as dist
         from .rollout import DeviceRolloutBuffer
-        if not engine.adj_compact or getattr(engine, "node_form", "rows") != "table":
+        if not engine.adj_compact or engine.node_form != "table":
             raise ValueError("ShardedRolloutCollector needs an engine created with adj_compact=True, node_form='table' (it ships one ExE matrix and the entity table per env-step)")
-        self.dist, self.group, self.dst = dist, group, int(dst)
-        self.engine, self.world, self.T = engine, int(world), int(episode_length)
-        self.rank = dist.get_rank(group) if rank is None else int(rank)
-        self.cfg = engine.cfg
-        self.with_adj = getattr(engine, "adj_form", "compact") != "none"
-        self.layout, self.slab_bytes = rollout_slab_layout(self.cfg, self.T, self.with_adj)
-        dev = engine.device
-        n = torch.tensor([self.cfg.num_envs], dtype=torch.int64, device=dev if dist.get_backend(group) == "nccl" else "cpu")
-        lo, hi = n.clone(), n.clone()
-        dist.all_reduce(lo, op=dist.ReduceOp.MIN, group=group); dist.all_reduce(hi, op=dist.ReduceOp.MAX, group=group)
-        if int(lo.item()) != int(hi.item()):
-            raise ValueError("ShardedRolloutCollector: every rank must hold the same number of envs (got %d..%d)" % (int(lo.item()), int(hi.item())))
-        self.slabs = [torch.zeros(self.slab_bytes, dtype=torch.uint8, device=dev) for _ in range(2)]
+        self.T, self.cfg = int(episode_length), engine.cfg
+        self.with_adj = engine.adj_form != "none"
+        self.layout, slab_bytes = rollout_slab_layout(self.cfg, self.T, self.with_adj)
+        _TwoSlabs.__init__(self, engine, world, rank, group, dst, slab_bytes)
         self.bufs = [DeviceRolloutBuffer(engine, self.T, storage=rollout_slab_views(s, self.layout)) for s in self.slabs]
-        self.gathered = [torch.zeros((self.world, self.slab_bytes), dtype=torch.uint8, device=dev) if self.rank == self.dst else None for _ in range(2)]
-        self._work = [None, None]
-        self._flip = 0
         self._last = None
-        self._expand, self._expand_adj = expand, expand_adj
+        self._expand, self._expand_adj = expand or _engine.expand_node_obs, expand_adj or _engine.expand_adj
 
     def warmup(self):
         """GMPERunner.warmup (graph_mpe_runner.py:213-238): the reset observations go to slot 0 of the first rollout."""
         self.bufs[0].warmup()
         self._flip, self._last = 0, None
 
-    def _issue(self, b):
-        d, g = self.dist, self.group
-        dst_global = self.dst if g is None else d.get_global_rank(g, self.dst)
-        lst = list(self.gathered[b].unbind(0)) if self.rank == self.dst else None
-        return d.gather(self.slabs[b], lst, dst=dst_global, group=g, async_op=True)
-
     def collect_and_gather_async(self, action_sets):
         """One WHOLE T-step rollout into the next slab (ONE launch; step k reads action_sets[k % S]), then start its gather; returns the slab index. The previous gather
         of that slab is waited for first. (Partial rollouts have no place here: the slab that travels is a complete [T+1, N, ...] rollout.)"""
-        b = self._flip
-        self._flip ^= 1
-        if self._work[b] is not None:
-            self._work[b].wait(); self._work[b] = None
+        b = self._next()
         if self._last is not None and self._last != b:
             self.bufs[b].carry_from(self.bufs[self._last])          # after_update across the two slabs: slot 0 <- the previous rollout's last slot
         elif self._last == b:
@@ -247,11 +244,6 @@ class ShardedRolloutCollector(object):
         self._last = b
         self._work[b] = self._issue(b)
         return b
-
-    def wait(self, b):
-        if self._work[b] is not None:
-            self._work[b].wait(); self._work[b] = None
-        return self.gathered[b]
 
     def unpack(self, b, out=None):
         """Learner rank: global arrays of rollout slab `b` in env order (rank-major) — obs [T+1, W*N, A, D], node_obs [T+1, W*N, A, E, F] (expanded from every rank's
@@ -282,18 +274,12 @@ class ShardedRolloutCollector(object):
             dn[:, r * N:(r + 1) * N].copy_(per[r]["dones"] != 0)
         T1 = self.T + 1
         node = dest("node_obs", torch.float32, (T1, Wd * N, A, E, c.node_feats))
-        expand = self._expand
-        if expand is None:
-            from .engine import expand_node_obs as expand
         for r in range(Wd):
-            expand(c, per[r]["entity_table"].contiguous(), out=node, out_envs=Wd * N, env_offset=r * N)
+            self._expand(c, per[r]["entity_table"].contiguous(), out=node, out_envs=Wd * N, env_offset=r * N)
         if not self.with_adj:                                        # the adjacency was not shipped: rebuild it from the tables (bit-identical, gmpe_expand_adj)
             adj = dest("adj", torch.float32, (T1, Wd * N, E, E))
-            expand_a = self._expand_adj
-            if expand_a is None:
-                from .engine import expand_adj as expand_a
             for r in range(Wd):
-                expand_a(c, per[r]["entity_table"].contiguous(), out=adj, out_envs=Wd * N, env_offset=r * N)
+                self._expand_adj(c, per[r]["entity_table"].contiguous(), out=adj, out_envs=Wd * N, env_offset=r * N)
         if "agent_id" not in out:
             out["agent_id"] = torch.arange(A, dtype=torch.int32, device=dev).view(1, 1, A, 1).expand(T1, Wd * N, A, 1)
         return out

@@ -383,6 +383,68 @@ def test_prepared_rollout_is_the_same_launch_and_refuses_a_closed_engine():
         launch()
 
 
+def test_prepared_rollout_keeps_the_outputs_it_writes_alive_across_a_rebind():
+    """prepare_rollout(slot0=None) writes the outputs the engine was bound to at prepare time and owns them: after a rebind to other buffers, with every other
+    reference to the old outputs dropped, the launch still writes them — not memory the allocator has handed out again, not the buffers bound now."""
+    import gc
+    import weakref
+    import torch
+    from gmpe.engine import StepOutputs
+    cfg = gmpe.make_config(scenario_name="navigation_graph", num_envs=33, num_agents=10, world_size=4.0, episode_length=6, seed=5)
+    e1, e2 = _engine(cfg), _engine(cfg)
+    e1.reset(); e2.reset()
+    g = torch.Generator(device="cuda"); g.manual_seed(3)
+    acts = torch.randint(0, cfg.n_actions, (4, 33, 10), generator=g, device="cuda", dtype=torch.int32)
+    launch = e2.prepare_rollout(acts, 9)
+    old = {k: weakref.ref(getattr(e2.out, k)) for k in OUT_KEYS}
+    like = {k: (tuple(getattr(e2.out, k).shape), getattr(e2.out, k).dtype) for k in OUT_KEYS}
+    bound = StepOutputs(**{k: torch.full(s, 7, dtype=dt, device="cuda") for k, (s, dt) in like.items()})
+    e2.rebind(bound)
+    gc.collect()
+    fresh = {k: torch.zeros(s, dtype=dt, device="cuda") for k, (s, dt) in like.items()}
+    o1 = e1.rollout(acts, 9); launch()
+    torch.cuda.synchronize()
+    for k in OUT_KEYS:
+        t = old[k]()
+        assert t is not None, k
+        assert torch.equal(t, getattr(o1, k)), k
+        assert not fresh[k].any(), k
+        assert (getattr(bound, k) == 7).all(), k
+    _compare_state(e1, e2, "prepared launch after rebind")
+
+
+def test_prepared_rollout_refuses_a_bad_slot0_before_launching():
+    """A slot0 of the wrong dtype, or one whose storage holds fewer than num_slots slots (outputs or masks), raises ValueError in prepare_rollout and rollout alike,
+    and nothing is launched: slots, engine outputs and state stay as they were."""
+    import torch
+    from gmpe.engine import StepOutputs
+    cfg = gmpe.make_config(scenario_name="navigation_graph", num_envs=21, num_agents=6, world_size=3.0, episode_length=6, seed=9)
+    eng = _engine(cfg)
+    eng.reset()
+    N, A, T = 21, 6, 5
+    acts = torch.zeros((3, N, A), dtype=torch.int32, device="cuda")
+    st = _slots(eng, T)
+    strides = {k: st[k][0].numel() for k in OUT_KEYS}
+    strides["masks"] = N * A
+    good = {k: st[k][0] for k in OUT_KEYS}
+    bad = [(StepOutputs(**dict(good, obs=st["obs"][0].double())), None),                             # wrong dtype
+           (StepOutputs(**dict(good, reward=torch.zeros((T - 1, N, A), device="cuda")[0])), None),    # T - 1 slots of storage
+           (StepOutputs(**good), torch.zeros((T - 1, N, A), device="cuda"))]                          # masks: T - 1 slots
+    outs = {k: getattr(eng.out, k).clone() for k in OUT_KEYS}
+    state = eng.get_state()
+    for slot0, masks in bad:
+        with pytest.raises(ValueError):
+            eng.prepare_rollout(acts, 4, slot0=slot0, num_slots=T, strides=strides, masks=masks)
+        with pytest.raises(ValueError):
+            eng.rollout(acts, 4, slot0=slot0, num_slots=T, strides=strides, masks=masks)
+    torch.cuda.synchronize()
+    for k in OUT_KEYS:
+        assert not st[k].any(), k
+        assert torch.equal(getattr(eng.out, k), outs[k]), k
+    for f, v in eng.get_state().items():
+        np.testing.assert_array_equal(v, state[f], err_msg=f)
+
+
 @pytest.mark.parametrize("scen,ws,tape_len,expect", [("navigation_graph", 2.5, 0, "clean"), (JULY, 3.0, 0, "clean"), ("navigation_graph", 2.0, 0, "forced"), (JULY, 2.5, 0, "forced"),
                                                      ("navigation_graph", 4.0, 170, "tape"), (JULY, 4.0, 150, "tape")],
                          ids=["nav-ws2.5", "july-ws3", "nav-ws2-forced", "july-ws2.5-forced", "nav-tape-runs-out", "july-tape-runs-out"])

@@ -262,6 +262,66 @@ class _OracleBackedEngine(object):
         masks.copy_((~d).float().view(masks.shape)); active_masks.copy_((~(d & ~alld)).float().view(active_masks.shape))
 
 
+class _PreparingEngine(_OracleBackedEngine):
+    """Stand-in whose tuning takes DeviceRolloutBuffer.collect's one-launch path: records every prepare_rollout call and counts tuning() calls and launches."""
+
+    def __init__(self, cfg, node_form, adj_form):
+        _OracleBackedEngine.__init__(self, cfg, node_form=node_form, do_reset=False, adj_form=adj_form)
+        self.n_tuning, self.prepared = 0, []
+
+    def tuning(self):
+        self.n_tuning += 1
+        return {"split": 0, "roll": 1}
+
+    def prepare_rollout(self, action_sets, num_steps, slot0=None, num_slots=1, first_slot=0, strides=None, masks=None, active_masks=None):
+        call = dict(a=action_sets, K=num_steps, slot0=slot0, num_slots=num_slots, first_slot=first_slot, strides=strides, masks=masks, active_masks=active_masks, launches=0)
+        self.prepared.append(call)
+
+        def launch():
+            call["launches"] += 1
+        return launch
+
+
+@pytest.mark.parametrize("node_form,adj_form", [("rows", None), ("table", "none")])
+def test_collect_reuses_prepared_launches_per_view_and_binds_storage_spec_slots(node_form, adj_form):
+    """DeviceRolloutBuffer.collect: tuning() read once per buffer; the same action tensor reuses its prepared launch; another view of the same address (dtype,
+    shape) is prepared, and so checked, again; slot0 / strides / masks handed to prepare_rollout are slot 1 (rewards / dones slot 0) of the storage_spec arrays."""
+    import torch
+    from gmpe.rollout import DeviceRolloutBuffer, storage_spec
+    N, A, T = 3, 2, 5
+    cfg = gmpe.make_config(num_envs=N, num_agents=A, episode_length=4, seed=1)
+    eng = _PreparingEngine(cfg, node_form, adj_form)
+    buf = DeviceRolloutBuffer(eng, T)
+    assert eng.n_tuning == 1
+    acts = torch.zeros((T, N, A), dtype=torch.int32)
+    buf.collect(acts)
+    buf.collect(acts)
+    assert len(eng.prepared) == 1 and eng.prepared[0]["launches"] == 2 and eng.n_tuning == 1 and buf.step == 0
+    for view in (acts.view(torch.float32), acts[:2], acts.view(T, N * A)):
+        buf.collect(view)
+        assert eng.prepared[-1]["a"] is view and eng.prepared[-1]["launches"] == 1
+    assert len(eng.prepared) == 4 and eng.n_tuning == 1
+    spec = storage_spec(cfg, T, eng.adj_compact, node_form, with_adj=adj_form != "none")
+    names = dict(obs="obs", agent_id="agent_id", node_obs="node_obs", entity_table="entity_table", adj="_adj", reward="rewards", done="dones")
+    call = eng.prepared[0]
+    expect = {k: int(np.prod(spec[s][1][1:])) for k, s in names.items() if s in spec}
+    expect["masks"] = int(np.prod(spec["masks"][1][1:]))
+    assert call["strides"] == expect
+    assert (call["K"], call["num_slots"], call["first_slot"]) == (T, T, 0)
+    for k, s in names.items():
+        v = getattr(call["slot0"], k)
+        if s not in spec:
+            assert v is None, k
+            continue
+        dt, shape = spec[s]
+        arr = getattr(buf, s if s != "node_obs" else "_node_obs")
+        slot = 0 if k in ("reward", "done") else 1
+        assert v.dtype == dt and v.numel() == expect[k] and v.data_ptr() == arr.data_ptr() + slot * expect[k] * v.element_size(), k
+    assert tuple(call["slot0"].reward.shape) == (N, A) and call["slot0"].info is None
+    for m in ("masks", "active_masks"):
+        assert call[m].data_ptr() == getattr(buf, m).data_ptr() + expect["masks"] * 4, m
+
+
 def _gather_worker(rank, world, port, q, scen, mode):
     import torch
     import torch.distributed as dist
