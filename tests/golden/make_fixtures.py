@@ -12,6 +12,7 @@ Vectors (data only — inputs and the reference's outputs):
                              reference's np.random draws.
   rk45_airtaxi.npz           AirTaxiXYState.update_state (core.py:300-316, scipy RK45) on random
                              states x all 25 controls.
+  rk45_unicycle.npz          the same for UnicycleVehicleXYState.update_state (core.py:80-141).
   force_classic.npz          onpolicy/envs/mpe/core.py World.step (live force path) on random worlds.
   force_di.npz               multiagent/core.py dead-code force methods called in the order
                              calculate_distances -> apply_action_force -> apply_environment_force ->
@@ -160,10 +161,14 @@ def july_rollout(num_agents, seed, T, world_size=4.0, episode_length=25, guided=
     return out
 
 
-def rk45_fixture(n=40, seed=5):
+def rk45_fixture(n=40, seed=5, vehicle="AirTaxi"):
+    """`vehicle` 'AirTaxi': AirTaxiXYState (core.py:300-316); 'Unicycle': UnicycleVehicleXYState (core.py:80-141) with UnicycleVehicleConfig's
+    constants and control range. Controls as MultiAgentEnv._set_action makes them (environment.py:424-460: linspace tables x sensitivity 5)."""
     H.install_stubs()
-    from multiagent.core import AirTaxiXYState
-    from multiagent.config import AirTaxiConfig as C
+    import multiagent.config as mc
+    import multiagent.core as core
+    AirTaxiXYState = getattr(core, {"AirTaxi": "AirTaxiXYState", "Unicycle": "UnicycleVehicleXYState"}[vehicle])
+    C = getattr(mc, {"AirTaxi": "AirTaxiConfig", "Unicycle": "UnicycleVehicleConfig"}[vehicle])
     rng = np.random.RandomState(seed)
     w_opt = np.linspace(-C.ANGULAR_RATE_MAX, C.ANGULAR_RATE_MAX, 5)
     a_opt = np.linspace(C.ACCEL_MIN, C.ACCEL_MAX, 5)
@@ -379,7 +384,7 @@ def main_global(scenario_name="nav_metered_one_goal_graph_rotate_tube_july", pre
               "steps with a done agent", int(d["st_status"].any(axis=1).sum()), "phase_reached", d["st_phase_reached"].max(axis=0))
 
 
-def main_formation():
+def main_formation(only=None):
     # formation_type 'line' / 'circle' (…_july.py:492-495 -> custom_scenarios/utils.py:77-130, 231-267; the same call sites in the rot_inv family's
     # files): DISTINCT landmark positions, so the landmark x landmark adjacency block, per-agent goals, landmark masks on distinct rows and
     # info_callback's nearest-landmark logic are pinned against the reference in their general form ('point' makes every landmark coincide).
@@ -390,7 +395,9 @@ def main_formation():
             ("nav_graph_metered_single_corridor_rot_inv", "rotinv", "line", 4, 80, 130, 2.4, 60),
             ("nav_graph_metered_single_corridor_rot_inv", "rotinv", "circle", 6, 84, 140, 3.0, 70),
             ("three_phase_graph", "threephase", "line", 3, 90, 130, 2.0, 60), ("three_phase_graph", "threephase", "circle", 5, 94, 140, 3.0, 70),
-            ("two_phase_graph", "twophase", "line", 3, 100, 90, 2.0, 45)]
+            ("two_phase_graph", "twophase", "line", 3, 100, 90, 2.0, 45), ("two_phase_graph", "twophase", "circle", 3, 100, 90, 2.0, 45)]
+    if only:
+        jobs = [j for j in jobs if j[1] + j[2] in only]
     for name, prefix, form, A, seed, T, ws, el in jobs:
         seed -= 1
         while True:                                   # the reference crashes at construction for some seeds (see main_rot)
@@ -409,13 +416,20 @@ def main_formation():
 
 def main_blocks():
     np.savez_compressed(os.path.join(HERE, "rk45_airtaxi.npz"), **rk45_fixture())
+    main_unicycle()
     np.savez_compressed(os.path.join(HERE, "force_classic.npz"), **force_classic_fixture())
     np.savez_compressed(os.path.join(HERE, "force_di.npz"), **force_di_fixture())
     np.savez_compressed(os.path.join(HERE, "misc.npz"), **misc_fixture())
 
 
+def main_unicycle():
+    # the unicycle integrator as a block: a rollout cannot be captured, make_world of every tube scenario reads
+    # UnicycleVehicleConfig.COORDINATION_RANGE, which that class does not define (AttributeError)
+    np.savez_compressed(os.path.join(HERE, "rk45_unicycle.npz"), **rk45_fixture(vehicle="Unicycle"))
+
+
 def main(which):
-    """`python make_fixtures.py [july|rot|phase|blocks ...]` regenerates the named groups (default: all)."""
+    """`python make_fixtures.py [july|rot|phase|blocks|unicycle|twophasecircle ...]` regenerates the named groups (default: all)."""
     H.selfcheck_uniform_patch()
     which = which or ["july", "global", "globalrot", "rot", "phase", "formation", "blocks"]
     if "july" in which:
@@ -432,6 +446,10 @@ def main(which):
         main_rot("three_phase_graph", "threephase", seed=40, phase_col=14)
     if "formation" in which:
         main_formation()
+    elif any(w.endswith(("line", "circle")) for w in which):      # one formation fixture, e.g. `twophasecircle`
+        main_formation([w for w in which if w.endswith(("line", "circle"))])
+    if "unicycle" in which and "blocks" not in which:
+        main_unicycle()
     if "blocks" in which:
         main_blocks()
     print("done")

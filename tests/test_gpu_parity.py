@@ -12,12 +12,13 @@ import pytest
 import gmpe
 from gmpe.config import INFO_KEYS
 import oracle_lib as ol
+import replay_lib
 
 pytestmark = pytest.mark.gpu
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 JULY = [q for pre in ("july", "julyglobal", "rotinv", "twophase", "threephase", "rotinvglobal", "twophaseglobal",
-                       "julyline", "julycircle", "rotinvline", "rotinvcircle", "twophaseline", "threephaseline", "threephasecircle") for q in sorted(glob.glob(os.path.join(GOLD, pre + "_A*_s*.npz")))]
+                       "julyline", "julycircle", "rotinvline", "rotinvcircle", "twophaseline", "twophasecircle", "threephaseline", "threephasecircle") for q in sorted(glob.glob(os.path.join(GOLD, pre + "_A*_s*.npz")))]
 ROT = "nav_graph_metered_single_corridor_rot_inv"
 ROTFAM = [ROT, "two_phase_graph", "three_phase_graph"]
 TOL = 1e-5
@@ -64,8 +65,9 @@ def test_golden_replay_on_gpu(path):
     np.testing.assert_allclose(_np(o.node_obs)[0], d["reset0_node"], rtol=0, atol=TOL)
     np.testing.assert_allclose(_np(o.adj)[0], np.broadcast_to(d["reset0_adj"], (A, E, E)), rtol=0, atol=TOL)
     np.testing.assert_array_equal(_np(o.agent_id)[0], d["reset0_id"])
+    replay_lib.check_placement(eng, d, "reset0_", None, [0], "reset0")
     guided = bool(d["guided"])
-    n_inj = 0
+    n_inj = n_reset = 0
 
     def inject():
         nonlocal n_inj
@@ -94,9 +96,15 @@ def test_golden_replay_on_gpu(path):
             np.testing.assert_array_equal(eng.get("status")[0].astype(bool), d["st_status"][t])
             np.testing.assert_array_equal(eng.get("prev_phase")[0], d["st_prev_phase"][t])
             np.testing.assert_array_equal(eng.get("phase_reached")[0], d["st_phase_reached"][t])
-        elif guided:
-            inject()
+        else:
+            # the post-reset state the reference recorded (placement, tube geometry, prev_phase), before any injection
+            replay_lib.check_placement(eng, d, "rs_", n_reset, [0], "reset t=%d" % t)
+            np.testing.assert_array_equal(eng.get("prev_phase")[0], d["rs_prev_phase"][n_reset], err_msg="rs prev_phase t=%d" % t)
+            n_reset += 1
+            if guided:
+                inject()
         assert eng.get("rng_ctr")[0] == d["tape_pos"][t + 1], "draw count t=%d" % t
+    assert n_reset == int(d["did_reset"].sum())
     eng.check_errors()
     eng.close()
 

@@ -587,12 +587,22 @@ def test_oracle_under_sanitizers():
     assert out.stdout.count("checksum") == 5 and "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr
 
 
+_RU = []
+
+
+def _resource_usage():
+    """`make resource-usage`: the compiler's register / scratch report of every kernel instantiation (made once per session)."""
+    if not _RU:
+        out = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "contracts-marl-aam-corridors_amd", "csrc"), "resource-usage"],
+                             capture_output=True, text=True, timeout=600)
+        _RU.append(out.stdout + out.stderr)
+    return _RU[0]
+
+
 def test_kernels_do_not_spill():
     """Every instantiation of the fused kernel must fit the register file (a spill costs 3x on this kernel:
     the inlined per-agent code is large and a non-inlined closure silently moves its state to scratch)."""
-    out = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "contracts-marl-aam-corridors_amd", "csrc"), "resource-usage"],
-                         capture_output=True, text=True, timeout=600)
-    txt = out.stdout + out.stderr
+    txt = _resource_usage()
     names = re.findall(r"Function Name: (\S*k_env\S*)", txt)
     scratch = re.findall(r"Function Name: \S*k_env\S*.*?ScratchSize \[bytes/lane\]: (\d+)", txt, flags=re.S)
     assert len(names) >= 96 and len(scratch) == len(names)      # 6 scenario variants x (3 tile shapes x 3 exact sizes + the steady-state one + 3 rollout ones)
@@ -607,6 +617,37 @@ def test_kernels_do_not_spill():
     allowed = lambda n: (24 if "Li256ELi10ELi2ELi1ELi0E" in n else 16) if re.search(r"ELi10ELi2ELi[01]E", n) else (24 if "Li256ELi10ELi0ELi2E" in n else (12 if "Li256ELi10ELi3ELi1ELi4E" in n else 0))
     bad = [(n, x) for n, x in zip(names, scratch) if int(x) > allowed(n)]
     assert not bad, bad
+
+
+def test_every_instantiation_has_a_variant_row():
+    """Every k_env<BLOCK, AP, SC, FL, GC> in libgmpe.so has a row in tests/test_gpu_reference_variants.py VARIANTS, and every row is run for every
+    scenario variant: the tube scenarios (SC 2..5) replay the reference's own rollouts through it, navigation_graph (SC 0, 1 with walls: no
+    reference rollout exists) is compared with the oracle through it. A new instantiation without a row fails here."""
+    import test_gpu_reference_variants as V
+    inst = sorted({tuple(int(q) for q in m) for m in re.findall(r"k_envILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)E", _resource_usage())})
+    assert len(inst) == 96, len(inst)                       # 6 scenario variants x 16
+    for sc in range(6):
+        rows = sorted((b, ap, fl, gc) for b, ap, sc2, fl, gc in inst if sc2 == sc)
+        assert rows == sorted(V.VARIANTS), (sc, sorted(set(rows) ^ set(V.VARIANTS)))
+    # every row runs for every scenario variant: four tube scenarios against the reference, navigation_graph without and with walls against the oracle
+    assert set(V.SCEN) == set(V.FIXTURES) and len(V.SCEN) == 4
+    assert sorted(bool(kw.get("num_walls")) for kw in V.NAV_SCEN.values()) == [False, True]
+    cases = {(key, i) for _, key, i in V.CASES}
+    assert cases == {(key, i) for _, key, i in V.NAV_CASES} == {(key, i) for key, rs in V.VARIANTS.items() for i in range(len(rs))}
+    assert len(V.CASES) == 4 * len(cases) and len(V.NAV_CASES) == 2 * len(cases)
+    for row, recipes in V.VARIANTS.items():                 # every recipe reaches its row by what the selector reads (gmpe_sc.hip env_kernel)
+        b, ap, fl, gc = row
+        for r in recipes:
+            t, knobs = r["tuning"], r["knobs"]
+            if fl == 2:
+                assert r["path"] in ("rollout", "step_many") and t["block_roll"] == (64 if knobs.get("BLOCK") == 64 else 256) == b
+                assert ap == (10 if (r["fx"] == "A10" and knobs.get("AP") != 0 and b == 256) else 0)
+                assert gc == (t["G_roll"] if ap == 10 and t["G_roll"] in (4, 6) else 0)
+            else:
+                assert r["path"] == "step" and t["block"] == knobs["BLOCK"] == b and t["G"] == knobs["G"]
+                assert ap == t["ap"] == ({"A10": 10, "A3": 3}.get(r["fx"], 0) if knobs.get("AP") != 0 else 0)
+                steady = b == 256 and ap == 10 and t.get("nt", 0) == 0 and t.get("spec", 1) == 1
+                assert fl == (1 if steady else 0) and gc == (4 if fl == 1 and t["G"] == 4 else 0)
 
 
 def test_bench_multi_rank_branch_inits_the_process_group_before_any_gpu_work():
