@@ -16,7 +16,8 @@ SYMBOLS = ["gmpe_abi_version", "gmpe_last_error", "gmpe_obs_dim", "gmpe_node_fea
            "gmpe_timing_enable", "gmpe_timing_read", "gmpe_timing_mark", "gmpe_timing_region_ms",
            "gmpe_rollout_steps", "gmpe_get_tuning", "gmpe_step_many_launches", "gmpe_edges_from_adj_compact",
            "gmpe_set_control_override", "gmpe_field_device_ptr", "gmpe_step_envs", "gmpe_step_many_envs",
-           "gmpe_entity_table_width", "gmpe_expand_node_obs", "gmpe_expand_adj"]
+           "gmpe_entity_table_width", "gmpe_expand_node_obs", "gmpe_expand_adj",
+           "gmpe_returns_workspace_bytes", "gmpe_compute_returns", "gmpe_available_actions_from_dones"]
 
 
 class GmpeOutputs(C.Structure):
@@ -38,6 +39,24 @@ class GmpeTuning(C.Structure):
                 ("roll", C.c_int32), ("ap", C.c_int32), ("lds_bytes", C.c_int32), ("diag_build", C.c_int32),
                 ("G_roll", C.c_int32), ("block_roll", C.c_int32), ("chunks", C.c_int32), ("ahead", C.c_int32), ("xstep", C.c_int32), ("chunks_x", C.c_int32), ("ahead_x", C.c_int32),
                 ("lds_bytes_roll", C.c_int32)]
+
+
+class GmpeReturnsPlan(C.Structure):
+    """gmpe_returns_plan (include/gmpe.h): GraphReplayBuffer.compute_returns + GR_MAPPO.train's advantages, handle-less."""
+    _fields_ = [("num_steps", C.c_int32), ("flags", C.c_int32), ("lanes", C.c_int64), ("stride", C.c_int64),
+                ("gamma", C.c_double), ("gae_lambda", C.c_double),
+                ("rewards", C.c_void_p), ("masks", C.c_void_p), ("bad_masks", C.c_void_p), ("value_preds", C.c_void_p), ("returns", C.c_void_p),
+                ("next_value", C.c_void_p), ("denorm_mean", C.c_void_p), ("denorm_std", C.c_void_p), ("advantages", C.c_void_p),
+                ("active_masks", C.c_void_p), ("normalized", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
+RETURNS_GAE, RETURNS_PROPER_TIME_LIMITS, RETURNS_ADVANTAGES_ONLY = 1, 2, 4
+
+
+class GmpeAvailPlan(C.Structure):
+    """gmpe_avail_plan (include/gmpe.h): the stop-action rows of available_actions from the previous step's dones."""
+    _fields_ = [("dones", C.c_void_p), ("available_actions", C.c_void_p), ("lanes", C.c_int64), ("n_actions", C.c_int32),
+                ("num_positions", C.c_int32), ("first", C.c_int32), ("count", C.c_int32), ("stride_dones", C.c_int64), ("stride_out", C.c_int64)]
 
 
 class GmpeError(RuntimeError):
@@ -88,6 +107,9 @@ def load():
     lib.gmpe_entity_table_width.argtypes = [C.POINTER(GmpeConfig)]
     lib.gmpe_expand_node_obs.argtypes = [C.POINTER(GmpeConfig), I, P, C.c_int64, C.c_int64, P, C.c_int64, C.c_int64, P]
     lib.gmpe_expand_adj.argtypes = [C.POINTER(GmpeConfig), I, P, C.c_int64, C.c_int64, P, C.c_int64, C.c_int64, C.c_int32, P]
+    lib.gmpe_returns_workspace_bytes.argtypes = [C.c_int64, C.POINTER(C.c_size_t)]
+    lib.gmpe_compute_returns.argtypes = [I, C.POINTER(GmpeReturnsPlan), P]
+    lib.gmpe_available_actions_from_dones.argtypes = [I, C.POINTER(GmpeAvailPlan), P]
     from .config import ABI_VERSION
     if lib.gmpe_abi_version() != ABI_VERSION:
         raise GmpeError("libgmpe.so ABI version mismatch")

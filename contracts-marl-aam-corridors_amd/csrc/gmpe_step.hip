@@ -267,6 +267,8 @@ struct gmpe_handle {
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string& m) { g_err = m; return code; }
+// the other host translation unit (gmpe_returns.hip) reports through the same gmpe_last_error text
+namespace gmpe { int report_error(int code, const std::string& m) { return fail(code, m); } }
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(GMPE_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
 
 // All persistent state lives in ONE slab (256-B aligned sub-arrays): a tile's ~30 state loads then touch a

@@ -420,3 +420,129 @@ def expand_adj(cfg, table, copies=1, out=None, out_envs=None, env_offset=0):
     this step's mask words: bit-identical to the adjacency the engine writes (gmpe_step.hip k_adj_from_table). No handle needed."""
     E = cfg.num_entities
     return _expand("gmpe_expand_adj", cfg, table, out, out_envs, env_offset, (E, E) if copies == 1 else (int(copies), E, E), int(copies))
+
+
+# ---------------------------------------------------------------------- learner side of a rollout (gmpe_returns.hip)
+def _stream_of(device):
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _dev_f32(name, t, shape, device, dtype=torch.float32):
+    """`t` must be a contiguous `dtype` tensor of `shape` on `device`, else ValueError — checked before anything is launched (layout first, then device)."""
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise ValueError("%s must be a contiguous %s tensor of shape %s" % (name, dtype, tuple(shape)))
+    if t.device != device:
+        raise ValueError("%s must be on %s (the device of the other arrays)" % (name, device))
+    return t.data_ptr()
+
+
+def _need_cuda(device):
+    if device.type != "cuda":
+        raise ValueError("the arrays must be CUDA (HIP) device tensors: these kernels have no CPU fallback")
+
+
+def returns_workspace_bytes(lanes):
+    """Device scratch (bytes) that compute_returns(..., normalized=...) needs for `lanes` = N*A lanes (gmpe_returns_workspace_bytes)."""
+    n = C.c_size_t()
+    _lib.check(_lib.load().gmpe_returns_workspace_bytes(int(lanes), C.byref(n)), "gmpe_returns_workspace_bytes")
+    return int(n.value)
+
+
+@torch.no_grad()
+def denorm_scalars(value_normalizer, device):
+    """(mean, sqrt(var)) of a ValueNorm (running_mean_var, onpolicy/utils/valuenorm.py:48-55) or a PopArt (debiased_mean_var,
+    onpolicy/algorithms/utils/popart.py:101-106) as float32 [1] tensors on `device`. sqrt is taken where the normaliser keeps its statistics,
+    as its own denormalize does (valuenorm.py:87-99), so x * std + mean has the reference's roundings. No host sync on a device normaliser."""
+    f = getattr(value_normalizer, "running_mean_var", None) or getattr(value_normalizer, "debiased_mean_var", None)
+    if f is None:
+        raise TypeError("value_normalizer must have running_mean_var() (ValueNorm) or debiased_mean_var() (PopArt)")
+    mean, var = f()
+    std = torch.sqrt(var)
+    if mean.numel() != 1 or std.numel() != 1:
+        raise ValueError("the value normaliser must be scalar (input_shape 1, the runner's ValueNorm(1) / PopArt(..., 1))")
+    cvt = lambda t: t.detach().reshape(1).to(device=device, dtype=torch.float32).contiguous()
+    return cvt(mean), cvt(std)
+
+
+def compute_returns(rewards, masks, value_preds, returns, next_value=None, gamma=0.99, gae_lambda=0.95, use_gae=True, use_proper_time_limits=False,
+                    bad_masks=None, denorm=None, advantages=None, active_masks=None, normalized=None, workspace=None, advantages_only=False):
+    """GraphReplayBuffer.compute_returns (onpolicy/utils/graph_buffer.py:285-366) and the head of GR_MAPPO.train (graph_mappo.py:294-304) on the device,
+    on the current stream, bit-identical to the reference's float32 NumPy for returns and raw advantages (gmpe_compute_returns).
+      value_preds, returns, masks, bad_masks, active_masks: float32 [T+1, ...lane dims] (e.g. [T+1, N, A, 1]); rewards, advantages, normalized: [T, ...];
+      next_value: float32 with one value per lane (e.g. [N, A, 1]); denorm: (mean, std) float32 [1] device tensors (denorm_scalars) or None.
+    Side effects as the reference: with use_gae value_preds[T] = next_value, without it returns[T] = next_value. advantages (optional) receives
+    returns[t] - denorm(value_preds[t]); normalized (optional, may be `advantages` itself) receives (adv - mean) / (std + 1e-5) over the entries with
+    active_masks[t] != 0 — which needs `workspace` (uint8, returns_workspace_bytes(lanes) bytes; allocated here when None). advantages_only=True skips
+    the recurrence and takes returns / value_preds as they stand (what train reads). Every argument is checked (ValueError) before the launch."""
+    if not isinstance(value_preds, torch.Tensor) or value_preds.dim() < 1 or value_preds.shape[0] < 2:
+        raise ValueError("value_preds must be a float32 tensor [T+1, ...] with T >= 1")
+    dev = value_preds.device
+    T1 = int(value_preds.shape[0])
+    slot = tuple(value_preds.shape[1:])
+    lanes = int(np.prod(slot, dtype=np.int64))
+    full, half = (T1,) + slot, (T1 - 1,) + slot
+    if lanes < 1:
+        raise ValueError("value_preds has no lanes")
+    ptr = lambda name, t, shape: None if t is None else _dev_f32(name, t, shape, dev)
+    for name, t in (("returns", returns),) + (() if advantages_only else (("rewards", rewards), ("masks", masks), ("next_value", next_value))):
+        if t is None:
+            raise ValueError("%s is required" % name)
+    if use_proper_time_limits and not advantages_only and bad_masks is None:
+        raise ValueError("use_proper_time_limits needs bad_masks")
+    if advantages_only and advantages is None and normalized is None:
+        raise ValueError("advantages_only needs advantages or normalized")
+    if normalized is not None and active_masks is None:
+        raise ValueError("normalized advantages need active_masks")
+    plan = _lib.GmpeReturnsPlan()
+    plan.num_steps, plan.lanes, plan.stride = T1 - 1, lanes, lanes
+    plan.flags = (_lib.RETURNS_GAE if use_gae else 0) | (_lib.RETURNS_PROPER_TIME_LIMITS if use_proper_time_limits else 0) | \
+                 (_lib.RETURNS_ADVANTAGES_ONLY if advantages_only else 0)
+    plan.gamma, plan.gae_lambda = float(gamma), float(gae_lambda)
+    plan.value_preds, plan.returns = ptr("value_preds", value_preds, full), ptr("returns", returns, full)
+    if not advantages_only:
+        plan.rewards, plan.masks = ptr("rewards", rewards, half), ptr("masks", masks, full)
+        if not isinstance(next_value, torch.Tensor) or next_value.numel() != lanes:
+            raise ValueError("next_value must hold one value per lane (%d)" % lanes)
+        plan.next_value = ptr("next_value", next_value, tuple(next_value.shape))
+        if use_proper_time_limits:
+            plan.bad_masks = ptr("bad_masks", bad_masks, full)
+    if denorm is not None:
+        if len(denorm) != 2:
+            raise ValueError("denorm must be a (mean, std) pair")
+        plan.denorm_mean, plan.denorm_std = ptr("denorm mean", denorm[0], (1,)), ptr("denorm std", denorm[1], (1,))
+    plan.advantages = ptr("advantages", advantages, half)
+    if normalized is not None:
+        plan.normalized = ptr("normalized", normalized, half)
+        plan.active_masks = ptr("active_masks", active_masks, full)
+        nbytes = returns_workspace_bytes(lanes)
+        if workspace is None:
+            workspace = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        elif workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous() or workspace.numel() < nbytes:
+            raise ValueError("workspace must be a contiguous uint8 tensor of at least %d bytes on %s" % (nbytes, dev))
+        plan.workspace, plan.workspace_bytes = workspace.data_ptr(), workspace.numel()
+    _need_cuda(dev)
+    _lib.check(_lib.load().gmpe_compute_returns(dev.index, C.byref(plan), _stream_of(dev)), "gmpe_compute_returns")
+    return returns
+
+
+def available_actions_from_dones(dones, out, first=0, count=None):
+    """The available_actions of the shipped training loop (graph_mpe_runner.py:73-141 collect_with_mask + get_finished, stored at slot step + 1 by
+    GraphReplayBuffer.insert) for the positions t = (first + k) % T, k < count (default: first .. T - 1), one launch on the current stream:
+    out[t] = ones at t = 0; for t >= 1 a one-hot "stop" row at n_actions // 2 for every agent done at step t - 1 (dones[t - 1]), ones otherwise.
+      dones: uint8 / bool [T, ...lane dims] (a rollout buffer's dones); out: float32 [T, ...lane dims, n_actions] (a buffer's available_actions[1:])."""
+    if not isinstance(dones, torch.Tensor) or dones.dtype not in (torch.uint8, torch.bool) or not dones.is_contiguous() or dones.dim() < 2:
+        raise ValueError("dones must be a contiguous uint8 / bool tensor [T, ...]")
+    dev = dones.device
+    T = int(dones.shape[0])
+    if not isinstance(out, torch.Tensor) or out.dim() != dones.dim() + 1:
+        raise ValueError("out must be a float32 tensor [T, ..., n_actions] matching dones")
+    n = int(out.shape[-1])
+    _dev_f32("out", out, tuple(dones.shape) + (n,), dev)
+    lanes = int(dones[0].numel())
+    count = T - int(first) if count is None else int(count)
+    if not 0 <= int(first) < T or count < 0 or n < 1 or lanes < 1:
+        raise ValueError("need 0 <= first < T, count >= 0, n_actions >= 1 and at least one lane")
+    _need_cuda(dev)
+    plan = _lib.GmpeAvailPlan(dones.data_ptr(), out.data_ptr(), lanes, n, T, int(first), count, lanes, lanes * n)
+    _lib.check(_lib.load().gmpe_available_actions_from_dones(dev.index, C.byref(plan), _stream_of(dev)), "gmpe_available_actions_from_dones")
+    return out

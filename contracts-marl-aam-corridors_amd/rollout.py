@@ -6,12 +6,16 @@ onpolicy/runner/shared/graph_mpe_runner.py:384-428): `[T+1, N, A, ...]` float32/
 obs / share_obs / node_obs / adj / agent_id / share_agent_id / masks / active_masks and `[T, N, A, 1]`
 rewards. The engine's output pointers are re-bound to slot t+1 before every step, so the kernel writes
 the rollout in place: no host hop and no device-to-device copy of the 16 KB/env adjacency.
-Policy-side fields (rnn states, values, log-probs, actions) stay with the learner.
+Opt-in policy-side storage (policy_storage_spec): value_preds / returns / bad_masks / available_actions [T+1, ...] and advantages [T, ...],
+with compute_returns / normalized_advantages (GraphReplayBuffer.compute_returns, GR_MAPPO.train's advantage lines) and the stop-action rows of
+available_actions (graph_mpe_runner.py:263-335) computed on the device. rnn states, log-probs and actions stay with the learner.
 """
 import torch
 
 from .config import NODE_FEATS
-from .engine import StepOutputs
+from .engine import StepOutputs, available_actions_from_dones, compute_returns, denorm_scalars, returns_workspace_bytes
+
+POLICY_FIELDS = ("value_preds", "returns", "bad_masks", "available_actions", "advantages")
 
 
 def storage_spec(cfg, episode_length, adj_compact, node_form, with_adj=True):
@@ -35,28 +39,54 @@ def storage_spec(cfg, episode_length, adj_compact, node_form, with_adj=True):
     return spec
 
 
+def policy_storage_spec(cfg, episode_length, fields=POLICY_FIELDS):
+    """name -> (dtype, shape) of the policy-side arrays a DeviceRolloutBuffer keeps on request (graph_buffer.py:118-138, 162 shapes; advantages: the
+    [T, N, A, 1] array GR_MAPPO.train computes)."""
+    N, A = cfg.num_envs, cfg.num_agents
+    T, T1 = int(episode_length), int(episode_length) + 1
+    shapes = dict(value_preds=(T1, N, A, 1), returns=(T1, N, A, 1), bad_masks=(T1, N, A, 1), available_actions=(T1, N, A, cfg.n_actions),
+                  advantages=(T, N, A, 1))
+    unknown = set(fields) - set(shapes)
+    if unknown:
+        raise ValueError("unknown policy fields: %s" % sorted(unknown))
+    return {k: (torch.float32, shapes[k]) for k in POLICY_FIELDS if k in fields}
+
+
+_ONES = ("masks", "active_masks", "bad_masks", "available_actions")   # what GraphReplayBuffer starts with ones (graph_buffer.py:132, 155-162)
+
+
 class DeviceRolloutBuffer(object):
-    def __init__(self, engine, episode_length, use_centralized_V=True, storage=None):
+    def __init__(self, engine, episode_length, use_centralized_V=True, storage=None, policy_fields=None, args=None):
         """storage: optional dict name -> caller-owned tensor for some or all of the arrays of storage_spec (e.g. views of ONE byte slab that a collective ships
-        as a whole, sharding.ShardedRolloutCollector); anything missing is allocated here."""
+        as a whole, sharding.ShardedRolloutCollector); anything missing is allocated here.
+        policy_fields: None (none), "all", or some of POLICY_FIELDS — the policy-side arrays of policy_storage_spec this buffer keeps (a storage entry of
+        such a name requests it too). args: the runner's args (gamma, gae_lambda, use_gae, use_proper_time_limits, use_valuenorm, use_popart), read by
+        compute_returns / normalized_advantages."""
         self.engine = engine
         self.T = int(episode_length)
         self.use_centralized_V = bool(use_centralized_V)
         c, dev = engine.cfg, engine.device
         self.node_form, self.adj_form = engine.node_form, engine.adj_form
+        self.args = args
         storage = dict(storage or {})
+        policy = set(POLICY_FIELDS if policy_fields == "all" else (policy_fields or ())) | (set(storage) & set(POLICY_FIELDS))
+        spec = storage_spec(c, self.T, engine.adj_compact, self.node_form, with_adj=self.adj_form != "none")
+        spec.update(policy_storage_spec(c, self.T, policy))
         self._adj = None
-        for name, (dt, shape) in storage_spec(c, self.T, engine.adj_compact, self.node_form, with_adj=self.adj_form != "none").items():
+        for name in POLICY_FIELDS:
+            setattr(self, name, None)
+        for name, (dt, shape) in spec.items():
             t = storage.pop(name, None)
             if t is None:
-                t = (torch.ones if name in ("masks", "active_masks") else torch.zeros)(shape, dtype=dt, device=dev)
+                t = (torch.ones if name in _ONES else torch.zeros)(shape, dtype=dt, device=dev)
             elif tuple(t.shape) != tuple(shape) or t.dtype != dt or t.device != dev or not t.is_contiguous():
                 raise ValueError("storage[%r] must be a contiguous %s tensor of shape %s on %s" % (name, dt, tuple(shape), dev))
-            elif name in ("masks", "active_masks"):
+            elif name in _ONES:
                 t.fill_(1.0)
             setattr(self, name if name != "node_obs" else "_node_obs", t)
         if storage:
             raise ValueError("unknown storage entries: %s" % sorted(storage))
+        self._ws = torch.empty((returns_workspace_bytes(c.num_envs * c.num_agents),), dtype=torch.uint8, device=dev) if self.advantages is not None else None
         if self.node_form == "table":
             self._node_obs = None
         if self.node_form == "rows":
@@ -126,9 +156,15 @@ class DeviceRolloutBuffer(object):
         self.engine.reset()
         self.step = 0
 
-    def insert_step(self, action_idx):
-        """One env step written straight into slot step+1 (+ masks), GraphReplayBuffer.insert semantics."""
+    def insert_step(self, action_idx, values=None):
+        """One env step written straight into slot step+1 (+ masks), GraphReplayBuffer.insert semantics. `values` (the policy's [N, A, 1] values of this
+        step, buffer with value_preds) go to value_preds[step] (graph_buffer.py:234); with available_actions the step's stop-action slot is written too."""
         t = self.step
+        if values is not None:
+            if self.value_preds is None:
+                raise ValueError("insert_step(values=...) needs a buffer with value_preds (policy_fields)")
+            self.value_preds[t].copy_(torch.as_tensor(values).reshape(self.value_preds[t].shape))
+        self.available_actions_for(t)
         self._bind(t + 1)
         self.engine.step(action_idx)
         # masks[dones] = 0; active_masks[dones] = 0 except where the whole env is done — one small kernel instead of eight torch ops
@@ -153,6 +189,7 @@ class DeviceRolloutBuffer(object):
             a = a[:, 0]                                   # the A per-agent matrices are one matrix (…_july.py:1625)
         elif not e.adj_compact and a.dim() == 3:
             a = a[:, None].expand(-1, e.A, -1, -1)
+        self.available_actions_for(t)
         put(self._adj[t + 1], a); put(self.rewards[t], rewards); put(self.dones[t], torch.as_tensor(dones).to(torch.uint8))
         e.masks_from_dones(self.dones[t], self.masks[t + 1], self.active_masks[t + 1])
         self.step = (t + 1) % self.T
@@ -180,6 +217,8 @@ class DeviceRolloutBuffer(object):
                 self._prepared.clear()
             hit = self._prepared[key] = (launch, a)             # keeps the action tensor alive: its address is part of the key
         hit[0]()
+        if self.available_actions is not None:                  # the K steps' stop-action slots from the dones just written: one more launch
+            available_actions_from_dones(self.dones, self.available_actions[1:], first=self.step, count=K)
         # the engine's "current outputs" are the last slot written, as after insert_step
         self._bind((self.step + K - 1) % self.T + 1)
         self.step = (self.step + K) % self.T
@@ -191,7 +230,57 @@ class DeviceRolloutBuffer(object):
             buf[0].copy_(buf[-1])
 
     def _carried(self):
-        return [b for b in (self.obs, self._node_obs, self.entity_table, self._adj, self.agent_id, self.masks, self.active_masks) if b is not None]
+        return [b for b in (self.obs, self._node_obs, self.entity_table, self._adj, self.agent_id, self.masks, self.active_masks,
+                            self.bad_masks, self.available_actions) if b is not None]
+
+    # ------------------------------------------------------------------ policy side (opt-in: policy_fields)
+    def available_actions_for(self, step):
+        """The [N, A, n_actions] availability the policy acts with at `step` (graph_mpe_runner.py:73-141: all ones at step 0, else collect_with_mask's
+        stop rows from the dones of step - 1), written into its buffer slot step + 1 (graph_buffer.py:249-250) by one small launch and returned as a view.
+        None when the buffer keeps no available_actions."""
+        if self.available_actions is None:
+            return None
+        available_actions_from_dones(self.dones, self.available_actions[1:], first=int(step), count=1)
+        return self.available_actions[int(step) + 1]
+
+    def _flags(self, what):
+        a = self.args
+        if a is None:
+            raise ValueError("%s needs the runner's args (DeviceRolloutBuffer(..., args=...))" % what)
+        return a, bool(getattr(a, "use_popart", False) or getattr(a, "use_valuenorm", False))
+
+    def _denorm(self, use_norm, value_normalizer, what):
+        if not use_norm:
+            return None
+        if value_normalizer is None:
+            raise ValueError("%s: args.use_valuenorm / use_popart is set, so a value_normalizer is required" % what)
+        return denorm_scalars(value_normalizer, self.engine.device)
+
+    def compute_returns(self, next_value, value_normalizer=None):
+        """GraphReplayBuffer.compute_returns (graph_buffer.py:285-366) with the runner's args, one launch on the current stream: returns[0..T-1], the
+        reference's side effect (value_preds[T] = next_value with use_gae, returns[T] = next_value without), and — buffer with advantages — the raw
+        advantages returns[t] - denorm(value_preds[t]). next_value: [N, A, 1] values of the last slot (graph_mpe_runner.py:431-443)."""
+        if self.value_preds is None or self.returns is None:
+            raise ValueError("compute_returns needs a buffer with value_preds and returns (policy_fields)")
+        a, use_norm = self._flags("compute_returns")
+        proper = bool(getattr(a, "use_proper_time_limits", False))
+        if proper and self.bad_masks is None:
+            raise ValueError("use_proper_time_limits needs a buffer with bad_masks (policy_fields)")
+        nv = torch.as_tensor(next_value).to(device=self.engine.device, dtype=torch.float32).contiguous()
+        compute_returns(self.rewards, self.masks, self.value_preds, self.returns, nv, gamma=a.gamma, gae_lambda=a.gae_lambda, use_gae=bool(a.use_gae),
+                        use_proper_time_limits=proper, bad_masks=self.bad_masks, denorm=self._denorm(use_norm, value_normalizer, "compute_returns"),
+                        advantages=self.advantages)
+        return self.returns
+
+    def normalized_advantages(self, value_normalizer=None):
+        """The head of GR_MAPPO.train (graph_mappo.py:294-304): advantages = returns[:-1] - denorm(value_preds[:-1]), normalised by the mean / population
+        std of the entries with active_masks[:-1] != 0: (adv - mean) / (std + 1e-5), written into the buffer's advantages (three launches, no host sync)."""
+        if self.advantages is None or self.value_preds is None or self.returns is None:
+            raise ValueError("normalized_advantages needs a buffer with value_preds, returns and advantages (policy_fields)")
+        _, use_norm = self._flags("normalized_advantages")
+        compute_returns(None, None, self.value_preds, self.returns, advantages_only=True, denorm=self._denorm(use_norm, value_normalizer, "normalized_advantages"),
+                        advantages=self.advantages, normalized=self.advantages, active_masks=self.active_masks, workspace=self._ws)
+        return self.advantages
 
     def carry_from(self, other):
         """after_update across TWO buffers that alternate (sharding.ShardedRolloutCollector): slot 0 of this one = the last slot of `other`, and the engine's

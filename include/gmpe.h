@@ -341,6 +341,62 @@ int gmpe_expand_adj(const gmpe_config* cfg, int device, const double* table_dev,
  * the env are done. Either output may be NULL. */
 int gmpe_masks_from_dones(gmpe_handle* h, const uint8_t* done_dev, float* masks_dev, float* active_masks_dev, void* stream);
 
+/* ---- Learner side of a rollout (handle-less, like gmpe_expand_node_obs): returns, advantages, stop-action rows ----
+ * No allocation, no host synchronisation, every launch on `stream`: capturable in a hipGraph. Arrays are f32 device memory of
+ * `lanes` = N*A values per slot (the reference's [.., N, A, 1]), consecutive slots `stride` elements apart.
+ *
+ * gmpe_compute_returns = GraphReplayBuffer.compute_returns (onpolicy/utils/graph_buffer.py:285-366), all four branches (flags), with
+ * ValueNorm / PopArt denormalisation x * std + mean as two roundings (valuenorm.py:87-99, popart.py:101-111; device scalars, so the
+ * caller's stream never waits on the host), and the head of GR_MAPPO.train (graph_mappo.py:294-304): raw advantages
+ * returns[t] - denorm(value_preds[t]) and, optionally, (adv - mean) / (std + 1e-5) over the entries whose active_masks[t] != 0
+ * (population std). Returns and raw advantages are bit-identical to the reference's float32 NumPy (its operation order, no contraction,
+ * f32(gamma * gae_lambda) rounded from the double product); mean / std are accumulated in double from per-wave partials merged in a
+ * fixed order (bitwise reproducible; NaN when no entry is active, like np.nanmean). Side effects as the reference: with GAE
+ * value_preds[T] = next_value, without it returns[T] = next_value. One launch, three with `normalized`. */
+#define GMPE_RETURNS_GAE 1                  /* args.use_gae                                                                    */
+#define GMPE_RETURNS_PROPER_TIME_LIMITS 2   /* args.use_proper_time_limits: bad_masks                                          */
+#define GMPE_RETURNS_ADVANTAGES_ONLY 4      /* skip the recurrence: advantages from the returns / value_preds as they are (train) */
+typedef struct gmpe_returns_plan {
+    int32_t num_steps;          /* T >= 1                                                                                       */
+    int32_t flags;              /* GMPE_RETURNS_*                                                                               */
+    int64_t lanes;              /* N*A >= 1                                                                                     */
+    int64_t stride;             /* elements between consecutive slots of every array below (>= lanes)                          */
+    double gamma, gae_lambda;
+    const float* rewards;       /* [T]    (not read with ADVANTAGES_ONLY)                                                       */
+    const float* masks;         /* [T+1]  (idem)                                                                                */
+    const float* bad_masks;     /* [T+1]  PROPER_TIME_LIMITS only                                                               */
+    float* value_preds;         /* [T+1]  GAE: slot T receives next_value                                                       */
+    float* returns;             /* [T+1]  written for slots 0..T-1; without GAE slot T receives next_value                      */
+    const float* next_value;    /* [lanes] (not read with ADVANTAGES_ONLY)                                                      */
+    const float* denorm_mean;   /* f32 [1] device: the normaliser's mean, or NULL (no denormalisation)                          */
+    const float* denorm_std;    /* f32 [1] device: sqrt(var); set exactly when denorm_mean is                                   */
+    float* advantages;          /* [T] raw advantages, or NULL                                                                  */
+    const float* active_masks;  /* [T+1] (slots 0..T-1 read): needed with `normalized`                                          */
+    float* normalized;          /* [T] normalised advantages, or NULL; may be `advantages` itself (in place)                    */
+    void* workspace;            /* device scratch of gmpe_returns_workspace_bytes(lanes) bytes: needed with `normalized`        */
+    size_t workspace_bytes;
+} gmpe_returns_plan;
+int gmpe_returns_workspace_bytes(int64_t lanes, size_t* bytes_out);
+int gmpe_compute_returns(int device, const gmpe_returns_plan* plan, void* stream);
+
+/* available_actions of the shipped training loop (GMPERunner.run + collect_with_mask, graph_mpe_runner.py:73-141, 263-335, stored by
+ * GraphReplayBuffer.insert at slot step + 1, graph_buffer.py:249-250): the availability the policy acts with at step t >= 1 is a function of
+ * the dones of step t - 1 — a one-hot "stop" row at n_actions / 2 for an agent that was done, a row of ones otherwise (every agent of an env
+ * whose agents were all done gets the stop row, although that env has auto-reset) — and at step 0 it is all ones.
+ * Positions are the steps of one episode, t = (first + k) % num_positions for k < count: position t reads dones slot t - 1
+ * (u8 [lanes], `stride_dones` elements apart from slot 0) and writes f32 [lanes, n_actions] at available_actions + t * stride_out. */
+typedef struct gmpe_avail_plan {
+    const uint8_t* dones;       /* slot 0 of the dones (position t reads slot t - 1)                                           */
+    float* available_actions;   /* the rows of position 0 (the buffer's slot 1)                                                */
+    int64_t lanes;              /* N*A                                                                                         */
+    int32_t n_actions;
+    int32_t num_positions;      /* T (episode length)                                                                          */
+    int32_t first;              /* position of the first step, in [0, T)                                                       */
+    int32_t count;              /* steps (>= 0; more than T write every position once)                                         */
+    int64_t stride_dones, stride_out;
+} gmpe_avail_plan;
+int gmpe_available_actions_from_dones(int device, const gmpe_avail_plan* plan, void* stream);
+
 /* What gmpe_create chose for this handle (recorded by bench.py next to every number). Environment variables override the heuristics —
  * GMPE_G / GMPE_BLOCK (step tile shape), GMPE_GROLL (rollout tile shape), GMPE_AP=0 (run-time-size instead of exact-size kernels),
  * GMPE_NT / GMPE_ROLLNT (nontemporal graph stores of step / rollout launches), GMPE_SPEC (wave specialisation), GMPE_SPLIT / GMPE_CHUNKS

@@ -1,0 +1,187 @@
+"""CPU side of the learner-side rollout kernels (include/gmpe.h gmpe_compute_returns, gmpe_available_actions_from_dones): exported symbols, plan
+struct layouts, argument checks of the Python wrappers before any launch, the opt-in policy storage of DeviceRolloutBuffer, and the NumPy
+restatement the GPU tests compare with (tests/returns_lib.py) against the reference's own vectors."""
+import ctypes as C
+import os
+import subprocess
+import tempfile
+import types
+
+import numpy as np
+import pytest
+import torch
+
+import gmpe
+from gmpe import _lib
+import returns_lib as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLD = os.path.join(ROOT, "tests", "golden")
+NEW = ("gmpe_returns_workspace_bytes", "gmpe_compute_returns", "gmpe_available_actions_from_dones")
+
+
+def test_new_symbols_are_exported_and_bound():
+    lib = _lib.load()
+    for f in NEW:
+        assert f in _lib.SYMBOLS
+        assert hasattr(lib, f), f
+
+
+def test_plan_struct_layouts_match_c_header():
+    src = r'''
+    #include <stdio.h>
+    #include <stddef.h>
+    #include "gmpe.h"
+    int main(void) {
+      printf("%zu %zu %zu %zu %zu %zu\n", sizeof(gmpe_returns_plan), offsetof(gmpe_returns_plan, gamma), offsetof(gmpe_returns_plan, rewards),
+             offsetof(gmpe_returns_plan, denorm_std), offsetof(gmpe_returns_plan, workspace), offsetof(gmpe_returns_plan, workspace_bytes));
+      printf("%zu %zu %zu %zu\n", sizeof(gmpe_avail_plan), offsetof(gmpe_avail_plan, n_actions), offsetof(gmpe_avail_plan, count),
+             offsetof(gmpe_avail_plan, stride_out));
+      printf("%d %d %d\n", GMPE_RETURNS_GAE, GMPE_RETURNS_PROPER_TIME_LIMITS, GMPE_RETURNS_ADVANTAGES_ONLY);
+      return 0; }'''
+    with tempfile.TemporaryDirectory() as td:
+        cpath, exe = os.path.join(td, "t.c"), os.path.join(td, "t")
+        open(cpath, "w").write(src)
+        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", exe, cpath])
+        out = [int(x) for x in subprocess.check_output([exe]).decode().split()]
+    P, Q = _lib.GmpeReturnsPlan, _lib.GmpeAvailPlan
+    assert out[:6] == [C.sizeof(P), P.gamma.offset, P.rewards.offset, P.denorm_std.offset, P.workspace.offset, P.workspace_bytes.offset]
+    assert out[6:10] == [C.sizeof(Q), Q.n_actions.offset, Q.count.offset, Q.stride_out.offset]
+    assert out[10:] == [_lib.RETURNS_GAE, _lib.RETURNS_PROPER_TIME_LIMITS, _lib.RETURNS_ADVANTAGES_ONLY]
+
+
+def test_workspace_query_and_c_side_validation():
+    lib = _lib.load()
+    n = C.c_size_t()
+    assert lib.gmpe_returns_workspace_bytes(40960, C.byref(n)) == 0 and n.value >= 40960 // 64 * 24
+    assert lib.gmpe_returns_workspace_bytes(0, C.byref(n)) == -1
+    assert lib.gmpe_compute_returns(0, None, None) == -1
+    p = _lib.GmpeReturnsPlan()
+    p.num_steps, p.lanes, p.stride = 4, 8, 4                          # stride < lanes
+    assert lib.gmpe_compute_returns(0, C.byref(p), None) == -1
+    assert b"stride" in lib.gmpe_last_error()
+    q = _lib.GmpeAvailPlan(None, None, 8, 25, 4, 0, 4, 8, 200)
+    assert lib.gmpe_available_actions_from_dones(0, C.byref(q), None) == -1
+    assert gmpe.engine.returns_workspace_bytes(63) == 24 + 8            # one wave partial (count, mean, M2 in double) + mean / std
+
+
+def _arrays(T=5, N=3, A=2, device="cpu"):
+    z = lambda *s: torch.zeros(s, dtype=torch.float32, device=device)
+    return dict(rewards=z(T, N, A, 1), masks=z(T + 1, N, A, 1), value_preds=z(T + 1, N, A, 1), returns=z(T + 1, N, A, 1), next_value=z(N, A, 1))
+
+
+@pytest.mark.parametrize("bad, match", [
+    (dict(rewards=torch.zeros(6, 3, 2, 1)), "rewards.*shape"),                      # T+1 slots where T are due
+    (dict(masks=torch.zeros(6, 3, 2, 1, dtype=torch.float64)), "masks.*float32"),
+    (dict(next_value=torch.zeros(3, 3, 1)), "next_value"),
+    (dict(returns=torch.zeros(6, 3, 2, 1)[:, :, :1]), "returns.*shape"),
+    (dict(advantages=torch.zeros(6, 3, 2, 1)), "advantages.*shape"),
+    (dict(denorm=(torch.zeros(2), torch.ones(1))), "denorm mean"),
+    (dict(normalized=torch.zeros(5, 3, 2, 1)), "active_masks"),
+    (dict(use_proper_time_limits=True), "bad_masks"),
+    ({}, "CUDA"),                                                                   # well-formed host tensors: refused for the device
+])
+def test_compute_returns_refuses_bad_arguments_before_launch(bad, match):
+    a = _arrays()
+    a.update(bad)
+    with pytest.raises(ValueError, match=match):
+        gmpe.engine.compute_returns(**a)
+
+
+@pytest.mark.parametrize("bad, match", [
+    (dict(dones=torch.zeros(4, 3, 2, dtype=torch.int32)), "dones"),
+    (dict(out=torch.zeros(4, 3, 2, 25, dtype=torch.float64)), "out.*float32"),
+    (dict(out=torch.zeros(5, 3, 2, 25)), "out.*shape"),
+    (dict(first=4), "first"),
+    ({}, "CUDA"),
+])
+def test_available_actions_refuses_bad_arguments_before_launch(bad, match):
+    a = dict(dones=torch.zeros(4, 3, 2, dtype=torch.uint8), out=torch.zeros(4, 3, 2, 25))
+    a.update(bad)
+    with pytest.raises(ValueError, match=match):
+        gmpe.engine.available_actions_from_dones(**a)
+
+
+class _HostEngine(object):
+    """What DeviceRolloutBuffer.__init__ reads from an engine, on the host (no GPU): enough to see which arrays it allocates."""
+
+    def __init__(self, cfg, adj_compact=True):
+        self.cfg, self.device, self.adj_compact = cfg, torch.device("cpu"), adj_compact
+        self.node_form, self.adj_form = "rows", "compact" if adj_compact else "full"
+        self.N, self.A = cfg.num_envs, cfg.num_agents
+        self.out = types.SimpleNamespace(info=None)
+
+    def tuning(self):
+        return dict(roll=1, split=0)
+
+
+def test_buffer_without_policy_fields_keeps_todays_storage_spec():
+    from gmpe.rollout import DeviceRolloutBuffer, storage_spec
+    cfg = gmpe.make_config(num_envs=4, num_agents=3, episode_length=5)
+    N, A, E, D, T = 4, 3, cfg.num_entities, cfg.obs_dim, 6
+    spec = storage_spec(cfg, T, True, "rows")
+    f32 = torch.float32
+    assert spec == {"obs": (f32, (T + 1, N, A, D)), "node_obs": (f32, (T + 1, N, A, E, cfg.node_feats)), "_adj": (f32, (T + 1, N, E, E)),
+                    "agent_id": (torch.int32, (T + 1, N, A, 1)), "rewards": (f32, (T, N, A, 1)), "dones": (torch.uint8, (T, N, A)),
+                    "masks": (f32, (T + 1, N, A, 1)), "active_masks": (f32, (T + 1, N, A, 1))}
+    buf = DeviceRolloutBuffer(_HostEngine(cfg), T)
+    for k in ("value_preds", "returns", "bad_masks", "available_actions", "advantages"):
+        assert getattr(buf, k) is None
+    assert buf._ws is None
+    assert len(buf._carried()) == 6                              # obs, node_obs, adj, agent_id, masks, active_masks: nothing new is carried
+    with pytest.raises(ValueError, match="value_preds"):
+        buf.compute_returns(torch.zeros(N, A, 1))
+    assert buf.available_actions_for(0) is None
+
+
+def test_buffer_policy_fields_shapes_and_initial_values():
+    from gmpe.rollout import DeviceRolloutBuffer, POLICY_FIELDS
+    cfg = gmpe.make_config(num_envs=4, num_agents=3, episode_length=5)
+    N, A, T, n = 4, 3, 6, cfg.n_actions
+    buf = DeviceRolloutBuffer(_HostEngine(cfg), T, policy_fields="all")
+    shapes = dict(value_preds=(T + 1, N, A, 1), returns=(T + 1, N, A, 1), bad_masks=(T + 1, N, A, 1), available_actions=(T + 1, N, A, n),
+                  advantages=(T, N, A, 1))
+    for k in POLICY_FIELDS:
+        t = getattr(buf, k)
+        assert tuple(t.shape) == shapes[k] and t.dtype == torch.float32
+        assert float(t.min()) == float(t.max()) == (1.0 if k in ("bad_masks", "available_actions") else 0.0)   # graph_buffer.py:125-162
+    assert buf._ws.numel() == gmpe.engine.returns_workspace_bytes(N * A)
+    mine = torch.zeros(T + 1, N, A, 1)
+    b2 = DeviceRolloutBuffer(_HostEngine(cfg), T, storage={"returns": mine})        # a storage entry requests its field
+    assert b2.returns is mine and b2.value_preds is None
+    with pytest.raises(ValueError, match="unknown policy"):
+        DeviceRolloutBuffer(_HostEngine(cfg), T, policy_fields=("values",))
+    with pytest.raises(ValueError, match="args"):
+        DeviceRolloutBuffer(_HostEngine(cfg), T, policy_fields="all").compute_returns(torch.zeros(N, A, 1))
+
+
+def _denorm(d, name):
+    return None if name == "none" else (d[name + "_mean"].reshape(()), d[name + "_std"].reshape(()))
+
+
+def test_numpy_restatement_is_the_reference_bit_for_bit():
+    """tests/returns_lib.py against the vectors the reference produced (make_returns_fixture.py): returns, value_preds side effects and raw advantages
+    bitwise, normalised advantages within float32 noise of np.nanmean / np.nanstd — every branch x {no normaliser, ValueNorm, PopArt}."""
+    d = np.load(os.path.join(GOLD, "returns_advantages.npz"))
+    for gae in (True, False):
+        for proper in (False, True):
+            for name in ("none", "valuenorm", "popart"):
+                key = "%s_%s_%s" % ("gae" if gae else "mc", "proper" if proper else "plain", name)
+                den = _denorm(d, name)
+                ret, vp = R.np_returns(d["rewards"], d["masks"], d["value_preds"], d["returns_in"], d["next_value"], float(d["gamma"]),
+                                       float(d["gae_lambda"]), gae, proper, d["bad_masks"], den)
+                np.testing.assert_array_equal(ret.view(np.uint32), d["ret_" + key].view(np.uint32), err_msg=key)
+                np.testing.assert_array_equal(vp.view(np.uint32), d["vp_" + key].view(np.uint32), err_msg=key)
+                adv = R.np_advantages(ret, vp, den)
+                np.testing.assert_array_equal(adv.view(np.uint32), d["adv_" + key].view(np.uint32), err_msg=key)
+                np.testing.assert_allclose(R.np_normalized(adv, d["active_masks"]), d["advn_" + key], rtol=0, atol=1e-5, err_msg=key)
+
+
+def test_numpy_stop_action_rule_is_the_reference():
+    d = np.load(os.path.join(GOLD, "available_actions.npz"))
+    T, n = int(d["T"]), int(d["n_actions"])
+    for ep in range(d["dones"].shape[0]):
+        np.testing.assert_array_equal(R.np_available_actions(d["dones"][ep], n), d["slots"][ep][1:])
+        np.testing.assert_array_equal(d["policy_avail"][ep], d["slots"][ep][1:])          # what the policy acted with at step t sits in slot t + 1
+    np.testing.assert_array_equal(d["slots"][1][0], d["slots"][0][T])                      # after_update carries the last slot
+    assert (d["dones"].all(-1)).any() and (d["dones"].any(-1) & ~d["dones"].all(-1)).any()
