@@ -17,7 +17,7 @@ SYMBOLS = ["gmpe_abi_version", "gmpe_last_error", "gmpe_obs_dim", "gmpe_node_fea
            "gmpe_rollout_steps", "gmpe_get_tuning", "gmpe_step_many_launches", "gmpe_edges_from_adj_compact",
            "gmpe_set_control_override", "gmpe_field_device_ptr", "gmpe_step_envs", "gmpe_step_many_envs",
            "gmpe_entity_table_width", "gmpe_expand_node_obs", "gmpe_expand_adj",
-           "gmpe_returns_workspace_bytes", "gmpe_compute_returns", "gmpe_available_actions_from_dones"]
+           "gmpe_returns_workspace_bytes", "gmpe_compute_returns", "gmpe_available_actions_from_dones", "gmpe_minibatch_gather"]
 
 
 class GmpeOutputs(C.Structure):
@@ -57,6 +57,23 @@ class GmpeAvailPlan(C.Structure):
     """gmpe_avail_plan (include/gmpe.h): the stop-action rows of available_actions from the previous step's dones."""
     _fields_ = [("dones", C.c_void_p), ("available_actions", C.c_void_p), ("lanes", C.c_int64), ("n_actions", C.c_int32),
                 ("num_positions", C.c_int32), ("first", C.c_int32), ("count", C.c_int32), ("stride_dones", C.c_int64), ("stride_out", C.c_int64)]
+
+
+MB_FEED_FORWARD, MB_RECURRENT = 0, 1
+MB_ROW, MB_ENV_ROW, MB_CHUNK_HEAD, MB_TABLE_NODE, MB_TABLE_ADJ = 0, 1, 2, 3, 4
+MB_MAX_FIELDS = 20
+
+
+class GmpeMbField(C.Structure):
+    """gmpe_mb_field (include/gmpe.h): one field of a minibatch gather."""
+    _fields_ = [("kind", C.c_int32), ("row_bytes", C.c_int32), ("slot_stride", C.c_int64), ("src", C.c_void_p), ("dst", C.c_void_p)]
+
+
+class GmpeMinibatchPlan(C.Structure):
+    """gmpe_minibatch_plan (include/gmpe.h): one PPO minibatch gathered from a rollout through a device permutation."""
+    _fields_ = [("mode", C.c_int32), ("num_fields", C.c_int32), ("T", C.c_int32), ("N", C.c_int32), ("A", C.c_int32), ("L", C.c_int32),
+                ("perm", C.c_void_p), ("perm_len", C.c_int64), ("offset", C.c_int64), ("rows", C.c_int64),
+                ("fields", GmpeMbField * MB_MAX_FIELDS)]
 
 
 class GmpeError(RuntimeError):
@@ -110,6 +127,7 @@ def load():
     lib.gmpe_returns_workspace_bytes.argtypes = [C.c_int64, C.POINTER(C.c_size_t)]
     lib.gmpe_compute_returns.argtypes = [I, C.POINTER(GmpeReturnsPlan), P]
     lib.gmpe_available_actions_from_dones.argtypes = [I, C.POINTER(GmpeAvailPlan), P]
+    lib.gmpe_minibatch_gather.argtypes = [C.POINTER(GmpeConfig), I, C.POINTER(GmpeMinibatchPlan), P]
     from .config import ABI_VERSION
     if lib.gmpe_abi_version() != ABI_VERSION:
         raise GmpeError("libgmpe.so ABI version mismatch")

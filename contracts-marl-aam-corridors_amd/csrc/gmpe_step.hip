@@ -28,6 +28,7 @@
 #include <algorithm>
 #include <optional>
 
+#include "gmpe_expand.h"
 #include "gmpe_kernel.h"
 
 namespace gmpe {
@@ -538,10 +539,9 @@ static int create_split_path(gmpe_handle* h) {
 }
 
 // ---------------------------------------------------------------- learner side: node_obs rows from entity tables (gmpe_expand_node_obs)
-// One thread per (env-step b, ego i, entity k). The arithmetic repeats stream_graph_fn's three row variants operation for operation (this translation unit
-// is compiled with the same -ffp-contract=off), so the rows are bit-identical to what the engine writes: tests/test_gpu_gather.py compares them for every scenario x
-// feature type. KIND 0: relative, F = 8 (…_july.py:1694-1771); 1: rot_inv family, F = 7 (rot_inv.py:1690-1766; two: goal = corridor exit, two_phase_graph.py:1405);
-// 2: graph_feat_type 'global', F = 7 (…_july.py:1672-1691).
+// One thread per (env-step b, ego i, entity k). The row arithmetic is gmpe_expand.h node_row_from_table (shared with the minibatch gather, gmpe_minibatch.hip;
+// every user compiled with the same -ffp-contract=off), so the rows are bit-identical to what the engine writes: tests/test_gpu_gather.py compares them for every
+// scenario x feature type. KIND: 0 relative (F = 8), 1 rot_inv family (F = 7), 2 graph_feat_type 'global' (F = 7).
 template <int KIND>
 __global__ __launch_bounds__(256) void k_node_expand(const double* __restrict__ tab, float* __restrict__ out, long long total, int A, int L, int E, int W, int two,
                                                      long long n_in, long long n_out, long long off) {
@@ -552,49 +552,11 @@ __global__ __launch_bounds__(256) void k_node_expand(const double* __restrict__ 
     const int ei = (int)(r1 % A);
     const long long b = r1 / A;                                          // env-step index in the table: block * n_in + env
     const long long blk = b / n_in, n = b - blk * n_in;
-    const double* T = tab + (size_t)b * W;
-    const double* ex = T; const double* ey = T + E;
-    const double* vox = T + 2 * E; const double* voy = vox + A; const double* vnx = voy + A; const double* vny = vnx + A;
-    const bool kag = k < A;
-    const int kk = kag ? k : 0;
-    const bool post = k <= ei;                                           // agent k's re-drawn velocity is visible to ego ei iff k <= ei (ordered-visibility rule)
-    const float typ = kag ? 0.0f : (k < A + L ? 1.0f : 2.0f);
     const size_t row = ((size_t)(blk * n_out + off + n) * A + ei) * E + k;
-    if (KIND == 0) {
-        const double kx = ex[k], ky = ey[k];
-        const double kvox = kag ? vox[kk] : 0.0, kvoy = kag ? voy[kk] : 0.0, kvnx = kag ? vnx[kk] : 0.0, kvny = kag ? vny[kk] : 0.0;
-        const double gx = kag ? ex[A + kk] : kx, gy = kag ? ey[A + kk] : ky;
-        const double px = ex[ei], py = ey[ei], evx = vnx[ei], evy = vny[ei];
-        float4* d = reinterpret_cast<float4*>(out + row * 8);
-        d[0] = make_float4((float)((post ? kvnx : kvox) - evx), (float)((post ? kvny : kvoy) - evy), (float)(kx - px), (float)(ky - py));
-        d[1] = make_float4((float)(gx - px), (float)(gy - py), kag ? 0.0f : 1.0f, typ);
-    } else if (KIND == 1) {
-        const double* cn = vny + A; const double* sn = cn + A;
-        const float kx = (float)ex[k], ky = (float)ey[k];
-        const float kvox = kag ? (float)vox[kk] : 0.0f, kvoy = kag ? (float)voy[kk] : 0.0f, kvnx = kag ? (float)vnx[kk] : 0.0f, kvny = kag ? (float)vny[kk] : 0.0f;
-        const int wx = W - (E + 31) / 32 - 2;                              // two_phase_graph: exit x, y sit right before the mask words
-        const float gxk = two ? (float)T[wx] : (kag ? (float)ex[A + kk] : 0.0f), gyk = two ? (float)T[wx + 1] : (kag ? (float)ey[A + kk] : 0.0f);
-        const float apx = (float)ex[ei], apy = (float)ey[ei], avx = (float)vnx[ei], avy = (float)vny[ei];
-        const double cs = cn[ei], s_ = sn[ei];
-        const float rvx = (post ? kvnx : kvox) - avx, rvy = (post ? kvny : kvoy) - avy;
-        const float rpx = kx - apx, rpy = ky - apy;
-        double o0, o1, o2, o3, o4, o5;
-        rot2(cs, s_, (double)rvx, (double)rvy, o0, o1);
-        rot2(cs, s_, (double)rpx, (double)rpy, o2, o3);
-        if (kag) rot2(cs, s_, (double)(gxk - apx), (double)(gyk - apy), o4, o5); else { o4 = o2; o5 = o3; }
-        float* d = out + row * 7;
-        d[0] = (float)o0; d[1] = (float)o1; d[2] = (float)o2; d[3] = (float)o3; d[4] = (float)o4; d[5] = (float)o5; d[6] = typ;
-    } else {
-        const float kx = (float)ex[k], ky = (float)ey[k];
-        const float kvox = kag ? (float)vox[kk] : 0.0f, kvoy = kag ? (float)voy[kk] : 0.0f, kvnx = kag ? (float)vnx[kk] : 0.0f, kvny = kag ? (float)vny[kk] : 0.0f;
-        const float gx = kag ? (float)ex[A + kk] : kx, gy = kag ? (float)ey[A + kk] : ky;
-        float* d = out + row * 7;
-        d[0] = post ? kvnx : kvox; d[1] = post ? kvny : kvoy; d[2] = kx; d[3] = ky; d[4] = gx; d[5] = gy; d[6] = typ;
-    }
+    node_row_from_table<KIND>(tab + (size_t)b * W, out + row * (KIND == 0 ? 8 : 7), A, L, E, W, two, ei, k);
 }
 
-// The E x E adjacency of an env-step from its entity table: f32(sqrt(dx^2 + dy^2)) with delta = pos[min(r,c)] - pos[max(r,c)] (World.calculate_distances,
-// core.py:600-624 — distance_trip's expression, so the bits are the engine's), zero diagonal, rows / columns of masked nodes zeroed (…_july.py:1627-1648).
+// The E x E adjacency of an env-step from its entity table (gmpe_expand.h adj_entry_from_table: the engine's own expression and mask rule).
 // One thread per group of VEC consecutive entries of one matrix; `copies` = 1 writes [.., E, E], `copies` = A the materialised [.., A, E, E].
 template <int VEC>
 __global__ __launch_bounds__(256) void k_adj_from_table(const double* __restrict__ tab, float* __restrict__ out, long long total, int E, int W, int copies,
@@ -606,17 +568,11 @@ __global__ __launch_bounds__(256) void k_adj_from_table(const double* __restrict
     const int q = (int)(t - b * per) * VEC;
     const long long blk = b / n_in, n = b - blk * n_in;
     const double* T = tab + (size_t)b * W;
-    const double* ex = T; const double* ey = T + E;
-    const double* mw = T + (W - (E + 31) / 32);
     float v[VEC];
 #pragma unroll
     for (int u = 0; u < VEC; ++u) {
         const int r = (q + u) / E, c = (q + u) - r * E;
-        const int lo = r < c ? r : c, hi = r < c ? c : r;
-        const unsigned wr = (unsigned)mw[r >> 5], wc = (unsigned)mw[c >> 5];
-        const bool masked = ((wr >> (r & 31)) | (wc >> (c & 31))) & 1u;
-        const double dx = ex[lo] - ex[hi], dy = ey[lo] - ey[hi];
-        v[u] = (r == c || masked) ? 0.0f : (float)sqrt(dx * dx + dy * dy);
+        v[u] = adj_entry_from_table(T, E, W, r, c);
     }
     float* dst = out + (size_t)(blk * n_out + off + n) * copies * EE + q;
     for (int a = 0; a < copies; ++a) {

@@ -14,6 +14,7 @@ import torch
 
 from .config import NODE_FEATS
 from .engine import StepOutputs, available_actions_from_dones, compute_returns, denorm_scalars, returns_workspace_bytes
+from .minibatch import LEARNER, feed_forward_generator, recurrent_generator
 
 POLICY_FIELDS = ("value_preds", "returns", "bad_masks", "available_actions", "advantages")
 
@@ -281,6 +282,60 @@ class DeviceRolloutBuffer(object):
         compute_returns(None, None, self.value_preds, self.returns, advantages_only=True, denorm=self._denorm(use_norm, value_normalizer, "normalized_advantages"),
                         advantages=self.advantages, normalized=self.advantages, active_masks=self.active_masks, workspace=self._ws)
         return self.advantages
+
+    # ------------------------------------------------------------------ PPO minibatches (GraphReplayBuffer's generators, gmpe_minibatch_gather)
+    def minibatch_arrays(self, learner=None):
+        """The arrays a minibatch gathers from, in the storage form the buffer keeps (node rows or entity table; materialised, compact or no adjacency) plus the
+        caller-owned learner arrays (rnn_states / rnn_states_critic [T+1, N, A, R, H], actions / action_log_probs [T, N, A, k]; DESIGN §10: not the buffer's)."""
+        e = self.engine
+        N, A, T1 = e.N, e.A, self.T + 1
+        arrays = dict(obs=self.obs, agent_id=self.agent_id, masks=self.masks, active_masks=self.active_masks, value_preds=self.value_preds,
+                      returns=self.returns, available_actions=self.available_actions)
+        if self._node_obs is not None:
+            arrays["node_obs"] = self._node_obs
+        else:
+            arrays["entity_table"] = self.entity_table
+        if self._adj is not None:
+            arrays["adj"] = self._adj
+        elif self.entity_table is not None:
+            arrays["entity_table"] = self.entity_table
+        learner = dict(learner or {})
+        unknown = set(learner) - set(LEARNER)
+        if unknown:
+            raise ValueError("unknown learner arrays: %s (expected some of %s)" % (sorted(unknown), list(LEARNER)))
+        for name, t in learner.items():
+            lead, nd = ((T1, N, A), 5) if name.startswith("rnn") else ((self.T, N, A), 4)
+            if not isinstance(t, torch.Tensor) or t.dim() != nd or tuple(t.shape[:3]) != lead:
+                raise ValueError("learner[%r] must be a tensor of shape %s + %s" % (name, lead, "(R, H)" if nd == 5 else "(k,)"))
+        arrays.update(learner)
+        return arrays
+
+    def _advantages(self, advantages):
+        if advantages is None:
+            return None
+        t = torch.as_tensor(advantages)
+        if tuple(t.shape) != (self.T, self.engine.N, self.engine.A, 1):
+            raise ValueError("advantages must have shape %s" % ((self.T, self.engine.N, self.engine.A, 1),))
+        return t.to(device=self.engine.device, dtype=torch.float32).contiguous()
+
+    def feed_forward_generator(self, advantages, num_mini_batch=None, mini_batch_size=None, *, learner=None, perm=None):
+        """GraphReplayBuffer.feed_forward_generator (graph_buffer.py:368-465) from the device arrays: the reference's 16-tuple per minibatch as fresh device
+        tensors (agent_id / share_agent_id int32; available_actions None when the buffer keeps none, learner slots None
+        unless `learner` holds them), one gather launch per minibatch (two with the entity-table forms). perm: None draws torch.randperm on the CPU default
+        generator as the reference does (a seeded run trains on the same minibatches) and uploads it once; "device" draws on the device; or an int64 tensor."""
+        return feed_forward_generator(self.engine.cfg, self.minibatch_arrays(learner), self._advantages(advantages), num_mini_batch, mini_batch_size,
+                                      perm=perm, use_centralized_V=self.use_centralized_V)
+
+    def recurrent_generator(self, advantages, num_mini_batch, data_chunk_length, *, learner=None, perm=None):
+        """GraphReplayBuffer.recurrent_generator (graph_buffer.py:599-758): chunks of data_chunk_length samples in the reference's [N, A, T] order, rows
+        l * chunks + k, rnn states [chunks, R, H] from each chunk's first sample. perm as feed_forward_generator (over the T*N*A // L chunks)."""
+        return recurrent_generator(self.engine.cfg, self.minibatch_arrays(learner), self._advantages(advantages), num_mini_batch, data_chunk_length,
+                                   perm=perm, use_centralized_V=self.use_centralized_V)
+
+    def naive_recurrent_generator(self, advantages, num_mini_batch):
+        raise NotImplementedError(
+            "naive_recurrent_generator is not provided: the reference's version cannot run for any batch larger than 1 — it flattens masks to [T*N*A, 1] "
+            "(graph_buffer.py:501) and then indexes masks[:-1, ind] (:541), which raises IndexError. Use recurrent_generator or feed_forward_generator.")
 
     def carry_from(self, other):
         """after_update across TWO buffers that alternate (sharding.ShardedRolloutCollector): slot 0 of this one = the last slot of `other`, and the engine's

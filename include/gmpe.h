@@ -397,6 +397,45 @@ typedef struct gmpe_avail_plan {
 } gmpe_avail_plan;
 int gmpe_available_actions_from_dones(int device, const gmpe_avail_plan* plan, void* stream);
 
+/* PPO minibatches from a rollout (GraphReplayBuffer.feed_forward_generator / recurrent_generator, onpolicy/utils/graph_buffer.py:368-758): one minibatch's rows
+ * of every field gathered from the [T+1, N, ...] arrays through a device permutation, as exact byte copies (16-byte vectors where row size and alignment allow)
+ * or, for the table kinds, expanded from the f64 entity table with the arithmetic of gmpe_expand_node_obs / gmpe_expand_adj (bit-identical to the engine).
+ * Output row r of a minibatch reads sample (t, n, a):
+ *   GMPE_MB_FEED_FORWARD: j = perm[offset + r] over the [T, N, A] flattening: t = j / (N*A), n = (j / A) % N, a = j % A. Output rows: `rows`.
+ *   GMPE_MB_RECURRENT:    the samples in [N, A, T] order (graph_buffer.py:15-16 _cast) cut into chunks of L; r = l * rows + k (np.stack(axis=1) then _flatten),
+ *                         c = perm[offset + k], f = c*L + l: n = f / (A*T), a = (f / T) % A, t = f % T (a chunk may cross agent and env boundaries when
+ *                         T % L != 0). Output rows: rows * L; GMPE_MB_CHUNK_HEAD fields: `rows`, from each chunk's first sample f = c*L.
+ * Permutation entries outside [0, T*N*A) (feed-forward) or [0, T*N*A / L) (recurrent) are not read: their output rows are left unwritten.
+ * Handle-less: `cfg` (NULL allowed without table kinds) supplies scenario, feature type and E / W for the table kinds. No allocation, no host synchronisation,
+ * no atomics; one launch, two with table kinds, on `stream`: capturable in a hipGraph. Every argument the host can see is checked before any device call. */
+#define GMPE_MB_FEED_FORWARD 0
+#define GMPE_MB_RECURRENT 1
+#define GMPE_MB_ROW 0          /* row of sample (t, n, a): src + t * slot_stride + (n*A + a) * row_bytes                                          */
+#define GMPE_MB_ENV_ROW 1      /* row of env-step (t, n):  src + t * slot_stride + n * row_bytes (compact adj; share_obs = obs[t, n] with A*D floats)   */
+#define GMPE_MB_CHUNK_HEAD 2   /* recurrent only: GMPE_MB_ROW addressing, one output row per chunk (rnn_states / rnn_states_critic)                */
+#define GMPE_MB_TABLE_NODE 3   /* node rows of ego a at (t, n) from the entity table src + t * slot_stride + n * W * 8: row_bytes = E * F * 4          */
+#define GMPE_MB_TABLE_ADJ 4    /* the E x E matrix of (t, n) from the entity table: row_bytes = E * E * 4                                          */
+#define GMPE_MB_MAX_FIELDS 20
+typedef struct gmpe_mb_field {
+    int32_t kind;               /* GMPE_MB_ROW .. GMPE_MB_TABLE_ADJ                                                                         */
+    int32_t row_bytes;          /* bytes of one OUTPUT row (a multiple of 4); source rows have the same size except for the table kinds     */
+    int64_t slot_stride;        /* bytes between slot t and t + 1 of src (at least one slot: N*A rows, N rows, or N*W doubles)             */
+    const void* src;            /* slot 0 of the source array, device memory (8-byte aligned for the table kinds)                          */
+    void* dst;                  /* output rows, row_bytes apart, device memory                                                              */
+} gmpe_mb_field;
+typedef struct gmpe_minibatch_plan {
+    int32_t mode;               /* GMPE_MB_FEED_FORWARD or GMPE_MB_RECURRENT                                                                */
+    int32_t num_fields;         /* 1 .. GMPE_MB_MAX_FIELDS                                                                                  */
+    int32_t T, N, A;            /* episode length, envs, agents of the arrays (T*N*A < 2^31); A = cfg->num_agents with table kinds           */
+    int32_t L;                  /* data_chunk_length (recurrent), >= 1; ignored feed-forward                                                */
+    const int64_t* perm;        /* device permutation: samples (feed-forward) or chunks (recurrent)                                         */
+    int64_t perm_len;           /* its entries                                                                                              */
+    int64_t offset;             /* first entry of this minibatch                                                                            */
+    int64_t rows;               /* samples (feed-forward) or chunks (recurrent) of this minibatch: offset + rows <= perm_len                 */
+    gmpe_mb_field fields[GMPE_MB_MAX_FIELDS];
+} gmpe_minibatch_plan;
+int gmpe_minibatch_gather(const gmpe_config* cfg, int device, const gmpe_minibatch_plan* plan, void* stream);
+
 /* What gmpe_create chose for this handle (recorded by bench.py next to every number). Environment variables override the heuristics —
  * GMPE_G / GMPE_BLOCK (step tile shape), GMPE_GROLL (rollout tile shape), GMPE_AP=0 (run-time-size instead of exact-size kernels),
  * GMPE_NT / GMPE_ROLLNT (nontemporal graph stores of step / rollout launches), GMPE_SPEC (wave specialisation), GMPE_SPLIT / GMPE_CHUNKS

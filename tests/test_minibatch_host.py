@@ -1,0 +1,167 @@
+"""CPU side of the PPO minibatch gather (include/gmpe.h gmpe_minibatch_gather; gmpe.minibatch; DeviceRolloutBuffer.feed_forward_generator /
+recurrent_generator): the exported symbol, the plan struct layout, the argument checks of the C entry point and of the Python wrappers before any launch, and the
+NumPy restatement of the sampler arithmetic and the two index maps (tests/minibatch_lib.py) against the reference's own yields."""
+import ctypes as C
+import os
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+import torch
+
+import gmpe
+from gmpe import _lib
+import minibatch_lib as M
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLD = os.path.join(ROOT, "tests", "golden", "minibatch_generators.npz")
+
+
+def test_symbol_is_exported_and_bound():
+    lib = _lib.load()
+    assert "gmpe_minibatch_gather" in _lib.SYMBOLS and hasattr(lib, "gmpe_minibatch_gather")
+
+
+def test_plan_struct_layout_matches_c_header():
+    src = r'''
+    #include <stdio.h>
+    #include <stddef.h>
+    #include "gmpe.h"
+    int main(void) {
+      printf("%zu %zu %zu %zu %zu\n", sizeof(gmpe_mb_field), offsetof(gmpe_mb_field, slot_stride), offsetof(gmpe_mb_field, src),
+             offsetof(gmpe_mb_field, dst), offsetof(gmpe_mb_field, row_bytes));
+      printf("%zu %zu %zu %zu %zu %zu %zu\n", sizeof(gmpe_minibatch_plan), offsetof(gmpe_minibatch_plan, L), offsetof(gmpe_minibatch_plan, perm),
+             offsetof(gmpe_minibatch_plan, perm_len), offsetof(gmpe_minibatch_plan, offset), offsetof(gmpe_minibatch_plan, rows),
+             offsetof(gmpe_minibatch_plan, fields));
+      printf("%d %d %d %d %d %d %d %d\n", GMPE_MB_FEED_FORWARD, GMPE_MB_RECURRENT, GMPE_MB_ROW, GMPE_MB_ENV_ROW, GMPE_MB_CHUNK_HEAD, GMPE_MB_TABLE_NODE,
+             GMPE_MB_TABLE_ADJ, GMPE_MB_MAX_FIELDS);
+      return 0; }'''
+    with tempfile.TemporaryDirectory() as td:
+        cpath, exe = os.path.join(td, "t.c"), os.path.join(td, "t")
+        open(cpath, "w").write(src)
+        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", exe, cpath])
+        out = [int(x) for x in subprocess.check_output([exe]).decode().split()]
+    Fd, P = _lib.GmpeMbField, _lib.GmpeMinibatchPlan
+    assert out[:5] == [C.sizeof(Fd), Fd.slot_stride.offset, Fd.src.offset, Fd.dst.offset, Fd.row_bytes.offset]
+    assert out[5:12] == [C.sizeof(P), P.L.offset, P.perm.offset, P.perm_len.offset, P.offset.offset, P.rows.offset, P.fields.offset]
+    assert out[12:] == [_lib.MB_FEED_FORWARD, _lib.MB_RECURRENT, _lib.MB_ROW, _lib.MB_ENV_ROW, _lib.MB_CHUNK_HEAD, _lib.MB_TABLE_NODE, _lib.MB_TABLE_ADJ,
+                        _lib.MB_MAX_FIELDS]
+
+
+def _plan(**kw):
+    p = _lib.GmpeMinibatchPlan()
+    p.mode, p.num_fields, p.T, p.N, p.A, p.L = _lib.MB_FEED_FORWARD, 1, 4, 3, 2, 1
+    p.perm, p.perm_len, p.offset, p.rows = 0x10000, 24, 0, 8                  # fake device addresses: nothing may be touched before the checks pass
+    f = p.fields[0]
+    f.kind, f.row_bytes, f.slot_stride, f.src, f.dst = _lib.MB_ROW, 16, 3 * 2 * 16, 0x20000, 0x30000
+    for k, v in kw.items():
+        if k.startswith("f_"):
+            setattr(f, k[2:], v)
+        else:
+            setattr(p, k, v)
+    return p
+
+
+@pytest.mark.parametrize("bad", [
+    dict(mode=7), dict(num_fields=0), dict(num_fields=_lib.MB_MAX_FIELDS + 1), dict(T=0), dict(N=0), dict(mode=_lib.MB_RECURRENT, L=0),
+    dict(T=1 << 16, N=1 << 16, A=1), dict(perm=None), dict(perm=0x10004), dict(rows=0), dict(offset=-1), dict(offset=20),
+    dict(f_kind=9), dict(f_src=None), dict(f_dst=None), dict(f_row_bytes=6), dict(f_row_bytes=0), dict(f_slot_stride=16),
+    dict(f_kind=_lib.MB_CHUNK_HEAD), dict(f_dst=0x30002), dict(f_kind=_lib.MB_TABLE_NODE),
+])
+def test_c_entry_point_refuses_bad_plans_before_any_device_call(bad):
+    lib = _lib.load()
+    assert lib.gmpe_minibatch_gather(None, 0, C.byref(_plan(**bad)), None) == -1
+    assert lib.gmpe_last_error().decode().startswith("gmpe_minibatch_gather:")
+
+
+def test_c_entry_point_checks_table_kinds_against_the_config():
+    lib = _lib.load()
+    cfg = gmpe.make_config(num_envs=3, num_agents=2, episode_length=4)
+    E, W, F = cfg.num_entities, cfg.entity_table_width, cfg.node_feats
+    ok = dict(f_kind=_lib.MB_TABLE_ADJ, f_row_bytes=E * E * 4, f_slot_stride=3 * W * 8)
+    assert lib.gmpe_minibatch_gather(None, 0, C.byref(_plan(**ok)), None) == -1                        # no config
+    for bad in (dict(f_row_bytes=E * E * 4 + 4), dict(f_slot_stride=3 * W * 8 - 8), dict(f_src=0x20004), dict(A=3),
+                dict(f_kind=_lib.MB_TABLE_NODE, f_row_bytes=E * E * 4), dict(f_kind=_lib.MB_TABLE_NODE, f_row_bytes=E * F * 4, f_dst=0x30004)):
+        assert lib.gmpe_minibatch_gather(C.byref(cfg), 0, C.byref(_plan(**dict(ok, **bad))), None) == -1, bad
+    assert lib.gmpe_minibatch_gather(None, 0, None, None) == -1
+
+
+def test_python_wrappers_refuse_bad_arguments_before_any_launch():
+    from gmpe.minibatch import Gather, device_perm, feed_forward_sizes
+    cfg = gmpe.make_config(num_envs=3, num_agents=2, episode_length=4)
+    T, N, A, E = 4, 3, 2, cfg.num_entities
+    z = lambda *s, dt=torch.float32: torch.zeros(s, dtype=dt)
+    arrays = dict(obs=z(T + 1, N, A, cfg.obs_dim), agent_id=z(T + 1, N, A, 1, dt=torch.int32), masks=z(T + 1, N, A, 1), active_masks=z(T + 1, N, A, 1),
+                  node_obs=z(T + 1, N, A, E, cfg.node_feats), adj=z(T + 1, N, E, E))
+    with pytest.raises(ValueError, match="CUDA"):
+        Gather(cfg, arrays)                                                     # host tensors: no CPU fallback
+    for k, v in (("obs", None), ("masks", None)):
+        with pytest.raises(ValueError):
+            Gather(cfg, dict(arrays, **{k: v}))
+    with pytest.raises(ValueError, match="unknown"):
+        Gather(cfg, dict(arrays, values=z(1)))
+    with pytest.raises(ValueError, match="agents"):
+        Gather(gmpe.make_config(num_envs=3, num_agents=3, episode_length=4), arrays)
+    with pytest.raises(AssertionError, match=r"PPO requires the number of processes \(3\) \* number of steps \(4\) \* number of agents \(2\) = 24"):
+        feed_forward_sizes(T, N, A, num_mini_batch=25)
+    with pytest.raises(ValueError):
+        device_perm(torch.arange(5), 6, "cpu")                                  # wrong length
+    with pytest.raises(ValueError):
+        device_perm(torch.arange(6, dtype=torch.int32), 6, "cpu")              # wrong dtype
+    with pytest.raises(ValueError, match="lie in"):
+        device_perm(torch.tensor([0, 1, 2, 3, 4, 6]), 6, "cpu")
+    with pytest.raises(ValueError):
+        device_perm("host", 6, "cpu")
+
+
+def test_buffer_methods_refuse_bad_learner_arrays_and_the_naive_generator():
+    from gmpe.rollout import DeviceRolloutBuffer
+    b = DeviceRolloutBuffer.__new__(DeviceRolloutBuffer)                       # no engine needed for the checks
+    b.T, b.engine = 4, type("E", (), dict(N=3, A=2, device=torch.device("cpu")))()
+    b.obs = b.agent_id = b.masks = b.active_masks = b.value_preds = b.returns = b.available_actions = b.entity_table = None
+    b._node_obs, b._adj = torch.zeros(1), torch.zeros(1)
+    with pytest.raises(ValueError, match="rnn_states"):
+        b.minibatch_arrays(dict(rnn_states=torch.zeros(4, 3, 2, 1, 8)))        # T, not T+1 slots
+    with pytest.raises(ValueError, match="actions"):
+        b.minibatch_arrays(dict(actions=torch.zeros(5, 3, 2, 1)))
+    with pytest.raises(ValueError, match="unknown"):
+        b.minibatch_arrays(dict(values=torch.zeros(5, 3, 2, 1)))
+    with pytest.raises(ValueError, match="advantages"):
+        b._advantages(torch.zeros(5, 3, 2, 1))
+    with pytest.raises(NotImplementedError, match="IndexError"):
+        b.naive_recurrent_generator(torch.zeros(4, 3, 2, 1), 2)
+
+
+def test_numpy_restatement_equals_the_reference_bit_for_bit():
+    g = np.load(GOLD)
+    T, N, A = int(g["T"]), int(g["N"]), int(g["A"])
+    inp = {k[3:]: g[k] for k in g.files if k.startswith("in_")}
+    assert "IndexError" in str(g["naive_error"])
+    seen_rec_cross = left_chunks = False
+    for case in g["cases"]:
+        case = str(case)
+        perm, nmb, L = g[case + "_perm"], int(g[case + "_num_mini_batch"]), int(g[case + "_data_chunk_length"])
+        central, avail = bool(g[case + "_centralized"]), bool(g[case + "_avail"])
+        arrays = dict(inp, available_actions=inp["available_actions"] if avail else None)
+        if bool(g[case + "_recurrent"]):
+            sampler = M.rec_sampler(T, N, A, nmb, L)
+            assert T % L and (N * T * A) % L, case                            # chunks cross agents / envs; samples left over
+            left_chunks |= bool((N * T * A // L) % nmb)
+        else:
+            sampler = M.ff_sampler(T, N, A, nmb)
+        assert len(sampler) == int(g[case + "_num_batches"])
+        for b, (off, rows) in enumerate(sampler):
+            if bool(g[case + "_recurrent"]):
+                (t, n, a), heads = M.rec_samples(perm, off, rows, T, N, A, L)
+                seen_rec_cross |= bool((np.diff(n) != 0).any() or (np.diff(a.reshape(L, -1), axis=0) != 0).any())
+                o = M.gather(arrays, t, n, a, central, heads)
+            else:
+                o = M.gather(arrays, *M.ff_samples(perm, off, rows, T, N, A), central)
+            for k in M.NAMES:
+                ref = g["%s_%d_%s" % (case, b, k)]
+                if bool(g["%s_%d_%s_none" % (case, b, k)]):
+                    assert o[k] is None, (case, b, k)
+                    continue
+                assert o[k].dtype == ref.dtype and o[k].shape == ref.shape and np.array_equal(o[k], ref), (case, b, k)
+    assert seen_rec_cross and left_chunks
