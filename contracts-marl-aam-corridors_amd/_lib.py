@@ -17,7 +17,8 @@ SYMBOLS = ["gmpe_abi_version", "gmpe_last_error", "gmpe_obs_dim", "gmpe_node_fea
            "gmpe_rollout_steps", "gmpe_get_tuning", "gmpe_step_many_launches", "gmpe_edges_from_adj_compact",
            "gmpe_set_control_override", "gmpe_field_device_ptr", "gmpe_step_envs", "gmpe_step_many_envs",
            "gmpe_entity_table_width", "gmpe_expand_node_obs", "gmpe_expand_adj",
-           "gmpe_returns_workspace_bytes", "gmpe_compute_returns", "gmpe_available_actions_from_dones", "gmpe_minibatch_gather"]
+           "gmpe_returns_workspace_bytes", "gmpe_compute_returns", "gmpe_available_actions_from_dones", "gmpe_minibatch_gather",
+           "gmpe_insert_learner"]
 
 
 class GmpeOutputs(C.Structure):
@@ -57,6 +58,17 @@ class GmpeAvailPlan(C.Structure):
     """gmpe_avail_plan (include/gmpe.h): the stop-action rows of available_actions from the previous step's dones."""
     _fields_ = [("dones", C.c_void_p), ("available_actions", C.c_void_p), ("lanes", C.c_int64), ("n_actions", C.c_int32),
                 ("num_positions", C.c_int32), ("first", C.c_int32), ("count", C.c_int32), ("stride_dones", C.c_int64), ("stride_out", C.c_int64)]
+
+
+class GmpeLearnerPlan(C.Structure):
+    """gmpe_learner_plan (include/gmpe.h): the policy's outputs of one step into the rollout buffer's slots, done rows of the RNN states zeroed."""
+    _fields_ = [("lanes", C.c_int64), ("t", C.c_int32), ("num_steps", C.c_int32), ("recurrent_n", C.c_int32), ("hidden", C.c_int32),
+                ("hidden_critic", C.c_int32), ("act_dim", C.c_int32), ("actions_int64", C.c_int32), ("reserved", C.c_int32),
+                ("dones", C.c_void_p), ("values", C.c_void_p), ("actions_in", C.c_void_p), ("log_probs_in", C.c_void_p), ("rnn_in", C.c_void_p),
+                ("rnn_critic_in", C.c_void_p), ("value_preds", C.c_void_p), ("actions", C.c_void_p), ("action_log_probs", C.c_void_p),
+                ("rnn_states", C.c_void_p), ("rnn_states_critic", C.c_void_p), ("stride_dones", C.c_int64), ("stride_value_preds", C.c_int64),
+                ("stride_actions", C.c_int64), ("stride_action_log_probs", C.c_int64), ("stride_rnn_states", C.c_int64),
+                ("stride_rnn_states_critic", C.c_int64)]
 
 
 MB_FEED_FORWARD, MB_RECURRENT = 0, 1
@@ -128,6 +140,7 @@ def load():
     lib.gmpe_compute_returns.argtypes = [I, C.POINTER(GmpeReturnsPlan), P]
     lib.gmpe_available_actions_from_dones.argtypes = [I, C.POINTER(GmpeAvailPlan), P]
     lib.gmpe_minibatch_gather.argtypes = [C.POINTER(GmpeConfig), I, C.POINTER(GmpeMinibatchPlan), P]
+    lib.gmpe_insert_learner.argtypes = [I, C.POINTER(GmpeLearnerPlan), P]
     from .config import ABI_VERSION
     if lib.gmpe_abi_version() != ABI_VERSION:
         raise GmpeError("libgmpe.so ABI version mismatch")

@@ -546,3 +546,87 @@ def available_actions_from_dones(dones, out, first=0, count=None):
     plan = _lib.GmpeAvailPlan(dones.data_ptr(), out.data_ptr(), lanes, n, T, int(first), count, lanes, lanes * n)
     _lib.check(_lib.load().gmpe_available_actions_from_dones(dev.index, C.byref(plan), _stream_of(dev)), "gmpe_available_actions_from_dones")
     return out
+
+
+# ---------------------------------------------------------------------- the learner's fields of a rollout step (gmpe_learner.hip)
+# input name -> (buffer array, whether it has slot T, dtypes the input may have)
+LEARNER_INPUTS = dict(values=("value_preds", True, (torch.float32,)), actions=("actions", False, (torch.int64, torch.float32)),
+                      action_log_probs=("action_log_probs", False, (torch.float32,)), rnn_states=("rnn_states", True, (torch.float32,)),
+                      rnn_states_critic=("rnn_states_critic", True, (torch.float32,)))
+
+
+def _slots(name, t, lead, tail_dim, dev):
+    """A buffer array [S, *lead, *tail] (tail_dim trailing dims): float32 on `dev`, each slot contiguous, slots stride(0) elements apart; returns the tail."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 1 + len(lead) + tail_dim or tuple(t.shape[1:1 + len(lead)]) != lead:
+        raise ValueError("%s must be a float32 tensor [slots, %s, ...] with %d trailing dims" % (name, ", ".join(str(x) for x in lead), tail_dim))
+    if not t[0].is_contiguous() or t.stride(0) < t[0].numel():
+        raise ValueError("%s: every slot must be contiguous and the slots must not overlap" % name)
+    if t.device != dev:
+        raise ValueError("%s must be on %s (the device of the other arrays)" % (name, dev))
+    return tuple(int(x) for x in t.shape[1 + len(lead):])
+
+
+def insert_learner(step, dones, arrays, values=None, actions=None, action_log_probs=None, rnn_states=None, rnn_states_critic=None):
+    """GMPERunner.insert's learner fields of step `step` (graph_mpe_runner.py:384-392 + graph_buffer.py:229-234) as one launch on the current stream
+    (gmpe_insert_learner): value_preds[step] = values, actions[step] = float32(actions), action_log_probs[step] = action_log_probs, and
+    rnn_states[step + 1] / rnn_states_critic[step + 1] = the policy's states with the rows of every agent done at `step` (dones[step] != 0) zeroed.
+      dones: uint8 / bool [T, N, A] (each slot contiguous; slot `step` is read on the device, no host sync);
+      arrays: dict of the buffer's arrays, some of value_preds [T+1, N, A, 1], actions / action_log_probs [T, N, A, k],
+              rnn_states / rnn_states_critic [T+1, N, A, R, H] (float32; each slot contiguous, any stride(0) of at least one slot: views of a slab);
+      inputs: the policy's outputs as contiguous device tensors with N*A rows — values f32 [N*A, 1], actions int64 (what the policy returns) or f32
+              [N*A, k], action_log_probs f32 [N*A, k], rnn_states / rnn_states_critic f32 [N*A, R, H]. None skips a field.
+    Every argument is checked (ValueError) before the launch."""
+    if not isinstance(dones, torch.Tensor) or dones.dtype not in (torch.uint8, torch.bool) or dones.dim() < 2 or not dones[0].is_contiguous():
+        raise ValueError("dones must be a uint8 / bool tensor [T, ...] with contiguous slots")
+    dev = dones.device
+    T, lead = int(dones.shape[0]), tuple(int(x) for x in dones.shape[1:])
+    lanes = int(np.prod(lead, dtype=np.int64))
+    if not 0 <= int(step) < T or lanes < 1:
+        raise ValueError("need 0 <= step < T = %d and at least one lane" % T)
+    unknown = set(arrays) - {v[0] for v in LEARNER_INPUTS.values()}
+    if unknown:
+        raise ValueError("unknown learner arrays: %s" % sorted(unknown))
+    given = dict(values=values, actions=actions, action_log_probs=action_log_probs, rnn_states=rnn_states, rnn_states_critic=rnn_states_critic)
+    plan = _lib.GmpeLearnerPlan()
+    plan.lanes, plan.t, plan.num_steps = lanes, int(step), T
+    plan.dones, plan.stride_dones = dones.data_ptr(), dones.stride(0)
+    plan.recurrent_n, plan.hidden, plan.hidden_critic, plan.act_dim = 1, 1, 1, 1
+    keep = []
+    for name, x in given.items():
+        if x is None:
+            continue
+        out, has_last, dtypes = LEARNER_INPUTS[name]
+        buf = arrays.get(out)
+        if buf is None:
+            raise ValueError("%s given without the %s array it goes to" % (name, out))
+        tail = _slots(out, buf, lead, 2 if name.startswith("rnn") else 1, dev)
+        if buf.shape[0] != T + (1 if has_last else 0):
+            raise ValueError("%s must hold %d slots (T = %d)" % (out, T + (1 if has_last else 0), T))
+        if not isinstance(x, torch.Tensor) or x.dtype not in dtypes or not x.is_contiguous() or x.numel() != lanes * int(np.prod(tail)) or \
+                (name != "values" and tuple(x.shape[-len(tail):]) != tail):
+            raise ValueError("%s must be a contiguous %s tensor [%d, %s]" % (name, "/".join(str(d) for d in dtypes), lanes, ", ".join(map(str, tail))))
+        if x.device != dev:
+            raise ValueError("%s must be on %s (the device of the other arrays)" % (name, dev))
+        keep.append(x)
+        if name == "values":
+            plan.values, plan.value_preds, plan.stride_value_preds = x.data_ptr(), buf.data_ptr(), buf.stride(0)
+        elif name == "actions":
+            plan.actions_in, plan.actions, plan.stride_actions = x.data_ptr(), buf.data_ptr(), buf.stride(0)
+            plan.actions_int64, plan.act_dim = int(x.dtype == torch.int64), tail[0]
+        elif name == "action_log_probs":
+            plan.log_probs_in, plan.action_log_probs, plan.stride_action_log_probs = x.data_ptr(), buf.data_ptr(), buf.stride(0)
+            plan.act_dim = tail[0]
+        elif name == "rnn_states":
+            plan.rnn_in, plan.rnn_states, plan.stride_rnn_states = x.data_ptr(), buf.data_ptr(), buf.stride(0)
+            plan.recurrent_n, plan.hidden = tail
+        else:
+            plan.rnn_critic_in, plan.rnn_states_critic, plan.stride_rnn_states_critic = x.data_ptr(), buf.data_ptr(), buf.stride(0)
+            plan.recurrent_n, plan.hidden_critic = tail
+    if actions is not None and action_log_probs is not None and arrays["actions"].shape[-1] != arrays["action_log_probs"].shape[-1]:
+        raise ValueError("actions and action_log_probs must have the same last dim")
+    if rnn_states is not None and rnn_states_critic is not None and arrays["rnn_states"].shape[-2] != arrays["rnn_states_critic"].shape[-2]:
+        raise ValueError("rnn_states and rnn_states_critic must have the same recurrent_N")
+    if not keep:
+        return
+    _need_cuda(dev)
+    _lib.check(_lib.load().gmpe_insert_learner(dev.index, C.byref(plan), _stream_of(dev)), "gmpe_insert_learner")

@@ -8,15 +8,21 @@ rewards. The engine's output pointers are re-bound to slot t+1 before every step
 the rollout in place: no host hop and no device-to-device copy of the 16 KB/env adjacency.
 Opt-in policy-side storage (policy_storage_spec): value_preds / returns / bad_masks / available_actions [T+1, ...] and advantages [T, ...],
 with compute_returns / normalized_advantages (GraphReplayBuffer.compute_returns, GR_MAPPO.train's advantage lines) and the stop-action rows of
-available_actions (graph_mpe_runner.py:263-335) computed on the device. rnn states, log-probs and actions stay with the learner.
+available_actions (graph_mpe_runner.py:263-335) computed on the device.
+Opt-in learner-side storage (learner_storage_spec): rnn_states / rnn_states_critic [T+1, N, A, R, H] and actions / action_log_probs [T, N, A, k], written
+with value_preds by ONE launch per step from the policy's outputs (insert_step / insert_external keywords, gmpe_insert_learner: the runner's
+`rnn_states[dones] = 0` on the device, no host sync) and carried by after_update: with every field kept, the buffer is a whole device GraphReplayBuffer.
+The open-loop collect(action_sets) and the sharded collectors (sharding.ShardedRolloutCollector, vec_env.MultiDeviceGraphMPEVecEnv) have no policy output
+to store: they never write the learner fields.
 """
 import torch
 
 from .config import NODE_FEATS
-from .engine import StepOutputs, available_actions_from_dones, compute_returns, denorm_scalars, returns_workspace_bytes
+from .engine import StepOutputs, available_actions_from_dones, compute_returns, denorm_scalars, insert_learner, returns_workspace_bytes
 from .minibatch import LEARNER, feed_forward_generator, recurrent_generator
 
 POLICY_FIELDS = ("value_preds", "returns", "bad_masks", "available_actions", "advantages")
+LEARNER_FIELDS = ("rnn_states", "rnn_states_critic", "actions", "action_log_probs")
 
 
 def storage_spec(cfg, episode_length, adj_compact, node_form, with_adj=True):
@@ -53,16 +59,37 @@ def policy_storage_spec(cfg, episode_length, fields=POLICY_FIELDS):
     return {k: (torch.float32, shapes[k]) for k in POLICY_FIELDS if k in fields}
 
 
+def learner_storage_spec(cfg, episode_length, fields=LEARNER_FIELDS, recurrent_N=1, hidden_size=64, hidden_size_critic=None, act_dim=1):
+    """name -> (dtype, shape) of the learner-side arrays a DeviceRolloutBuffer keeps on request (graph_buffer.py:114-120, 142-154 shapes, float32, zeros):
+    rnn_states [T+1, N, A, recurrent_N, hidden_size], rnn_states_critic the same with hidden_size_critic (default hidden_size, as the reference's
+    zeros_like), actions / action_log_probs [T, N, A, act_dim] (1 for the discrete action space)."""
+    N, A = cfg.num_envs, cfg.num_agents
+    T, T1 = int(episode_length), int(episode_length) + 1
+    R, H, k = int(recurrent_N), int(hidden_size), int(act_dim)
+    Hc = H if hidden_size_critic is None else int(hidden_size_critic)
+    if min(R, H, Hc, k) < 1:
+        raise ValueError("recurrent_N, hidden_size, hidden_size_critic and act_dim must be >= 1")
+    shapes = dict(rnn_states=(T1, N, A, R, H), rnn_states_critic=(T1, N, A, R, Hc), actions=(T, N, A, k), action_log_probs=(T, N, A, k))
+    unknown = set(fields) - set(shapes)
+    if unknown:
+        raise ValueError("unknown learner fields: %s" % sorted(unknown))
+    return {k_: (torch.float32, shapes[k_]) for k_ in LEARNER_FIELDS if k_ in fields}
+
+
 _ONES = ("masks", "active_masks", "bad_masks", "available_actions")   # what GraphReplayBuffer starts with ones (graph_buffer.py:132, 155-162)
 
 
 class DeviceRolloutBuffer(object):
-    def __init__(self, engine, episode_length, use_centralized_V=True, storage=None, policy_fields=None, args=None):
+    def __init__(self, engine, episode_length, use_centralized_V=True, storage=None, policy_fields=None, args=None, learner_fields=None,
+                 recurrent_N=None, hidden_size=None, hidden_size_critic=None, act_dim=None):
         """storage: optional dict name -> caller-owned tensor for some or all of the arrays of storage_spec (e.g. views of ONE byte slab that a collective ships
         as a whole, sharding.ShardedRolloutCollector); anything missing is allocated here.
         policy_fields: None (none), "all", or some of POLICY_FIELDS — the policy-side arrays of policy_storage_spec this buffer keeps (a storage entry of
         such a name requests it too). args: the runner's args (gamma, gae_lambda, use_gae, use_proper_time_limits, use_valuenorm, use_popart), read by
-        compute_returns / normalized_advantages."""
+        compute_returns / normalized_advantages.
+        learner_fields: None (none), "all", or some of LEARNER_FIELDS — the learner-side arrays of learner_storage_spec this buffer keeps (a storage entry
+        of such a name requests it too), written by insert_step / insert_external from the policy's outputs. Their sizes: recurrent_N / hidden_size from
+        these keywords, else from args, else the reference's defaults (1, 64); hidden_size_critic defaults to hidden_size, act_dim to 1 (Discrete)."""
         self.engine = engine
         self.T = int(episode_length)
         self.use_centralized_V = bool(use_centralized_V)
@@ -73,8 +100,12 @@ class DeviceRolloutBuffer(object):
         policy = set(POLICY_FIELDS if policy_fields == "all" else (policy_fields or ())) | (set(storage) & set(POLICY_FIELDS))
         spec = storage_spec(c, self.T, engine.adj_compact, self.node_form, with_adj=self.adj_form != "none")
         spec.update(policy_storage_spec(c, self.T, policy))
+        learner = set(LEARNER_FIELDS if learner_fields == "all" else (learner_fields or ())) | (set(storage) & set(LEARNER_FIELDS))
+        pick = lambda v, name, default: int(v) if v is not None else int(getattr(args, name, default) if args is not None else default)
+        spec.update(learner_storage_spec(c, self.T, learner, recurrent_N=pick(recurrent_N, "recurrent_N", 1), hidden_size=pick(hidden_size, "hidden_size", 64),
+                                         hidden_size_critic=hidden_size_critic, act_dim=1 if act_dim is None else act_dim))
         self._adj = None
-        for name in POLICY_FIELDS:
+        for name in POLICY_FIELDS + LEARNER_FIELDS:
             setattr(self, name, None)
         for name, (dt, shape) in spec.items():
             t = storage.pop(name, None)
@@ -157,10 +188,23 @@ class DeviceRolloutBuffer(object):
         self.engine.reset()
         self.step = 0
 
-    def insert_step(self, action_idx, values=None):
+    def insert_step(self, action_idx, values=None, *, actions=None, action_log_probs=None, rnn_states=None, rnn_states_critic=None):
         """One env step written straight into slot step+1 (+ masks), GraphReplayBuffer.insert semantics. `values` (the policy's [N, A, 1] values of this
-        step, buffer with value_preds) go to value_preds[step] (graph_buffer.py:234); with available_actions the step's stop-action slot is written too."""
+        step, buffer with value_preds) go to value_preds[step] (graph_buffer.py:234); with available_actions the step's stop-action slot is written too.
+        The learner keywords take the policy's own outputs of this step in its [N*A, ...] shapes — actions int64 [N*A, k], action_log_probs [N*A, k],
+        rnn_states / rnn_states_critic [N*A, R, H] — each needing its buffer array (learner_fields). With any of them the env step runs first, then ONE launch
+        (gmpe_insert_learner) writes values, actions[step], action_log_probs[step] and the RNN states of slot step + 1 with the rows of the agents this
+        step made done zeroed (GMPERunner.insert, graph_mpe_runner.py:386-392)."""
         t = self.step
+        learner = self._learner_inputs(values, actions, action_log_probs, rnn_states, rnn_states_critic, "insert_step")
+        if learner is not None:
+            self.available_actions_for(t)
+            self._bind(t + 1)
+            self.engine.step(action_idx)
+            self.engine.masks_from_dones(self.dones[t], self.masks[t + 1], self.active_masks[t + 1])
+            insert_learner(t, self.dones, self._learner_arrays(), **learner)
+            self.step = (t + 1) % self.T
+            return self.engine.out
         if values is not None:
             if self.value_preds is None:
                 raise ValueError("insert_step(values=...) needs a buffer with value_preds (policy_fields)")
@@ -173,11 +217,14 @@ class DeviceRolloutBuffer(object):
         self.step = (t + 1) % self.T
         return self.engine.out
 
-    def insert_external(self, obs, agent_id, node_obs, adj, rewards, dones):
+    def insert_external(self, obs, agent_id, node_obs, adj, rewards, dones, values=None, *, actions=None, action_log_probs=None, rnn_states=None,
+                        rnn_states_critic=None):
         """GraphReplayBuffer.insert's env-side arguments for step outputs produced elsewhere (a replayed log, another engine):
         device or host tensors in the engine's shapes ([N,A,D], [N,A,1], [N,A,E,F], [N,E,E] or [N,A,E,E], [N,A], [N,A] bool/u8).
-        Same slot placement and mask rules as insert_step (graph_buffer.py:223-251, graph_mpe_runner.py:395-405)."""
+        Same slot placement and mask rules as insert_step (graph_buffer.py:223-251, graph_mpe_runner.py:395-405); the policy keywords as insert_step's,
+        written by one launch after the dones."""
         t, e = self.step, self.engine
+        learner = self._learner_inputs(values, actions, action_log_probs, rnn_states, rnn_states_critic, "insert_external")
         dev = e.device
         put = lambda dst, src: dst.copy_(torch.as_tensor(src).to(device=dev, dtype=dst.dtype).reshape(dst.shape))
         if self._node_obs is None:
@@ -193,13 +240,38 @@ class DeviceRolloutBuffer(object):
         self.available_actions_for(t)
         put(self._adj[t + 1], a); put(self.rewards[t], rewards); put(self.dones[t], torch.as_tensor(dones).to(torch.uint8))
         e.masks_from_dones(self.dones[t], self.masks[t + 1], self.active_masks[t + 1])
+        if learner is not None:
+            insert_learner(t, self.dones, self._learner_arrays(), **learner)
         self.step = (t + 1) % self.T
+
+    def _learner_arrays(self):
+        return {k: getattr(self, k) for k in ("value_preds",) + LEARNER_FIELDS if getattr(self, k) is not None}
+
+    def _learner_inputs(self, values, actions, action_log_probs, rnn_states, rnn_states_critic, what):
+        """The policy's outputs as device tensors for insert_learner (no copy when they already are: float32, int64 actions kept), or None when only
+        `values` (or nothing) is given to insert_step, which keeps its own path. A field the buffer does not keep raises ValueError."""
+        given = dict(values=values, actions=actions, action_log_probs=action_log_probs, rnn_states=rnn_states, rnn_states_critic=rnn_states_critic)
+        if all(given[k] is None for k in LEARNER_FIELDS) and (what == "insert_step" or values is None):
+            return None
+        dev = self.engine.device
+        out = {}
+        for name, x in given.items():
+            if x is None:
+                continue
+            dst = "value_preds" if name == "values" else name
+            if getattr(self, dst) is None:
+                raise ValueError("%s(%s=...) needs a buffer with %s (%s)" % (what, name, dst, "policy_fields" if name == "values" else "learner_fields"))
+            x = torch.as_tensor(x).to(device=dev)
+            if not (name == "actions" and x.dtype == torch.int64):
+                x = x.to(torch.float32)
+            out[name] = x.contiguous()
+        return out
 
     def collect(self, action_sets, num_steps=None):
         """The runner's collect loop with a fixed action source (graph_mpe_runner.py:57-103: `for step in range(episode_length)`:
         envs.step -> buffer.insert) as ONE launch of the persistent rollout kernel: step k reads action_sets[k % S] and writes slot
         step+k+1 of every array in place, masks / active_masks included (gmpe_rollout_steps). Same results as `num_steps`
-        insert_step calls. Falls back to that loop on the split big-E path."""
+        insert_step calls. Falls back to that loop on the split big-E path. There is no policy output here: the learner fields are not written."""
         K = self.T - self.step if num_steps is None else int(num_steps)
         e, a = self.engine, action_sets
         if not self._one_launch:
@@ -226,13 +298,14 @@ class DeviceRolloutBuffer(object):
         return e.out
 
     def after_update(self):
-        """graph_buffer.py:253-283: the last slot becomes slot 0 of the next rollout."""
+        """graph_buffer.py:253-283: the last slot becomes slot 0 of the next rollout (rnn_states / rnn_states_critic included; actions and
+        action_log_probs have no slot T)."""
         for buf in self._carried():
             buf[0].copy_(buf[-1])
 
     def _carried(self):
         return [b for b in (self.obs, self._node_obs, self.entity_table, self._adj, self.agent_id, self.masks, self.active_masks,
-                            self.bad_masks, self.available_actions) if b is not None]
+                            self.bad_masks, self.available_actions, self.rnn_states, self.rnn_states_critic) if b is not None]
 
     # ------------------------------------------------------------------ policy side (opt-in: policy_fields)
     def available_actions_for(self, step):
@@ -286,7 +359,8 @@ class DeviceRolloutBuffer(object):
     # ------------------------------------------------------------------ PPO minibatches (GraphReplayBuffer's generators, gmpe_minibatch_gather)
     def minibatch_arrays(self, learner=None):
         """The arrays a minibatch gathers from, in the storage form the buffer keeps (node rows or entity table; materialised, compact or no adjacency) plus the
-        caller-owned learner arrays (rnn_states / rnn_states_critic [T+1, N, A, R, H], actions / action_log_probs [T, N, A, k]; DESIGN §10: not the buffer's)."""
+        learner arrays (rnn_states / rnn_states_critic [T+1, N, A, R, H], actions / action_log_probs [T, N, A, k]): the buffer's own (learner_fields), each
+        overridden by an array of the same name in `learner`."""
         e = self.engine
         N, A, T1 = e.N, e.A, self.T + 1
         arrays = dict(obs=self.obs, agent_id=self.agent_id, masks=self.masks, active_masks=self.active_masks, value_preds=self.value_preds,
@@ -299,6 +373,9 @@ class DeviceRolloutBuffer(object):
             arrays["adj"] = self._adj
         elif self.entity_table is not None:
             arrays["entity_table"] = self.entity_table
+        for name in LEARNER_FIELDS:
+            if getattr(self, name, None) is not None:
+                arrays[name] = getattr(self, name)
         learner = dict(learner or {})
         unknown = set(learner) - set(LEARNER)
         if unknown:
@@ -321,7 +398,7 @@ class DeviceRolloutBuffer(object):
     def feed_forward_generator(self, advantages, num_mini_batch=None, mini_batch_size=None, *, learner=None, perm=None):
         """GraphReplayBuffer.feed_forward_generator (graph_buffer.py:368-465) from the device arrays: the reference's 16-tuple per minibatch as fresh device
         tensors (agent_id / share_agent_id int32; available_actions None when the buffer keeps none, learner slots None
-        unless `learner` holds them), one gather launch per minibatch (two with the entity-table forms). perm: None draws torch.randperm on the CPU default
+        unless the buffer or `learner` holds them), one gather launch per minibatch (two with the entity-table forms). perm: None draws torch.randperm on the CPU default
         generator as the reference does (a seeded run trains on the same minibatches) and uploads it once; "device" draws on the device; or an int64 tensor."""
         return feed_forward_generator(self.engine.cfg, self.minibatch_arrays(learner), self._advantages(advantages), num_mini_batch, mini_batch_size,
                                       perm=perm, use_centralized_V=self.use_centralized_V)

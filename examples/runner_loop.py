@@ -4,7 +4,8 @@
   (2) device-resident, open loop: `DeviceRolloutBuffer.collect` — ONE launch writes the whole `[T+1, N, A, ...]` rollout in HBM,
       and the GNN's edge list (`process_adj`, onpolicy/algorithms/utils/gnn_new.py:329-358) is built on the device;
   (3) device-resident, policy in the loop: the policy reads slot `step` of the buffer as device tensors and `insert_step` writes slot `step + 1`
-      in place — the runner change of INTEGRATION.md §7 (no NumPy one-hot up, no seven arrays down per step).
+      in place, the policy's outputs (values, actions, log-probs, RNN states) included — the runner change of INTEGRATION.md §7 (no NumPy one-hot up,
+      no seven arrays down per step), followed by returns, PPO minibatches and after_update on the device.
 
 The policy is a stand-in (uniform random actions): the learner is outside this package's scope.
 
@@ -76,31 +77,45 @@ def device_loop(args, episodes, max_edge_dist=1.0):
                 masks_zero=int((buf.masks == 0).sum()))
 
 
-def device_closed_loop(args, episodes):
-    """Policy in the loop without leaving the GPU: GMPERunner.collect's inputs are slot `step` of the device buffer, its integer actions
-    go straight into `insert_step`. The stand-in policy is one linear layer on `obs` (the learner is out of scope); what matters is the data flow."""
+def device_closed_loop(args, episodes, hidden_size=16):
+    """Policy in the loop without leaving the GPU: GMPERunner.collect's inputs are slot `step` of the device buffer, the policy's outputs
+    (values, int64 actions, log-probs, RNN states) go straight into `insert_step`, which writes every learner field in one launch after the env step; then
+    compute_returns -> the PPO generators -> after_update, with no learner-owned array outside the buffer. The stand-in policy is a linear layer on `obs` and a
+    tanh recurrence (the learner is out of scope); what matters is the data flow."""
     import torch
     from gmpe.engine import GmpeEngine
     from gmpe.rollout import DeviceRolloutBuffer
     from gmpe.config import config_from_args
     cfg = config_from_args(args)
     eng = GmpeEngine(cfg, adj_compact=True)
-    buf = DeviceRolloutBuffer(eng, args.episode_length)
+    run_args = argparse.Namespace(gamma=0.99, gae_lambda=0.95, use_gae=True, use_proper_time_limits=False, use_valuenorm=False, use_popart=False,
+                                  recurrent_N=1, hidden_size=hidden_size)
+    buf = DeviceRolloutBuffer(eng, args.episode_length, policy_fields="all", learner_fields="all", args=run_args)
     buf.warmup()                                                                 # GMPERunner.warmup, :213-238
     T, N, A = args.episode_length, cfg.num_envs, cfg.num_agents
     torch.manual_seed(0)
-    head = torch.nn.Linear(cfg.obs_dim, cfg.n_actions).to(eng.device)
+    head = torch.nn.Linear(cfg.obs_dim + hidden_size, cfg.n_actions + 1 + hidden_size).to(eng.device)
+    n_mb = 0
     torch.cuda.synchronize(); t0 = time.perf_counter()
     with torch.no_grad():
         for ep in range(episodes):
             for step in range(T):
-                logits = head(buf.obs[step])                                     # [N, A, n_act] from the slot the env wrote: device tensors, no host hop
-                action = torch.distributions.Categorical(logits=logits).sample() # policy.get_actions' sampled action (:346-355)
-                buf.insert_step(action.to(torch.int32))                          # envs.step + buffer.insert (:82-83, :384-428): slot step+1 written in place
+                h = buf.rnn_states[step].flatten(0, 1)                           # [N*A, 1, H]: zeroed for agents done at step - 1, carried by after_update
+                out = head(torch.cat([buf.obs[step].flatten(0, 1), h[:, 0]], -1))   # slot the env wrote: device tensors, no host hop
+                logits, value, rnn = out[:, :cfg.n_actions], out[:, cfg.n_actions:cfg.n_actions + 1], torch.tanh(out[:, None, cfg.n_actions + 1:])
+                dist = torch.distributions.Categorical(logits=logits)
+                action = dist.sample()[:, None]                                  # int64 [N*A, 1], as policy.get_actions returns it (:346-355)
+                buf.insert_step(action.view(N, A).to(torch.int32), values=value, actions=action, action_log_probs=dist.log_prob(action[:, 0])[:, None],
+                                rnn_states=rnn, rnn_states_critic=rnn)          # envs.step + buffer.insert (:82-83, :384-428), learner fields in one launch
+            buf.compute_returns(head(torch.cat([buf.obs[T].flatten(0, 1), buf.rnn_states[T].flatten(0, 1)[:, 0]], -1))[:, cfg.n_actions].view(N, A, 1))
+            advantages = buf.normalized_advantages()
+            for sample in buf.recurrent_generator(advantages, 2, min(T, 4)):     # the reference's 16-tuple; learner slots from the buffer
+                n_mb += sample[6] is not None and sample[13] is not None
             buf.after_update()
     torch.cuda.synchronize(); dt = time.perf_counter() - t0
     return dict(path="device-resident, policy in the loop", env_steps_per_s=N * episodes * T / dt, mean_step_reward=float(buf.rewards.mean()),
-                shapes=dict(obs=tuple(buf.obs.shape), node_obs=tuple(buf.node_obs.shape), adj=tuple(buf.adj.shape)))
+                minibatches_with_learner_fields=n_mb,
+                shapes=dict(obs=tuple(buf.obs.shape), node_obs=tuple(buf.node_obs.shape), adj=tuple(buf.adj.shape), rnn_states=tuple(buf.rnn_states.shape)))
 
 
 def main(argv=None):

@@ -397,6 +397,40 @@ typedef struct gmpe_avail_plan {
 } gmpe_avail_plan;
 int gmpe_available_actions_from_dones(int device, const gmpe_avail_plan* plan, void* stream);
 
+/* The learner's fields of one rollout step (GMPERunner.insert + GraphReplayBuffer.insert, graph_mpe_runner.py:384-392, graph_buffer.py:229-234) in one launch:
+ *   value_preds[t] = values;  actions[t] = float32(actions_in);  action_log_probs[t] = log_probs_in;
+ *   rnn_states[t + 1] = rnn_in, rnn_states_critic[t + 1] = rnn_critic_in, with the rows of every lane done at step t (dones[t][lane] != 0) zeroed.
+ * The zeroing is per agent (the runner's `rnn_states[dones] = 0`, not dones_env). An input left NULL skips its field; a field's output is required
+ * when its input is given. Slot s of an array is at its slot-0 pointer + s * stride elements; a slot's rows are contiguous ([lanes, k] / [lanes, R, H]).
+ * Inputs are the policy's outputs, contiguous: values f32 [lanes], actions_in int64 or f32 [lanes, k], log_probs_in f32 [lanes, k], rnn_in f32 [lanes, R, H],
+ * rnn_critic_in f32 [lanes, R, hidden_critic]. dones is read from the device (written by the step before on the same stream): no host synchronisation.
+ * Every argument the host can see is checked before any device call; one launch on `stream` (none when no input is given). */
+typedef struct gmpe_learner_plan {
+    int64_t lanes;              /* N*A >= 1                                                                                      */
+    int32_t t;                  /* step, 0 <= t < num_steps                                                                      */
+    int32_t num_steps;          /* T (episode length): value_preds / rnn arrays hold T + 1 slots, actions / log-probs T          */
+    int32_t recurrent_n;        /* R, 1 .. 64                                                                                    */
+    int32_t hidden;             /* H of rnn_states, 1 .. 65536                                                                   */
+    int32_t hidden_critic;      /* H of rnn_states_critic, 1 .. 65536                                                            */
+    int32_t act_dim;            /* k of actions / action_log_probs, 1 .. 64                                                      */
+    int32_t actions_int64;      /* 1: actions_in is int64 (what the policy returns), 0: float32                                  */
+    int32_t reserved;           /* 0                                                                                             */
+    const uint8_t* dones;       /* slot 0 of u8 [T][lanes]; needed with rnn_in or rnn_critic_in                                  */
+    const float* values;        /* [lanes] or NULL                                                                               */
+    const void* actions_in;     /* [lanes, k] or NULL (8-byte aligned when int64)                                               */
+    const float* log_probs_in;  /* [lanes, k] or NULL                                                                            */
+    const float* rnn_in;        /* [lanes, R, H] or NULL                                                                         */
+    const float* rnn_critic_in; /* [lanes, R, hidden_critic] or NULL                                                             */
+    float* value_preds;         /* slot 0 of [T+1][lanes]                                                                        */
+    float* actions;             /* slot 0 of [T][lanes, k]                                                                       */
+    float* action_log_probs;    /* slot 0 of [T][lanes, k]                                                                       */
+    float* rnn_states;          /* slot 0 of [T+1][lanes, R, H]                                                                  */
+    float* rnn_states_critic;   /* slot 0 of [T+1][lanes, R, hidden_critic]                                                      */
+    int64_t stride_dones, stride_value_preds, stride_actions, stride_action_log_probs, stride_rnn_states, stride_rnn_states_critic;
+                                /* elements between consecutive slots, at least one slot each (slots do not overlap)             */
+} gmpe_learner_plan;
+int gmpe_insert_learner(int device, const gmpe_learner_plan* plan, void* stream);
+
 /* PPO minibatches from a rollout (GraphReplayBuffer.feed_forward_generator / recurrent_generator, onpolicy/utils/graph_buffer.py:368-758): one minibatch's rows
  * of every field gathered from the [T+1, N, ...] arrays through a device permutation, as exact byte copies (16-byte vectors where row size and alignment allow)
  * or, for the table kinds, expanded from the f64 entity table with the arithmetic of gmpe_expand_node_obs / gmpe_expand_adj (bit-identical to the engine).
