@@ -13,12 +13,15 @@ __all__ = ["config", "make_config", "config_from_args"]
 
 def __getattr__(name):
     # torch / HIP-dependent modules are imported on first use
-    if name in ("engine", "vec_env", "spaces", "_lib", "sharding", "rollout", "minibatch"):
+    if name in ("engine", "vec_env", "spaces", "_lib", "sharding", "rollout", "minibatch", "evaluate"):
         import importlib
         return importlib.import_module("." + name, __name__)
     if name in ("BatchedGraphMPEVecEnv", "MultiDeviceGraphMPEVecEnv", "GraphMPEEnv", "make_train_env", "make_eval_env"):
         from . import vec_env
         return getattr(vec_env, name)
+    if name == "BatchedEvaluator":
+        from . import evaluate
+        return evaluate.BatchedEvaluator
     if name == "GmpeEngine":
         from . import engine
         return engine.GmpeEngine

@@ -18,7 +18,7 @@ SYMBOLS = ["gmpe_abi_version", "gmpe_last_error", "gmpe_obs_dim", "gmpe_node_fea
            "gmpe_set_control_override", "gmpe_field_device_ptr", "gmpe_step_envs", "gmpe_step_many_envs",
            "gmpe_entity_table_width", "gmpe_expand_node_obs", "gmpe_expand_adj",
            "gmpe_returns_workspace_bytes", "gmpe_compute_returns", "gmpe_available_actions_from_dones", "gmpe_minibatch_gather",
-           "gmpe_insert_learner"]
+           "gmpe_insert_learner", "gmpe_episode_record", "gmpe_episode_metrics", "gmpe_episode_summary"]
 
 
 class GmpeOutputs(C.Structure):
@@ -69,6 +69,30 @@ class GmpeLearnerPlan(C.Structure):
                 ("rnn_states", C.c_void_p), ("rnn_states_critic", C.c_void_p), ("stride_dones", C.c_int64), ("stride_value_preds", C.c_int64),
                 ("stride_actions", C.c_int64), ("stride_action_log_probs", C.c_int64), ("stride_rnn_states", C.c_int64),
                 ("stride_rnn_states_critic", C.c_int64)]
+
+
+class GmpeEpisodeRecordPlan(C.Structure):
+    """gmpe_episode_record_plan (include/gmpe.h): one step of a batch of evaluation episodes, and the masks / stop rows for the next act."""
+    _fields_ = [("num_envs", C.c_int32), ("num_agents", C.c_int32), ("t", C.c_int32), ("num_steps", C.c_int32), ("n_actions", C.c_int32),
+                ("rnn_row", C.c_int32), ("reward", C.c_void_p), ("done", C.c_void_p), ("info", C.c_void_p), ("live", C.c_void_p),
+                ("steps", C.c_void_p), ("ret", C.c_void_p), ("final_info", C.c_void_p), ("masks", C.c_void_p), ("available_actions", C.c_void_p),
+                ("rnn_states", C.c_void_p)]
+
+
+class GmpeEpisodeMetricsPlan(C.Structure):
+    """gmpe_episode_metrics_plan (include/gmpe.h): the per-episode metric columns and the per-agent sums over episodes."""
+    _fields_ = [("num_envs", C.c_int32), ("num_agents", C.c_int32), ("num_steps", C.c_int32), ("reserved", C.c_int32), ("dt", C.c_double),
+                ("min_dist_thresh", C.c_double), ("steps", C.c_void_p), ("ret", C.c_void_p), ("final_info", C.c_void_p), ("episodes", C.c_void_p),
+                ("dists_traveled", C.c_void_p), ("time_taken", C.c_void_p)]
+
+
+class GmpeEpisodeSummaryPlan(C.Structure):
+    """gmpe_episode_summary_plan (include/gmpe.h): min, p10, median, p90, max, mean, std of every column of an f64 table."""
+    _fields_ = [("num_rows", C.c_int64), ("num_columns", C.c_int32), ("success_column", C.c_int32), ("success_agents", C.c_int32),
+                ("reserved", C.c_int32), ("table", C.c_void_p), ("out", C.c_void_p)]
+
+
+EVAL_INFO_WIDTH, EVAL_NUM_COLUMNS, EVAL_NUM_STATS = 18, 16, 7
 
 
 MB_FEED_FORWARD, MB_RECURRENT = 0, 1
@@ -141,6 +165,9 @@ def load():
     lib.gmpe_available_actions_from_dones.argtypes = [I, C.POINTER(GmpeAvailPlan), P]
     lib.gmpe_minibatch_gather.argtypes = [C.POINTER(GmpeConfig), I, C.POINTER(GmpeMinibatchPlan), P]
     lib.gmpe_insert_learner.argtypes = [I, C.POINTER(GmpeLearnerPlan), P]
+    lib.gmpe_episode_record.argtypes = [I, C.POINTER(GmpeEpisodeRecordPlan), P]
+    lib.gmpe_episode_metrics.argtypes = [I, C.POINTER(GmpeEpisodeMetricsPlan), P]
+    lib.gmpe_episode_summary.argtypes = [I, C.POINTER(GmpeEpisodeSummaryPlan), P]
     from .config import ABI_VERSION
     if lib.gmpe_abi_version() != ABI_VERSION:
         raise GmpeError("libgmpe.so ABI version mismatch")

@@ -431,6 +431,97 @@ typedef struct gmpe_learner_plan {
 } gmpe_learner_plan;
 int gmpe_insert_learner(int device, const gmpe_learner_plan* plan, void* stream);
 
+/* ---- Evaluation of a policy over a batch of episodes (handle-less): GMPERunner.render(get_metrics=True) as one episode per env ----
+ * (onpolicy/runner/shared/graph_mpe_runner.py:526-1060, base_runner.py:194-574). Every env plays one episode from a reset; the caller's policy acts,
+ * the engine steps, gmpe_episode_record books the step. No allocation, no host synchronisation, every launch on `stream`.
+ *
+ * gmpe_episode_record, once per step t = 0 .. T-1 after the env step, same stream. For an env that is live:
+ *   ret[n, a] += double(reward[n, a]) (the terminal step's reward counts); when every agent of env n is done or t == T-1 (the render loop's
+ *   break on reset_count > 0, or the end of its range(episode_length)): final_info[n] = info[n], steps[n] = t + 1, live[n] = 0.
+ * A finished env is frozen: the engine's auto-reset keeps stepping it and its later steps are ignored. Info rows are read only for envs that
+ * finish at this step. The same launch writes what the policy acts with at step t + 1, for every env:
+ *   masks f32 [N, A, 1]: 0 where done, all ones in an env whose agents are all done (:630-638);
+ *   available_actions f32 [N, A, n_actions]: the one-hot stop row at n_actions / 2 where the mask is 0, else ones (:570-583);
+ *   rnn_states f32 [N, A, rnn_row] (optional): the rows of done agents zeroed (:628). */
+#define GMPE_EVAL_INFO_WIDTH 18          /* config.INFO_KEYS: 17 render keys + Phase_reached                                          */
+#define GMPE_EVAL_NUM_COLUMNS 16         /* columns of gmpe_episode_metrics, in this order:                                           */
+#define GMPE_EVAL_REWARD 0               /* mean over agents of ret (graph_mpe_runner.py:668)                                         */
+#define GMPE_EVAL_FRAC 1                 /* max over agents of ttg / (T*dt) (np.any(list == 1) is always False there: :661-665)       */
+#define GMPE_EVAL_SUCCESS 2              /* mean over agents of Dist_to_goal < min_dist_thresh (base_runner.py:499-505)              */
+#define GMPE_EVAL_COLLISIONS 3           /* sum over agents, in agent order, of Num_agent_collisions / 2, then Num_obst_collisions     */
+#define GMPE_EVAL_FAIRNESS 4             /* Mean_by_variance of agent A-1                                                             */
+#define GMPE_EVAL_DIST_MEAN 5            /* Distance_mean of agent A-1                                                                */
+#define GMPE_EVAL_TIME_MEAN 6            /* Time_mean of agent A-1                                                                    */
+#define GMPE_EVAL_TIME_FAIRNESS 7        /* Time_mean_by_stddev of agent A-1                                                          */
+#define GMPE_EVAL_STDDEV_PARAM 8         /* 1 / (Distance_variance[A-1] + 0.0001)                                                     */
+#define GMPE_EVAL_TIME_STDDEV_PARAM 9    /* 1 / (Time_stddev[A-1] + 0.0001)                                                           */
+#define GMPE_EVAL_TOTAL_DISTS 10         /* sum over agents of Dists_traveled                                                         */
+#define GMPE_EVAL_TOTAL_TIME 11          /* sum over agents of ttg                                                                    */
+#define GMPE_EVAL_CONFORMANCE 12         /* mean over agents of Conformance                                                           */
+#define GMPE_EVAL_DELTA_SPACE 13         /* mean over agents of Delta_spacing                                                         */
+#define GMPE_EVAL_SPACING_VIOLATIONS 14  /* mean over agents of Spacing_violations                                                     */
+#define GMPE_EVAL_STEPS 15               /* episode length (0: not finished)                                                          */
+typedef struct gmpe_episode_record_plan {
+    int32_t num_envs, num_agents;   /* N >= 1, 1 <= A <= GMPE_MAX_AGENTS                                                            */
+    int32_t t, num_steps;           /* step index 0 <= t < T = episode_length                                                      */
+    int32_t n_actions;              /* row width of available_actions, 1 .. 4096                                                   */
+    int32_t rnn_row;                /* R * H floats per agent of rnn_states, 1 .. 2^20 with rnn_states, else ignored               */
+    const float* reward;            /* [N, A]       the step's outputs (gmpe_outputs of the engine)                                 */
+    const uint8_t* done;            /* [N, A]                                                                                       */
+    const float* info;              /* [N, A, GMPE_EVAL_INFO_WIDTH]                                                                 */
+    uint8_t* live;                  /* [N]          state: 1 until the env's episode ends (the caller sets 1 at the reset)           */
+    int32_t* steps;                 /* [N]          state: episode length once finished                                             */
+    double* ret;                    /* [N, A]       state: sum of rewards                                                           */
+    float* final_info;              /* [N, A, GMPE_EVAL_INFO_WIDTH] state: the info rows of the terminal step                        */
+    float* masks;                   /* [N, A]       out                                                                             */
+    float* available_actions;       /* [N, A, n_actions] out                                                                        */
+    float* rnn_states;              /* [N, A, rnn_row] in place, or NULL                                                            */
+} gmpe_episode_record_plan;
+int gmpe_episode_record(int device, const gmpe_episode_record_plan* plan, void* stream);
+
+/* gmpe_episode_metrics: one f64 row of the GMPE_EVAL_* columns per env from its record, ttg_a = Time_req_to_goal with -1 -> T*dt
+ * (base_runner.py:214-217; the reference never assigns the runner's dt: the world's dt is meant). Sums and means over agents follow NumPy's
+ * pairwise order, so every column equals the reference's float64 NumPy on the same f32 info rows bit for bit. The same launch writes the
+ * per-agent sums over episodes dists_traveled[A] (Dists_traveled) and time_taken[A] (ttg), the render loop's dists_trav_list / time_taken_list
+ * (:680-686), as a fixed-order tree over the N envs: no atomics, bitwise reproducible. One launch. */
+typedef struct gmpe_episode_metrics_plan {
+    int32_t num_envs, num_agents, num_steps, reserved;  /* N, A, T as recorded; reserved 0                                          */
+    double dt;                      /* > 0                                                                                          */
+    double min_dist_thresh;         /* success threshold on Dist_to_goal                                                            */
+    const int32_t* steps;           /* [N]                                                                                          */
+    const double* ret;              /* [N, A]                                                                                       */
+    const float* final_info;        /* [N, A, GMPE_EVAL_INFO_WIDTH]                                                                 */
+    double* episodes;               /* [N, GMPE_EVAL_NUM_COLUMNS] out                                                               */
+    double* dists_traveled;         /* [A] out, or NULL (then time_taken too)                                                       */
+    double* time_taken;             /* [A] out, or NULL                                                                             */
+} gmpe_episode_metrics_plan;
+int gmpe_episode_metrics(int device, const gmpe_episode_metrics_plan* plan, void* stream);
+
+/* gmpe_episode_summary: per column of an f64 [n, num_columns] row-major table, the row of GMPE_EVAL_STAT_* values. Order statistics are exact
+ * (radix selection of the ranks on the f64 bit patterns) and then combined as NumPy 2.x does: p10 / p90 = np.percentile(x, q) with the default
+ * linear method (index (n-1) * (q/100), its floor and floor + 1, _lerp with its t >= 0.5 branch), median = np.median (the middle element, or the
+ * two middle ones added and halved). A NaN in a column makes its order statistics NaN, as in NumPy. Mean and population std (np.std) in f64 with a
+ * fixed-order tree. Column `success_column` (or none when < 0) holds per-episode means over `success_agents` 0/1 values: its statistics are
+ * those of the flattened [n, success_agents] 0/1 matrix, as the render loop's success_rates_arr (:784-789). One workgroup per column, one launch. */
+#define GMPE_EVAL_STAT_MIN 0
+#define GMPE_EVAL_STAT_P10 1
+#define GMPE_EVAL_STAT_MEDIAN 2
+#define GMPE_EVAL_STAT_P90 3
+#define GMPE_EVAL_STAT_MAX 4
+#define GMPE_EVAL_STAT_MEAN 5
+#define GMPE_EVAL_STAT_STD 6
+#define GMPE_EVAL_NUM_STATS 7
+typedef struct gmpe_episode_summary_plan {
+    int64_t num_rows;               /* n, 1 .. 2^31 - 1                                                                             */
+    int32_t num_columns;            /* 1 .. 64                                                                                      */
+    int32_t success_column;         /* -1 or a column index                                                                         */
+    int32_t success_agents;         /* 1 .. GMPE_MAX_AGENTS when success_column >= 0                                                */
+    int32_t reserved;               /* 0                                                                                            */
+    const double* table;            /* [n, num_columns]                                                                             */
+    double* out;                    /* [num_columns, GMPE_EVAL_NUM_STATS]                                                           */
+} gmpe_episode_summary_plan;
+int gmpe_episode_summary(int device, const gmpe_episode_summary_plan* plan, void* stream);
+
 /* PPO minibatches from a rollout (GraphReplayBuffer.feed_forward_generator / recurrent_generator, onpolicy/utils/graph_buffer.py:368-758): one minibatch's rows
  * of every field gathered from the [T+1, N, ...] arrays through a device permutation, as exact byte copies (16-byte vectors where row size and alignment allow)
  * or, for the table kinds, expanded from the f64 entity table with the arithmetic of gmpe_expand_node_obs / gmpe_expand_adj (bit-identical to the engine).
