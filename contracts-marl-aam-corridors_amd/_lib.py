@@ -18,7 +18,8 @@ SYMBOLS = ["gmpe_abi_version", "gmpe_last_error", "gmpe_obs_dim", "gmpe_node_fea
            "gmpe_set_control_override", "gmpe_field_device_ptr", "gmpe_step_envs", "gmpe_step_many_envs",
            "gmpe_entity_table_width", "gmpe_expand_node_obs", "gmpe_expand_adj",
            "gmpe_returns_workspace_bytes", "gmpe_compute_returns", "gmpe_available_actions_from_dones", "gmpe_minibatch_gather",
-           "gmpe_insert_learner", "gmpe_episode_record", "gmpe_episode_metrics", "gmpe_episode_summary"]
+           "gmpe_insert_learner", "gmpe_episode_record", "gmpe_episode_metrics", "gmpe_episode_summary",
+           "gmpe_minibatch_edges", "gmpe_minibatch_edges_workspace_bytes"]
 
 
 class GmpeOutputs(C.Structure):
@@ -112,6 +113,18 @@ class GmpeMinibatchPlan(C.Structure):
                 ("fields", GmpeMbField * MB_MAX_FIELDS)]
 
 
+MBE_ADJ, MBE_ADJ_COMPACT, MBE_TABLE = 0, 1, 2
+
+
+class GmpeMbEdgesPlan(C.Structure):
+    """gmpe_mb_edges_plan (include/gmpe.h): the edge list of one minibatch from the stored adjacency."""
+    _fields_ = [("mode", C.c_int32), ("source", C.c_int32), ("T", C.c_int32), ("N", C.c_int32), ("A", C.c_int32), ("L", C.c_int32), ("E", C.c_int32),
+                ("inclusive", C.c_int32), ("index64", C.c_int32), ("reuse_counts", C.c_int32), ("max_edge_dist", C.c_float), ("reserved", C.c_int32),
+                ("perm", C.c_void_p), ("perm_len", C.c_int64), ("offset", C.c_int64), ("rows", C.c_int64), ("src", C.c_void_p), ("slot_stride", C.c_int64),
+                ("edge_index", C.c_void_p), ("edge_attr", C.c_void_p), ("cap", C.c_int64), ("n_edges", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_size_t)]
+
+
 class GmpeError(RuntimeError):
     pass
 
@@ -164,6 +177,8 @@ def load():
     lib.gmpe_compute_returns.argtypes = [I, C.POINTER(GmpeReturnsPlan), P]
     lib.gmpe_available_actions_from_dones.argtypes = [I, C.POINTER(GmpeAvailPlan), P]
     lib.gmpe_minibatch_gather.argtypes = [C.POINTER(GmpeConfig), I, C.POINTER(GmpeMinibatchPlan), P]
+    lib.gmpe_minibatch_edges.argtypes = [C.POINTER(GmpeConfig), I, C.POINTER(GmpeMbEdgesPlan), P]
+    lib.gmpe_minibatch_edges_workspace_bytes.argtypes = [C.c_int64, C.POINTER(C.c_size_t)]
     lib.gmpe_insert_learner.argtypes = [I, C.POINTER(GmpeLearnerPlan), P]
     lib.gmpe_episode_record.argtypes = [I, C.POINTER(GmpeEpisodeRecordPlan), P]
     lib.gmpe_episode_metrics.argtypes = [I, C.POINTER(GmpeEpisodeMetricsPlan), P]

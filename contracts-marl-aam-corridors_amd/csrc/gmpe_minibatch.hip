@@ -15,6 +15,7 @@
 
 #include "../../include/gmpe.h"
 #include "gmpe_expand.h"
+#include "gmpe_mb_map.h"
 
 #pragma clang fp contract(off)
 
@@ -50,32 +51,9 @@ struct MbArgs {
     MbField f[GMPE_MB_MAX_FIELDS];
 };
 
-// Sample (t, n, a) of output row r (chunk r for a chunk head); ok = false for a permutation entry out of range.
-struct Sample { uint32_t t, n, a; bool ok; };
-
-__device__ __forceinline__ Sample sample_of(const MbArgs& p, uint32_t r, bool head) {
-    Sample s{0u, 0u, 0u, false};
-    if (p.mode == GMPE_MB_FEED_FORWARD) {
-        const int64_t j = p.perm[p.offset + r];
-        if (j < 0 || j >= (int64_t)p.n_valid) return s;
-        const uint32_t u = (uint32_t)j, na = p.N * p.A;
-        s.t = u / na;
-        const uint32_t rem = u - s.t * na;
-        s.n = rem / p.A;
-        s.a = rem - s.n * p.A;
-    } else {
-        const uint32_t k = head ? r : r % p.chunks, l = head ? 0u : r / p.chunks;
-        const int64_t c = p.perm[p.offset + k];
-        if (c < 0 || c >= (int64_t)p.n_valid) return s;
-        const uint32_t f = (uint32_t)c * p.L + l, at = p.A * p.T;
-        s.n = f / at;
-        const uint32_t rem = f - s.n * at;
-        s.a = rem / p.T;
-        s.t = rem - s.a * p.T;
-    }
-    s.ok = true;
-    return s;
-}
+// Sample (t, n, a) of output row r: gmpe_mb_map.h, shared with the edge lists (gmpe_mb_edges.hip)
+using gmpe::Sample;
+using gmpe::sample_of;
 
 __device__ __forceinline__ int field_of(const MbArgs& p) {
     int f = 0;

@@ -5,8 +5,14 @@ One minibatch is one gmpe_minibatch_gather call (include/gmpe.h; csrc/gmpe_minib
 fresh slab, in the reference's shapes, dtypes and order — the 16-tuple ppo_update consumes unchanged. The arrays may be in any storage form of the rollout buffer:
 node rows or the fp64 entity table, materialised [.., A, E, E] / compact [.., E, E] / no adjacency (rebuilt from the table, bit-identical to the engine). No engine
 is needed, so a learner rank can run this on a ShardedRolloutCollector.unpack result or on raw entity tables.
+
+The policy consumes an edge list, not the matrices (GNNBase.forward -> TransformerConvNet.process_adj, onpolicy/algorithms/utils/gnn_new.py:329-358, 492-510):
+Gather.edges / adj="edges" emit that list for a minibatch straight from the stored adjacency form (gmpe_minibatch_edges; csrc/gmpe_mb_edges.hip), so the
+[rows, E, E] batch is never written.
 """
+import collections
 import ctypes as C
+import numbers
 
 import torch
 
@@ -17,6 +23,71 @@ TUPLE = ("share_obs", "obs", "node_obs", "adj", "agent_id", "share_agent_id", "r
          "active_masks", "action_log_probs", "advantages", "available_actions")
 LEARNER = ("rnn_states", "rnn_states_critic", "actions", "action_log_probs")
 _ALIGN = 256
+
+# process_adj's result for one minibatch: edge_index [2, n] (row 0 sources, row 1 destinations; node ids graph * num_nodes + i), edge_attr [n, 1], and the
+# true edge count n_edges — an int in the exact mode, an int32 device tensor [1] with an explicit cap (then n = cap and only min(n_edges, cap) entries are edges)
+EdgeList = collections.namedtuple("EdgeList", ("edge_index", "edge_attr", "num_graphs", "num_nodes", "n_edges"))
+ADJ_MODES = ("matrix", "edges")
+
+
+def check_edge_args(adj, max_edge_dist, cap=None):
+    """The arguments of an edge-list request, checked before anything is launched."""
+    if adj not in ADJ_MODES:
+        raise ValueError("adj must be one of %s (got %r)" % (ADJ_MODES, adj))
+    if adj == "edges":
+        if max_edge_dist is None or isinstance(max_edge_dist, bool) or not isinstance(max_edge_dist, numbers.Real) or max_edge_dist != max_edge_dist:
+            raise ValueError('adj="edges" needs max_edge_dist (a number; the policy\'s args.max_edge_dist)')
+    if cap is not None and (isinstance(cap, bool) or int(cap) != cap or int(cap) <= 0):
+        raise ValueError("cap must be a positive integer or None (exact mode)")
+
+
+def edge_list(cfg, device, source, src, T, N, A, E, max_edge_dist, perm=None, offset=0, rows=None, data_chunk_length=None, inclusive=False, index64=True,
+              cap=None):
+    """gmpe_minibatch_edges on one source: `source` _lib.MBE_ADJ / MBE_ADJ_COMPACT / MBE_TABLE, `src` the contiguous device tensor whose slot 0 is read
+    ([T(+1), N, A, E, E] / [T(+1), N, E, E] f32 / [T(+1), N, W] f64). perm None: the identity. cap None: the exact mode — a count call, one read of the
+    count, outputs of that size, a write call on the same workspace; cap int: one call, no host synchronisation. Enqueued on the current stream."""
+    check_edge_args("edges", max_edge_dist, cap)
+    lib = _lib.load()
+    recurrent = data_chunk_length is not None
+    L = int(data_chunk_length) if recurrent else 1
+    rows = int(rows)
+    graphs = rows * L
+    if rows < 1:
+        raise ValueError("rows must be >= 1")
+    pl = _lib.GmpeMbEdgesPlan()
+    pl.mode = _lib.MB_RECURRENT if recurrent else _lib.MB_FEED_FORWARD
+    pl.source, pl.T, pl.N, pl.A, pl.L, pl.E = source, T, N, A, L, E
+    pl.inclusive, pl.index64, pl.max_edge_dist = int(bool(inclusive)), int(bool(index64)), float(max_edge_dist)
+    if perm is not None:
+        pl.perm, pl.perm_len = perm.data_ptr(), int(perm.shape[0])
+    pl.offset, pl.rows = int(offset), rows
+    pl.src, pl.slot_stride = src.data_ptr(), src.stride(0) * src.element_size()
+    nbytes = C.c_size_t()
+    _lib.check(lib.gmpe_minibatch_edges_workspace_bytes(graphs, C.byref(nbytes)), "gmpe_minibatch_edges_workspace_bytes")
+    ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=device)
+    ne = torch.empty((1,), dtype=torch.int32, device=device)
+    pl.n_edges, pl.workspace, pl.workspace_bytes = ne.data_ptr(), ws.data_ptr(), nbytes.value
+    idt = torch.int64 if index64 else torch.int32
+    cfg_ref = C.byref(cfg) if cfg is not None else None
+    stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    run = lambda: _lib.check(lib.gmpe_minibatch_edges(cfg_ref, device.index or 0, C.byref(pl), stream), "gmpe_minibatch_edges")
+    if cap is None:
+        run()                                                 # count only: edge_index is NULL
+        m = int(ne.item())                                    # the one host synchronisation of the exact mode
+        if m >= 2 ** 31 - 1:
+            raise _lib.GmpeError("gmpe_minibatch_edges: more than 2^31 - 2 edges (the count saturates, include/gmpe.h): split the minibatch")
+        ei = torch.empty((2, m), dtype=idt, device=device)
+        ea = torch.empty((m, 1), dtype=torch.float32, device=device)
+        if m:
+            pl.edge_index, pl.edge_attr, pl.cap, pl.reuse_counts = ei.data_ptr(), ea.data_ptr(), m, 1
+            run()
+        return EdgeList(ei, ea, graphs, E, m)
+    cap = int(cap)
+    ei = torch.empty((2, cap), dtype=idt, device=device)
+    ea = torch.empty((cap, 1), dtype=torch.float32, device=device)
+    pl.edge_index, pl.edge_attr, pl.cap = ei.data_ptr(), ea.data_ptr(), cap
+    run()
+    return EdgeList(ei, ea, graphs, E, ne)
 
 
 def _slot_array(name, t, lead, tail_dims, dtypes, device):
@@ -45,7 +116,8 @@ class Gather(object):
     Every name of TUPLE that cannot be formed is None in the result. share_obs / share_agent_id are obs[t, n] / agent_id[t, n] of all agents with
     use_centralized_V (DeviceRolloutBuffer.share_obs), the agent's own row without."""
 
-    def __init__(self, cfg, arrays, data_chunk_length=None, use_centralized_V=True):
+    def __init__(self, cfg, arrays, data_chunk_length=None, use_centralized_V=True, adj="matrix"):
+        check_edge_args(adj, 0.0)
         arrays = {k: v for k, v in dict(arrays).items() if v is not None}
         unknown = set(arrays) - set(TUPLE) - {"entity_table"}
         if unknown:
@@ -53,6 +125,8 @@ class Gather(object):
         for k in ("obs", "agent_id", "masks", "active_masks"):
             if k not in arrays:
                 raise ValueError("arrays[%r] is required" % k)
+        if adj == "edges" and "adj" not in arrays and "entity_table" not in arrays:
+            raise ValueError('adj="edges" needs an adjacency form in the arrays: adj (materialised or compact) or the entity_table')
         obs = arrays["obs"]
         if not isinstance(obs, torch.Tensor) or obs.dim() != 4 or obs.shape[0] < 2:
             raise ValueError("obs must be a float32 tensor [T+1, N, A, D] with T >= 1")
@@ -93,16 +167,23 @@ class Gather(object):
             add("node_obs", _lib.MB_TABLE_NODE, tab, E * F * 4, torch.float32, (E, F))
         else:
             raise ValueError("arrays need node_obs rows or the entity_table")
+        nfields = len(fields)
         if "adj" in arrays:
             a = arrays["adj"]
             if isinstance(a, torch.Tensor) and a.dim() == 4:
                 add("adj", _lib.MB_ENV_ROW, chk("adj", (T1, N), (E, E), f32), E * E * 4, torch.float32, (E, E))
+                self._edge_source = (_lib.MBE_ADJ_COMPACT, a)
             else:
                 add("adj", _lib.MB_ROW, chk("adj", full, (E, E), f32), E * E * 4, torch.float32, (E, E))
+                self._edge_source = (_lib.MBE_ADJ, a)
         elif tab is not None:
             add("adj", _lib.MB_TABLE_ADJ, tab, E * E * 4, torch.float32, (E, E))
+            self._edge_source = (_lib.MBE_TABLE, tab)
         else:
             raise ValueError("arrays need an adjacency (adj) or the entity_table")
+        self.adj_mode = adj
+        if adj == "edges":
+            del fields[nfields:]                             # no [rows, E, E] batch: the minibatch's entry 3 is the EdgeList (edges)
         ids = arrays["agent_id"]
         add("agent_id", _lib.MB_ROW, ids, 4, torch.int32, (1,))
         if use_centralized_V:
@@ -178,6 +259,22 @@ class Gather(object):
                                                    C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)), "gmpe_minibatch_gather")
         return out
 
+    def edges(self, perm, offset, rows, max_edge_dist, inclusive=False, index64=True, cap=None):
+        """The edge list of the minibatch perm[offset : offset + rows] (perm None: the identity) — process_adj of the adj batch __call__ would return, graph r its
+        row r — straight from the stored adjacency form: -> EdgeList. cap None: exact sizes, one host synchronisation; cap int: [2, cap] / [cap, 1] outputs,
+        n_edges a device tensor, no synchronisation (truncation is the caller's to check)."""
+        check_edge_args("edges", max_edge_dist, cap)
+        if perm is not None and (not isinstance(perm, torch.Tensor) or perm.dtype != torch.int64 or perm.dim() != 1 or not perm.is_contiguous()
+                                 or perm.device != self.device):
+            raise ValueError("perm must be None or a contiguous 1-D int64 tensor on %s" % self.device)
+        offset, rows = int(offset), int(rows)
+        n = self.num_units if perm is None else perm.shape[0]
+        if rows < 1 or offset < 0 or offset + rows > n:
+            raise ValueError("the minibatch [%d, %d) does not lie in the permutation's %d entries" % (offset, offset + rows, n))
+        source, src = self._edge_source
+        return edge_list(self.cfg, self.device, source, src, self.T, self.N, self.A, self.cfg.num_entities, max_edge_dist, perm=perm, offset=offset, rows=rows,
+                         data_chunk_length=self.L if self.recurrent else None, inclusive=inclusive, index64=index64, cap=cap)
+
     def tuple(self, out):
         """the reference's 16-tuple order (None where a field was not given)"""
         return tuple(out.get(k) for k in TUPLE)
@@ -236,32 +333,42 @@ def _empty(g):
     return {name: torch.empty((0,) + shape, dtype=dt, device=g.device) for name, _, _, _, _, dt, shape in g.fields}
 
 
-def feed_forward_generator(cfg, arrays, advantages, num_mini_batch=None, mini_batch_size=None, perm=None, use_centralized_V=True):
+def feed_forward_generator(cfg, arrays, advantages, num_mini_batch=None, mini_batch_size=None, perm=None, use_centralized_V=True, adj="matrix",
+                           max_edge_dist=None, inclusive=False):
     """GraphReplayBuffer.feed_forward_generator on the device: yields the reference's 16-tuple per minibatch (available_actions_batch None without
-    available_actions). The arguments are checked here; the permutation is drawn at the first next(), as the reference's."""
+    available_actions). The arguments are checked here; the permutation is drawn at the first next(), as the reference's.
+    adj="edges": entry 3 of the tuple is the minibatch's EdgeList (process_adj with max_edge_dist; exact sizes) and no adj batch is written."""
+    check_edge_args(adj, max_edge_dist)
     if advantages is None:
         raise ValueError("feed_forward_generator needs the advantages (the reference reshapes them unconditionally, graph_buffer.py:422)")
     arrays = dict(arrays, advantages=advantages)
-    g = Gather(cfg, arrays, None, use_centralized_V)
+    g = Gather(cfg, arrays, None, use_centralized_V, adj=adj)
     _, _, sampler = feed_forward_sizes(g.T, g.N, g.A, num_mini_batch, mini_batch_size)
-    return _run(g, sampler, perm)
+    return _run(g, sampler, perm, max_edge_dist, inclusive)
 
 
-def recurrent_generator(cfg, arrays, advantages, num_mini_batch, data_chunk_length, perm=None, use_centralized_V=True):
+def recurrent_generator(cfg, arrays, advantages, num_mini_batch, data_chunk_length, perm=None, use_centralized_V=True, adj="matrix", max_edge_dist=None,
+                        inclusive=False):
     """GraphReplayBuffer.recurrent_generator on the device: chunks of data_chunk_length samples in the [N, A, T] order (a chunk crosses agent / env boundaries
-    when T % L != 0, as the reference's), rows l * chunks + k, rnn states from each chunk's first sample."""
+    when T % L != 0, as the reference's), rows l * chunks + k, rnn states from each chunk's first sample. adj="edges": as feed_forward_generator."""
+    check_edge_args(adj, max_edge_dist)
     if advantages is None:
         raise ValueError("recurrent_generator needs the advantages (the reference casts them unconditionally, graph_buffer.py:632)")
     arrays = dict(arrays, advantages=advantages)
-    g = Gather(cfg, arrays, int(data_chunk_length), use_centralized_V)
+    g = Gather(cfg, arrays, int(data_chunk_length), use_centralized_V, adj=adj)
     data_chunks, mbc, sampler = recurrent_sizes(g.T, g.N, g.A, num_mini_batch, data_chunk_length)
     if mbc < 1:
         raise ValueError("recurrent_generator: %d chunks of %d samples do not fill %d minibatches (the reference's np.stack of an empty list fails)"
                          % (data_chunks, int(data_chunk_length), int(num_mini_batch)))
-    return _run(g, sampler, perm)
+    return _run(g, sampler, perm, max_edge_dist, inclusive)
 
 
-def _run(g, sampler, perm):
+def _empty_edges(g):
+    return EdgeList(torch.empty((2, 0), dtype=torch.int64, device=g.device), torch.empty((0, 1), dtype=torch.float32, device=g.device), 0,
+                    g.cfg.num_entities, 0)
+
+
+def _run(g, sampler, perm, max_edge_dist=None, inclusive=False):
     n = g.num_units
     if perm is not None and not isinstance(perm, str):
         perm = device_perm(perm, n, g.device)                # checked once, before the first next()
@@ -271,5 +378,8 @@ def _run(g, sampler, perm):
     def gen(perm=perm):
         p = device_perm(perm, n, g.device) if perm is None or isinstance(perm, str) else perm
         for off, rows in sampler:
-            yield g.tuple(g(p, off, rows) if rows else _empty(g))
+            out = g(p, off, rows) if rows else _empty(g)
+            if g.adj_mode == "edges":
+                out["adj"] = g.edges(p, off, rows, max_edge_dist, inclusive) if rows else _empty_edges(g)
+            yield g.tuple(out)
     return gen()

@@ -19,7 +19,8 @@ import torch
 
 from .config import NODE_FEATS
 from .engine import StepOutputs, available_actions_from_dones, compute_returns, denorm_scalars, insert_learner, returns_workspace_bytes
-from .minibatch import LEARNER, feed_forward_generator, recurrent_generator
+from . import _lib
+from .minibatch import LEARNER, EdgeList, check_edge_args, edge_list, feed_forward_generator, recurrent_generator
 
 POLICY_FIELDS = ("value_preds", "returns", "bad_masks", "available_actions", "advantages")
 LEARNER_FIELDS = ("rnn_states", "rnn_states_critic", "actions", "action_log_probs")
@@ -395,19 +396,51 @@ class DeviceRolloutBuffer(object):
             raise ValueError("advantages must have shape %s" % ((self.T, self.engine.N, self.engine.A, 1),))
         return t.to(device=self.engine.device, dtype=torch.float32).contiguous()
 
-    def feed_forward_generator(self, advantages, num_mini_batch=None, mini_batch_size=None, *, learner=None, perm=None):
+    def feed_forward_generator(self, advantages, num_mini_batch=None, mini_batch_size=None, *, learner=None, perm=None, adj="matrix", max_edge_dist=None,
+                               inclusive=False):
         """GraphReplayBuffer.feed_forward_generator (graph_buffer.py:368-465) from the device arrays: the reference's 16-tuple per minibatch as fresh device
         tensors (agent_id / share_agent_id int32; available_actions None when the buffer keeps none, learner slots None
         unless the buffer or `learner` holds them), one gather launch per minibatch (two with the entity-table forms). perm: None draws torch.randperm on the CPU default
-        generator as the reference does (a seeded run trains on the same minibatches) and uploads it once; "device" draws on the device; or an int64 tensor."""
+        generator as the reference does (a seeded run trains on the same minibatches) and uploads it once; "device" draws on the device; or an int64 tensor.
+        adj="edges" (with max_edge_dist, inclusive): entry 3 is the minibatch's EdgeList — process_adj's result, computed once for actor and critic from the
+        adjacency form the buffer stores (gmpe_minibatch_edges) — and no [rows, E, E] batch is written."""
+        check_edge_args(adj, max_edge_dist)
         return feed_forward_generator(self.engine.cfg, self.minibatch_arrays(learner), self._advantages(advantages), num_mini_batch, mini_batch_size,
-                                      perm=perm, use_centralized_V=self.use_centralized_V)
+                                      perm=perm, use_centralized_V=self.use_centralized_V, adj=adj, max_edge_dist=max_edge_dist, inclusive=inclusive)
 
-    def recurrent_generator(self, advantages, num_mini_batch, data_chunk_length, *, learner=None, perm=None):
+    def recurrent_generator(self, advantages, num_mini_batch, data_chunk_length, *, learner=None, perm=None, adj="matrix", max_edge_dist=None, inclusive=False):
         """GraphReplayBuffer.recurrent_generator (graph_buffer.py:599-758): chunks of data_chunk_length samples in the reference's [N, A, T] order, rows
-        l * chunks + k, rnn states [chunks, R, H] from each chunk's first sample. perm as feed_forward_generator (over the T*N*A // L chunks)."""
+        l * chunks + k, rnn states [chunks, R, H] from each chunk's first sample. perm as feed_forward_generator (over the T*N*A // L chunks); adj,
+        max_edge_dist, inclusive as feed_forward_generator."""
+        check_edge_args(adj, max_edge_dist)
         return recurrent_generator(self.engine.cfg, self.minibatch_arrays(learner), self._advantages(advantages), num_mini_batch, data_chunk_length,
-                                   perm=perm, use_centralized_V=self.use_centralized_V)
+                                   perm=perm, use_centralized_V=self.use_centralized_V, adj=adj, max_edge_dist=max_edge_dist, inclusive=inclusive)
+
+    def step_edges(self, step, max_edge_dist, inclusive=False, index64=True, cap=None):
+        """process_adj's edge list of slot `step` for the closed loop (the [N*A, E, E] batch the runner feeds the policy), from whichever adjacency form the
+        buffer stores -> EdgeList. The compact matrix goes through gmpe_edges_from_adj_compact (each matrix read once for its A copies); the materialised
+        matrices and the table-only form (adj_form "none") through gmpe_minibatch_edges with the identity permutation. All give the same result."""
+        check_edge_args("edges", max_edge_dist, cap)
+        step = int(step)
+        if not 0 <= step <= self.T:
+            raise ValueError("step must lie in [0, %d]" % self.T)
+        e = self.engine
+        E = e.cfg.num_entities
+        if self._adj is not None and self._adj.dim() == 4:
+            ei, ea, m = e.edges_from_adj_compact(self._adj[step], e.A, max_edge_dist, inclusive=inclusive, cap=cap, index64=index64)
+            return EdgeList(ei, ea.view(-1, 1), e.N * e.A, E, m)
+        if self._adj is not None:
+            source, src = _lib.MBE_ADJ, self._adj
+        elif self.entity_table is not None:
+            source, src = _lib.MBE_TABLE, self.entity_table
+        else:
+            raise ValueError("the buffer stores no adjacency form (neither adj nor the entity table)")
+        out = edge_list(e.cfg, e.device, source, src[step:], 1, e.N, e.A, E, max_edge_dist, perm=None, offset=0, rows=e.N * e.A, inclusive=inclusive,
+                        index64=index64, cap=cap)
+        if cap is None:
+            return out
+        m = int(out.n_edges.item())                          # as edges_from_adj_compact: the count on the host, the outputs cut to it
+        return EdgeList(out.edge_index[:, :min(m, cap)], out.edge_attr[:min(m, cap)], out.num_graphs, E, m)
 
     def naive_recurrent_generator(self, advantages, num_mini_batch):
         raise NotImplementedError(

@@ -561,6 +561,48 @@ typedef struct gmpe_minibatch_plan {
 } gmpe_minibatch_plan;
 int gmpe_minibatch_gather(const gmpe_config* cfg, int device, const gmpe_minibatch_plan* plan, void* stream);
 
+/* The edge list of a minibatch straight from the adjacency the rollout stores: what TransformerConvNet.process_adj (onpolicy/algorithms/utils/gnn_new.py:329-358)
+ * makes of the adj_batch that gmpe_minibatch_gather would write, without that [rows, E, E] tensor. Graph r is output row r of gmpe_minibatch_gather: the same
+ * (t, n, a) from the same mode, perm, offset, rows, L (the map above; recurrent: rows * L graphs, r = l * rows + k). perm == NULL is the identity, entry k = offset + k:
+ * the edges of one rollout step are the feed-forward call with T = 1, rows = N * A and `src` at that slot.
+ * Rule: (adj < max_edge_dist) & (adj > 0) on fp32 (`inclusive`: <=), edges in (graph, row i, col j) lexicographic order, node ids r*E + i and r*E + j,
+ * edge_attr the adjacency value. Only the first `cap` edges are written; n_edges holds the true count (saturating at INT32_MAX) whatever `cap` is.
+ * A graph whose permutation entry is out of range has zero edges and its source is not read (the gather leaves such rows unwritten; an edge list cannot).
+ * Three launches on `stream` (per-graph count, scan of the per-workgroup totals in fixed chunks, ordered write): no atomics, no allocation, no host
+ * synchronisation, capturable in a hipGraph, same input -> same bits. Count-only call: edge_index == NULL runs count + scan and leaves n_edges and the offsets
+ * in the workspace; a following call on the same workspace and the same plan with `reuse_counts` runs the write alone (n_edges is then left as it is).
+ * Every argument the host can see is checked before any device call. */
+#define GMPE_MBE_ADJ 0          /* src f32 [T+1, N, A, E, E]: graph r reads ego a's copy                                                          */
+#define GMPE_MBE_ADJ_COMPACT 1  /* src f32 [T+1, N, E, E]: graph r reads (t, n)                                                                      */
+#define GMPE_MBE_TABLE 2        /* src f64 entity table [T+1, N, W]: entries rebuilt as GMPE_MB_TABLE_ADJ does (needs cfg; E, A must be the config's) */
+typedef struct gmpe_mb_edges_plan {
+    int32_t mode;               /* GMPE_MB_FEED_FORWARD or GMPE_MB_RECURRENT                                                                */
+    int32_t source;             /* GMPE_MBE_*                                                                                               */
+    int32_t T, N, A;            /* episode length, envs, agents of the source (T*N*A < 2^31)                                               */
+    int32_t L;                  /* data_chunk_length (recurrent), >= 1; ignored feed-forward                                                */
+    int32_t E;                  /* nodes per graph, 1 .. GMPE_MAX_ENTITIES                                                                  */
+    int32_t inclusive;          /* 0: adj < max_edge_dist; 1: adj <= max_edge_dist                                                          */
+    int32_t index64;            /* 0: edge_index int32 (graphs * E must fit); 1: int64                                                      */
+    int32_t reuse_counts;       /* 1: the workspace holds the counts of a count-only call on this plan: write only (needs edge_index)      */
+    float max_edge_dist;        /* not NaN                                                                                                  */
+    int32_t reserved;           /* 0                                                                                                        */
+    const int64_t* perm;        /* device permutation (samples feed-forward, chunks recurrent), or NULL: the identity                       */
+    int64_t perm_len;           /* its entries (ignored with perm == NULL)                                                                  */
+    int64_t offset;             /* first entry of this minibatch                                                                            */
+    int64_t rows;               /* samples (feed-forward) or chunks (recurrent) of this minibatch; with a perm offset + rows <= perm_len     */
+    const void* src;            /* slot 0 of the source, device memory (4-byte aligned; 8-byte for GMPE_MBE_TABLE)                          */
+    int64_t slot_stride;        /* bytes between slot t and t + 1 of src (at least one slot)                                                */
+    void* edge_index;           /* [2, cap] int32 / int64 (row 0 sources, row 1 destinations), or NULL: count only                          */
+    float* edge_attr;           /* [cap] (needed with edge_index)                                                                           */
+    int64_t cap;                /* >= 0                                                                                                     */
+    int32_t* n_edges;           /* [1] device                                                                                               */
+    void* workspace;            /* device scratch of gmpe_minibatch_edges_workspace_bytes(graphs) bytes, 8-byte aligned                     */
+    size_t workspace_bytes;
+} gmpe_mb_edges_plan;
+/* bytes of workspace for `graphs` graphs (rows feed-forward, rows * L recurrent): the per-workgroup offsets (int64) followed by the per-graph counts (int32) */
+int gmpe_minibatch_edges_workspace_bytes(int64_t graphs, size_t* bytes_out);
+int gmpe_minibatch_edges(const gmpe_config* cfg, int device, const gmpe_mb_edges_plan* plan, void* stream);
+
 /* What gmpe_create chose for this handle (recorded by bench.py next to every number). Environment variables override the heuristics —
  * GMPE_G / GMPE_BLOCK (step tile shape), GMPE_GROLL (rollout tile shape), GMPE_AP=0 (run-time-size instead of exact-size kernels),
  * GMPE_NT / GMPE_ROLLNT (nontemporal graph stores of step / rollout launches), GMPE_SPEC (wave specialisation), GMPE_SPLIT / GMPE_CHUNKS
