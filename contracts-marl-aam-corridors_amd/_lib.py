@@ -19,7 +19,7 @@ SYMBOLS = ["gmpe_abi_version", "gmpe_last_error", "gmpe_obs_dim", "gmpe_node_fea
            "gmpe_entity_table_width", "gmpe_expand_node_obs", "gmpe_expand_adj",
            "gmpe_returns_workspace_bytes", "gmpe_compute_returns", "gmpe_available_actions_from_dones", "gmpe_minibatch_gather",
            "gmpe_insert_learner", "gmpe_episode_record", "gmpe_episode_metrics", "gmpe_episode_summary",
-           "gmpe_minibatch_edges", "gmpe_minibatch_edges_workspace_bytes"]
+           "gmpe_minibatch_edges", "gmpe_minibatch_edges_workspace_bytes", "gmpe_episode_record_series"]
 
 
 class GmpeOutputs(C.Structure):
@@ -78,6 +78,14 @@ class GmpeEpisodeRecordPlan(C.Structure):
                 ("rnn_row", C.c_int32), ("reward", C.c_void_p), ("done", C.c_void_p), ("info", C.c_void_p), ("live", C.c_void_p),
                 ("steps", C.c_void_p), ("ret", C.c_void_p), ("final_info", C.c_void_p), ("masks", C.c_void_p), ("available_actions", C.c_void_p),
                 ("rnn_states", C.c_void_p)]
+
+
+class GmpeEpisodeSeriesPlan(C.Structure):
+    """gmpe_episode_series_plan (include/gmpe.h): one step of R back-to-back evaluation episodes per env; every env carries its own episode and step."""
+    _fields_ = [("num_envs", C.c_int32), ("num_agents", C.c_int32), ("num_steps", C.c_int32), ("num_episodes", C.c_int32), ("n_actions", C.c_int32),
+                ("rnn_row", C.c_int32), ("reward", C.c_void_p), ("done", C.c_void_p), ("info", C.c_void_p), ("episode", C.c_void_p),
+                ("t_in_ep", C.c_void_p), ("ret", C.c_void_p), ("steps", C.c_void_p), ("ret_out", C.c_void_p), ("final_info", C.c_void_p),
+                ("masks", C.c_void_p), ("available_actions", C.c_void_p), ("rnn_states", C.c_void_p)]
 
 
 class GmpeEpisodeMetricsPlan(C.Structure):
@@ -181,6 +189,7 @@ def load():
     lib.gmpe_minibatch_edges_workspace_bytes.argtypes = [C.c_int64, C.POINTER(C.c_size_t)]
     lib.gmpe_insert_learner.argtypes = [I, C.POINTER(GmpeLearnerPlan), P]
     lib.gmpe_episode_record.argtypes = [I, C.POINTER(GmpeEpisodeRecordPlan), P]
+    lib.gmpe_episode_record_series.argtypes = [I, C.POINTER(GmpeEpisodeSeriesPlan), P]
     lib.gmpe_episode_metrics.argtypes = [I, C.POINTER(GmpeEpisodeMetricsPlan), P]
     lib.gmpe_episode_summary.argtypes = [I, C.POINTER(GmpeEpisodeSummaryPlan), P]
     from .config import ABI_VERSION

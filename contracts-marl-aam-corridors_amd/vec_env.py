@@ -404,6 +404,11 @@ class MultiDeviceGraphMPEVecEnv(object):
         self.waiting = False
         self._pending = None
 
+    @property
+    def shard_engines(self):
+        """The shards' GmpeEngines in shard (global env) order: engine g steps envs sharding.shard_range(N, G, g) on devices[g]."""
+        return [s.engine for s in self._shards]
+
     def _make_shard(self, device, **kw):
         """One shard: a BatchedGraphMPEVecEnv over envs [env_id_base, env_id_base + num_envs) on `device`."""
         return BatchedGraphMPEVecEnv(self._all_args, device=device, **kw)

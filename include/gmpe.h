@@ -479,6 +479,37 @@ typedef struct gmpe_episode_record_plan {
 } gmpe_episode_record_plan;
 int gmpe_episode_record(int device, const gmpe_episode_record_plan* plan, void* stream);
 
+/* gmpe_episode_record_series: gmpe_episode_record for R episodes per env played back to back across the engine's auto-resets (the render loop's
+ * `for episode in range(render_episodes)`). There is no global step index: env n carries episode[n] in 0 .. R and t_in_ep[n]. One call per env step
+ * on the same stream; for an env with episode[n] = e < R:
+ *   ret[n, a] += double(reward[n, a]); t_in_ep[n] += 1; when every agent of env n is done or t_in_ep[n] == T (so T must be the engine's
+ *   episode_length: an episode has to end where the engine resets): steps[e, n] = t_in_ep[n], ret_out[e, n] = ret[n], final_info[e, n] = info[n],
+ *   then episode[n] = e + 1, t_in_ep[n] = 0, ret[n] = 0. The terminal step's reward belongs to the episode it ends.
+ * An env with episode[n] == R is frozen. The outputs are episode-major: row e * N + n of the [R * N, ...] arrays is one episode, which is what
+ * gmpe_episode_metrics (num_envs = R * N) and gmpe_episode_summary (num_rows = R * N) read. masks, available_actions and rnn_states are written
+ * for every env by gmpe_episode_record's rules, so an env that just ended an episode acts next on the auto-reset observation with ones and zeroed
+ * RNN rows. The caller zeroes episode, t_in_ep and ret at the reset. With R = 1 every state and output equals gmpe_episode_record's. */
+typedef struct gmpe_episode_series_plan {
+    int32_t num_envs, num_agents;   /* N >= 1, 1 <= A <= GMPE_MAX_AGENTS                                                            */
+    int32_t num_steps;              /* T = the engine's episode_length >= 1                                                         */
+    int32_t num_episodes;           /* R >= 1 episodes per env, R * N <= 2^31 - 1 (gmpe_episode_summary's row limit)                */
+    int32_t n_actions;              /* row width of available_actions, 1 .. 4096                                                   */
+    int32_t rnn_row;                /* R * H floats per agent of rnn_states, 1 .. 2^20 with rnn_states, else ignored               */
+    const float* reward;            /* [N, A]       the step's outputs (gmpe_outputs of the engine)                                 */
+    const uint8_t* done;            /* [N, A]                                                                                       */
+    const float* info;              /* [N, A, GMPE_EVAL_INFO_WIDTH]                                                                 */
+    int32_t* episode;               /* [N]          state: episodes this env has completed, 0 .. R                                  */
+    int32_t* t_in_ep;               /* [N]          state: steps booked to the env's running episode                                */
+    double* ret;                    /* [N, A]       state: the running episode's sum of rewards                                     */
+    int32_t* steps;                 /* [R, N]       out: episode lengths                                                            */
+    double* ret_out;                /* [R, N, A]    out: episode returns                                                            */
+    float* final_info;              /* [R, N, A, GMPE_EVAL_INFO_WIDTH] out: the info rows of each episode's terminal step            */
+    float* masks;                   /* [N, A]       out                                                                             */
+    float* available_actions;       /* [N, A, n_actions] out                                                                        */
+    float* rnn_states;              /* [N, A, rnn_row] in place, or NULL                                                            */
+} gmpe_episode_series_plan;
+int gmpe_episode_record_series(int device, const gmpe_episode_series_plan* plan, void* stream);
+
 /* gmpe_episode_metrics: one f64 row of the GMPE_EVAL_* columns per env from its record, ttg_a = Time_req_to_goal with -1 -> T*dt
  * (base_runner.py:214-217; the reference never assigns the runner's dt: the world's dt is meant). Sums and means over agents follow NumPy's
  * pairwise order, so every column equals the reference's float64 NumPy on the same f32 info rows bit for bit. The same launch writes the
