@@ -13,7 +13,7 @@ __all__ = ["config", "make_config", "config_from_args"]
 
 def __getattr__(name):
     # torch / HIP-dependent modules are imported on first use
-    if name in ("engine", "vec_env", "spaces", "_lib", "sharding", "rollout", "minibatch", "evaluate"):
+    if name in ("engine", "vec_env", "spaces", "_lib", "sharding", "rollout", "minibatch", "evaluate", "ppo_loss"):
         import importlib
         return importlib.import_module("." + name, __name__)
     if name in ("BatchedGraphMPEVecEnv", "MultiDeviceGraphMPEVecEnv", "GraphMPEEnv", "make_train_env", "make_eval_env"):
@@ -22,6 +22,9 @@ def __getattr__(name):
     if name == "BatchedEvaluator":
         from . import evaluate
         return evaluate.BatchedEvaluator
+    if name in ("ppo_losses", "PPOLosses"):
+        from . import ppo_loss
+        return getattr(ppo_loss, name)
     if name == "GmpeEngine":
         from . import engine
         return engine.GmpeEngine

@@ -19,7 +19,8 @@ SYMBOLS = ["gmpe_abi_version", "gmpe_last_error", "gmpe_obs_dim", "gmpe_node_fea
            "gmpe_entity_table_width", "gmpe_expand_node_obs", "gmpe_expand_adj",
            "gmpe_returns_workspace_bytes", "gmpe_compute_returns", "gmpe_available_actions_from_dones", "gmpe_minibatch_gather",
            "gmpe_insert_learner", "gmpe_episode_record", "gmpe_episode_metrics", "gmpe_episode_summary",
-           "gmpe_minibatch_edges", "gmpe_minibatch_edges_workspace_bytes", "gmpe_episode_record_series"]
+           "gmpe_minibatch_edges", "gmpe_minibatch_edges_workspace_bytes", "gmpe_episode_record_series",
+           "gmpe_ppo_loss", "gmpe_ppo_loss_workspace_bytes"]
 
 
 class GmpeOutputs(C.Structure):
@@ -133,6 +134,22 @@ class GmpeMbEdgesPlan(C.Structure):
                 ("workspace_bytes", C.c_size_t)]
 
 
+PPO_POLICY_ACTIVE_MASKS, PPO_VALUE_ACTIVE_MASKS, PPO_CLIPPED_VALUE_LOSS, PPO_HUBER_LOSS, PPO_VALUENORM = 1, 2, 4, 8, 16
+PPO_MAX_ACTIONS, PPO_NUM_OUT = 64, 7
+PPO_OUT = ("policy_loss", "dist_entropy", "actor_loss", "value_loss", "ratio_mean", "denom_policy", "denom_value")
+
+
+class GmpePpoLossPlan(C.Structure):
+    """gmpe_ppo_loss_plan (include/gmpe.h): the loss arithmetic of one PPO minibatch with its gradients."""
+    _fields_ = [("rows", C.c_int64), ("n_actions", C.c_int32), ("flags", C.c_int32), ("actions_int64", C.c_int32), ("reserved", C.c_int32),
+                ("clip_param", C.c_double), ("huber_delta", C.c_double), ("entropy_coef", C.c_double), ("beta", C.c_double), ("epsilon", C.c_double),
+                ("logits", C.c_void_p), ("values", C.c_void_p), ("actions", C.c_void_p), ("available_actions", C.c_void_p),
+                ("old_action_log_probs", C.c_void_p), ("adv_targ", C.c_void_p), ("value_preds", C.c_void_p), ("returns", C.c_void_p),
+                ("active_masks", C.c_void_p), ("running_mean", C.c_void_p), ("running_mean_sq", C.c_void_p), ("debiasing_term", C.c_void_p),
+                ("out", C.c_void_p), ("grad_logits", C.c_void_p), ("grad_values", C.c_void_p), ("action_log_probs", C.c_void_p),
+                ("imp_weights", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
 class GmpeError(RuntimeError):
     pass
 
@@ -192,6 +209,8 @@ def load():
     lib.gmpe_episode_record_series.argtypes = [I, C.POINTER(GmpeEpisodeSeriesPlan), P]
     lib.gmpe_episode_metrics.argtypes = [I, C.POINTER(GmpeEpisodeMetricsPlan), P]
     lib.gmpe_episode_summary.argtypes = [I, C.POINTER(GmpeEpisodeSummaryPlan), P]
+    lib.gmpe_ppo_loss.argtypes = [I, C.POINTER(GmpePpoLossPlan), P]
+    lib.gmpe_ppo_loss_workspace_bytes.argtypes = [C.c_int64, C.POINTER(C.c_size_t)]
     from .config import ABI_VERSION
     if lib.gmpe_abi_version() != ABI_VERSION:
         raise GmpeError("libgmpe.so ABI version mismatch")

@@ -1,0 +1,196 @@
+"""The loss arithmetic of GR_MAPPO.ppo_update on the device (include/gmpe.h gmpe_ppo_loss): logits and values in, two differentiable scalars out.
+
+    for sample in dbuf.feed_forward_generator(advantages, num_mini_batch):
+        logits = actor.act.action_out.linear(actor_features)          # the head's linear layer, before Categorical masks it
+        res = gmpe.ppo_losses(logits, values, sample, args, value_normalizer)
+        scaler.scale(res.actor_loss).backward()
+        scaler.scale(res.value_loss * args.value_loss_coef).backward()
+
+One call of gmpe_ppo_loss (four launches) evaluates the masked categorical (onpolicy/algorithms/utils/distributions.py:84-91, act.py:212-220), the
+ratio / clip / surrogate block (onpolicy/algorithms/graph_mappo.py:176-197) and cal_value_loss with ValueNorm.update + normalize (:89-117,
+onpolicy/utils/valuenorm.py:48-85), and leaves d actor_loss / d logits and d value_loss / d values; backward multiplies them by the incoming
+scalar. There is no torch fallback: the arrays must be on a HIP device.
+"""
+import collections
+import ctypes as C
+
+import torch
+
+from . import _lib
+from .engine import _need_cuda, _stream_of
+
+PPOLosses = collections.namedtuple("PPOLosses", ["actor_loss", "value_loss", "policy_loss", "dist_entropy", "ratio_mean", "action_log_probs",
+                                                 "imp_weights"])
+FIELDS = ("actions", "value_preds", "returns", "active_masks", "old_action_log_probs", "adv_targ", "available_actions")
+# positions in the 16-tuple of GraphReplayBuffer's generators (graph_mappo.py:147-151)
+_TUPLE = dict(actions=8, value_preds=9, returns=10, active_masks=12, old_action_log_probs=13, adv_targ=14, available_actions=15)
+_DEFAULTS = dict(clip_param=0.2, huber_delta=10.0, entropy_coef=0.01, use_policy_active_masks=True, use_value_active_masks=True,
+                 use_clipped_value_loss=True, use_huber_loss=True, use_valuenorm=True, use_popart=False)
+
+
+def workspace_bytes(rows):
+    """Device scratch (bytes) one ppo_losses call over `rows` rows needs (gmpe_ppo_loss_workspace_bytes)."""
+    n = C.c_size_t()
+    _lib.check(_lib.load().gmpe_ppo_loss_workspace_bytes(int(rows), C.byref(n)), "gmpe_ppo_loss_workspace_bytes")
+    return int(n.value)
+
+
+def _fields(sample):
+    if isinstance(sample, dict):
+        unknown = set(sample) - set(FIELDS)
+        if unknown:
+            raise ValueError("unknown fields: %s (expected %s)" % (sorted(unknown), list(FIELDS)))
+        f = {k: sample.get(k) for k in FIELDS}
+    elif isinstance(sample, (tuple, list)) and len(sample) == 16:
+        f = {k: sample[i] for k, i in _TUPLE.items()}
+    else:
+        raise ValueError("sample_or_fields must be the generators' 16-tuple or a dict with %s" % (list(FIELDS),))
+    missing = [k for k in FIELDS[:-1] if f[k] is None]
+    if missing:
+        raise ValueError("the sample holds no %s" % ", ".join(missing))
+    return f
+
+
+def _flags(args):
+    get = lambda k: getattr(args, k, _DEFAULTS[k])
+    if get("use_popart"):
+        raise NotImplementedError("use_popart: PopArt rewrites the critic's output layer; ppo_losses supports ValueNorm or no normaliser")
+    flags = 0
+    for name, bit in (("use_policy_active_masks", _lib.PPO_POLICY_ACTIVE_MASKS), ("use_value_active_masks", _lib.PPO_VALUE_ACTIVE_MASKS),
+                      ("use_clipped_value_loss", _lib.PPO_CLIPPED_VALUE_LOSS), ("use_huber_loss", _lib.PPO_HUBER_LOSS),
+                      ("use_valuenorm", _lib.PPO_VALUENORM)):
+        if get(name):
+            flags |= bit
+    return flags, float(get("clip_param")), float(get("huber_delta")), float(get("entropy_coef"))
+
+
+def _valuenorm_state(vn, dev):
+    """The three tensors of the reference's ValueNorm(1) (valuenorm.py:34-39), updated in place by the kernel."""
+    if vn is None:
+        raise ValueError("args.use_valuenorm is set, so a value_normalizer (ValueNorm) is required")
+    names = ("running_mean", "running_mean_sq", "debiasing_term")
+    if not all(isinstance(getattr(vn, n, None), torch.Tensor) for n in names):
+        raise NotImplementedError("value_normalizer must be a ValueNorm (running_mean, running_mean_sq, debiasing_term); PopArt is not supported")
+    if int(getattr(vn, "norm_axes", 1)) != 1 or bool(getattr(vn, "per_element_update", False)) or vn.running_mean.numel() != 1 or \
+            vn.running_mean_sq.numel() != 1 or vn.debiasing_term.numel() != 1:
+        raise NotImplementedError("only ValueNorm(1) is supported: input_shape 1, norm_axes 1, per_element_update=False")
+    st = [getattr(vn, n) for n in names]
+    for n, t in zip(names, st):
+        if t.dtype != torch.float32 or t.device != dev or not t.is_contiguous():
+            raise ValueError("value_normalizer.%s must be a float32 tensor on %s (ValueNorm(1, device=...)): it is updated in place" % (n, dev))
+    return st, float(getattr(vn, "beta", 0.99999)), float(getattr(vn, "epsilon", 1e-5))
+
+
+def _column(name, t, rows, dev, dtypes=(torch.float32,)):
+    if not isinstance(t, torch.Tensor):
+        raise ValueError("%s must be a tensor" % name)
+    if t.dtype not in dtypes:
+        raise ValueError("%s must be %s, not %s" % (name, " or ".join(str(d) for d in dtypes), t.dtype))
+    if tuple(t.shape) not in ((rows, 1), (rows,)):
+        if name == "actions" and t.dim() == 2 and t.shape[0] == rows:
+            raise NotImplementedError("actions of shape %s: only a single Discrete head is supported (MultiDiscrete, mixed and continuous heads are not)"
+                                      % (tuple(t.shape),))
+        raise ValueError("%s must have shape (%d, 1), not %s" % (name, rows, tuple(t.shape)))
+    if t.device != dev:
+        raise ValueError("%s must be on %s (the device of logits)" % (name, dev))
+    return t.detach().contiguous()
+
+
+class _Attach(torch.autograd.Function):
+    """A scalar the kernel computed from `x`, with its gradient d scalar / d x already known: backward multiplies it by the incoming scalar. The two
+    losses are two such nodes, so each is backpropagated on its own, as ppo_update does."""
+
+    @staticmethod
+    def forward(ctx, x, scalar, grad):
+        ctx.save_for_backward(grad)
+        return scalar.clone()                          # owns its storage
+
+    @staticmethod
+    def backward(ctx, g):
+        grad, = ctx.saved_tensors
+        return grad * g, None, None
+
+
+def _launch(logits, values, plan, keep):
+    """One call of gmpe_ppo_loss on the current stream: (scalars f32 [PPO_NUM_OUT], grad_logits, grad_values, action_log_probs, imp_weights)."""
+    dev = logits.device
+    rows = logits.shape[0]
+    lg, vl = logits.detach().contiguous(), values.detach().contiguous()
+    out = torch.empty((_lib.PPO_NUM_OUT,), dtype=torch.float64, device=dev)
+    grad_logits, grad_values = torch.empty_like(lg), torch.empty_like(vl)
+    logp, ratio = (torch.empty((rows, 1), dtype=torch.float32, device=dev) for _ in range(2))
+    plan.logits, plan.values, plan.out = lg.data_ptr(), vl.data_ptr(), out.data_ptr()
+    plan.grad_logits, plan.grad_values = grad_logits.data_ptr(), grad_values.data_ptr()
+    plan.action_log_probs, plan.imp_weights = logp.data_ptr(), ratio.data_ptr()
+    _lib.check(_lib.load().gmpe_ppo_loss(dev.index if dev.index is not None else torch.cuda.current_device(), C.byref(plan), _stream_of(dev)),
+               "gmpe_ppo_loss")
+    del keep                                           # the inputs the plan points to lived until the launches were enqueued on this stream
+    return out.to(torch.float32), grad_logits, grad_values, logp, ratio      # doubles are written as doubles; rounded once here
+
+
+def ppo_losses(logits, values, sample_or_fields, args, value_normalizer=None, workspace=None):
+    """actor_loss (policy_loss - entropy_coef * dist_entropy) and value_loss of GR_MAPPO.ppo_update for one minibatch, differentiable with respect to
+    `logits` [rows, n_actions] (the policy head's linear output, before masking) and `values` [rows, 1]; policy_loss, dist_entropy, ratio_mean
+    (imp_weights.mean()), action_log_probs and imp_weights come detached. sample_or_fields: the generators' 16-tuple as it comes out of
+    DeviceRolloutBuffer.feed_forward_generator, or a dict with actions (float32 or int64), value_preds, returns, active_masks, old_action_log_probs,
+    adv_targ and optionally available_actions. args: the runner's args (clip_param, huber_delta, entropy_coef, use_policy_active_masks,
+    use_value_active_masks, use_clipped_value_loss, use_huber_loss, use_valuenorm, use_popart; the reference's defaults where absent).
+    With use_valuenorm the ValueNorm's three tensors (on the device) are updated in place before the returns are normalised, as cal_value_loss does.
+    f16 / bf16 logits and values are widened to float32 first. A zero sum of active_masks gives NaN losses, like the reference's 0 / 0; nothing here
+    waits for the device. workspace: an optional uint8 device tensor of workspace_bytes(rows) to reuse between calls."""
+    flags, clip, delta, ent = _flags(args)
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or not logits.is_floating_point():
+        raise ValueError("logits must be a floating-point tensor [rows, n_actions]")
+    dev = logits.device
+    rows, K = int(logits.shape[0]), int(logits.shape[1])
+    if rows < 1 or K < 1:
+        raise ValueError("logits must have at least one row and one action")
+    if K > _lib.PPO_MAX_ACTIONS:
+        raise ValueError("n_actions = %d is above the supported %d" % (K, _lib.PPO_MAX_ACTIONS))
+    if not isinstance(values, torch.Tensor) or not values.is_floating_point() or tuple(values.shape) not in ((rows, 1), (rows,)):
+        raise ValueError("values must be a floating-point tensor of shape (%d, 1)" % rows)
+    if values.device != dev:
+        raise ValueError("values must be on %s (the device of logits)" % dev)
+    if logits.dtype in (torch.float16, torch.bfloat16):
+        logits = logits.float()
+    if values.dtype in (torch.float16, torch.bfloat16):
+        values = values.float()
+    if logits.dtype != torch.float32 or values.dtype != torch.float32:
+        raise ValueError("logits and values must be float32 (or float16 / bfloat16, widened here)")
+    f = _fields(sample_or_fields)
+    cols = {k: _column(k, f[k], rows, dev) for k in ("value_preds", "returns", "active_masks", "old_action_log_probs", "adv_targ")}
+    actions = _column("actions", f["actions"], rows, dev, (torch.float32, torch.int64))
+    avail = f["available_actions"]
+    if avail is not None:
+        if not isinstance(avail, torch.Tensor) or avail.dtype != torch.float32 or tuple(avail.shape) != (rows, K):
+            raise ValueError("available_actions must be a float32 tensor of shape (%d, %d) or None" % (rows, K))
+        if avail.device != dev:
+            raise ValueError("available_actions must be on %s (the device of logits)" % dev)
+        avail = avail.detach().contiguous()
+    state = None
+    plan = _lib.GmpePpoLossPlan()
+    if flags & _lib.PPO_VALUENORM:
+        state, plan.beta, plan.epsilon = _valuenorm_state(value_normalizer, dev)
+        plan.running_mean, plan.running_mean_sq, plan.debiasing_term = (t.data_ptr() for t in state)
+    else:
+        plan.beta, plan.epsilon = 0.99999, 1e-5
+    _need_cuda(dev)
+    nbytes = workspace_bytes(rows)
+    if workspace is None:
+        workspace = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    elif not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous() or \
+            workspace.numel() < nbytes:
+        raise ValueError("workspace must be a contiguous uint8 tensor of at least %d bytes on %s" % (nbytes, dev))
+    plan.rows, plan.n_actions, plan.flags, plan.actions_int64 = rows, K, flags, int(actions.dtype == torch.int64)
+    plan.clip_param, plan.huber_delta, plan.entropy_coef = clip, delta, ent
+    plan.actions = actions.data_ptr()
+    plan.available_actions = None if avail is None else avail.data_ptr()
+    for k, t in cols.items():
+        setattr(plan, k, t.data_ptr())
+    plan.workspace, plan.workspace_bytes = workspace.data_ptr(), workspace.numel()
+    keep = (cols, actions, avail, state, workspace)
+    values2 = values if values.dim() == 2 else values.reshape(rows, 1)
+    s, grad_logits, grad_values, logp, ratio = _launch(logits, values2, plan, keep)
+    o = _lib.PPO_OUT.index
+    return PPOLosses(_Attach.apply(logits, s[o("actor_loss")], grad_logits), _Attach.apply(values2, s[o("value_loss")], grad_values),
+                     s[o("policy_loss")], s[o("dist_entropy")], s[o("ratio_mean")], logp, ratio)

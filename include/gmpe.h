@@ -431,6 +431,61 @@ typedef struct gmpe_learner_plan {
 } gmpe_learner_plan;
 int gmpe_insert_learner(int device, const gmpe_learner_plan* plan, void* stream);
 
+/* The loss arithmetic of one PPO minibatch (GR_MAPPO.ppo_update, onpolicy/algorithms/graph_mappo.py:176-207 + cal_value_loss :89-117) between the policy
+ * head's logits / the critic's values and the two scalars the reference calls .backward() on, with their gradients, in four launches on `stream`
+ * (no atomics, no allocation, no host synchronisation; capturable):
+ *   the masked categorical of Categorical.forward + ACTLayer.evaluate_actions (distributions.py:84-91, act.py:212-220): logits at finfo(float32).min where
+ *   available_actions == 0, log-prob of the action, entropy; ratio = exp(logp - old_action_log_probs), the clipped surrogate; the value loss (huber as
+ *   util.py:24-27 writes it, one-sided: zero for errors below -delta; or mse), clipped or not, with ValueNorm.update applied to the three state scalars
+ *   BEFORE returns are normalised (valuenorm.py:56-85). Means are over active_masks (sum(x * m) / sum(m)) or plain, per flag; a zero mask sum gives NaN.
+ * Per-row arithmetic is float32 as the reference computes it; sums over rows are double, merged in a fixed order: the same rows give the same bits
+ * wherever they lie in memory. Every [rows, 1] array is a contiguous f32 [rows]; logits / available_actions / grad_logits are contiguous [rows, n_actions]
+ * (read and written in 16-byte units when all three are 16-byte aligned, in 4-byte units otherwise). */
+#define GMPE_PPO_POLICY_ACTIVE_MASKS 1   /* args.use_policy_active_masks: policy loss and entropy are means over active_masks        */
+#define GMPE_PPO_VALUE_ACTIVE_MASKS 2    /* args.use_value_active_masks                                                               */
+#define GMPE_PPO_CLIPPED_VALUE_LOSS 4    /* args.use_clipped_value_loss: max(original, clipped)                                       */
+#define GMPE_PPO_HUBER_LOSS 8            /* args.use_huber_loss (else mse)                                                            */
+#define GMPE_PPO_VALUENORM 16            /* args.use_valuenorm: update the three scalars, then normalise returns with them            */
+#define GMPE_PPO_MAX_ACTIONS 64          /* n_actions above this: GMPE_ERR_INVALID_ARG                                                */
+#define GMPE_PPO_OUT_POLICY_LOSS 0       /* columns of `out` (f64)                                                                    */
+#define GMPE_PPO_OUT_DIST_ENTROPY 1
+#define GMPE_PPO_OUT_ACTOR_LOSS 2        /* policy_loss - entropy_coef * dist_entropy                                                 */
+#define GMPE_PPO_OUT_VALUE_LOSS 3
+#define GMPE_PPO_OUT_RATIO_MEAN 4        /* imp_weights.mean()                                                                        */
+#define GMPE_PPO_OUT_DENOM_POLICY 5      /* sum(active_masks) or rows                                                                 */
+#define GMPE_PPO_OUT_DENOM_VALUE 6
+#define GMPE_PPO_NUM_OUT 7
+typedef struct gmpe_ppo_loss_plan {
+    int64_t rows;                       /* B >= 1                                                                                     */
+    int32_t n_actions;                  /* K, 1 .. GMPE_PPO_MAX_ACTIONS                                                               */
+    int32_t flags;                      /* GMPE_PPO_*                                                                                 */
+    int32_t actions_int64;              /* 1: actions is int64 [rows], 0: f32 [rows] (truncated like .long())                         */
+    int32_t reserved;                   /* 0                                                                                          */
+    double clip_param, huber_delta, entropy_coef;
+    double beta, epsilon;               /* ValueNorm's (0.99999, 1e-5); read with GMPE_PPO_VALUENORM                                  */
+    const float* logits;                /* [rows, K] the head's linear output, before masking                                         */
+    const float* values;                /* [rows]                                                                                     */
+    const void* actions;                /* [rows]; values outside 0 .. K-1 are the caller's error (read as the nearest column)        */
+    const float* available_actions;     /* [rows, K] or NULL (all available)                                                          */
+    const float* old_action_log_probs;  /* [rows]                                                                                     */
+    const float* adv_targ;              /* [rows]                                                                                     */
+    const float* value_preds;           /* [rows]                                                                                     */
+    const float* returns;               /* [rows]                                                                                     */
+    const float* active_masks;          /* [rows]                                                                                     */
+    float* running_mean;                /* f32 [1] each, updated in place; all three set exactly with GMPE_PPO_VALUENORM              */
+    float* running_mean_sq;
+    float* debiasing_term;
+    double* out;                        /* f64 [GMPE_PPO_NUM_OUT]                                                                     */
+    float* grad_logits;                 /* [rows, K] d actor_loss / d logits (already divided by the denominator)                     */
+    float* grad_values;                 /* [rows]    d value_loss / d values                                                          */
+    float* action_log_probs;            /* [rows] or NULL                                                                             */
+    float* imp_weights;                 /* [rows] or NULL                                                                             */
+    void* workspace;                    /* device scratch of gmpe_ppo_loss_workspace_bytes(rows) bytes, 8-byte aligned                */
+    size_t workspace_bytes;
+} gmpe_ppo_loss_plan;
+int gmpe_ppo_loss_workspace_bytes(int64_t rows, size_t* bytes_out);
+int gmpe_ppo_loss(int device, const gmpe_ppo_loss_plan* plan, void* stream);
+
 /* ---- Evaluation of a policy over a batch of episodes (handle-less): GMPERunner.render(get_metrics=True) as one episode per env ----
  * (onpolicy/runner/shared/graph_mpe_runner.py:526-1060, base_runner.py:194-574). Every env plays one episode from a reset; the caller's policy acts,
  * the engine steps, gmpe_episode_record books the step. No allocation, no host synchronisation, every launch on `stream`.
