@@ -253,6 +253,59 @@ def test_determinism_across_calls_and_alignments():
                     np.testing.assert_array_equal(v.view(np.uint32), r[k].view(np.uint32), err_msg=k)
 
 
+def test_graph_capture_replays_identically():
+    """Forward and both backwards of one minibatch captured into a graph: every replay gives the bits of the eager call made in the same ValueNorm state,
+    and the three state tensors after r replays are those after r eager calls."""
+    import torch
+    case = ("generic", 257, 25, dict(valuenorm=True), "mixed", "given")
+    inp, c, st, _ = _ref(case)
+    assert c.use_valuenorm
+    lg = torch.tensor(inp["logits"], device="cuda", requires_grad=True)
+    vl = torch.tensor(inp["values"], device="cuda", requires_grad=True)
+    f = {k: torch.tensor(inp[k], device="cuda") for k in P.COLS + ("actions", "available_actions")}
+    vn = _VN(torch, st)
+    ws = torch.empty(gmpe.ppo_loss.workspace_bytes(257), dtype=torch.uint8, device="cuda")
+    names = ("running_mean", "running_mean_sq", "debiasing_term")
+
+    def reset():
+        for k in names:
+            getattr(vn, k).copy_(torch.tensor(np.asarray(st[k], np.float32)))
+
+    def call():
+        res = gmpe.ppo_losses(lg, vl, f, _args(c), vn, workspace=ws)
+        gl, = torch.autograd.grad(res.actor_loss, lg)
+        gv, = torch.autograd.grad(res.value_loss, vl)
+        return tuple(getattr(res, k).detach() for k in res._fields) + (gl, gv)
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        call()                                                       # warm-up on a side stream, as torch.cuda.graph wants
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+    reps = 3
+    reset()
+    eager, states = [], []
+    for _ in range(reps):
+        eager.append([t.cpu().numpy().copy() for t in call()])
+        states.append(vn.state())
+    eager_state = states[-1]
+    assert all((states[0][k] != eager_state[k]).all() for k in names)                # every call moves the state: r replays must be told from one
+    reset()
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        static = call()
+    for t in static:
+        t.fill_(-7.0)
+    for r in range(reps):
+        graph.replay()
+        torch.cuda.synchronize()
+        for i, (x, y) in enumerate(zip(eager[r], static)):
+            np.testing.assert_array_equal(x.view(np.uint32), y.cpu().numpy().view(np.uint32), err_msg="replay %d output %d" % (r, i))
+    for k, v in vn.state().items():
+        np.testing.assert_array_equal(v.view(np.uint32), eager_state[k].view(np.uint32), err_msg=k)
+
+
 def _torch_ops(torch, logits, values, f, c):
     """The same arithmetic as device torch ops (float32, autograd), valuenorm off."""
     x = logits.clone()

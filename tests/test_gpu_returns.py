@@ -121,6 +121,7 @@ def test_normalisation_edge_cases_and_determinism():
     _, _, adv, advn = _run(torch, d, True, False, None)
     assert advn[3, 17, 0] == 0.0
     np.testing.assert_allclose(advn, (adv - adv[3, 17, 0]) / np.float32(1e-5), rtol=1e-5)
+    np.testing.assert_array_equal(_bits(advn), _bits((adv - adv[3, 17, 0]) / np.float32(1e-5)))   # mean = the entry, den = float32(1e-5): exact
     d = _random_inputs(np.random.RandomState(4), 25, 40960)
     a = _run(torch, d, True, True, None)
     b = _run(torch, d, True, True, None)

@@ -185,3 +185,147 @@ def test_numpy_stop_action_rule_is_the_reference():
         np.testing.assert_array_equal(d["policy_avail"][ep], d["slots"][ep][1:])          # what the policy acted with at step t sits in slot t + 1
     np.testing.assert_array_equal(d["slots"][1][0], d["slots"][0][T])                      # after_update carries the last slot
     assert (d["dones"].all(-1)).any() and (d["dones"].any(-1) & ~d["dones"].all(-1)).any()
+
+
+# ------------------------------------------------------------------------------------------------ the advantage statistics: the inputs must discriminate
+_V = R.VARIANTS
+_ALWAYS = ("weight_b", "no_shortcuts", "ddof1", "inactive_kept", "last_wave_dropped")
+_NINE = _ALWAYS + ("tail_dropped",)
+# case -> the wrong variants of the kernel's order that leave the candidate set on it, (k_returns' order, k_advantages' order)
+CAUGHT = {
+    "offset": (("float32", "naive32") + _NINE, ("naive32",) + _NINE),            # float32 Welford happens to survive the ascending order ...
+    "offset2": ((("float32", "naive32") + _NINE),) * 2,                          # ... of that seed, not of this one
+    "unequal": (("float32", "naive32") + _NINE, ("float32",) + _NINE),
+    "nan": (_NINE + ("nan_kept",),) * 2,
+    "tail_partial": (("naive32",) + _NINE + ("hi_partials_dropped",),) * 2,      # T = 2: its only chunk is a tail
+    "steps8": (_ALWAYS,) * 2,
+    "steps9": (_NINE,) * 2,
+    "steps16": (_ALWAYS,) * 2,
+    "steps17": (_NINE,) * 2,
+}
+# where the float64 emulation of the kernel's order lands among the candidates: (dm, dd) in ulps, either order
+HOST_OFFSETS = {k: (0, 0) for k in CAUGHT}
+assert all(HOST_OFFSETS[k] == R.KERNEL_ORDER_OFFSETS for k in CAUGHT)            # what the GPU test holds the device to
+
+
+def _candidate_cases():
+    return [k for k in R.stat_cases() if k not in R.EXACT_CASES]
+
+
+def test_statistics_cases_have_the_shapes_and_contents_they_claim():
+    c = R.stat_cases()
+    assert set(c) == set(CAUGHT) | set(R.EXACT_CASES)
+    shapes = dict(offset=(9, 130), offset2=(9, 130), unequal=(9, 193), nan=(9, 130), tail_partial=(2, 64 * 257 + 5), const=(9, 130), two_equal=(3, 70),
+                  **{"steps%d" % T: (T, 65) for T in (8, 9, 16, 17)})
+    for k, (a, am) in c.items():
+        assert a.shape == shapes[k] and am.shape == (a.shape[0] + 1, a.shape[1]), k
+    a, am = c["offset"]
+    m, s, n = R.stats64(a, am)
+    assert abs(m - 100) < 0.1 and abs(s - 0.1) < 0.01 and 900 < np.hypot(m, s) / s < 1024
+    m, s, n = R.stats64(*c["offset2"])
+    assert abs(m - 100) < 0.1 and abs(s - 0.1) < 0.01 and 900 < np.hypot(m, s) / s < 1024
+    a, am = c["unequal"]
+    act = am[:9] != 0
+    assert act[:, :64].all() and act[:, 64:128].sum() == 1 and a[:, 64:128][act[:, 64:128]] == 50 and not act[:, 128:192].any() and act[:, 192].all()
+    a, am = c["nan"]
+    act = am[:9] != 0
+    assert np.isnan(a[act]).mean() >= 0.10 and np.isnan(a[~act]).any() and np.isposinf(a[~act]).any() and np.isneginf(a[~act]).any()
+    assert (a[~act] == np.float32(1e30)).any() and (np.abs(a[~act]) < 100).any()
+    a, am = c["tail_partial"]
+    act = am[:2] != 0
+    assert a.shape[1] > 257 * 64 and np.abs(a[:, :256 * 64][act[:, :256 * 64]]).max() < 0.2 and np.abs(a[:, 256 * 64:][act[:, 256 * 64:]] - 10).max() < 3
+    assert act[:, 256 * 64:257 * 64].any() and act[:, 257 * 64:].any()
+    a, am = c["const"]
+    assert (a[am[:9] != 0] == R.CONST_VALUE).all() and (a[am[:9] == 0] != R.CONST_VALUE).all() and (am[:9] == 0).any()
+    a, am = c["two_equal"]
+    t, q = np.nonzero(am[:3])
+    assert len(t) == 2 and q[0] // 64 != q[1] // 64 and a[t[0], q[0]] == a[t[1], q[1]]
+    for k, (a, am) in c.items():                                                # a partial last wave and an inactive entry everywhere
+        assert a.shape[1] % 64 and (am[:-1] == 0).any(), k
+
+
+def test_stats64_and_candidates():
+    rng = np.random.RandomState(0)
+    a = (3 + rng.randn(5, 7, 1)).astype(np.float32)
+    am = (rng.rand(6, 7, 1) > 0.3).astype(np.float32)
+    a[1, 2] = np.nan
+    x = a[:, :, 0][(am[:5, :, 0] != 0) & ~np.isnan(a[:, :, 0])].astype(np.float64)
+    m, s, n = R.stats64(a, am)
+    assert n == x.size and abs(m - x.mean()) < 1e-15 and abs(s - x.std()) < 1e-15
+    assert R.stats64(a, np.zeros_like(am))[2] == 0
+    pairs = R.candidate_pairs(m, s, n)
+    assert len(pairs) == 15 and len({(p[2], p[3]) for p in pairs}) == 15
+    one = np.float32(m)
+    assert {p[2] for p in pairs} == {np.nextafter(one, np.float32(-9)), one, np.nextafter(one, np.float32(9))}
+    d0 = np.float32(np.float32(s) + np.float32(1e-5))
+    assert max(abs(float(p[3]) - float(d0)) for p in pairs) == 2 * float(np.spacing(d0))
+    for bad in ((m, s, 1), (m, s, 2 ** 16 + 1), (m, 0.0, n), (2000.0, 1.0, n), (1e-4, 1.0, n), (0.0, 1.0, n)):
+        with pytest.raises(AssertionError):
+            R.candidate_pairs(*bad)
+    # match_pair: the one candidate, NaN as NaN, None outside the set, and a constant input refused
+    for dm, dd, mm, d in pairs:
+        assert R.match_pair(a.view(np.uint32), R.normalize32(a, mm, d).view(np.uint32), pairs) == (dm, dd)
+    far = R.normalize32(a, pairs[0][2], np.nextafter(pairs[0][3], np.float32(-9)))
+    assert R.match_pair(a.view(np.uint32), far.view(np.uint32), pairs) is None
+    c = np.full((4, 3), 2.5, np.float32)
+    with pytest.raises(AssertionError, match="discriminate"):
+        R.match_pair(c.view(np.uint32), R.normalize32(c, np.float32(2.5), d0).view(np.uint32), [(0, 0, np.float32(2.5), d0), (0, 1, np.float32(2.5), 2 * d0)])
+
+
+@pytest.mark.parametrize("case", list(CAUGHT))
+def test_kernel_order_lands_inside_and_every_wrong_variant_outside(case):
+    """The float64 emulation of the kernel's order is inside the candidate set of every case, and the table of which wrong variant leaves it on
+    which case is what CAUGHT says. Together the cases catch all ten."""
+    a, am = R.stat_cases()[case]
+    pairs = R.candidate_pairs(*R.stats64(a, am))
+    for asc, want in zip((False, True), CAUGHT[case]):
+        m, d = R.kernel_order_stats(a, am, asc)
+        assert R.pair_offsets(m, d, pairs) == HOST_OFFSETS[case], (case, asc)
+        # ... and the array it implies is told apart from every other candidate's
+        assert R.match_pair(a.view(np.uint32), R.normalize32(a, m, d).view(np.uint32), pairs) == HOST_OFFSETS[case]
+        caught = {v for v in _V if R.pair_offsets(*R.kernel_order_stats(a, am, asc, v), pairs) is None}
+        assert caught == set(want), (case, asc, sorted(caught))
+
+
+def test_every_wrong_variant_is_caught_by_a_named_case():
+    for path in (0, 1):
+        assert set(_V) == set().union(*(CAUGHT[k][path] for k in CAUGHT))
+    assert [k for k in CAUGHT if "hi_partials_dropped" in CAUGHT[k][0]] == ["tail_partial"]
+    assert [k for k in CAUGHT if "nan_kept" in CAUGHT[k][0]] == ["nan"]
+    assert {k for k in CAUGHT if "tail_dropped" not in CAUGHT[k][0]} == {"steps8", "steps16"}     # no tail at a multiple of the unroll factor
+    for path in (0, 1):                                                          # float32 accumulators: more than one case on either call site
+        assert len([k for k in CAUGHT if "float32" in CAUGHT[k][path]]) >= 2
+
+
+@pytest.mark.parametrize("T", R.STEP_TS)
+def test_branch_inputs_stay_inside_the_candidate_limits(T):
+    """The all-branches GPU test matches its normalised advantages to a candidate pair too: on the CPU, the advantages of every branch are inside
+    candidate_pairs' limits (it asserts n and both condition numbers) and the kernel's order lands at the expected offsets in either order."""
+    d = R.branch_inputs(T)
+    for gae in (True, False):
+        for proper in (False, True):
+            for den in (None, R.DENORM):
+                adv = R.branch_expectations(d, gae, proper, den)[2]
+                pairs = R.candidate_pairs(*R.stats64(adv, d["active_masks"]))
+                for asc in (False, True):
+                    assert R.pair_offsets(*R.kernel_order_stats(adv, d["active_masks"], asc), pairs) == R.KERNEL_ORDER_OFFSETS, (T, gae, proper, asc)
+
+
+@pytest.mark.parametrize("case", R.EXACT_CASES)
+def test_constant_cases_are_exact_in_the_kernel_order(case):
+    a, am = R.stat_cases()[case]
+    m, s, n = R.stats64(a, am)
+    assert m == float(R.CONST_VALUE) and s == 0.0 and n >= 2
+    for asc in (False, True):
+        assert R.kernel_order_stats(a, am, asc) == (R.CONST_VALUE, np.float32(1e-5))
+
+
+def test_prescribed_inputs_give_the_prescribed_advantages():
+    for case, (a, am) in R.stat_cases().items():
+        T, L = a.shape
+        p = R.prescribed_inputs(a, "advantages")
+        assert R._same_bits(R.np_advantages(p["returns"], p["value_preds"]), a.reshape(T, L, 1)), case
+        p = R.prescribed_inputs(a, "recurrence")
+        with np.errstate(invalid="ignore"):
+            ret, vp = R.np_returns(p["rewards"], p["masks"], p["value_preds"], p["returns"], p["next_value"], 0.99, 0.95, False, False)
+            assert R._same_bits(R.np_advantages(ret, vp), a.reshape(T, L, 1)), case
