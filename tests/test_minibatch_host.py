@@ -1,6 +1,8 @@
 """CPU side of the PPO minibatch gather (include/gmpe.h gmpe_minibatch_gather; gmpe.minibatch; DeviceRolloutBuffer.feed_forward_generator /
 recurrent_generator): the exported symbol, the plan struct layout, the argument checks of the C entry point and of the Python wrappers before any launch, and the
-NumPy restatement of the sampler arithmetic and the two index maps (tests/minibatch_lib.py) against the reference's own yields."""
+NumPy restatement of the sampler arithmetic and the two index maps (tests/minibatch_lib.py) against the reference's own yields; the byte-level form of that
+restatement (gather_bytes) against the shaped one on the same yields, and the cases the kernel tests draw from it (KERNEL_CASES): which case tells which wrong
+restatement from the right one, and what the cases cover."""
 import ctypes as C
 import os
 import subprocess
@@ -68,6 +70,8 @@ def _plan(**kw):
     dict(T=1 << 16, N=1 << 16, A=1), dict(perm=None), dict(perm=0x10004), dict(rows=0), dict(offset=-1), dict(offset=20),
     dict(f_kind=9), dict(f_src=None), dict(f_dst=None), dict(f_row_bytes=6), dict(f_row_bytes=0), dict(f_slot_stride=16),
     dict(f_kind=_lib.MB_CHUNK_HEAD), dict(f_dst=0x30002), dict(f_kind=_lib.MB_TABLE_NODE),
+    dict(T=1 << 11, N=1 << 10, A=1 << 10, f_slot_stride=1 << 24),                                   # T * N * A exactly 2^31
+    dict(perm_len=1 << 27, rows=1 << 27, f_row_bytes=1040, f_slot_stride=6 * 1040),                 # 2^27 rows of 65 units: rows * units above 2^31 - 1
 ])
 def test_c_entry_point_refuses_bad_plans_before_any_device_call(bad):
     lib = _lib.load()
@@ -165,3 +169,186 @@ def test_numpy_restatement_equals_the_reference_bit_for_bit():
                     continue
                 assert o[k].dtype == ref.dtype and o[k].shape == ref.shape and np.array_equal(o[k], ref), (case, b, k)
     assert seen_rec_cross and left_chunks
+
+
+def test_the_two_size_refusals_name_their_reason():
+    lib = _lib.load()
+    for bad, why in ((dict(T=1 << 11, N=1 << 10, A=1 << 10, f_slot_stride=1 << 24), "T * N * A must be below 2^31"),
+                     (dict(perm_len=1 << 27, rows=1 << 27, f_row_bytes=1040, f_slot_stride=6 * 1040), "too many units")):
+        assert lib.gmpe_minibatch_gather(None, 0, C.byref(_plan(**bad)), None) == -1
+        assert why in lib.gmpe_last_error().decode(), bad
+    ok = _plan(T=(1 << 11) - 1, N=1 << 10, A=1 << 10, f_slot_stride=1 << 24, f_row_bytes=6)          # 2^31 - 2^20 samples pass that check: refused for the row size
+    assert lib.gmpe_minibatch_gather(None, 0, C.byref(ok), None) == -1 and "row_bytes" in lib.gmpe_last_error().decode()
+
+
+def test_byte_level_constants_are_the_bindings():
+    assert (M.FEED_FORWARD, M.RECURRENT, M.ROW, M.ENV_ROW, M.CHUNK_HEAD, M.MAX_FIELDS) == \
+        (_lib.MB_FEED_FORWARD, _lib.MB_RECURRENT, _lib.MB_ROW, _lib.MB_ENV_ROW, _lib.MB_CHUNK_HEAD, _lib.MB_MAX_FIELDS)
+
+
+def test_byte_level_restatement_equals_the_shaped_one_on_the_reference_yields():
+    """gather_bytes on a contiguous image of the fixture's arrays == gather + ff_samples / rec_samples, which the test above pins to the reference"""
+    g = np.load(GOLD)
+    T, N, A = int(g["T"]), int(g["N"]), int(g["A"])
+    inp = {k[3:]: np.ascontiguousarray(g[k]) for k in g.files if k.startswith("in_")}
+    checked = 0
+    for case in (str(c) for c in g["cases"]):
+        perm, nmb, L = g[case + "_perm"], int(g[case + "_num_mini_batch"]), int(g[case + "_data_chunk_length"])
+        central, avail, rec = bool(g[case + "_centralized"]), bool(g[case + "_avail"]), bool(g[case + "_recurrent"])
+        arrays = dict(inp, available_actions=inp["available_actions"] if avail else None)
+        share = M.ENV_ROW if central else M.ROW
+        spec = [("share_obs", share, "obs"), ("share_agent_id", share, "agent_id")] + \
+            [(k, M.CHUNK_HEAD if rec and k.startswith("rnn") else M.ROW, k) for k in M.NAMES if not k.startswith("share") and arrays[k] is not None]
+        for off, rows in (M.rec_sampler(T, N, A, nmb, L) if rec else M.ff_sampler(T, N, A, nmb)):
+            if rec:
+                (t, n, a), heads = M.rec_samples(perm, off, rows, T, N, A, L)
+                want = M.gather(arrays, t, n, a, central, heads)
+            else:
+                want = M.gather(arrays, *M.ff_samples(perm, off, rows, T, N, A), central)
+            fields, cur = [], 256
+            for name, kind, src in spec:                                       # destinations, 256 sentinel bytes between them
+                x = arrays[src]
+                rb = x[0, 0].nbytes if kind == M.ENV_ROW else x[0, 0, 0].nbytes
+                n_out = rows if kind == M.CHUNK_HEAD or not rec else rows * L
+                fields.append(dict(kind=kind, row_bytes=rb, slot_stride=x[0].nbytes, dst=cur))
+                cur = -(-(cur + n_out * rb) // 256) * 256 + 256
+            for f, (name, kind, src) in zip(fields, spec):                     # the arrays as they lie in memory: contiguous, exactly one slot apart
+                f["src"], cur = cur, -(-(cur + arrays[src].nbytes) // 256) * 256
+            image = np.full(cur, M.SENTINEL, dtype=np.uint8)
+            for f, (name, kind, src) in zip(fields, spec):
+                image[f["src"]:f["src"] + arrays[src].nbytes] = arrays[src].reshape(-1).view(np.uint8)
+            plan = dict(mode=M.RECURRENT if rec else M.FEED_FORWARD, T=T, N=N, A=A, L=L if rec else 1, perm=perm, offset=off, rows=rows, fields=fields)
+            out = M.gather_bytes(plan, image)
+            expect = image.copy()
+            for f, (name, kind, src) in zip(fields, spec):
+                w = np.ascontiguousarray(want[name]).reshape(-1).view(np.uint8)
+                assert w.size == M.out_rows(plan, kind) * f["row_bytes"], (case, name)
+                expect[f["dst"]:f["dst"] + w.size] = w
+                checked += 1
+            assert np.array_equal(out, expect), (case, off)
+    assert checked > 100
+
+
+class _Narrow(M.Header):
+    def entry(self, e):
+        return e & 0xffffffff
+
+
+class _LessEqual(M.Header):
+    def in_range(self, e, n_valid):
+        return (e >= 0) & (e <= n_valid)
+
+
+class _Swapped(M.Header):
+    def split(self, r, rows):
+        return r // rows, r % rows
+
+
+class _HeadLast(M.Header):
+    def head_l(self, rows):
+        return rows - 1
+
+
+class _EnvAsSample(M.Header):
+    def row_index(self, kind, n, a, A):
+        return n * A + a
+
+
+class _ExactSlot(M.Header):
+    def stride(self, field, slot):
+        return slot
+
+
+class _FieldGreater(M.Header):
+    def unwritten_prefix(self, plan, i):                                       # the field's first workgroup finds its predecessor's thread count and returns
+        return M.BLOCK * M.unit_width(plan["fields"][i]) if i else 0
+
+
+class _NoModN(M.Header):
+    def ff_tna(self, j, T, N, A):
+        return j // (N * A), j // A, j % A
+
+
+class _CeilCount(M.Header):
+    def valid_count(self, samples, L, recurrent):
+        return -(-samples // L) if recurrent else samples
+
+
+# wrong restatement -> (rules, a case that must tell it from the right one)
+WRONG = {
+    "range check after narrowing to 32 bits": (_Narrow(), "oor_ff"),
+    "entry <= valid count": (_LessEqual(), "oor_ff"),
+    "recurrent r % rows and r / rows swapped": (_Swapped(), "rec_L7"),
+    "chunk heads at l = rows - 1": (_HeadLast(), "rec_LT"),
+    "GMPE_MB_ENV_ROW addressed as a sample row": (_EnvAsSample(), "align_ff_env_row_16"),
+    "slot_stride replaced by the exact slot": (_ExactSlot(), "widths_alone"),
+    "fields matched to workgroups with >": (_FieldGreater(), "wl_255"),
+    "n = j / A without % N": (_NoModN(), "single"),
+    "valid chunk count ceil(T*N*A / L)": (_CeilCount(), "oor_rec"),
+}
+
+
+@pytest.fixture(scope="module")
+def kernel_cases():
+    built = []
+    for case in M.KERNEL_CASES:
+        plan, image = M.build_case(case)
+        built.append((case["name"], plan, image, M.gather_bytes(plan, image)))
+    assert len({b[0] for b in built}) == len(built)
+    return built
+
+
+def _inside(plan, image, trace, what):
+    """every source byte read lies behind the destinations and inside the image; every permutation entry read exists"""
+    assert plan["src0"] <= trace["src_min"] and trace["src_max"] <= image.size and trace["perm_max"] < len(plan["perm"]), (what, trace, image.size)
+
+
+def test_every_wrong_restatement_is_told_by_a_named_case(kernel_cases):
+    for what, (rules, named) in WRONG.items():
+        told = []
+        for name, plan, image, right in kernel_cases:
+            trace = {}
+            wrong = M.gather_bytes(plan, image, rules, trace)
+            _inside(plan, image, trace, (what, name))                         # so the same mistake made in the kernel reads nothing outside the buffer
+            if not np.array_equal(wrong, right):
+                told.append(name)
+        print("%-45s told by %d cases: %s" % (what, len(told), " ".join(told[:6])))
+        assert named in told, (what, named, told)
+    # the second case of the pairs the issue names twice
+    by = {b[0]: b for b in kernel_cases}
+    for what, named in (("range check after narrowing to 32 bits", "oor_rec"), ("chunk heads at l = rows - 1", "oor_rec"),
+                        ("fields matched to workgroups with >", "wl_257_reversed"), ("recurrent r % rows and r / rows swapped", "wl_256")):
+        _, plan, image, right = by[named]
+        assert not np.array_equal(M.gather_bytes(plan, image, WRONG[what][0]), right), (what, named)
+
+
+def test_kernel_cases_cover_widths_thread_totals_and_the_field_limit(kernel_cases):
+    alone = {(q, w): [] for q in ("src", "dst", "slot_stride", "row_bytes") for w in (16, 8, 4)}
+    totals, max_fields, between = set(), [], []
+    for name, plan, image, right in kernel_cases:
+        trace = {}
+        assert np.array_equal(M.gather_bytes(plan, image, trace=trace), right)
+        _inside(plan, image, trace, name)
+        fields = plan["fields"]
+        for f in fields:
+            assert f["kind"] in (M.ROW, M.ENV_ROW, M.CHUNK_HEAD) and f["row_bytes"] in M.ROW_SIZES and (f["src"] | f["dst"] | f["slot_stride"]) % 4 == 0
+            slot = f["row_bytes"] * (plan["N"] if f["kind"] == M.ENV_ROW else plan["N"] * plan["A"])
+            assert f["slot_stride"] - slot in M.PADS and f["src"] % 256 in M.OFFSETS and f["dst"] % 256 in M.OFFSETS
+            for q in ("src", "dst", "slot_stride", "row_bytes"):
+                if all(f[o] % 16 == 0 for o in ("src", "dst", "slot_stride", "row_bytes") if o != q):
+                    alone[(q, M.unit_width(f))].append(name)
+            totals.add(M.field_threads(plan, f))
+        # guards: at least 256 sentinel bytes before and behind every destination, and they are still there in the expected image
+        for f in fields:
+            end = f["dst"] + M.out_rows(plan, f["kind"]) * f["row_bytes"]
+            assert (right[f["dst"] - 256:f["dst"]] == M.SENTINEL).all() and (right[end:end + 256] == M.SENTINEL).all() and end + 256 <= plan["src0"], name
+        if len(fields) == M.MAX_FIELDS:
+            max_fields.append(name)
+        groups = [-(-M.field_threads(plan, f) // M.BLOCK) for f in fields]
+        if any(groups[i] == 1 and groups[i - 1] > 1 and groups[i + 1] > 1 for i in range(1, len(fields) - 1)):
+            between.append(name)
+    assert all(alone.values()), {k: len(v) for k, v in alone.items()}
+    assert {255, 256, 257} <= totals and 1 in totals and max(totals) > 16 * M.BLOCK
+    assert "wl_255" in max_fields and "wl_255_reversed" in max_fields
+    assert "wl_255" in between and "wl_255_reversed" in between
+    assert any(len(b[1]["fields"]) == 1 for b in kernel_cases)
