@@ -22,7 +22,7 @@ def __getattr__(name):
     if name == "BatchedEvaluator":
         from . import evaluate
         return evaluate.BatchedEvaluator
-    if name in ("ppo_losses", "PPOLosses"):
+    if name in ("ppo_losses", "PPOLosses", "ppo_losses_popart", "PPOPopArtLosses"):
         from . import ppo_loss
         return getattr(ppo_loss, name)
     if name == "GmpeEngine":

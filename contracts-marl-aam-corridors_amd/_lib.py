@@ -20,7 +20,7 @@ SYMBOLS = ["gmpe_abi_version", "gmpe_last_error", "gmpe_obs_dim", "gmpe_node_fea
            "gmpe_returns_workspace_bytes", "gmpe_compute_returns", "gmpe_available_actions_from_dones", "gmpe_minibatch_gather",
            "gmpe_insert_learner", "gmpe_episode_record", "gmpe_episode_metrics", "gmpe_episode_summary",
            "gmpe_minibatch_edges", "gmpe_minibatch_edges_workspace_bytes", "gmpe_episode_record_series",
-           "gmpe_ppo_loss", "gmpe_ppo_loss_workspace_bytes"]
+           "gmpe_ppo_loss", "gmpe_ppo_loss_workspace_bytes", "gmpe_ppo_loss_popart", "gmpe_ppo_loss_popart_workspace_bytes"]
 
 
 class GmpeOutputs(C.Structure):
@@ -150,6 +150,22 @@ class GmpePpoLossPlan(C.Structure):
                 ("imp_weights", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
+POPART_MAX_HIDDEN = 1024
+
+
+class GmpePopartLossPlan(C.Structure):
+    """gmpe_popart_loss_plan (include/gmpe.h): the same minibatch with PopArt, from the critic's features to the rescaled output layer."""
+    _fields_ = [("rows", C.c_int64), ("n_actions", C.c_int32), ("hidden", C.c_int32), ("flags", C.c_int32), ("actions_int64", C.c_int32),
+                ("clip_param", C.c_double), ("huber_delta", C.c_double), ("entropy_coef", C.c_double), ("beta", C.c_double), ("epsilon", C.c_double),
+                ("logits", C.c_void_p), ("critic_features", C.c_void_p), ("actions", C.c_void_p), ("available_actions", C.c_void_p),
+                ("old_action_log_probs", C.c_void_p), ("adv_targ", C.c_void_p), ("value_preds", C.c_void_p), ("returns", C.c_void_p),
+                ("active_masks", C.c_void_p), ("weight", C.c_void_p), ("bias", C.c_void_p), ("stddev", C.c_void_p), ("mean", C.c_void_p),
+                ("mean_sq", C.c_void_p), ("debiasing_term", C.c_void_p), ("weight_out", C.c_void_p), ("bias_out", C.c_void_p),
+                ("stddev_out", C.c_void_p), ("values_out", C.c_void_p), ("out", C.c_void_p), ("grad_logits", C.c_void_p),
+                ("grad_features", C.c_void_p), ("grad_weight", C.c_void_p), ("grad_bias", C.c_void_p), ("action_log_probs", C.c_void_p),
+                ("imp_weights", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
 class GmpeError(RuntimeError):
     pass
 
@@ -211,6 +227,8 @@ def load():
     lib.gmpe_episode_summary.argtypes = [I, C.POINTER(GmpeEpisodeSummaryPlan), P]
     lib.gmpe_ppo_loss.argtypes = [I, C.POINTER(GmpePpoLossPlan), P]
     lib.gmpe_ppo_loss_workspace_bytes.argtypes = [C.c_int64, C.POINTER(C.c_size_t)]
+    lib.gmpe_ppo_loss_popart.argtypes = [I, C.POINTER(GmpePopartLossPlan), P]
+    lib.gmpe_ppo_loss_popart_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.POINTER(C.c_size_t)]
     from .config import ABI_VERSION
     if lib.gmpe_abi_version() != ABI_VERSION:
         raise GmpeError("libgmpe.so ABI version mismatch")

@@ -29,6 +29,7 @@
 #include <string>
 
 #include "../../include/gmpe.h"
+#include "gmpe_ppo_rows.h"
 
 #pragma clang fp contract(off)
 
@@ -38,12 +39,10 @@ int report_error(int code, const std::string& m);   // gmpe_step.hip: the librar
 
 namespace {
 
-constexpr int TILE = 256;         // rows per workgroup = lanes per workgroup: one lane per row
-constexpr int NW = TILE / 64;
-constexpr int NSTAT = 3;          // sum returns, sum returns^2, sum active_masks
+using namespace gmpe_ppo;         // gmpe_ppo_rows.h: TILE, the fixed-order sums, tile_copy and the row arithmetic, shared with gmpe_ppo_popart.hip
+
 constexpr int NROW = 4;           // sum -min(surr1, surr2) * w, sum H * w, sum value_loss * w, sum ratio
 constexpr int HDR_DOUBLES = 4;    // D_policy, D_value, then f32 mean, std (one double), one spare
-constexpr float FMIN = -FLT_MAX;  // torch.finfo(torch.float32).min
 
 struct LossArgs {
     int64_t B;
@@ -57,65 +56,10 @@ struct LossArgs {
     double *stat_part, *row_part, *hdr, *out;
 };
 
-// lane 0 of every wave holds the wave's sum; the lower lane of a pair is the left operand (one fixed order)
-template <int N>
-__device__ __forceinline__ void wave_sum(double (&v)[N]) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-#pragma unroll
-        for (int k = 0; k < N; ++k) {
-            const double o = __shfl_xor(v[k], off);
-            v[k] = (threadIdx.x & off) ? o + v[k] : v[k] + o;
-        }
-    }
-}
-
-// the workgroup's sum of v[] -> dst[0..N), waves added in wave order
-template <int N>
-__device__ __forceinline__ void block_sum(double (&v)[N], double* red, double* dst) {
-    wave_sum<N>(v);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int k = 0; k < N; ++k) red[w * N + k] = v[k];
-    __syncthreads();
-    if (threadIdx.x < N) {
-        double s = red[threadIdx.x];
-        for (int q = 1; q < NW; ++q) s += red[q * N + threadIdx.x];
-        dst[threadIdx.x] = s;
-    }
-}
-
-// N columns of `part` [nparts, N] -> sh[0..N): thread i adds partials i, i + TILE, ... in order, then a fixed tree. The result depends on nparts alone.
-template <int N>
-__device__ __forceinline__ void merge(const double* __restrict__ part, int64_t nparts, double (*sh)[N]) {
-    double s[N];
-#pragma unroll
-    for (int k = 0; k < N; ++k) s[k] = 0.0;
-    for (int64_t i = threadIdx.x; i < nparts; i += TILE)
-#pragma unroll
-        for (int k = 0; k < N; ++k) s[k] += part[i * N + k];
-#pragma unroll
-    for (int k = 0; k < N; ++k) sh[threadIdx.x][k] = s[k];
-    __syncthreads();
-    for (int w = TILE / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w)
-#pragma unroll
-            for (int k = 0; k < N; ++k) sh[threadIdx.x][k] += sh[threadIdx.x + w][k];
-        __syncthreads();
-    }
-}
-
 // 1: per-workgroup double sums of returns, returns^2, active_masks
 __global__ __launch_bounds__(TILE) void k_loss_stats(LossArgs p) {
     __shared__ double red[NW * NSTAT];
-    const int64_t r = (int64_t)blockIdx.x * TILE + threadIdx.x;
-    double v[NSTAT] = {0.0, 0.0, 0.0};
-    if (r < p.B) {
-        const double x = p.ret[r];
-        v[0] = x; v[1] = x * x; v[2] = p.am[r];
-    }
-    block_sum<NSTAT>(v, red, p.stat_part + (int64_t)blockIdx.x * NSTAT);
+    stats_tile(p.ret, p.am, p.B, p.stat_part, red);
 }
 
 // 2: merge; ValueNorm.update (valuenorm.py:56-73), BEFORE the normalisation as cal_value_loss does (graph_mappo.py:93-97); running_mean_var (:48-54)
@@ -142,71 +86,6 @@ __global__ __launch_bounds__(TILE) void k_loss_prepare(LossArgs p, int64_t npart
     f[0] = mean; f[1] = sd;
 }
 
-// A contiguous tile of n floats at g <-> its rows in LDS at stride S. VEC: 16-byte global accesses (g 16-byte aligned), else 4-byte ones.
-// LDS side: with K odd S == K, the tile's LDS image is its global image and a lane's four floats move as one 16-byte access. With K even (S = K + 1) the
-// four floats go one dword at a time; lane i starts at element (i / 8) % 4 of its four, so the lanes i, i + 8, i + 16, i + 24 of a 32-lane group, whose
-// floats lie 32 dwords apart, are on four different banks in every round instead of on one.
-template <bool VEC, bool IN>
-__device__ __forceinline__ void tile_copy(float* g, float* sh, int n, int K, int S, uint32_t magic) {
-    const int rot = (threadIdx.x >> 3) & 3;
-    for (int f = threadIdx.x * 4; f < n; f += TILE * 4) {
-        const int cnt = n - f < 4 ? n - f : 4;
-        float v[4];
-        if (IN) {
-            if (VEC && cnt == 4) {
-                const float4 t = *reinterpret_cast<const float4*>(g + f);
-                v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (k < cnt) v[k] = g[f + k];
-            }
-        }
-        if (S == K && cnt == 4) {
-            float4* q = reinterpret_cast<float4*>(sh + f);
-            if (IN) *q = make_float4(v[0], v[1], v[2], v[3]);
-            else { const float4 t = *q; v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
-        } else {
-            const uint32_t r = K == 1 ? (uint32_t)f : __umulhi((uint32_t)f, magic);
-            const uint32_t c = (uint32_t)f - r * (uint32_t)K;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int kk = (k + rot) & 3;
-                uint32_t rr = r, cc = c + (uint32_t)kk;
-                while (cc >= (uint32_t)K) { cc -= (uint32_t)K; ++rr; }
-                if (kk < cnt) {
-                    float* q = sh + rr * S + cc;
-                    if (IN) *q = kk == 0 ? v[0] : (kk == 1 ? v[1] : (kk == 2 ? v[2] : v[3]));
-                    else {
-                        const float t = *q;
-                        if (kk == 0) v[0] = t; else if (kk == 1) v[1] = t; else if (kk == 2) v[2] = t; else v[3] = t;
-                    }
-                }
-            }
-        }
-        if (!IN) {
-            if (VEC && cnt == 4) {
-                *reinterpret_cast<float4*>(g + f) = make_float4(v[0], v[1], v[2], v[3]);
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (k < cnt) g[f + k] = v[k];
-            }
-        }
-    }
-}
-
-__device__ __forceinline__ float value_term(float e, bool huber, float delta, float half_delta, float* dfde) {
-    if (!huber) {                                               // mse_loss: e**2 / 2
-        *dfde = e;
-        return __fdiv_rn(__fmul_rn(e, e), 2.0f);
-    }
-    const float ae = fabsf(e);
-    const float a = ae <= delta ? 1.0f : 0.0f, b = e > delta ? 1.0f : 0.0f;   // util.py:25-26: b = (e > d), one-sided
-    *dfde = __fadd_rn(__fmul_rn(a, e), __fmul_rn(b, delta));
-    return __fadd_rn(__fdiv_rn(__fmul_rn(a, __fmul_rn(e, e)), 2.0f), __fmul_rn(__fmul_rn(b, delta), __fsub_rn(ae, half_delta)));
-}
-
 // 3: the row pass. One lane per row; the tile's available_actions, then its logits, then its gradient pass through the same LDS rows.
 template <bool VEC, bool ACT64>
 __global__ __launch_bounds__(TILE) void k_loss_rows(LossArgs p) {
@@ -223,10 +102,7 @@ __global__ __launch_bounds__(TILE) void k_loss_rows(LossArgs p) {
     if (p.avail) {
         tile_copy<VEC, true>(const_cast<float*>(p.avail) + g0, sh, n, K, S, p.magic);
         __syncthreads();
-        if (live) {
-            avail = 0;
-            for (int j = 0; j < K; ++j) avail |= (uint64_t)(row[j] != 0.0f) << j;     // x[available_actions == 0] = finfo.min
-        }
+        if (live) avail = avail_bits(row, K);                                       // x[available_actions == 0] = finfo.min
         __syncthreads();
     }
     tile_copy<VEC, true>(const_cast<float*>(p.logits) + g0, sh, n, K, S, p.magic);
@@ -237,68 +113,23 @@ __global__ __launch_bounds__(TILE) void k_loss_rows(LossArgs p) {
         const double Dp = p.hdr[0], Dv = p.hdr[1];
         const float am = p.am[r];
         const float wp = (p.flags & GMPE_PPO_POLICY_ACTIVE_MASKS) ? am : 1.0f, wv = (p.flags & GMPE_PPO_VALUE_ACTIVE_MASKS) ? am : 1.0f;
-        // ---- the masked categorical (torch: logits - logsumexp, probs = softmax of that)
-        float m = -INFINITY;
-        for (int j = 0; j < K; ++j) m = fmaxf(m, (avail >> j & 1) ? row[j] : FMIN);
-        float s = 0.0f;
-        for (int j = 0; j < K; ++j) s = __fadd_rn(s, expf(__fsub_rn((avail >> j & 1) ? row[j] : FMIN, m)));
-        const float lse = __fadd_rn(logf(s), m), ml = __fsub_rn(m, lse);          // ml = max_j l_j: rounding is monotone
-        int64_t ai = ACT64 ? static_cast<const int64_t*>(p.actions)[r] : (int64_t)static_cast<const float*>(p.actions)[r];   // .long() truncates
-        const int a = ai < 0 ? 0 : (ai >= K ? K - 1 : (int)ai);                   // out of range is the caller's error (torch raises): stay inside the row
-        float s2 = 0.0f;
-        for (int j = 0; j < K; ++j) {                                             // the row now holds l = x - logsumexp(x): Categorical's normalised logits
-            const float l = __fsub_rn((avail >> j & 1) ? row[j] : FMIN, lse);
-            row[j] = l;
-            s2 = __fadd_rn(s2, expf(__fsub_rn(l, ml)));                           // probs = softmax(l): torch renormalises the normalised logits
-        }
-        const float la = row[a];
-        float t = 0.0f;
-        for (int j = 0; j < K; ++j) {
-            const float l = row[j];
-            t = __fadd_rn(t, __fmul_rn(fmaxf(l, FMIN), __fdiv_rn(expf(__fsub_rn(l, ml)), s2)));      // clamp(l, min=finfo.min) * p
-        }
-        const float H = -t;
-        // ---- ratio, clip, surrogates (graph_mappo.py:176-197)
-        const float adv = p.adv[r];
-        const float ratio = expf(__fsub_rn(la, p.old_lp[r]));
-        const float surr1 = __fmul_rn(ratio, adv), surr2 = __fmul_rn(fminf(fmaxf(ratio, p.lo), p.hi), adv);
-        const bool pass = surr1 < surr2 || (surr1 == surr2 && ratio >= p.lo && ratio <= p.hi);
-        acc[0] = (double)__fmul_rn(-fminf(surr1, surr2), wp);
-        acc[1] = (double)__fmul_rn(H, wp);
+        PolicyRow q;
+        q.avail = avail;
+        q.action = ACT64 ? static_cast<const int64_t*>(p.actions)[r] : (int64_t)static_cast<const float*>(p.actions)[r];   // .long() truncates
+        q.adv = p.adv[r]; q.old_lp = p.old_lp[r]; q.wp = wp; q.Dp = (float)Dp; q.lo = p.lo; q.hi = p.hi; q.ent_coef = p.ent_coef;
+        float la, ratio;
+        policy_row(row, K, q, &la, &ratio, &acc[0], &acc[1]);
         acc[3] = (double)ratio;
         if (p.out_lp) p.out_lp[r] = la;
         if (p.out_ratio) p.out_ratio[r] = ratio;
-        const float cw = __fdiv_rn(wp, (float)Dp);
-        const float ca = pass ? -__fmul_rn(__fmul_rn(cw, adv), ratio) : 0.0f, ce = __fmul_rn(p.ent_coef, cw);
-        for (int j = 0; j < K; ++j) {
-            float g = 0.0f;
-            if (avail >> j & 1) {
-                const float l = row[j], pj = __fdiv_rn(expf(__fsub_rn(l, ml)), s2);
-                g = __fadd_rn(__fmul_rn(ca, __fsub_rn(j == a ? 1.0f : 0.0f, pj)), __fmul_rn(ce, __fmul_rn(pj, __fadd_rn(l, H))));
-            }
-            row[j] = g;
-        }
         // ---- the value branch (graph_mappo.py:89-117)
-        const float v = p.values[r], vp = p.vp[r];
         float R = p.ret[r];
         if (p.flags & GMPE_PPO_VALUENORM) {
             const float* st = reinterpret_cast<const float*>(p.hdr + 2);
             R = __fdiv_rn(__fsub_rn(R, st[0]), st[1]);
         }
-        const bool huber = p.flags & GMPE_PPO_HUBER_LOSS;
-        const float d = __fsub_rn(v, vp);
-        const float vpc = __fadd_rn(vp, fminf(fmaxf(d, -p.clip), p.clip));
-        float fo, fc;
-        const float Lo = value_term(__fsub_rn(R, v), huber, p.delta, p.half_delta, &fo);
-        const float Lc = value_term(__fsub_rn(R, vpc), huber, p.delta, p.half_delta, &fc);
-        const float go = -fo, gc = (d >= -p.clip && d <= p.clip) ? -fc : 0.0f;
-        float L = Lo, g = go;
-        if (p.flags & GMPE_PPO_CLIPPED_VALUE_LOSS) {
-            L = fmaxf(Lo, Lc);
-            g = Lo > Lc ? go : (Lc > Lo ? gc : __fmul_rn(0.5f, __fadd_rn(go, gc)));
-        }
-        acc[2] = (double)__fmul_rn(L, wv);
-        p.grad_values[r] = __fmul_rn(__fdiv_rn(wv, (float)Dv), g);
+        p.grad_values[r] = value_row<false>(p.values[r], p.vp[r], R, p.flags & GMPE_PPO_HUBER_LOSS, p.flags & GMPE_PPO_CLIPPED_VALUE_LOSS, p.clip, p.delta,
+                                     p.half_delta, wv, (float)Dv, &acc[2]);
     }
     block_sum<NROW>(acc, red, p.row_part + (int64_t)blockIdx.x * NROW);     // its barrier also orders the gradient rows before the copy out
     tile_copy<VEC, false>(p.grad_logits + g0, sh, n, K, S, p.magic);

@@ -10,6 +10,11 @@ One call of gmpe_ppo_loss (four launches) evaluates the masked categorical (onpo
 ratio / clip / surrogate block (onpolicy/algorithms/graph_mappo.py:176-197) and cal_value_loss with ValueNorm.update + normalize (:89-117,
 onpolicy/utils/valuenorm.py:48-85), and leaves d actor_loss / d logits and d value_loss / d values; backward multiplies them by the incoming
 scalar. There is no torch fallback: the arrays must be on a HIP device.
+
+With --use_popart the value normaliser is the critic's output layer, so the critic hands over its features and ppo_losses_popart (gmpe_ppo_loss_popart)
+evaluates that layer, updates and rescales it, and leaves the gradients of features, weight and bias:
+
+        res = gmpe.ppo_losses_popart(logits, critic_features, sample, args, critic.v_out)
 """
 import collections
 import ctypes as C
@@ -19,6 +24,8 @@ import torch
 from . import _lib
 from .engine import _need_cuda, _stream_of
 
+PPOPopArtLosses = collections.namedtuple("PPOPopArtLosses", ["actor_loss", "value_loss", "policy_loss", "dist_entropy", "ratio_mean", "action_log_probs",
+                                                             "imp_weights", "values"])
 PPOLosses = collections.namedtuple("PPOLosses", ["actor_loss", "value_loss", "policy_loss", "dist_entropy", "ratio_mean", "action_log_probs",
                                                  "imp_weights"])
 FIELDS = ("actions", "value_preds", "returns", "active_masks", "old_action_log_probs", "adv_targ", "available_actions")
@@ -51,15 +58,22 @@ def _fields(sample):
     return f
 
 
-def _flags(args):
+def _flags(args, popart=False):
     get = lambda k: getattr(args, k, _DEFAULTS[k])
-    if get("use_popart"):
-        raise NotImplementedError("use_popart: PopArt rewrites the critic's output layer; ppo_losses supports ValueNorm or no normaliser")
+    if popart:
+        if not get("use_popart"):
+            raise ValueError("args.use_popart is not set: ppo_losses_popart is the --use_popart path, ppo_losses the other")
+        if getattr(args, "use_valuenorm", False):
+            raise ValueError("use_popart and use_valuenorm can not be set True simultaneously")        # graph_mappo.py:61
+    elif get("use_popart"):
+        raise NotImplementedError("use_popart: PopArt rewrites the critic's output layer, so the critic hands over its features, not its values: "
+                                  "call ppo_losses_popart(logits, critic_features, sample, args, critic.v_out); ppo_losses supports ValueNorm or no "
+                                  "normaliser")
     flags = 0
     for name, bit in (("use_policy_active_masks", _lib.PPO_POLICY_ACTIVE_MASKS), ("use_value_active_masks", _lib.PPO_VALUE_ACTIVE_MASKS),
                       ("use_clipped_value_loss", _lib.PPO_CLIPPED_VALUE_LOSS), ("use_huber_loss", _lib.PPO_HUBER_LOSS),
                       ("use_valuenorm", _lib.PPO_VALUENORM)):
-        if get(name):
+        if get(name) and not (popart and bit == _lib.PPO_VALUENORM):
             flags |= bit
     return flags, float(get("clip_param")), float(get("huber_delta")), float(get("entropy_coef"))
 
@@ -194,3 +208,148 @@ def ppo_losses(logits, values, sample_or_fields, args, value_normalizer=None, wo
     o = _lib.PPO_OUT.index
     return PPOLosses(_Attach.apply(logits, s[o("actor_loss")], grad_logits), _Attach.apply(values2, s[o("value_loss")], grad_values),
                      s[o("policy_loss")], s[o("dist_entropy")], s[o("ratio_mean")], logp, ratio)
+
+
+def popart_workspace_bytes(rows, hidden):
+    """Device scratch (bytes) one ppo_losses_popart call over `rows` rows of `hidden` critic features needs (gmpe_ppo_loss_popart_workspace_bytes)."""
+    n = C.c_size_t()
+    _lib.check(_lib.load().gmpe_ppo_loss_popart_workspace_bytes(int(rows), int(hidden), C.byref(n)), "gmpe_ppo_loss_popart_workspace_bytes")
+    return int(n.value)
+
+
+def _popart_state(popart, hidden, dev):
+    """The tensors of the reference's PopArt(hidden, 1) (onpolicy/algorithms/utils/popart.py:30-41), duck-typed: (weight, bias, stddev, mean, mean_sq,
+    debiasing_term), beta, epsilon. Everything is checked before the device is touched."""
+    if popart is None:
+        raise ValueError("popart (the critic's v_out, a PopArt(hidden, 1)) is required")
+    names = ("weight", "bias", "stddev", "mean", "mean_sq", "debiasing_term")
+    for n in names:
+        if not isinstance(getattr(popart, n, None), torch.Tensor):
+            raise NotImplementedError("popart.%s is missing or no tensor: popart must be a PopArt (%s)" % (n, ", ".join(names)))
+    if int(getattr(popart, "norm_axes", 1)) != 1:
+        raise NotImplementedError("popart.norm_axes = %r: only norm_axes 1 is supported" % (popart.norm_axes,))
+    if int(getattr(popart, "output_shape", 1)) != 1:
+        raise NotImplementedError("popart.output_shape = %r: only PopArt(hidden, 1) is supported" % (popart.output_shape,))
+    st = [getattr(popart, n) for n in names]
+    if tuple(st[0].shape) != (1, hidden):
+        if st[0].dim() == 2 and st[0].shape[0] > 1:
+            raise NotImplementedError("popart.weight of shape %s: only PopArt(hidden, 1) is supported" % (tuple(st[0].shape),))
+        raise ValueError("popart.weight must have shape (1, %d) (critic_features has %d columns), not %s" % (hidden, hidden, tuple(st[0].shape)))
+    for n, t in zip(names[1:5], st[1:5]):
+        if tuple(t.shape) != (1,):
+            raise ValueError("popart.%s must have shape (1,), not %s" % (n, tuple(t.shape)))
+    if st[5].numel() != 1:
+        raise ValueError("popart.debiasing_term must hold one element, not %s" % (tuple(st[5].shape),))
+    for n, t in zip(names, st):
+        if t.dtype != torch.float32 or t.device != dev or not t.is_contiguous():
+            raise ValueError("popart.%s must be a contiguous float32 tensor on %s (the device of logits): the kernel reads and writes it where it lies"
+                             % (n, dev))
+    return st, float(getattr(popart, "beta", 0.99999)), float(getattr(popart, "epsilon", 1e-5))
+
+
+class _AttachHead(torch.autograd.Function):
+    """value_loss as ONE node over (critic_features, weight, bias): the kernel evaluated v_out and left the three gradients; backward multiplies them
+    by the incoming scalar. No tensor of the layer is saved, so rewriting the weight after the call is no hazard."""
+
+    @staticmethod
+    def forward(ctx, features, weight, bias, scalar, gf, gw, gb):
+        ctx.save_for_backward(gf, gw, gb)
+        return scalar.clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        gf, gw, gb = ctx.saved_tensors
+        return gf * g, gw * g, gb * g, None, None, None, None
+
+
+def ppo_losses_popart(logits, critic_features, sample_or_fields, args, popart, install="replace", workspace=None):
+    """ppo_losses for --use_popart, where trainer.value_normalizer is the critic's output layer v_out = PopArt(hidden, 1) (graph_mappo.py:63-64): the
+    critic is called up to `critic_features` [rows, hidden] (the input of v_out), and one call of gmpe_ppo_loss_popart (four launches) does what
+    evaluate_actions' last line and cal_value_loss do, in their order: values = F.linear(critic_features, weight, bias) with the weights as they are
+    BEFORE the update; PopArt.update(returns) (popart.py:62-83: float32, all rows, stddev from the raw statistics, the bias through the aliased
+    old_mean, i.e. ((stddev * b + mean') - mean') / stddev'); normalize(returns) with the debiased statistics; the losses; the gradients.
+    popart: duck-typed — weight [1, hidden], bias, stddev, mean, mean_sq [1], debiasing_term (one element), float32, contiguous, on the device of
+    logits; beta, epsilon (PopArt's defaults where absent); norm_axes == 1, output_shape == 1. mean, mean_sq and debiasing_term are updated in place.
+    install="replace" (the reference): popart.weight, .bias and .stddev become NEW nn.Parameters holding the rescaled layer; the objects that were
+    there at the call receive this minibatch's gradients, and an optimiser built over them keeps them — it never trains the new ones.
+    install="in_place": the rescaled layer is written into the existing storage; the Parameters keep their identity and the optimiser trains them.
+    Returns PPOPopArtLosses: the PPOLosses fields plus `values` (detached [rows, 1], what v_out gave with the pre-update weights). value_loss is one
+    autograd node over (critic_features, the weight and bias objects of the call); actor_loss is as in ppo_losses. f16 / bf16 logits and features
+    are widened to float32 first. Nothing here waits for the device. workspace: an optional uint8 device tensor of popart_workspace_bytes(rows, hidden)."""
+    flags, clip, delta, ent = _flags(args, popart=True)
+    if install not in ("replace", "in_place"):
+        raise ValueError("install must be 'replace' (the reference: new Parameters) or 'in_place', not %r" % (install,))
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or not logits.is_floating_point():
+        raise ValueError("logits must be a floating-point tensor [rows, n_actions]")
+    dev = logits.device
+    rows, K = int(logits.shape[0]), int(logits.shape[1])
+    if rows < 1 or K < 1:
+        raise ValueError("logits must have at least one row and one action")
+    if K > _lib.PPO_MAX_ACTIONS:
+        raise ValueError("n_actions = %d is above the supported %d" % (K, _lib.PPO_MAX_ACTIONS))
+    if not isinstance(critic_features, torch.Tensor) or not critic_features.is_floating_point() or critic_features.dim() != 2 or \
+            critic_features.shape[0] != rows or critic_features.shape[1] < 1:
+        raise ValueError("critic_features must be a floating-point tensor of shape (%d, hidden)" % rows)
+    H = int(critic_features.shape[1])
+    if H > _lib.POPART_MAX_HIDDEN:
+        raise ValueError("hidden = %d is above the supported %d" % (H, _lib.POPART_MAX_HIDDEN))
+    if critic_features.device != dev:
+        raise ValueError("critic_features must be on %s (the device of logits)" % dev)
+    if logits.dtype in (torch.float16, torch.bfloat16):
+        logits = logits.float()
+    if critic_features.dtype in (torch.float16, torch.bfloat16):
+        critic_features = critic_features.float()
+    if logits.dtype != torch.float32 or critic_features.dtype != torch.float32:
+        raise ValueError("logits and critic_features must be float32 (or float16 / bfloat16, widened here)")
+    f = _fields(sample_or_fields)
+    cols = {k: _column(k, f[k], rows, dev) for k in ("value_preds", "returns", "active_masks", "old_action_log_probs", "adv_targ")}
+    actions = _column("actions", f["actions"], rows, dev, (torch.float32, torch.int64))
+    avail = f["available_actions"]
+    if avail is not None:
+        if not isinstance(avail, torch.Tensor) or avail.dtype != torch.float32 or tuple(avail.shape) != (rows, K):
+            raise ValueError("available_actions must be a float32 tensor of shape (%d, %d) or None" % (rows, K))
+        if avail.device != dev:
+            raise ValueError("available_actions must be on %s (the device of logits)" % dev)
+        avail = avail.detach().contiguous()
+    (w_obj, b_obj, s_obj, mean, mean_sq, debias), beta, epsilon = _popart_state(popart, H, dev)
+    _need_cuda(dev)
+    nbytes = popart_workspace_bytes(rows, H)
+    if workspace is None:
+        workspace = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    elif not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous() or \
+            workspace.numel() < nbytes:
+        raise ValueError("workspace must be a contiguous uint8 tensor of at least %d bytes on %s" % (nbytes, dev))
+    lg, ft = logits.detach().contiguous(), critic_features.detach().contiguous()
+    if install == "replace":
+        w_out, b_out, s_out = torch.empty_like(w_obj.detach()), torch.empty_like(b_obj.detach()), torch.empty_like(s_obj.detach())
+    else:
+        w_out, b_out, s_out = w_obj, b_obj, s_obj                       # the aliasing case of the C contract: written after the rows have read them
+    out = torch.empty((_lib.PPO_NUM_OUT,), dtype=torch.float64, device=dev)
+    grad_logits, grad_features = torch.empty_like(lg), torch.empty_like(ft)
+    grad_weight, grad_bias = torch.empty_like(w_obj.detach()), torch.empty_like(b_obj.detach())
+    logp, ratio, values = (torch.empty((rows, 1), dtype=torch.float32, device=dev) for _ in range(3))
+    plan = _lib.GmpePopartLossPlan()
+    plan.rows, plan.n_actions, plan.hidden, plan.flags, plan.actions_int64 = rows, K, H, flags, int(actions.dtype == torch.int64)
+    plan.clip_param, plan.huber_delta, plan.entropy_coef, plan.beta, plan.epsilon = clip, delta, ent, beta, epsilon
+    plan.logits, plan.critic_features, plan.actions = lg.data_ptr(), ft.data_ptr(), actions.data_ptr()
+    plan.available_actions = None if avail is None else avail.data_ptr()
+    for k, t in cols.items():
+        setattr(plan, k, t.data_ptr())
+    plan.weight, plan.bias, plan.stddev = w_obj.data_ptr(), b_obj.data_ptr(), s_obj.data_ptr()
+    plan.mean, plan.mean_sq, plan.debiasing_term = mean.data_ptr(), mean_sq.data_ptr(), debias.data_ptr()
+    plan.weight_out, plan.bias_out, plan.stddev_out = w_out.data_ptr(), b_out.data_ptr(), s_out.data_ptr()
+    plan.values_out, plan.out = values.data_ptr(), out.data_ptr()
+    plan.grad_logits, plan.grad_features, plan.grad_weight, plan.grad_bias = (t.data_ptr() for t in (grad_logits, grad_features, grad_weight, grad_bias))
+    plan.action_log_probs, plan.imp_weights = logp.data_ptr(), ratio.data_ptr()
+    plan.workspace, plan.workspace_bytes = workspace.data_ptr(), workspace.numel()
+    _lib.check(_lib.load().gmpe_ppo_loss_popart(dev.index if dev.index is not None else torch.cuda.current_device(), C.byref(plan), _stream_of(dev)),
+               "gmpe_ppo_loss_popart")
+    s = out.to(torch.float32)
+    o = _lib.PPO_OUT.index
+    actor = _Attach.apply(logits, s[o("actor_loss")], grad_logits)
+    value = _AttachHead.apply(critic_features, w_obj, b_obj, s[o("value_loss")], grad_features, grad_weight, grad_bias)
+    if install == "replace":                                            # popart.py:79-83: three new nn.Parameter objects
+        popart.stddev = torch.nn.Parameter(s_out)
+        popart.weight = torch.nn.Parameter(w_out)
+        popart.bias = torch.nn.Parameter(b_out)
+    return PPOPopArtLosses(actor, value, s[o("policy_loss")], s[o("dist_entropy")], s[o("ratio_mean")], logp, ratio, values)

@@ -486,6 +486,63 @@ typedef struct gmpe_ppo_loss_plan {
 int gmpe_ppo_loss_workspace_bytes(int64_t rows, size_t* bytes_out);
 int gmpe_ppo_loss(int device, const gmpe_ppo_loss_plan* plan, void* stream);
 
+/* The same minibatch with --use_popart: the value normaliser is the critic's output layer v_out = PopArt(hidden, 1)
+ * (onpolicy/algorithms/utils/popart.py, graph_mappo.py:63-64), so the line to the critic is its FEATURES [rows, hidden], not its values. In four
+ * launches on `stream` (no atomics, no allocation, no host synchronisation; capturable), in the reference's order:
+ *   1. values = critic_features . weight + bias with the weights as they are BEFORE the update (evaluate_actions runs first, graph_mappo.py:160-172);
+ *   2. PopArt.update(returns) (popart.py:62-83) in float32 over ALL rows: mean, mean_sq, debiasing_term move in place;
+ *      stddev' = clamp(sqrt(mean_sq - mean^2), 1e-4) from the RAW statistics (NaN stays NaN); weight' = (weight * stddev) / stddev';
+ *      bias' = ((stddev * bias + mean') - mean') / stddev' — old_mean is an alias of the updated mean there, and that is restated, not corrected;
+ *   3. the losses of gmpe_ppo_loss with returns normalised by the DEBIASED statistics (popart.py:85-99: mean / clamp(debiasing_term, epsilon),
+ *      sqrt(clamp(mean_sq / ... - mean_d^2, 1e-2)));
+ *   4. d value_loss / d critic_features, d weight, d bias, all through the pre-update weights;
+ *   5. weight', bias', stddev' are published by the last launch: each *_out may be the very pointer of its input (rescaled in place), and is written
+ *      only after every row has read the input. Any other overlap between arrays is the caller's error.
+ * The dot product of a row is float32 in one fixed order that depends on `hidden` alone: columns in quads (4q .. 4q+3), quad q on lane q mod L of L
+ * lanes (L = the power of two >= ceil(hidden / 4), at most 64), a lane adds its products in column order, the L lanes are added as a tree (lower lane
+ * the left operand), then the bias. critic_features and grad_features move in 16-byte units when hidden % 4 == 0 and both are 16-byte aligned, in
+ * 4-byte units otherwise; the bits do not depend on which. grad_weight / grad_bias are double sums over rows, rounded to float32 once. */
+#define GMPE_POPART_MAX_HIDDEN 1024
+typedef struct gmpe_popart_loss_plan {
+    int64_t rows;                       /* B >= 1                                                                                     */
+    int32_t n_actions;                  /* K, 1 .. GMPE_PPO_MAX_ACTIONS                                                               */
+    int32_t hidden;                     /* H, 1 .. GMPE_POPART_MAX_HIDDEN                                                             */
+    int32_t flags;                      /* the four boolean GMPE_PPO_* flags; GMPE_PPO_VALUENORM is not accepted                      */
+    int32_t actions_int64;              /* as gmpe_ppo_loss_plan                                                                      */
+    double clip_param, huber_delta, entropy_coef;
+    double beta, epsilon;               /* PopArt's (0.99999, 1e-5)                                                                   */
+    const float* logits;                /* [rows, K]                                                                                  */
+    const float* critic_features;       /* [rows, H] the input of v_out                                                               */
+    const void* actions;                /* [rows]                                                                                     */
+    const float* available_actions;     /* [rows, K] or NULL                                                                          */
+    const float* old_action_log_probs;  /* [rows]                                                                                     */
+    const float* adv_targ;              /* [rows]                                                                                     */
+    const float* value_preds;           /* [rows]                                                                                     */
+    const float* returns;               /* [rows]                                                                                     */
+    const float* active_masks;          /* [rows]                                                                                     */
+    const float* weight;                /* [H]  v_out.weight, read                                                                    */
+    const float* bias;                  /* [1]  v_out.bias, read                                                                      */
+    const float* stddev;                /* [1]  v_out.stddev, read                                                                    */
+    float* mean;                        /* f32 [1] each, updated in place                                                             */
+    float* mean_sq;
+    float* debiasing_term;
+    float* weight_out;                  /* [H], [1], [1]: the rescaled layer; each may be the pointer of its input                    */
+    float* bias_out;
+    float* stddev_out;
+    float* values_out;                  /* [rows] or NULL: what v_out gave with the pre-update weights                                */
+    double* out;                        /* f64 [GMPE_PPO_NUM_OUT]                                                                     */
+    float* grad_logits;                 /* [rows, K] d actor_loss / d logits                                                          */
+    float* grad_features;               /* [rows, H] d value_loss / d critic_features                                                 */
+    float* grad_weight;                 /* [H]       d value_loss / d weight                                                          */
+    float* grad_bias;                   /* [1]       d value_loss / d bias                                                            */
+    float* action_log_probs;            /* [rows] or NULL                                                                             */
+    float* imp_weights;                 /* [rows] or NULL                                                                             */
+    void* workspace;                    /* device scratch of gmpe_ppo_loss_popart_workspace_bytes(rows, hidden) bytes, 8-byte aligned */
+    size_t workspace_bytes;
+} gmpe_popart_loss_plan;
+int gmpe_ppo_loss_popart_workspace_bytes(int64_t rows, int32_t hidden, size_t* bytes_out);
+int gmpe_ppo_loss_popart(int device, const gmpe_popart_loss_plan* plan, void* stream);
+
 /* ---- Evaluation of a policy over a batch of episodes (handle-less): GMPERunner.render(get_metrics=True) as one episode per env ----
  * (onpolicy/runner/shared/graph_mpe_runner.py:526-1060, base_runner.py:194-574). Every env plays one episode from a reset; the caller's policy acts,
  * the engine steps, gmpe_episode_record books the step. No allocation, no host synchronisation, every launch on `stream`.
