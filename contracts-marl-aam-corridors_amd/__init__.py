@@ -13,7 +13,7 @@ __all__ = ["config", "make_config", "config_from_args"]
 
 def __getattr__(name):
     # torch / HIP-dependent modules are imported on first use
-    if name in ("engine", "vec_env", "spaces", "_lib", "sharding", "rollout", "minibatch", "evaluate", "ppo_loss"):
+    if name in ("engine", "vec_env", "spaces", "_lib", "sharding", "rollout", "minibatch", "evaluate", "ppo_loss", "act"):
         import importlib
         return importlib.import_module("." + name, __name__)
     if name in ("BatchedGraphMPEVecEnv", "MultiDeviceGraphMPEVecEnv", "GraphMPEEnv", "make_train_env", "make_eval_env"):
@@ -25,6 +25,9 @@ def __getattr__(name):
     if name in ("ppo_losses", "PPOLosses", "ppo_losses_popart", "PPOPopArtLosses"):
         from . import ppo_loss
         return getattr(ppo_loss, name)
+    if name == "sample_actions":
+        from . import act
+        return act.sample_actions
     if name == "GmpeEngine":
         from . import engine
         return engine.GmpeEngine

@@ -20,7 +20,8 @@ SYMBOLS = ["gmpe_abi_version", "gmpe_last_error", "gmpe_obs_dim", "gmpe_node_fea
            "gmpe_returns_workspace_bytes", "gmpe_compute_returns", "gmpe_available_actions_from_dones", "gmpe_minibatch_gather",
            "gmpe_insert_learner", "gmpe_episode_record", "gmpe_episode_metrics", "gmpe_episode_summary",
            "gmpe_minibatch_edges", "gmpe_minibatch_edges_workspace_bytes", "gmpe_episode_record_series",
-           "gmpe_ppo_loss", "gmpe_ppo_loss_workspace_bytes", "gmpe_ppo_loss_popart", "gmpe_ppo_loss_popart_workspace_bytes"]
+           "gmpe_ppo_loss", "gmpe_ppo_loss_workspace_bytes", "gmpe_ppo_loss_popart", "gmpe_ppo_loss_popart_workspace_bytes",
+           "gmpe_act_sample"]
 
 
 class GmpeOutputs(C.Structure):
@@ -166,6 +167,14 @@ class GmpePopartLossPlan(C.Structure):
                 ("imp_weights", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
+class GmpeActPlan(C.Structure):
+    """gmpe_act_plan (include/gmpe.h): the rollout half of the action head — one action and its log-prob per row of logits."""
+    _fields_ = [("rows", C.c_int64), ("n_actions", C.c_int32), ("num_agents", C.c_int32), ("stop_action", C.c_int32), ("deterministic", C.c_int32),
+                ("env_id_base", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64), ("draw", C.c_uint64), ("draw_inc", C.c_uint64),
+                ("draw_dev", C.c_void_p), ("logits", C.c_void_p), ("available_actions", C.c_void_p), ("dones_prev", C.c_void_p),
+                ("action_idx", C.c_void_p), ("log_probs", C.c_void_p), ("actions_f32", C.c_void_p), ("actions_i64", C.c_void_p)]
+
+
 class GmpeError(RuntimeError):
     pass
 
@@ -229,6 +238,7 @@ def load():
     lib.gmpe_ppo_loss_workspace_bytes.argtypes = [C.c_int64, C.POINTER(C.c_size_t)]
     lib.gmpe_ppo_loss_popart.argtypes = [I, C.POINTER(GmpePopartLossPlan), P]
     lib.gmpe_ppo_loss_popart_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.POINTER(C.c_size_t)]
+    lib.gmpe_act_sample.argtypes = [I, C.POINTER(GmpeActPlan), P]
     from .config import ABI_VERSION
     if lib.gmpe_abi_version() != ABI_VERSION:
         raise GmpeError("libgmpe.so ABI version mismatch")

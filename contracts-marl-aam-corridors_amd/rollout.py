@@ -12,6 +12,8 @@ available_actions (graph_mpe_runner.py:263-335) computed on the device.
 Opt-in learner-side storage (learner_storage_spec): rnn_states / rnn_states_critic [T+1, N, A, R, H] and actions / action_log_probs [T, N, A, k], written
 with value_preds by ONE launch per step from the policy's outputs (insert_step / insert_external keywords, gmpe_insert_learner: the runner's
 `rnn_states[dones] = 0` on the device, no host sync) and carried by after_update: with every field kept, the buffer is a whole device GraphReplayBuffer.
+act_step puts the action head itself into the step's launch sequence: the policy hands over its logits, one launch (gmpe_act_sample, act.py) masks them from
+the previous step's dones, draws the action and writes actions[t] / action_log_probs[t] in place, then the env steps.
 The open-loop collect(action_sets) and the sharded collectors (sharding.ShardedRolloutCollector, vec_env.MultiDeviceGraphMPEVecEnv) have no policy output
 to store: they never write the learner fields.
 """
@@ -217,6 +219,51 @@ class DeviceRolloutBuffer(object):
         self.engine.masks_from_dones(self.dones[t], self.masks[t + 1], self.active_masks[t + 1])
         self.step = (t + 1) % self.T
         return self.engine.out
+
+    act_draw = 0            # the call counter of act_step's action stream: one value per act, carried by carry_from
+    _act_idx = _act_logp = None
+
+    def act_step(self, logits, values=None, *, rnn_states=None, rnn_states_critic=None, deterministic=False):
+        """insert_step with the action head in the launch sequence: `logits` (the policy head's linear output of this step, [N*A, n_actions], before
+        masking) instead of an action. One launch (gmpe_act_sample, act.sample_actions) masks them with the availability of this step — taken from
+        dones[step - 1] directly, all available at step 0; the available_actions slot is still written when the buffer keeps that field —, draws the
+        action (or takes the mode with deterministic=True) and writes actions[step] and action_log_probs[step] into their slots in place (when the
+        buffer keeps them) and the int32 action into a tensor the buffer owns; then the env step, the masks, and one gmpe_insert_learner launch for
+        whatever else was given (values, rnn_states, rnn_states_critic, as insert_step's). The draw of a row is keyed by the engine's seed, the env's
+        global id (cfg.env_id_base), the agent and `act_draw`, which advances by one per call: the same envs take the same actions however they are
+        spread over buffers. The stored log-probs are bit for bit what ppo_losses recomputes from the same logits."""
+        from .act import sample_actions
+        t, e = self.step, self.engine
+        c, rows = e.cfg, e.N * e.A
+        learner = self._learner_inputs(values, None, None, rnn_states, rnn_states_critic, "act_step")
+        if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or tuple(logits.shape) != (rows, c.n_actions):
+            raise ValueError("logits must be a tensor of shape (%d, %d)" % (rows, c.n_actions))
+        out = {}
+        for name, key in (("actions", "actions_f32"), ("action_log_probs", "action_log_probs")):
+            buf = getattr(self, name)
+            if buf is not None:
+                if buf.shape[-1] != 1:
+                    raise NotImplementedError("%s of shape %s: only a single Discrete head is supported (MultiDiscrete, mixed and continuous heads "
+                                              "are not)" % (name, tuple(buf.shape)))
+                out[key] = buf[t]
+        if self._act_idx is None:
+            self._act_idx = torch.zeros((e.N, e.A), dtype=torch.int32, device=e.device)
+        if "action_log_probs" not in out:
+            if self._act_logp is None:
+                self._act_logp = torch.zeros((rows, 1), dtype=torch.float32, device=e.device)
+            out["action_log_probs"] = self._act_logp
+        out["action_idx"] = self._act_idx
+        self.available_actions_for(t)
+        sample_actions(logits, dones_prev=self.dones[t - 1] if t else None, stop_action=c.n_actions // 2 if t else None, seed=c.seed,
+                       env_id_base=c.env_id_base, num_agents=e.A, draw=self.act_draw, deterministic=deterministic, out=out)
+        self._bind(t + 1)
+        e.step(self._act_idx)
+        e.masks_from_dones(self.dones[t], self.masks[t + 1], self.active_masks[t + 1])
+        if learner is not None:
+            insert_learner(t, self.dones, self._learner_arrays(), **learner)
+        self.act_draw += 1
+        self.step = (t + 1) % self.T
+        return e.out
 
     def insert_external(self, obs, agent_id, node_obs, adj, rewards, dones, values=None, *, actions=None, action_log_probs=None, rnn_states=None,
                         rnn_states_critic=None):
@@ -452,4 +499,5 @@ class DeviceRolloutBuffer(object):
         outputs are re-bound to this buffer's storage by the next collect / insert_step."""
         for dst, src in zip(self._carried(), other._carried()):
             dst[0].copy_(src[-1])
+        self.act_draw = other.act_draw
         self.step = 0

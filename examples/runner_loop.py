@@ -1,11 +1,15 @@
-"""The reference runner's collect loop (onpolicy/runner/shared/graph_mpe_runner.py:57-103) over the batched engine, three ways:
+"""The reference runner's collect loop (onpolicy/runner/shared/graph_mpe_runner.py:57-103) over the batched engine, three ways, and a fourth
+with the action head inside the loop:
 
   (1) drop-in: `BatchedGraphMPEVecEnv` in place of `GraphSubprocVecEnv` — NumPy in, NumPy out, the runner unchanged;
   (2) device-resident, open loop: `DeviceRolloutBuffer.collect` — ONE launch writes the whole `[T+1, N, A, ...]` rollout in HBM,
       and the GNN's edge list (`process_adj`, onpolicy/algorithms/utils/gnn_new.py:329-358) is built on the device;
   (3) device-resident, policy in the loop: the policy reads slot `step` of the buffer as device tensors and `insert_step` writes slot `step + 1`
       in place, the policy's outputs (values, actions, log-probs, RNN states) included — the runner change of INTEGRATION.md §7 (no NumPy one-hot up,
-      no seven arrays down per step), followed by returns, PPO minibatches and after_update on the device.
+      no seven arrays down per step), followed by returns, PPO minibatches and after_update on the device;
+  (4) as (3), with the action head in the launch sequence: the policy stops at its logits and `act_step` masks them from the previous step's dones, draws
+      the action on the engine's Philox stream, writes action and log-prob into the buffer slots and steps the env (one launch instead of the
+      Categorical's torch ops); the stored log-probs are bit for bit what `gmpe.ppo_losses` recomputes.
 
 The policy is a stand-in (uniform random actions): the learner is outside this package's scope.
 
@@ -118,6 +122,49 @@ def device_closed_loop(args, episodes, hidden_size=16):
                 shapes=dict(obs=tuple(buf.obs.shape), node_obs=tuple(buf.node_obs.shape), adj=tuple(buf.adj.shape), rnn_states=tuple(buf.rnn_states.shape)))
 
 
+def device_act_loop(args, episodes, hidden_size=16):
+    """Shape (3) with the head inside the loop (`act_step`): the stand-in policy hands over its LOGITS; one launch masks them with the
+    availability of the step (from dones[step - 1]), draws one action per (env, agent) and writes actions[step] / action_log_probs[step] in place; then the
+    env step, the masks and one launch for values and RNN states. After the rollout, the first minibatch of the unchanged policy is put through
+    `gmpe.ppo_losses`: its importance weights are exactly 1."""
+    import torch
+    from gmpe.engine import GmpeEngine
+    from gmpe.rollout import DeviceRolloutBuffer
+    from gmpe.config import config_from_args
+    cfg = config_from_args(args)
+    eng = GmpeEngine(cfg, adj_compact=True)
+    run_args = argparse.Namespace(gamma=0.99, gae_lambda=0.95, use_gae=True, use_proper_time_limits=False, use_valuenorm=False, use_popart=False,
+                                  recurrent_N=1, hidden_size=hidden_size)
+    buf = DeviceRolloutBuffer(eng, args.episode_length, policy_fields="all", learner_fields="all", args=run_args)
+    buf.warmup()
+    T, N, A, K = args.episode_length, cfg.num_envs, cfg.num_agents, cfg.n_actions
+    torch.manual_seed(0)
+    head = torch.nn.Linear(cfg.obs_dim + hidden_size, K + 1 + hidden_size).to(eng.device)
+    ratio_is_one = True
+    torch.cuda.synchronize(); t0 = time.perf_counter()
+    with torch.no_grad():
+        for ep in range(episodes):
+            kept = []
+            for step in range(T):
+                h = buf.rnn_states[step].flatten(0, 1)
+                out = head(torch.cat([buf.obs[step].flatten(0, 1), h[:, 0]], -1))
+                logits, value, rnn = out[:, :K].contiguous(), out[:, K:K + 1], torch.tanh(out[:, None, K + 1:])
+                buf.act_step(logits, value, rnn_states=rnn, rnn_states_critic=rnn)   # head + envs.step + buffer.insert: no Categorical, no .to(int32)
+                kept.append(logits)
+            buf.compute_returns(head(torch.cat([buf.obs[T].flatten(0, 1), buf.rnn_states[T].flatten(0, 1)[:, 0]], -1))[:, K].view(N, A, 1))
+            advantages = buf.normalized_advantages()
+            f = dict(actions=buf.actions[0].view(N * A, 1), value_preds=buf.value_preds[0].view(N * A, 1), returns=buf.returns[0].view(N * A, 1),
+                     active_masks=buf.active_masks[0].view(N * A, 1), old_action_log_probs=buf.action_log_probs[0].view(N * A, 1),
+                     adv_targ=advantages[0].view(N * A, 1), available_actions=buf.available_actions[1].view(N * A, K))
+            res = gmpe.ppo_losses(kept[0], buf.value_preds[0].view(N * A, 1), f, run_args)
+            ratio_is_one = ratio_is_one and bool((res.imp_weights == 1.0).all())
+            buf.after_update()
+    torch.cuda.synchronize(); dt = time.perf_counter() - t0
+    return dict(path="device-resident, action head in the loop", env_steps_per_s=N * episodes * T / dt, mean_step_reward=float(buf.rewards.mean()),
+                act_draw=buf.act_draw, ratio_exactly_one=ratio_is_one,
+                shapes=dict(obs=tuple(buf.obs.shape), actions=tuple(buf.actions.shape), action_log_probs=tuple(buf.action_log_probs.shape)))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=4096)
@@ -128,9 +175,9 @@ def main(argv=None):
     a = ap.parse_args(argv)
     args = reference_args(a.envs, a.agents, a.episode_length, a.scenario)
     out = [drop_in_loop(args, a.episodes), device_loop(args, a.episodes), device_closed_loop(args, a.episodes)]
-    for r in out:
+    for r in out + [device_act_loop(args, a.episodes)]:
         print(r)
-    return out
+    return out                                                                   # the three env-side shapes; shape (4) is printed, and callable on its own
 
 
 if __name__ == "__main__":

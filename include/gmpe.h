@@ -543,6 +543,46 @@ typedef struct gmpe_popart_loss_plan {
 int gmpe_ppo_loss_popart_workspace_bytes(int64_t rows, int32_t hidden, size_t* bytes_out);
 int gmpe_ppo_loss_popart(int device, const gmpe_popart_loss_plan* plan, void* stream);
 
+/* The rollout half of the same action head: ACTLayer.forward (onpolicy/algorithms/utils/act.py:107-113) — the masked Categorical
+ * (distributions.py:84-91), sample() or mode() (:15-16, 27-28), log_probs (:18-25) — and what the runner makes of the action for the env and the buffer
+ * (graph_mpe_runner.py:299-320, 356-377), in ONE launch on `stream` over rows = N*A rows of n_actions <= GMPE_PPO_MAX_ACTIONS float32 logits (no
+ * allocation, no host synchronisation; capturable).
+ *   Availability of a row, from at most one source: available_actions (f32 [rows, K], non-zero = available); or dones_prev (u8 [rows]) with stop_action —
+ *   a row whose dones_prev is non-zero may only take stop_action, every other row everything: collect_with_mask's rule (graph_mpe_runner.py:270-286), what
+ *   gmpe_available_actions_from_dones writes, without any [rows, K] array; or neither (everything available). A row with no available action is the
+ *   reference's uniform row over all K actions (every log-prob 0, as gmpe_ppo_loss computes it) and is sampled over all K.
+ *   Distribution: the float32 arithmetic of gmpe_ppo_loss's policy row in its order; log_probs[r] is bit-identical to the action_log_probs gmpe_ppo_loss
+ *   returns for the same logits, availability and action.
+ *   Sampling (deterministic == 0): u = philox(seed, env_id_base + r / num_agents, 2^63 | (draw * num_agents + r % num_agents)), the env streams' generator
+ *   (gmpe_create) with the top counter bit set, so the actions do not depend on how envs are spread over calls, handles or devices; the action is the
+ *   first available j whose running float32 sum of probabilities c_j has (double)c_j > u, else the mode. An unavailable action is never returned.
+ *   deterministic == 1 (FixedCategorical.mode): the first index of the largest masked logit.
+ *   Counter: with draw_dev (u64 [1] on the device) the rows use *draw_dev + draw and a second one-thread launch then adds draw_inc to *draw_dev, so a
+ *   captured graph draws fresh numbers at every replay; without it there is exactly one launch.
+ * logits / available_actions are contiguous [rows, K], read in 16-byte units when both are 16-byte aligned, in 4-byte units otherwise. Every argument
+ * the host can see is checked before any device call. */
+typedef struct gmpe_act_plan {
+    int64_t rows;                       /* N*A >= 1                                                                                   */
+    int32_t n_actions;                  /* K, 1 .. GMPE_PPO_MAX_ACTIONS                                                               */
+    int32_t num_agents;                 /* A >= 1: row r is agent r % A of env env_id_base + r / A                                    */
+    int32_t stop_action;                /* 0 .. K-1; read with dones_prev                                                             */
+    int32_t deterministic;              /* 1: the mode, 0: a sample                                                                   */
+    int32_t env_id_base;                /* global id of the env of row 0 (gmpe_config.env_id_base of the handle that steps these rows) */
+    int32_t reserved;                   /* 0                                                                                          */
+    uint64_t seed;                      /* gmpe_config.seed                                                                           */
+    uint64_t draw;                      /* call counter: one value per act of the rollout                                             */
+    uint64_t draw_inc;                  /* added to *draw_dev after the rows have read it                                             */
+    uint64_t* draw_dev;                 /* u64 [1] on the device, 8-byte aligned, or NULL                                             */
+    const float* logits;                /* [rows, K] the head's linear output, before masking                                         */
+    const float* available_actions;     /* [rows, K] or NULL                                                                          */
+    const uint8_t* dones_prev;          /* [rows] or NULL; not together with available_actions                                        */
+    int32_t* action_idx;                /* [rows] what gmpe_step takes                                                                */
+    float* log_probs;                   /* [rows]; may point into the buffer's action_log_probs[t]                                    */
+    float* actions_f32;                 /* [rows] or NULL; may point into the buffer's actions[t]                                     */
+    int64_t* actions_i64;               /* [rows] or NULL (what the policy returns), 8-byte aligned                                   */
+} gmpe_act_plan;
+int gmpe_act_sample(int device, const gmpe_act_plan* plan, void* stream);
+
 /* ---- Evaluation of a policy over a batch of episodes (handle-less): GMPERunner.render(get_metrics=True) as one episode per env ----
  * (onpolicy/runner/shared/graph_mpe_runner.py:526-1060, base_runner.py:194-574). Every env plays one episode from a reset; the caller's policy acts,
  * the engine steps, gmpe_episode_record books the step. No allocation, no host synchronisation, every launch on `stream`.
