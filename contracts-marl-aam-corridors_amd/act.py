@@ -18,6 +18,7 @@ import torch
 
 from . import _lib
 from .engine import _need_cuda, _stream_of
+from .ppo_loss import _available, _logits_shape, _ordinal, _widened
 
 OUT_KEYS = ("action_idx", "actions", "actions_f32", "action_log_probs")
 _OUT_DTYPES = dict(action_idx=torch.int32, actions=torch.int64, actions_f32=torch.float32, action_log_probs=torch.float32)
@@ -51,29 +52,16 @@ def sample_actions(logits, available_actions=None, *, dones_prev=None, stop_acti
         shape = tuple(logits.shape) if isinstance(logits, torch.Tensor) else "a list of %d heads" % len(logits)
         raise NotImplementedError("logits of shape %s: only a single Discrete head is supported (MultiDiscrete, mixed and continuous heads are not)"
                                   % (shape,))
-    if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or not logits.is_floating_point():
-        raise ValueError("logits must be a floating-point tensor [rows, n_actions]")
-    dev = logits.device
-    rows, K = int(logits.shape[0]), int(logits.shape[1])
-    if rows < 1 or K < 1:
-        raise ValueError("logits must have at least one row and one action")
-    if K > _lib.PPO_MAX_ACTIONS:
-        raise ValueError("n_actions = %d is above the supported %d" % (K, _lib.PPO_MAX_ACTIONS))
+    dev, rows, K = _logits_shape(logits)
     if not logits.is_contiguous():
         raise ValueError("logits must be contiguous")
-    if logits.dtype in (torch.float16, torch.bfloat16):
-        logits = logits.float()
+    logits = _widened(logits)
     if logits.dtype != torch.float32:
         raise ValueError("logits must be float32 (or float16 / bfloat16, widened here)")
     if available_actions is not None and dones_prev is not None:
         raise ValueError("available_actions and dones_prev are two sources of the availability: give at most one")
     if available_actions is not None:
-        if not isinstance(available_actions, torch.Tensor) or available_actions.dtype != torch.float32 or tuple(available_actions.shape) != (rows, K):
-            raise ValueError("available_actions must be a float32 tensor of shape (%d, %d) or None" % (rows, K))
-        if not available_actions.is_contiguous():
-            raise ValueError("available_actions must be contiguous")
-        if available_actions.device != dev:
-            raise ValueError("available_actions must be on %s (the device of logits)" % dev)
+        available_actions = _available(available_actions, rows, K, dev, contiguous=True)
     if dones_prev is not None:
         _rows_tensor("dones_prev", dones_prev, rows, dev, (torch.uint8, torch.bool))
     elif stop_action is not None:
@@ -123,5 +111,5 @@ def sample_actions(logits, available_actions=None, *, dones_prev=None, stop_acti
     plan.actions_f32 = None if actf is None else actf.data_ptr()
     plan.actions_i64 = None if act64 is None else act64.data_ptr()
     st = C.c_void_p(stream.cuda_stream) if stream is not None else _stream_of(dev)
-    _lib.check(_lib.load().gmpe_act_sample(dev.index if dev.index is not None else torch.cuda.current_device(), C.byref(plan), st), "gmpe_act_sample")
+    _lib.check(_lib.load().gmpe_act_sample(_ordinal(dev), C.byref(plan), st), "gmpe_act_sample")
     return idx, act64, logp

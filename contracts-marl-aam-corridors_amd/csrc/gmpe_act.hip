@@ -5,9 +5,9 @@
 // finfo(float32).min where available_actions == 0, FixedCategorical(logits=x)), then sample() or mode() (:15-16, 27-28), then log_probs (:18-25); and
 // what the runner does with the result (graph_mpe_runner.py:299-320, 356-377): the int action the env takes, the float32 / int64 action the buffer keeps.
 //
-// The distribution of a row is policy_row's (gmpe_ppo_rows.h), restated here with the same intrinsics in the same order — max, lse, l = x - lse, ml,
-// p_j = exp(l_j - ml) / s2 — so the log-prob l[a] written here has the bits gmpe_ppo_loss recomputes for the same logits, availability and action: the
-// first minibatch of an unchanged policy has importance weights of exactly 1. The header itself is included for its tile machinery and left as it is.
+// The distribution of a row is policy_row's: this kernel calls the helpers policy_row is made of (gmpe_ppo_rows.h masked_max, normalise_row, prob), so
+// the log-prob l[a] written here has the bits gmpe_ppo_loss recomputes for the same logits, availability and action: the first minibatch of an unchanged
+// policy has importance weights of exactly 1. The tile machinery is that header's too.
 //
 // Sampling: one draw u per row from the project's Philox stream (gmpe_device.h philox_uniform), keyed by the row's ENV and agent, not by where the row
 // lies in the batch: u = philox_uniform(seed, env_id_base + r / A, 2^63 | (draw * A + r % A)). The top bit keeps the action stream apart from the env's
@@ -20,27 +20,22 @@
 #include <math.h>
 #include <stdint.h>
 
-#include <atomic>
 #include <string>
 
-#include "../../include/gmpe.h"
 #include "gmpe_device.h"
+#include "gmpe_host.h"          // include/gmpe.h, the error text, GMPE_HIP_CHECK
 #include "gmpe_ppo_rows.h"
 
 #pragma clang fp contract(off)
 
-namespace gmpe {
-int report_error(int code, const std::string& m);   // gmpe_step.hip: the library's gmpe_last_error text
-}
-
 namespace {
 
-using namespace gmpe_ppo;         // gmpe_ppo_rows.h: TILE, FMIN, tile_copy, avail_bits
+using namespace gmpe_ppo;         // gmpe_ppo_rows.h: TILE, the tile machinery and the masked categorical
 
 struct ActArgs {
-    int64_t B;
-    int K, S, A, stop, det;        // S: LDS row stride in dwords, odd (gmpe_ppo_loss.hip LossArgs)
-    uint32_t magic, env_base;
+    Geom g;
+    int A, stop, det;
+    uint32_t env_base;
     uint64_t seed, draw;
     const uint64_t* draw_dev;
     const float *logits, *avail;
@@ -54,43 +49,25 @@ struct ActArgs {
 template <bool VEC>
 __global__ __launch_bounds__(TILE) void k_act_rows(ActArgs p) {
     extern __shared__ __attribute__((aligned(16))) float sh[];
-    const int K = p.K, S = p.S;
-    const int64_t row0 = (int64_t)blockIdx.x * TILE, r = row0 + threadIdx.x;
-    const int rows = p.B - row0 < TILE ? (int)(p.B - row0) : TILE, n = rows * K;
-    const bool live = (int)threadIdx.x < rows;
-    float* row = sh + threadIdx.x * S;
-    const int64_t g0 = row0 * K;
+    const int K = p.g.K;
+    const Tile t = tile_of(p.g, sh);
+    const int64_t r = t.r;
+    float* row = t.row;
     const uint64_t all = K == 64 ? ~0ull : (1ull << K) - 1ull;
 
     uint64_t avail = all;
-    if (p.avail) {
-        tile_copy<VEC, true>(const_cast<float*>(p.avail) + g0, sh, n, K, S, p.magic);
-        __syncthreads();
-        if (live) avail = avail_bits(row, K);                                       // x[available_actions == 0] = finfo.min
-        __syncthreads();
-    } else if (p.dones && live && p.dones[r]) {
-        avail = 1ull << p.stop;                                                     // collect_with_mask: a done agent may only stop
-    }
-    tile_copy<VEC, true>(const_cast<float*>(p.logits) + g0, sh, n, K, S, p.magic);
-    __syncthreads();
-    if (!live) return;
+    if (!p.avail && p.dones && t.live && p.dones[r]) avail = 1ull << p.stop;         // collect_with_mask: a done agent may only stop
+    avail = tile_in<VEC>(p.g, t, p.avail, p.logits, sh, avail);
+    if (!t.live) return;
 
-    // ---- the masked categorical, as policy_row forms it
-    float m = -INFINITY;
-    for (int j = 0; j < K; ++j) m = fmaxf(m, (avail >> j & 1) ? row[j] : FMIN);
+    // ---- the masked categorical, as policy_row forms it; the mode is taken while the row still holds the logits (rounding x - lse can make ties)
+    const float m = masked_max(row, K, avail);
     const uint64_t set = avail ? avail : all;                                       // nothing available: the uniform row over all K
     int mode = __builtin_ctzll(set);
     for (int j = K - 1; j >= 0; --j)
-        if ((set >> j & 1) && ((avail >> j & 1) ? row[j] : FMIN) == m) mode = j;    // the first index of the largest masked logit
-    float s = 0.0f;
-    for (int j = 0; j < K; ++j) s = __fadd_rn(s, expf(__fsub_rn((avail >> j & 1) ? row[j] : FMIN, m)));
-    const float lse = __fadd_rn(logf(s), m), ml = __fsub_rn(m, lse);
-    float s2 = 0.0f;
-    for (int j = 0; j < K; ++j) {                                                   // the row now holds l = x - logsumexp(x)
-        const float l = __fsub_rn((avail >> j & 1) ? row[j] : FMIN, lse);
-        row[j] = l;
-        s2 = __fadd_rn(s2, expf(__fsub_rn(l, ml)));
-    }
+        if ((set >> j & 1) && masked_logit(row, avail, j) == m) mode = j;           // the first index of the largest masked logit
+    float ml, s2;
+    normalise_row(row, K, avail, m, &ml, &s2);
     int a = mode;
     if (!p.det) {
         const int64_t env = r / p.A;
@@ -100,7 +77,7 @@ __global__ __launch_bounds__(TILE) void k_act_rows(ActArgs p) {
         float c = 0.0f;
         for (int j = 0; j < K; ++j) {
             if (!(set >> j & 1)) continue;
-            c = __fadd_rn(c, __fdiv_rn(expf(__fsub_rn(row[j], ml)), s2));
+            c = __fadd_rn(c, prob(row[j], ml, s2));
             if ((double)c > u) { a = j; break; }
         }
     }
@@ -116,8 +93,6 @@ __global__ void k_act_advance(uint64_t* draw_dev, uint64_t inc) { *draw_dev += i
 int fail(int code, const std::string& m) { return gmpe::report_error(code, m); }
 
 }  // namespace
-
-#define ACHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(GMPE_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
 
 extern "C" {
 
@@ -138,33 +113,28 @@ int gmpe_act_sample(int device, const gmpe_act_plan* pl, void* stream) {
     const uintptr_t a4 = (uintptr_t)pl->logits | (uintptr_t)pl->available_actions | (uintptr_t)pl->action_idx | (uintptr_t)pl->log_probs | (uintptr_t)pl->actions_f32;
     if ((a4 & 3) || (((uintptr_t)pl->actions_i64 | (uintptr_t)pl->draw_dev) & 7))
         return fail(GMPE_ERR_INVALID_ARG, "gmpe_act_sample: f32 / int32 arrays must be 4-byte aligned, actions_i64 and draw_dev 8-byte aligned");
-    const int64_t nt = (pl->rows + TILE - 1) / TILE;
+    const int64_t nt = num_tiles(pl->rows);
     if (nt > 0x7fffffffLL) return fail(GMPE_ERR_INVALID_ARG, "gmpe_act_sample: too many rows for one launch");
-    ACHK(hipSetDevice(device));
+    GMPE_HIP_CHECK(hipSetDevice(device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     ActArgs a;
-    a.B = pl->rows; a.K = pl->n_actions; a.S = pl->n_actions | 1; a.A = pl->num_agents; a.stop = pl->stop_action; a.det = pl->deterministic;
-    a.magic = (uint32_t)(0x100000000ULL / (uint64_t)(pl->n_actions > 1 ? pl->n_actions : 2)) + 1u;
+    a.g = geometry(pl->rows, pl->n_actions);
+    a.A = pl->num_agents; a.stop = pl->stop_action; a.det = pl->deterministic;
     a.env_base = (uint32_t)pl->env_id_base;
     a.seed = pl->seed; a.draw = pl->draw; a.draw_dev = pl->draw_dev;
     a.logits = pl->logits; a.avail = pl->available_actions; a.dones = pl->dones_prev;
     a.idx = pl->action_idx; a.lp = pl->log_probs; a.af = pl->actions_f32; a.ai = pl->actions_i64;
     const bool vec = !(((uintptr_t)pl->logits | (uintptr_t)pl->available_actions) & 15);        // tiles start at multiples of 1 KiB
-    const size_t lds = (size_t)TILE * a.S * sizeof(float);
+    const size_t lds = (size_t)TILE * a.g.S * sizeof(float);
     void (*fn)(ActArgs) = vec ? k_act_rows<true> : k_act_rows<false>;
-    if (lds > 48 * 1024) {                                                    // K = 64 only; once per device and instantiation, at the largest size there is
-        static std::atomic<bool> raised[64][2];
-        if (device < 0 || device >= 64 || !raised[device][vec].load()) {
-            ACHK(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)(TILE * (GMPE_PPO_MAX_ACTIONS | 1) * sizeof(float))));
-            if (device >= 0 && device < 64) raised[device][vec].store(true);
-        }
-    }
+    if (lds > 48 * 1024)                                                      // K = 64 only
+        if (int rc = raise_dynamic_lds_once(reinterpret_cast<const void*>(fn), device, vec, TILE * (GMPE_PPO_MAX_ACTIONS | 1) * sizeof(float)))
+            return rc;
     hipLaunchKernelGGL(fn, dim3((unsigned)nt), dim3(TILE), lds, st, a);
-    ACHK(hipGetLastError());
+    GMPE_HIP_CHECK(hipGetLastError());
     if (pl->draw_dev) {
         hipLaunchKernelGGL(k_act_advance, dim3(1), dim3(1), 0, st, pl->draw_dev, pl->draw_inc);
-        ACHK(hipGetLastError());
+        GMPE_HIP_CHECK(hipGetLastError());
     }
     return GMPE_OK;
 }

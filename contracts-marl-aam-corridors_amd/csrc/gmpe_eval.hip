@@ -17,13 +17,9 @@
 
 #include <string>
 
-#include "../../include/gmpe.h"
+#include "gmpe_host.h"          // include/gmpe.h, the error text, GMPE_HIP_CHECK
 
 #pragma clang fp contract(off)
-
-namespace gmpe {
-int report_error(int code, const std::string& m);   // gmpe_step.hip: the library's gmpe_last_error text
-}
 
 namespace {
 
@@ -365,8 +361,6 @@ int fail(const char* fn, const std::string& m) { return gmpe::report_error(GMPE_
 
 }  // namespace
 
-#define ECHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return gmpe::report_error(GMPE_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
-
 extern "C" {
 
 int gmpe_episode_record(int device, const gmpe_episode_record_plan* pl, void* stream) {
@@ -387,9 +381,9 @@ int gmpe_episode_record(int device, const gmpe_episode_record_plan* pl, void* st
     RecArgs a{pl->num_envs, pl->num_agents, pl->t, pl->num_steps, pl->n_actions, pl->rnn_states ? pl->rnn_row : 0, pl->reward, pl->done, pl->info,
               pl->live, pl->steps, pl->ret, pl->final_info, pl->masks, pl->available_actions, pl->rnn_states};
     const int64_t blocks = ((int64_t)pl->num_envs + ER_ENVS - 1) / ER_ENVS;
-    ECHK(hipSetDevice(device));
+    GMPE_HIP_CHECK(hipSetDevice(device));
     hipLaunchKernelGGL(k_episode_record, dim3((unsigned)blocks), dim3(ER_BLOCK), 0, static_cast<hipStream_t>(stream), a);
-    ECHK(hipGetLastError());
+    GMPE_HIP_CHECK(hipGetLastError());
     return GMPE_OK;
 }
 
@@ -408,10 +402,10 @@ int gmpe_episode_metrics(int device, const gmpe_episode_metrics_plan* pl, void* 
     const int row_blocks = (pl->num_envs + EM_BLOCK - 1) / EM_BLOCK;
     MetArgs a{pl->num_envs, pl->num_agents, pl->num_steps, row_blocks, (double)pl->num_steps * pl->dt, pl->min_dist_thresh, pl->steps, pl->ret,
               pl->final_info, pl->episodes, pl->dists_traveled, pl->time_taken};
-    ECHK(hipSetDevice(device));
+    GMPE_HIP_CHECK(hipSetDevice(device));
     hipLaunchKernelGGL(k_episode_metrics, dim3((unsigned)(row_blocks + (sums ? pl->num_agents : 0))), dim3(EM_BLOCK), 0,
                        static_cast<hipStream_t>(stream), a);
-    ECHK(hipGetLastError());
+    GMPE_HIP_CHECK(hipGetLastError());
     return GMPE_OK;
 }
 
@@ -425,9 +419,9 @@ int gmpe_episode_summary(int device, const gmpe_episode_summary_plan* pl, void* 
     if (!pl->table || !pl->out) return fail(fn, "null pointer");
     if (!aligned(pl->table, 8) || !aligned(pl->out, 8)) return fail(fn, "misaligned pointer: f64 arrays need 8-byte alignment");
     SumArgs a{pl->num_rows, pl->num_columns, pl->success_column, pl->success_agents, pl->table, pl->out};
-    ECHK(hipSetDevice(device));
+    GMPE_HIP_CHECK(hipSetDevice(device));
     hipLaunchKernelGGL(k_episode_summary, dim3((unsigned)pl->num_columns), dim3(ES_BLOCK), 0, static_cast<hipStream_t>(stream), a);
-    ECHK(hipGetLastError());
+    GMPE_HIP_CHECK(hipGetLastError());
     return GMPE_OK;
 }
 

@@ -11,13 +11,9 @@
 
 #include <string>
 
-#include "../../include/gmpe.h"
+#include "gmpe_host.h"          // include/gmpe.h, the error text, GMPE_HIP_CHECK
 
 #pragma clang fp contract(off)
-
-namespace gmpe {
-int report_error(int code, const std::string& m);   // gmpe_step.hip: the library's gmpe_last_error text
-}
 
 namespace {
 
@@ -118,8 +114,6 @@ int fail(const char* fn, const std::string& m) { return gmpe::report_error(GMPE_
 
 }  // namespace
 
-#define ECHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return gmpe::report_error(GMPE_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
-
 extern "C" int gmpe_episode_record_series(int device, const gmpe_episode_series_plan* pl, void* stream) {
     const char* fn = "gmpe_episode_record_series";
     if (!pl) return fail(fn, "null plan");
@@ -141,8 +135,8 @@ extern "C" int gmpe_episode_record_series(int device, const gmpe_episode_series_
     SeriesArgs a{pl->num_envs, pl->num_agents, pl->num_steps, pl->num_episodes, pl->n_actions, pl->rnn_states ? pl->rnn_row : 0, pl->reward, pl->done,
                  pl->info, pl->episode, pl->t_in_ep, pl->ret, pl->steps, pl->ret_out, pl->final_info, pl->masks, pl->available_actions, pl->rnn_states};
     const int64_t blocks = ((int64_t)pl->num_envs + ES_ENVS - 1) / ES_ENVS;
-    ECHK(hipSetDevice(device));
+    GMPE_HIP_CHECK(hipSetDevice(device));
     hipLaunchKernelGGL(k_episode_record_series, dim3((unsigned)blocks), dim3(ES_BLOCK), 0, static_cast<hipStream_t>(stream), a);
-    ECHK(hipGetLastError());
+    GMPE_HIP_CHECK(hipGetLastError());
     return GMPE_OK;
 }

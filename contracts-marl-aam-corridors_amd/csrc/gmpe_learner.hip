@@ -12,11 +12,7 @@
 
 #include <string>
 
-#include "../../include/gmpe.h"
-
-namespace gmpe {
-int report_error(int code, const std::string& m);   // gmpe_step.hip: the library's gmpe_last_error text
-}
+#include "gmpe_host.h"          // include/gmpe.h, the error text, GMPE_HIP_CHECK
 
 namespace {
 
@@ -102,8 +98,6 @@ bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0;
 
 }  // namespace
 
-#define LCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return gmpe::report_error(GMPE_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
-
 extern "C" int gmpe_insert_learner(int device, const gmpe_learner_plan* pl, void* stream) {
     if (!pl) return fail("null plan");
     if (pl->lanes < 1) return fail("need lanes >= 1");
@@ -151,8 +145,8 @@ extern "C" int gmpe_insert_learner(int device, const gmpe_learner_plan* pl, void
         a.rnn[f].row = (uint32_t)rows[f];
         a.rnn[f].vec = rows[f] % 4 == 0 && aligned(srcs[f], 16) && aligned(dsts[f], 16);
     }
-    LCHK(hipSetDevice(device));
+    GMPE_HIP_CHECK(hipSetDevice(device));
     hipLaunchKernelGGL(k_insert_learner, dim3((unsigned)blocks), dim3(LI_BLOCK), 0, static_cast<hipStream_t>(stream), a);
-    LCHK(hipGetLastError());
+    GMPE_HIP_CHECK(hipGetLastError());
     return GMPE_OK;
 }

@@ -15,15 +15,11 @@
 
 #include <string>
 
-#include "../../include/gmpe.h"
+#include "gmpe_host.h"          // include/gmpe.h, the error text, GMPE_HIP_CHECK
 #include "gmpe_expand.h"
 #include "gmpe_mb_map.h"
 
 #pragma clang fp contract(off)
-
-namespace gmpe {
-int report_error(int code, const std::string& m);   // gmpe_step.hip: the library's gmpe_last_error text
-}
 
 namespace {
 
@@ -195,8 +191,6 @@ size_t ws_bytes(int64_t graphs) {
 
 }  // namespace
 
-#define ECHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(GMPE_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
-
 extern "C" {
 
 int gmpe_minibatch_edges_workspace_bytes(int64_t graphs, size_t* bytes_out) {
@@ -269,16 +263,16 @@ int gmpe_minibatch_edges(const gmpe_config* cfg, int device, const gmpe_mb_edges
     a.counts = reinterpret_cast<int32_t*>(a.boff + a.nblocks);
     a.edge_index = pl->edge_index; a.edge_attr = pl->edge_attr; a.cap = pl->cap; a.n_edges = pl->n_edges;
     const bool vec4 = !table && (EE4 & 15) == 0 && (((uintptr_t)pl->src | (uintptr_t)pl->slot_stride) & 15) == 0;
-    ECHK(hipSetDevice(device));
+    GMPE_HIP_CHECK(hipSetDevice(device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid(a.nblocks), block(MBE_BLOCK);
     if (!pl->reuse_counts) {
         if (table) hipLaunchKernelGGL((k_mbe_count<true, 1>), grid, block, 0, st, a);
         else if (vec4) hipLaunchKernelGGL((k_mbe_count<false, 4>), grid, block, 0, st, a);
         else hipLaunchKernelGGL((k_mbe_count<false, 1>), grid, block, 0, st, a);
-        ECHK(hipGetLastError());
+        GMPE_HIP_CHECK(hipGetLastError());
         hipLaunchKernelGGL(k_mbe_scan, dim3(1), dim3(MBE_SCAN), 0, st, a.boff, a.nblocks, a.n_edges);
-        ECHK(hipGetLastError());
+        GMPE_HIP_CHECK(hipGetLastError());
     }
     if (write && pl->cap > 0) {
         const int which = (table ? 4 : (vec4 ? 2 : 0)) + (pl->index64 ? 1 : 0);
@@ -290,7 +284,7 @@ int gmpe_minibatch_edges(const gmpe_config* cfg, int device, const gmpe_mb_edges
         case 4: hipLaunchKernelGGL((k_mbe_write<true, 1, false>), grid, block, 0, st, a); break;
         default: hipLaunchKernelGGL((k_mbe_write<true, 1, true>), grid, block, 0, st, a); break;
         }
-        ECHK(hipGetLastError());
+        GMPE_HIP_CHECK(hipGetLastError());
     }
     return GMPE_OK;
 }

@@ -13,15 +13,11 @@
 
 #include <string>
 
-#include "../../include/gmpe.h"
+#include "gmpe_host.h"          // include/gmpe.h, the error text, GMPE_HIP_CHECK
 #include "gmpe_expand.h"
 #include "gmpe_mb_map.h"
 
 #pragma clang fp contract(off)
-
-namespace gmpe {
-int report_error(int code, const std::string& m);   // gmpe_step.hip: the library's gmpe_last_error text
-}
 
 namespace {
 
@@ -108,8 +104,6 @@ int fail(int code, const std::string& m) { return gmpe::report_error(code, m); }
 
 }  // namespace
 
-#define MCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(GMPE_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
-
 extern "C" {
 
 int gmpe_minibatch_gather(const gmpe_config* cfg, int device, const gmpe_minibatch_plan* pl, void* stream) {
@@ -194,11 +188,11 @@ int gmpe_minibatch_gather(const gmpe_config* cfg, int device, const gmpe_minibat
         if (blocks > 0x7fffffffLL) return bad("too many workgroups for one launch");
         dstargs.f[dstargs.nf++] = m;
     }
-    MCHK(hipSetDevice(device));
+    GMPE_HIP_CHECK(hipSetDevice(device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (a.nf) {
         hipLaunchKernelGGL(k_mb_copy, dim3((unsigned)blocks_a), dim3(MB_BLOCK), 0, st, a);
-        MCHK(hipGetLastError());
+        GMPE_HIP_CHECK(hipGetLastError());
     }
     if (b.nf) {
         const dim3 grid((unsigned)blocks_b), block(MB_BLOCK);
@@ -210,7 +204,7 @@ int gmpe_minibatch_gather(const gmpe_config* cfg, int device, const gmpe_minibat
         case 4: hipLaunchKernelGGL((k_mb_table<2, 1>), grid, block, 0, st, b); break;
         default: hipLaunchKernelGGL((k_mb_table<2, 4>), grid, block, 0, st, b); break;
         }
-        MCHK(hipGetLastError());
+        GMPE_HIP_CHECK(hipGetLastError());
     }
     return GMPE_OK;
 }

@@ -29,17 +29,12 @@
 #include <math.h>
 #include <stdint.h>
 
-#include <atomic>
 #include <string>
 
-#include "../../include/gmpe.h"
+#include "gmpe_host.h"          // include/gmpe.h, the error text, GMPE_HIP_CHECK
 #include "gmpe_ppo_rows.h"
 
 #pragma clang fp contract(off)
-
-namespace gmpe {
-int report_error(int code, const std::string& m);   // gmpe_step.hip: the library's gmpe_last_error text
-}
 
 namespace {
 
@@ -52,14 +47,12 @@ constexpr int FIN_COLS = 16, FIN_SLICES = TILE / FIN_COLS;   // finish: 16 colum
 static_assert(MAXQ == 4, "the feature mapping holds at most four quads per lane");
 
 struct PopArgs {
-    int64_t B;
-    int K, S, flags;               // as LossArgs of gmpe_ppo_loss.hip
-    uint32_t magic;
+    Geom g;
+    PolicyArgs pol;
     int H, NQ, L, lsh, vecf;       // NQ = ceil(H / 4); L = 1 << lsh lanes per row; vecf: features and grad_features move in 16-byte units
-    const float *logits, *avail, *feat, *W, *bias, *stddev, *old_lp, *adv, *vp, *ret, *am;
-    const void* actions;
-    float *grad_logits, *grad_feat, *grad_W, *grad_b, *values_out, *out_lp, *out_ratio, *W_out, *bias_out, *stddev_out;
-    float lo, hi, clip, delta, half_delta, ent_coef, wbeta, w1beta, eps;
+    const float *feat, *W, *bias, *stddev, *vp, *ret;
+    float *grad_logits, *grad_feat, *grad_W, *grad_b, *values_out, *W_out, *bias_out, *stddev_out;
+    float clip, delta, half_delta, wbeta, w1beta, eps;
     float *mean, *mean_sq, *db;
     double *stat_part, *row_part, *col_part, *hdr, *out;
 };
@@ -70,7 +63,7 @@ __device__ __forceinline__ float clamp_min(float x, float lo) { return x != x ? 
 // 1: per-workgroup double sums of returns, returns^2, active_masks
 __global__ __launch_bounds__(TILE) void k_pop_stats(PopArgs p) {
     __shared__ double red[NW * NSTAT];
-    stats_tile(p.ret, p.am, p.B, p.stat_part, red);
+    stats_tile(p.ret, p.pol.am, p.g.B, p.stat_part, red);
 }
 
 // 2: merge; PopArt.update (popart.py:62-83) BEFORE normalize, as cal_value_loss does. The new weight is left to `finish`; stddev' and b' wait in the header.
@@ -78,15 +71,10 @@ __global__ __launch_bounds__(TILE) void k_pop_prepare(PopArgs p, int64_t nparts)
     __shared__ double sh[TILE][NSTAT];
     merge<NSTAT>(p.stat_part, nparts, sh);
     if (threadIdx.x != 0) return;
-    const double n = (double)p.B, msum = sh[0][2];
-    p.hdr[0] = (p.flags & GMPE_PPO_POLICY_ACTIVE_MASKS) ? msum : n;
-    p.hdr[1] = (p.flags & GMPE_PPO_VALUE_ACTIVE_MASKS) ? msum : n;
-    const float bm = (float)(sh[0][0] / n), bsq = (float)(sh[0][1] / n);                     // input_vector.mean(0), (input_vector ** 2).mean(0)
+    denominators(p.hdr, p.pol.flags, p.g.B, sh[0][2]);
     const float s_old = *p.stddev, b = *p.bias;                                              // old_stddev; old_mean is NOT kept: it aliases self.mean
-    const float mean = __fadd_rn(__fmul_rn(*p.mean, p.wbeta), __fmul_rn(bm, p.w1beta));      // mean.mul_(beta).add_(batch_mean * (1.0 - beta))
-    const float msq = __fadd_rn(__fmul_rn(*p.mean_sq, p.wbeta), __fmul_rn(bsq, p.w1beta));
-    const float db = __fadd_rn(__fmul_rn(*p.db, p.wbeta), p.w1beta);                         // debiasing_term.mul_(beta).add_(1.0 * (1.0 - beta))
-    *p.mean = mean; *p.mean_sq = msq; *p.db = db;
+    const Running u = running_update(p.mean, p.mean_sq, p.db, sh[0], p.g.B, p.wbeta, p.w1beta);
+    const float mean = u.mean, msq = u.mean_sq, db = u.debias;
     const float s_new = clamp_min(__fsqrt_rn(__fsub_rn(msq, __fmul_rn(mean, mean))), 1e-4f);         // (mean_sq - mean ** 2).sqrt().clamp(min=1e-4)
     const float b_new = __fdiv_rn(__fsub_rn(__fadd_rn(__fmul_rn(s_old, b), mean), mean), s_new);     // (old_stddev * bias + old_mean - mean) / stddev
     const float dc = clamp_min(db, p.eps);                                                           // debiased_mean_var (popart.py:85-89)
@@ -113,13 +101,11 @@ __global__ __launch_bounds__(TILE) void k_pop_rows(PopArgs p) {
     extern __shared__ __attribute__((aligned(16))) float sh[];              // the logits tile [TILE, S], then the column sums: 4 * L * MAXQ doubles
     __shared__ double red[NW * NROWP];
     __shared__ float vsh[TILE], gsh[TILE];                                  // a row's value / gradient between the two mappings
-    const int K = p.K, S = p.S, H = p.H, NQ = p.NQ, L = p.L;
-    const int64_t row0 = (int64_t)blockIdx.x * TILE, r = row0 + threadIdx.x;
-    const int rows = p.B - row0 < TILE ? (int)(p.B - row0) : TILE, n = rows * K;
-    const bool live = (int)threadIdx.x < rows;
-    float* row = sh + threadIdx.x * S;
-    double* colsum = reinterpret_cast<double*>(sh + ((TILE * S + 3) & ~3));
-    const int64_t g0 = row0 * K;
+    const int H = p.H, NQ = p.NQ, L = p.L;
+    const Tile t = tile_of(p.g, sh);
+    const int64_t row0 = t.row0;
+    const int rows = t.rows;
+    double* colsum = reinterpret_cast<double*>(sh + ((TILE * p.g.S + 3) & ~3));
     const bool vecf = p.vecf;
 
     // ---- feature mapping: the value of every row of the tile
@@ -159,41 +145,24 @@ __global__ __launch_bounds__(TILE) void k_pop_rows(PopArgs p) {
     }
 
     // ---- row mapping: the policy block and the value branch, as gmpe_ppo_loss.hip
-    uint64_t avail = ~0ull;
-    if (p.avail) {
-        tile_copy<VEC, true>(const_cast<float*>(p.avail) + g0, sh, n, K, S, p.magic);
-        __syncthreads();
-        if (live) avail = avail_bits(row, K);
-        __syncthreads();
-    }
-    tile_copy<VEC, true>(const_cast<float*>(p.logits) + g0, sh, n, K, S, p.magic);
-    __syncthreads();                                                        // also orders vsh
+    const uint64_t avail = tile_in<VEC>(p.g, t, p.pol.avail, p.pol.logits, sh, ~0ull);      // its last barrier also orders vsh
 
     double acc[NROWP] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    if (live) {
+    if (t.live) {
+        const int64_t r = t.r;
         const double Dp = p.hdr[0], Dv = p.hdr[1];
-        const float am = p.am[r];
-        const float wp = (p.flags & GMPE_PPO_POLICY_ACTIVE_MASKS) ? am : 1.0f, wv = (p.flags & GMPE_PPO_VALUE_ACTIVE_MASKS) ? am : 1.0f;
-        PolicyRow q;
-        q.avail = avail;
-        q.action = ACT64 ? static_cast<const int64_t*>(p.actions)[r] : (int64_t)static_cast<const float*>(p.actions)[r];
-        q.adv = p.adv[r]; q.old_lp = p.old_lp[r]; q.wp = wp; q.Dp = (float)Dp; q.lo = p.lo; q.hi = p.hi; q.ent_coef = p.ent_coef;
-        float la, ratio;
-        policy_row(row, K, q, &la, &ratio, &acc[0], &acc[1]);
-        acc[3] = (double)ratio;
-        if (p.out_lp) p.out_lp[r] = la;
-        if (p.out_ratio) p.out_ratio[r] = ratio;
+        const float wv = policy_side<ACT64>(p.pol, t.row, p.g.K, r, avail, Dp, acc);
         const float v = vsh[threadIdx.x];
         if (p.values_out) p.values_out[r] = v;
         const float* st = reinterpret_cast<const float*>(p.hdr + 2);
         const float R = __fdiv_rn(__fsub_rn(p.ret[r], st[0]), st[1]);       // normalize: (returns - mean_d) / sqrt(var_d)
-        const float g = value_row<true>(v, p.vp[r], R, p.flags & GMPE_PPO_HUBER_LOSS, p.flags & GMPE_PPO_CLIPPED_VALUE_LOSS, p.clip, p.delta, p.half_delta, wv,
+        const float g = value_row<true>(v, p.vp[r], R, p.pol.flags & GMPE_PPO_HUBER_LOSS, p.pol.flags & GMPE_PPO_CLIPPED_VALUE_LOSS, p.clip, p.delta, p.half_delta, wv,
                                   (float)Dv, &acc[2]);
         gsh[threadIdx.x] = g;
         acc[4] = (double)g;
     }
     block_sum<NROWP>(acc, red, p.row_part + (int64_t)blockIdx.x * NROWP);    // its barrier also orders gsh and the gradient rows before the copy out
-    tile_copy<VEC, false>(p.grad_logits + g0, sh, n, K, S, p.magic);
+    tile_copy<VEC, false>(p.grad_logits + t.g0, sh, t.n, p.g.K, p.g.S, p.g.magic);
 
     // ---- feature mapping again: grad_features, and this workgroup's double sums of g * F over its rows
     double da[MAXQ][4];
@@ -257,15 +226,7 @@ __global__ __launch_bounds__(TILE) void k_pop_finish(PopArgs p, int64_t nparts) 
     if (blockIdx.x == 0) {
         merge<NROWP>(p.row_part, nparts, sh);
         if (threadIdx.x != 0) return;
-        const double Dp = p.hdr[0], Dv = p.hdr[1];
-        const double pol = sh[0][0] / Dp, ent = sh[0][1] / Dp;
-        p.out[GMPE_PPO_OUT_POLICY_LOSS] = pol;
-        p.out[GMPE_PPO_OUT_DIST_ENTROPY] = ent;
-        p.out[GMPE_PPO_OUT_ACTOR_LOSS] = pol - (double)p.ent_coef * ent;
-        p.out[GMPE_PPO_OUT_VALUE_LOSS] = sh[0][2] / Dv;
-        p.out[GMPE_PPO_OUT_RATIO_MEAN] = sh[0][3] / (double)p.B;
-        p.out[GMPE_PPO_OUT_DENOM_POLICY] = Dp;
-        p.out[GMPE_PPO_OUT_DENOM_VALUE] = Dv;
+        write_scalars(p.out, sh[0], p.hdr[0], p.hdr[1], p.pol.ent_coef, p.g.B);
         *p.grad_b = (float)sh[0][4];
         *p.stddev_out = st[3];                                              // every reader of stddev, bias and weight has finished: the row pass is over
         *p.bias_out = st[4];                                                // and this launch takes them from the header
@@ -288,13 +249,9 @@ __global__ __launch_bounds__(TILE) void k_pop_finish(PopArgs p, int64_t nparts) 
     }
 }
 
-int64_t num_tiles(int64_t rows) { return (rows + TILE - 1) / TILE; }
-
 int fail(int code, const std::string& m) { return gmpe::report_error(code, m); }
 
 }  // namespace
-
-#define LCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(GMPE_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
 
 extern "C" {
 
@@ -309,22 +266,17 @@ int gmpe_ppo_loss_popart(int device, const gmpe_popart_loss_plan* pl, void* stre
     if (!pl) return fail(GMPE_ERR_INVALID_ARG, "gmpe_ppo_loss_popart: null plan");
     const int known = GMPE_PPO_POLICY_ACTIVE_MASKS | GMPE_PPO_VALUE_ACTIVE_MASKS | GMPE_PPO_CLIPPED_VALUE_LOSS | GMPE_PPO_HUBER_LOSS;
     if (pl->flags & ~known) return fail(GMPE_ERR_INVALID_ARG, "gmpe_ppo_loss_popart: unknown flags (GMPE_PPO_VALUENORM is not accepted: PopArt is the normaliser)");
-    if (pl->rows < 1) return fail(GMPE_ERR_INVALID_ARG, "gmpe_ppo_loss_popart: need rows >= 1");
-    if (pl->n_actions < 1 || pl->n_actions > GMPE_PPO_MAX_ACTIONS)
-        return fail(GMPE_ERR_INVALID_ARG, "gmpe_ppo_loss_popart: n_actions must be in 1 .. " + std::to_string(GMPE_PPO_MAX_ACTIONS));
-    if (pl->hidden < 1 || pl->hidden > GMPE_POPART_MAX_HIDDEN)
-        return fail(GMPE_ERR_INVALID_ARG, "gmpe_ppo_loss_popart: hidden must be in 1 .. " + std::to_string(GMPE_POPART_MAX_HIDDEN));
-    if (pl->actions_int64 != 0 && pl->actions_int64 != 1) return fail(GMPE_ERR_INVALID_ARG, "gmpe_ppo_loss_popart: actions_int64 must be 0 or 1");
+    const bool bad_hidden = pl->hidden < 1 || pl->hidden > GMPE_POPART_MAX_HIDDEN;
+    const std::string dims = bad_hidden ? "hidden must be in 1 .. " + std::to_string(GMPE_POPART_MAX_HIDDEN) : std::string();
+    const char* missing = nullptr;
     if (!pl->logits || !pl->critic_features || !pl->actions || !pl->old_action_log_probs || !pl->adv_targ || !pl->value_preds || !pl->returns ||
         !pl->active_masks)
-        return fail(GMPE_ERR_INVALID_ARG, "gmpe_ppo_loss_popart: logits, critic_features, actions, old_action_log_probs, adv_targ, value_preds, returns and "
-                                          "active_masks are required");
-    if (!pl->weight || !pl->bias || !pl->stddev || !pl->mean || !pl->mean_sq || !pl->debiasing_term || !pl->weight_out || !pl->bias_out || !pl->stddev_out)
-        return fail(GMPE_ERR_INVALID_ARG, "gmpe_ppo_loss_popart: weight, bias, stddev, mean, mean_sq, debiasing_term, weight_out, bias_out and stddev_out are required");
-    if (!pl->out || !pl->grad_logits || !pl->grad_features || !pl->grad_weight || !pl->grad_bias)
-        return fail(GMPE_ERR_INVALID_ARG, "gmpe_ppo_loss_popart: out, grad_logits, grad_features, grad_weight and grad_bias are required");
-    if (!(pl->clip_param >= 0.0) || !(pl->huber_delta >= 0.0) || !(pl->beta >= 0.0 && pl->beta <= 1.0) || !(pl->epsilon > 0.0) || pl->entropy_coef != pl->entropy_coef)
-        return fail(GMPE_ERR_INVALID_ARG, "gmpe_ppo_loss_popart: need clip_param >= 0, huber_delta >= 0, 0 <= beta <= 1, epsilon > 0 and a number for entropy_coef");
+        missing = "logits, critic_features, actions, old_action_log_probs, adv_targ, value_preds, returns and active_masks are required";
+    else if (!pl->weight || !pl->bias || !pl->stddev || !pl->mean || !pl->mean_sq || !pl->debiasing_term || !pl->weight_out || !pl->bias_out || !pl->stddev_out)
+        missing = "weight, bias, stddev, mean, mean_sq, debiasing_term, weight_out, bias_out and stddev_out are required";
+    else if (!pl->out || !pl->grad_logits || !pl->grad_features || !pl->grad_weight || !pl->grad_bias)
+        missing = "out, grad_logits, grad_features, grad_weight and grad_bias are required";
+    if (int rc = check_loss_plan("gmpe_ppo_loss_popart", pl, bad_hidden ? dims.c_str() : nullptr, missing)) return rc;
     const uintptr_t a4 = (uintptr_t)pl->logits | (uintptr_t)pl->critic_features | (uintptr_t)pl->available_actions | (uintptr_t)pl->old_action_log_probs |
                          (uintptr_t)pl->adv_targ | (uintptr_t)pl->value_preds | (uintptr_t)pl->returns | (uintptr_t)pl->active_masks | (uintptr_t)pl->weight |
                          (uintptr_t)pl->bias | (uintptr_t)pl->stddev | (uintptr_t)pl->mean | (uintptr_t)pl->mean_sq | (uintptr_t)pl->debiasing_term |
@@ -339,24 +291,22 @@ int gmpe_ppo_loss_popart(int device, const gmpe_popart_loss_plan* pl, void* stre
         return fail(GMPE_ERR_INVALID_ARG, "gmpe_ppo_loss_popart: needs an 8-byte aligned workspace of gmpe_ppo_loss_popart_workspace_bytes(rows, hidden)");
     const int64_t nt = num_tiles(pl->rows);
     if (nt > 0x7fffffffLL) return fail(GMPE_ERR_INVALID_ARG, "gmpe_ppo_loss_popart: too many rows for one launch");
-    LCHK(hipSetDevice(device));
+    GMPE_HIP_CHECK(hipSetDevice(device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     PopArgs a;
-    a.B = pl->rows; a.K = pl->n_actions; a.S = pl->n_actions | 1; a.flags = pl->flags;
-    a.magic = (uint32_t)(0x100000000ULL / (uint64_t)(pl->n_actions > 1 ? pl->n_actions : 2)) + 1u;
+    a.g = geometry(pl->rows, pl->n_actions);
+    a.pol.flags = pl->flags;
     a.H = pl->hidden; a.NQ = (pl->hidden + 3) / 4;
     a.lsh = 0;
     while ((1 << a.lsh) < a.NQ && a.lsh < 6) ++a.lsh;
     a.L = 1 << a.lsh;
     a.vecf = pl->hidden % 4 == 0 && !(((uintptr_t)pl->critic_features | (uintptr_t)pl->grad_features) & 15);
-    a.logits = pl->logits; a.avail = pl->available_actions; a.feat = pl->critic_features; a.W = pl->weight; a.bias = pl->bias; a.stddev = pl->stddev;
-    a.old_lp = pl->old_action_log_probs; a.adv = pl->adv_targ; a.vp = pl->value_preds; a.ret = pl->returns; a.am = pl->active_masks; a.actions = pl->actions;
+    a.pol.logits = pl->logits; a.pol.avail = pl->available_actions; a.feat = pl->critic_features; a.W = pl->weight; a.bias = pl->bias; a.stddev = pl->stddev;
+    a.pol.old_lp = pl->old_action_log_probs; a.pol.adv = pl->adv_targ; a.vp = pl->value_preds; a.ret = pl->returns; a.pol.am = pl->active_masks;
+    a.pol.actions = pl->actions;
     a.grad_logits = pl->grad_logits; a.grad_feat = pl->grad_features; a.grad_W = pl->grad_weight; a.grad_b = pl->grad_bias; a.values_out = pl->values_out;
-    a.out_lp = pl->action_log_probs; a.out_ratio = pl->imp_weights; a.W_out = pl->weight_out; a.bias_out = pl->bias_out; a.stddev_out = pl->stddev_out;
-    // a Python float meets a float32 tensor as float32(value): 1.0 - clip_param, 1.0 - beta and huber_delta / 2 are formed in double first
-    a.lo = (float)(1.0 - pl->clip_param); a.hi = (float)(1.0 + pl->clip_param); a.clip = (float)pl->clip_param;
-    a.delta = (float)pl->huber_delta; a.half_delta = (float)(pl->huber_delta / 2.0); a.ent_coef = (float)pl->entropy_coef;
-    a.wbeta = (float)pl->beta; a.w1beta = (float)(1.0 - pl->beta); a.eps = (float)pl->epsilon;
+    a.pol.out_lp = pl->action_log_probs; a.pol.out_ratio = pl->imp_weights; a.W_out = pl->weight_out; a.bias_out = pl->bias_out; a.stddev_out = pl->stddev_out;
+    hyper_parameters(pl, a);
     a.mean = pl->mean; a.mean_sq = pl->mean_sq; a.db = pl->debiasing_term;
     a.stat_part = static_cast<double*>(pl->workspace);
     a.row_part = a.stat_part + nt * NSTAT;
@@ -365,27 +315,22 @@ int gmpe_ppo_loss_popart(int device, const gmpe_popart_loss_plan* pl, void* stre
     a.out = pl->out;
     const dim3 grid((unsigned)nt), block(TILE), one(1);
     hipLaunchKernelGGL(k_pop_stats, grid, block, 0, st, a);
-    LCHK(hipGetLastError());
+    GMPE_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(k_pop_prepare, one, block, 0, st, a, nt);
-    LCHK(hipGetLastError());
+    GMPE_HIP_CHECK(hipGetLastError());
     const bool vec = !(((uintptr_t)pl->logits | (uintptr_t)pl->available_actions | (uintptr_t)pl->grad_logits) & 15);   // tiles start at multiples of 1 KiB
-    const size_t lds = (size_t)((TILE * a.S + 3) & ~3) * sizeof(float) + (size_t)4 * a.L * MAXQ * sizeof(double);
+    const size_t lds = (size_t)((TILE * a.g.S + 3) & ~3) * sizeof(float) + (size_t)4 * a.L * MAXQ * sizeof(double);
     void (*fn)(PopArgs) = vec ? (pl->actions_int64 ? k_pop_rows<true, true> : k_pop_rows<true, false>)
                               : (pl->actions_int64 ? k_pop_rows<false, true> : k_pop_rows<false, false>);
-    if (lds > 48 * 1024) {                                                    // large K or H; once per device and instantiation, at the largest size there is
-        static std::atomic<bool> raised[64][4];
-        const int v = (vec ? 2 : 0) | (pl->actions_int64 ? 1 : 0);
-        if (device < 0 || device >= 64 || !raised[device][v].load()) {
-            LCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)(((TILE * (GMPE_PPO_MAX_ACTIONS | 1) + 3) & ~3) * sizeof(float) + 4 * 64 * MAXQ * sizeof(double))));
-            if (device >= 0 && device < 64) raised[device][v].store(true);
-        }
-    }
+    if (lds > 48 * 1024)                                                      // large K or H
+        if (int rc = raise_dynamic_lds_once(reinterpret_cast<const void*>(fn), device, (vec ? 2 : 0) | (pl->actions_int64 ? 1 : 0),
+                                            ((TILE * (GMPE_PPO_MAX_ACTIONS | 1) + 3) & ~3) * sizeof(float) + 4 * 64 * MAXQ * sizeof(double)))
+            return rc;
     hipLaunchKernelGGL(fn, grid, block, lds, st, a);
-    LCHK(hipGetLastError());
+    GMPE_HIP_CHECK(hipGetLastError());
     const dim3 fin(1 + (unsigned)((pl->hidden + FIN_COLS - 1) / FIN_COLS));
     hipLaunchKernelGGL(k_pop_finish, fin, block, 0, st, a, nt);
-    LCHK(hipGetLastError());
+    GMPE_HIP_CHECK(hipGetLastError());
     return GMPE_OK;
 }
 

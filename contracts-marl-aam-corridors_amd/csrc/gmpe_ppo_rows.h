@@ -1,17 +1,20 @@
-// gmpe_ppo_rows.h — the per-row arithmetic and the fixed-order reductions of the PPO loss kernels, shared by gmpe_ppo_loss.hip (values in) and
-// gmpe_ppo_popart.hip (critic features in, PopArt): one text, so the two entry points cannot drift apart. Everything here is float32 per row in the
-// reference's operation order (no contraction) and double across rows; the derivations of the gradients are at the head of gmpe_ppo_loss.hip.
+// gmpe_ppo_rows.h — the per-row arithmetic, the tile machinery and the fixed-order reductions of the row kernels over a policy head's logits, shared by
+// gmpe_ppo_loss.hip (values in), gmpe_ppo_popart.hip (critic features in, PopArt) and gmpe_act.hip (the rollout's action and log-prob): one text, so the
+// three entry points cannot drift apart — the log-prob the act kernel stores is the one the loss kernels recompute because both run the masked
+// categorical below. Everything here is float32 per row in the reference's operation order (no contraction) and double across rows; the derivations of
+// the gradients are at the head of gmpe_ppo_loss.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <math.h>
 #include <stdint.h>
 
+#include "gmpe_host.h"            // TILE, Geom
+
 #pragma clang fp contract(off)
 
 namespace gmpe_ppo {
 
-constexpr int TILE = 256;         // rows per workgroup = lanes per workgroup: one lane per row
 constexpr int NW = TILE / 64;
 constexpr int NSTAT = 3;          // sum returns, sum returns^2, sum active_masks
 constexpr float FMIN = -FLT_MAX;  // torch.finfo(torch.float32).min
@@ -137,6 +140,66 @@ __device__ __forceinline__ uint64_t avail_bits(const float* row, int K) {
     return avail;
 }
 
+// this lane's place in its workgroup's tile
+struct Tile {
+    int64_t row0, r, g0;           // the tile's first row, the lane's row; the tile's first float in a [B, K] array
+    int rows, n;                   // rows and floats in the tile (the last tile may be short)
+    bool live;                     // the lane has a row
+    float* row;                    // the row in LDS
+};
+
+__device__ __forceinline__ Tile tile_of(const Geom& g, float* sh) {
+    Tile t;
+    t.row0 = (int64_t)blockIdx.x * TILE; t.r = t.row0 + threadIdx.x; t.g0 = t.row0 * g.K;
+    t.rows = g.B - t.row0 < TILE ? (int)(g.B - t.row0) : TILE; t.n = t.rows * g.K;
+    t.live = (int)threadIdx.x < t.rows; t.row = sh + threadIdx.x * g.S;
+    return t;
+}
+
+// The head of a row kernel: the tile of available_actions (when given) passes through the LDS rows and leaves this lane's availability bits, else `avail`
+// stays what the caller gave; then the tile of logits, behind a barrier.
+template <bool VEC>
+__device__ __forceinline__ uint64_t tile_in(const Geom& g, const Tile& t, const float* avail_g, const float* logits, float* sh, uint64_t avail) {
+    if (avail_g) {
+        tile_copy<VEC, true>(const_cast<float*>(avail_g) + t.g0, sh, t.n, g.K, g.S, g.magic);
+        __syncthreads();
+        if (t.live) avail = avail_bits(t.row, g.K);                                 // x[available_actions == 0] = finfo.min
+        __syncthreads();
+    }
+    tile_copy<VEC, true>(const_cast<float*>(logits) + t.g0, sh, t.n, g.K, g.S, g.magic);
+    __syncthreads();
+    return avail;
+}
+
+// ---- the masked categorical (torch: logits - logsumexp, probs = softmax of that), in the three steps its users share
+__device__ __forceinline__ float masked_logit(const float* row, uint64_t avail, int j) { return (avail >> j & 1) ? row[j] : FMIN; }
+
+__device__ __forceinline__ float masked_max(const float* row, int K, uint64_t avail) {
+    float m = -INFINITY;
+    for (int j = 0; j < K; ++j) m = fmaxf(m, masked_logit(row, avail, j));
+    return m;
+}
+
+__device__ __forceinline__ float exp_below(float l, float ml) { return expf(__fsub_rn(l, ml)); }
+
+// m = masked_max of the row, which still holds the logits. On return the row holds l = x - logsumexp(x), Categorical's normalised logits; *ml = max_j l_j
+// (rounding is monotone) and *s2 = sum_j exp(l_j - ml): torch renormalises the normalised logits, probs = softmax(l).
+__device__ __forceinline__ void normalise_row(float* row, int K, uint64_t avail, float m, float* ml_out, float* s2_out) {
+    float s = 0.0f;
+    for (int j = 0; j < K; ++j) s = __fadd_rn(s, expf(__fsub_rn(masked_logit(row, avail, j), m)));
+    const float lse = __fadd_rn(logf(s), m), ml = __fsub_rn(m, lse);
+    float s2 = 0.0f;
+    for (int j = 0; j < K; ++j) {
+        const float l = __fsub_rn(masked_logit(row, avail, j), lse);
+        row[j] = l;
+        s2 = __fadd_rn(s2, exp_below(l, ml));
+    }
+    *ml_out = ml; *s2_out = s2;
+}
+
+// p_j of a normalised row
+__device__ __forceinline__ float prob(float l, float ml, float s2) { return __fdiv_rn(exp_below(l, ml), s2); }
+
 // what the policy side of a row needs besides its logits
 struct PolicyRow {
     uint64_t avail;                // bit j: action j is available
@@ -150,25 +213,15 @@ struct PolicyRow {
 // gradients on return. acc0 = -min(surr1, surr2) * w, acc1 = H * w (the terms of the two means), la the action's log-prob, ratio the importance weight.
 __device__ __forceinline__ void policy_row(float* row, int K, const PolicyRow& q, float* la_out, float* ratio_out, double* acc0, double* acc1) {
     const uint64_t avail = q.avail;
-    // ---- the masked categorical (torch: logits - logsumexp, probs = softmax of that)
-    float m = -INFINITY;
-    for (int j = 0; j < K; ++j) m = fmaxf(m, (avail >> j & 1) ? row[j] : FMIN);
-    float s = 0.0f;
-    for (int j = 0; j < K; ++j) s = __fadd_rn(s, expf(__fsub_rn((avail >> j & 1) ? row[j] : FMIN, m)));
-    const float lse = __fadd_rn(logf(s), m), ml = __fsub_rn(m, lse);          // ml = max_j l_j: rounding is monotone
+    float ml, s2;
+    normalise_row(row, K, avail, masked_max(row, K, avail), &ml, &s2);
     const int64_t ai = q.action;
     const int a = ai < 0 ? 0 : (ai >= K ? K - 1 : (int)ai);                   // out of range is the caller's error (torch raises): stay inside the row
-    float s2 = 0.0f;
-    for (int j = 0; j < K; ++j) {                                             // the row now holds l = x - logsumexp(x): Categorical's normalised logits
-        const float l = __fsub_rn((avail >> j & 1) ? row[j] : FMIN, lse);
-        row[j] = l;
-        s2 = __fadd_rn(s2, expf(__fsub_rn(l, ml)));                           // probs = softmax(l): torch renormalises the normalised logits
-    }
     const float la = row[a];
     float t = 0.0f;
     for (int j = 0; j < K; ++j) {
         const float l = row[j];
-        t = __fadd_rn(t, __fmul_rn(fmaxf(l, FMIN), __fdiv_rn(expf(__fsub_rn(l, ml)), s2)));      // clamp(l, min=finfo.min) * p
+        t = __fadd_rn(t, __fmul_rn(fmaxf(l, FMIN), prob(l, ml, s2)));         // clamp(l, min=finfo.min) * p
     }
     const float H = -t;
     // ---- ratio, clip, surrogates (graph_mappo.py:176-197)
@@ -185,11 +238,70 @@ __device__ __forceinline__ void policy_row(float* row, int K, const PolicyRow& q
     for (int j = 0; j < K; ++j) {
         float g = 0.0f;
         if (avail >> j & 1) {
-            const float l = row[j], pj = __fdiv_rn(expf(__fsub_rn(l, ml)), s2);
+            const float l = row[j], pj = prob(l, ml, s2);
             g = __fadd_rn(__fmul_rn(ca, __fsub_rn(j == a ? 1.0f : 0.0f, pj)), __fmul_rn(ce, __fmul_rn(pj, __fadd_rn(l, H))));
         }
         row[j] = g;
     }
+}
+
+// what the policy side of the loss kernels' row pass reads and writes (both entry points embed it in their arguments)
+struct PolicyArgs {
+    const float *logits, *avail, *old_lp, *adv, *am;
+    const void* actions;
+    float *out_lp, *out_ratio;     // optional
+    float lo, hi, ent_coef;        // 1 - clip, 1 + clip, entropy_coef
+    int flags;                     // GMPE_PPO_*
+};
+
+// The policy side of row r: its weights from active_masks, policy_row over the row's logits in LDS (its gradients on return), the terms of the two means
+// and of ratio_mean into acc[0], acc[1], acc[3], the two optional stores. Returns wv, the row's weight in the value mean. Dp: the policy denominator.
+template <bool ACT64>
+__device__ __forceinline__ float policy_side(const PolicyArgs& p, float* row, int K, int64_t r, uint64_t avail, double Dp, double* acc) {
+    const float am = p.am[r];
+    const float wp = (p.flags & GMPE_PPO_POLICY_ACTIVE_MASKS) ? am : 1.0f, wv = (p.flags & GMPE_PPO_VALUE_ACTIVE_MASKS) ? am : 1.0f;
+    PolicyRow q;
+    q.avail = avail;
+    q.action = ACT64 ? static_cast<const int64_t*>(p.actions)[r] : (int64_t)static_cast<const float*>(p.actions)[r];   // .long() truncates
+    q.adv = p.adv[r]; q.old_lp = p.old_lp[r]; q.wp = wp; q.Dp = (float)Dp; q.lo = p.lo; q.hi = p.hi; q.ent_coef = p.ent_coef;
+    float la, ratio;
+    policy_row(row, K, q, &la, &ratio, &acc[0], &acc[1]);
+    acc[3] = (double)ratio;
+    if (p.out_lp) p.out_lp[r] = la;
+    if (p.out_ratio) p.out_ratio[r] = ratio;
+    return wv;
+}
+
+// hdr[0], hdr[1]: the denominators of the policy means and of the value mean, from the merged sum of active_masks
+__device__ __forceinline__ void denominators(double* hdr, int flags, int64_t B, double msum) {
+    hdr[0] = (flags & GMPE_PPO_POLICY_ACTIVE_MASKS) ? msum : (double)B;
+    hdr[1] = (flags & GMPE_PPO_VALUE_ACTIVE_MASKS) ? msum : (double)B;
+}
+
+// The running statistics of ValueNorm.update (valuenorm.py:56-73) and PopArt.update (popart.py:62-77), in place, float32, over all B rows (no mask):
+// x.mul_(beta).add_(batch * (1.0 - beta)) for the mean and the mean of squares, debiasing_term.mul_(beta).add_(1.0 * (1.0 - beta)).
+// sums: the merged double sums of returns and returns^2.
+struct Running { float mean, mean_sq, debias; };
+__device__ __forceinline__ Running running_update(float* mean, float* mean_sq, float* debias, const double* sums, int64_t B, float beta, float one_minus_beta) {
+    const float bm = (float)(sums[0] / (double)B), bsq = (float)(sums[1] / (double)B);      // input_vector.mean(0), (input_vector ** 2).mean(0)
+    Running u;
+    u.mean = __fadd_rn(__fmul_rn(*mean, beta), __fmul_rn(bm, one_minus_beta));
+    u.mean_sq = __fadd_rn(__fmul_rn(*mean_sq, beta), __fmul_rn(bsq, one_minus_beta));
+    u.debias = __fadd_rn(__fmul_rn(*debias, beta), one_minus_beta);
+    *mean = u.mean; *mean_sq = u.mean_sq; *debias = u.debias;
+    return u;
+}
+
+// the seven scalars of a loss call from the merged row sums s[0..3] (the acc[] of the row pass)
+__device__ __forceinline__ void write_scalars(double* out, const double* s, double Dp, double Dv, float ent_coef, int64_t B) {
+    const double pol = s[0] / Dp, ent = s[1] / Dp;
+    out[GMPE_PPO_OUT_POLICY_LOSS] = pol;
+    out[GMPE_PPO_OUT_DIST_ENTROPY] = ent;
+    out[GMPE_PPO_OUT_ACTOR_LOSS] = pol - (double)ent_coef * ent;
+    out[GMPE_PPO_OUT_VALUE_LOSS] = s[2] / Dv;
+    out[GMPE_PPO_OUT_RATIO_MEAN] = s[3] / (double)B;
+    out[GMPE_PPO_OUT_DENOM_POLICY] = Dp;
+    out[GMPE_PPO_OUT_DENOM_VALUE] = Dv;
 }
 
 __device__ __forceinline__ float value_term(float e, bool huber, float delta, float half_delta, float* dfde) {

@@ -18,13 +18,9 @@
 
 #include <string>
 
-#include "../../include/gmpe.h"
+#include "gmpe_host.h"          // include/gmpe.h, the error text, GMPE_HIP_CHECK
 
 #pragma clang fp contract(off)
-
-namespace gmpe {
-int report_error(int code, const std::string& m);   // gmpe_step.hip: the library's gmpe_last_error text
-}
 
 namespace {
 
@@ -222,8 +218,6 @@ int fail(int code, const std::string& m) { return gmpe::report_error(code, m); }
 
 }  // namespace
 
-#define RCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(GMPE_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
-
 extern "C" {
 
 int gmpe_returns_workspace_bytes(int64_t lanes, size_t* bytes_out) {
@@ -252,7 +246,7 @@ int gmpe_compute_returns(int device, const gmpe_returns_plan* pl, void* stream) 
     if (pl->normalized && (!pl->active_masks || !pl->workspace || pl->workspace_bytes < need || ((uintptr_t)pl->workspace & 7)))
         return fail(GMPE_ERR_INVALID_ARG, "gmpe_compute_returns: normalized needs active_masks and an 8-byte aligned workspace of gmpe_returns_workspace_bytes(lanes)");
     if (nparts > 0x7fffffffLL) return fail(GMPE_ERR_INVALID_ARG, "gmpe_compute_returns: too many lanes for one launch");
-    RCHK(hipSetDevice(device));
+    GMPE_HIP_CHECK(hipSetDevice(device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     RetArgs a;
     a.T = pl->num_steps; a.lanes = pl->lanes; a.stride = pl->stride;
@@ -279,14 +273,14 @@ int gmpe_compute_returns(int device, const gmpe_returns_plan* pl, void* stream) 
         default: hipLaunchKernelGGL((k_returns<true, true, true>), grid, block, 0, st, a); break;
         }
     }
-    RCHK(hipGetLastError());
+    GMPE_HIP_CHECK(hipGetLastError());
     if (pl->normalized) {
         float* stats = reinterpret_cast<float*>(static_cast<Stat*>(pl->workspace) + nparts);
         hipLaunchKernelGGL(k_adv_stats, dim3(1), dim3(STAT_BLOCK), 0, st, a.part, nparts, stats);
-        RCHK(hipGetLastError());
+        GMPE_HIP_CHECK(hipGetLastError());
         hipLaunchKernelGGL(k_adv_normalize, dim3((unsigned)((pl->lanes + NORM_BLOCK - 1) / NORM_BLOCK)), dim3(NORM_BLOCK), 0, st, a.adv, pl->normalized, stats,
                            a.T, pl->lanes, pl->stride);
-        RCHK(hipGetLastError());
+        GMPE_HIP_CHECK(hipGetLastError());
     }
     return GMPE_OK;
 }
@@ -302,11 +296,11 @@ int gmpe_available_actions_from_dones(int device, const gmpe_avail_plan* pl, voi
         return fail(GMPE_ERR_INVALID_ARG, "gmpe_available_actions_from_dones: strides smaller than a slot");
     const int steps = pl->count < pl->num_positions ? pl->count : pl->num_positions;   // positions repeat after T steps: each is written once
     if (steps == 0) return GMPE_OK;
-    RCHK(hipSetDevice(device));
+    GMPE_HIP_CHECK(hipSetDevice(device));
     hipLaunchKernelGGL(k_stop_actions, dim3((unsigned)((per_pos + AVAIL_BLOCK - 1) / AVAIL_BLOCK), (unsigned)steps), dim3(AVAIL_BLOCK), 0,
                        static_cast<hipStream_t>(stream), pl->dones, pl->available_actions, (uint32_t)per_pos, (uint32_t)pl->n_actions,
                        pl->num_positions, pl->first, pl->stride_dones, pl->stride_out);
-    RCHK(hipGetLastError());
+    GMPE_HIP_CHECK(hipGetLastError());
     return GMPE_OK;
 }
 

@@ -110,6 +110,71 @@ def _column(name, t, rows, dev, dtypes=(torch.float32,)):
     return t.detach().contiguous()
 
 
+def _ordinal(dev):                                     # what the C entry points take
+    return dev.index if dev.index is not None else torch.cuda.current_device()
+
+
+def _logits_shape(logits):
+    """(device, rows, n_actions) of a policy head's logits [rows, n_actions], checked (sample_actions checks its logits here too)."""
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or not logits.is_floating_point():
+        raise ValueError("logits must be a floating-point tensor [rows, n_actions]")
+    rows, K = int(logits.shape[0]), int(logits.shape[1])
+    if rows < 1 or K < 1:
+        raise ValueError("logits must have at least one row and one action")
+    if K > _lib.PPO_MAX_ACTIONS:
+        raise ValueError("n_actions = %d is above the supported %d" % (K, _lib.PPO_MAX_ACTIONS))
+    return logits.device, rows, K
+
+
+def _widened(t):
+    return t.float() if t.dtype in (torch.float16, torch.bfloat16) else t
+
+
+def _available(avail, rows, K, dev, contiguous=False):
+    # contiguous=True refuses a strided one (sample_actions), else it is copied
+    if not isinstance(avail, torch.Tensor) or avail.dtype != torch.float32 or tuple(avail.shape) != (rows, K):
+        raise ValueError("available_actions must be a float32 tensor of shape (%d, %d) or None" % (rows, K))
+    if contiguous and not avail.is_contiguous():
+        raise ValueError("available_actions must be contiguous")
+    if avail.device != dev:
+        raise ValueError("available_actions must be on %s (the device of logits)" % dev)
+    return avail.detach().contiguous()
+
+
+def _minibatch(logits, other, other_name, sample, rows, K, dev):
+    """What both entry points do with their inputs once their shapes are checked: logits and `other` (values or critic_features) widened to float32, the
+    sample's five float32 columns, its actions and its available_actions (or None), each checked against logits."""
+    logits, other = _widened(logits), _widened(other)
+    if logits.dtype != torch.float32 or other.dtype != torch.float32:
+        raise ValueError("logits and %s must be float32 (or float16 / bfloat16, widened here)" % other_name)
+    f = _fields(sample)
+    cols = {k: _column(k, f[k], rows, dev) for k in ("value_preds", "returns", "active_masks", "old_action_log_probs", "adv_targ")}
+    actions = _column("actions", f["actions"], rows, dev, (torch.float32, torch.int64))
+    avail = f["available_actions"]
+    if avail is not None:
+        avail = _available(avail, rows, K, dev)
+    return logits, other, cols, actions, avail
+
+
+def _bind_minibatch(plan, rows, K, flags, clip, delta, ent, cols, actions, avail):
+    # the fields gmpe_ppo_loss_plan and gmpe_popart_loss_plan name alike
+    plan.rows, plan.n_actions, plan.flags, plan.actions_int64 = rows, K, flags, int(actions.dtype == torch.int64)
+    plan.clip_param, plan.huber_delta, plan.entropy_coef = clip, delta, ent
+    plan.actions = actions.data_ptr()
+    plan.available_actions = None if avail is None else avail.data_ptr()
+    for k, t in cols.items():
+        setattr(plan, k, t.data_ptr())
+
+
+def _workspace(nbytes, workspace, dev):
+    if workspace is None:
+        return torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    if not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous() or \
+            workspace.numel() < nbytes:
+        raise ValueError("workspace must be a contiguous uint8 tensor of at least %d bytes on %s" % (nbytes, dev))
+    return workspace
+
+
 class _Attach(torch.autograd.Function):
     """A scalar the kernel computed from `x`, with its gradient d scalar / d x already known: backward multiplies it by the incoming scalar. The two
     losses are two such nodes, so each is backpropagated on its own, as ppo_update does."""
@@ -125,23 +190,6 @@ class _Attach(torch.autograd.Function):
         return grad * g, None, None
 
 
-def _launch(logits, values, plan, keep):
-    """One call of gmpe_ppo_loss on the current stream: (scalars f32 [PPO_NUM_OUT], grad_logits, grad_values, action_log_probs, imp_weights)."""
-    dev = logits.device
-    rows = logits.shape[0]
-    lg, vl = logits.detach().contiguous(), values.detach().contiguous()
-    out = torch.empty((_lib.PPO_NUM_OUT,), dtype=torch.float64, device=dev)
-    grad_logits, grad_values = torch.empty_like(lg), torch.empty_like(vl)
-    logp, ratio = (torch.empty((rows, 1), dtype=torch.float32, device=dev) for _ in range(2))
-    plan.logits, plan.values, plan.out = lg.data_ptr(), vl.data_ptr(), out.data_ptr()
-    plan.grad_logits, plan.grad_values = grad_logits.data_ptr(), grad_values.data_ptr()
-    plan.action_log_probs, plan.imp_weights = logp.data_ptr(), ratio.data_ptr()
-    _lib.check(_lib.load().gmpe_ppo_loss(dev.index if dev.index is not None else torch.cuda.current_device(), C.byref(plan), _stream_of(dev)),
-               "gmpe_ppo_loss")
-    del keep                                           # the inputs the plan points to lived until the launches were enqueued on this stream
-    return out.to(torch.float32), grad_logits, grad_values, logp, ratio      # doubles are written as doubles; rounded once here
-
-
 def ppo_losses(logits, values, sample_or_fields, args, value_normalizer=None, workspace=None):
     """actor_loss (policy_loss - entropy_coef * dist_entropy) and value_loss of GR_MAPPO.ppo_update for one minibatch, differentiable with respect to
     `logits` [rows, n_actions] (the policy head's linear output, before masking) and `values` [rows, 1]; policy_loss, dist_entropy, ratio_mean
@@ -153,34 +201,12 @@ def ppo_losses(logits, values, sample_or_fields, args, value_normalizer=None, wo
     f16 / bf16 logits and values are widened to float32 first. A zero sum of active_masks gives NaN losses, like the reference's 0 / 0; nothing here
     waits for the device. workspace: an optional uint8 device tensor of workspace_bytes(rows) to reuse between calls."""
     flags, clip, delta, ent = _flags(args)
-    if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or not logits.is_floating_point():
-        raise ValueError("logits must be a floating-point tensor [rows, n_actions]")
-    dev = logits.device
-    rows, K = int(logits.shape[0]), int(logits.shape[1])
-    if rows < 1 or K < 1:
-        raise ValueError("logits must have at least one row and one action")
-    if K > _lib.PPO_MAX_ACTIONS:
-        raise ValueError("n_actions = %d is above the supported %d" % (K, _lib.PPO_MAX_ACTIONS))
+    dev, rows, K = _logits_shape(logits)
     if not isinstance(values, torch.Tensor) or not values.is_floating_point() or tuple(values.shape) not in ((rows, 1), (rows,)):
         raise ValueError("values must be a floating-point tensor of shape (%d, 1)" % rows)
     if values.device != dev:
         raise ValueError("values must be on %s (the device of logits)" % dev)
-    if logits.dtype in (torch.float16, torch.bfloat16):
-        logits = logits.float()
-    if values.dtype in (torch.float16, torch.bfloat16):
-        values = values.float()
-    if logits.dtype != torch.float32 or values.dtype != torch.float32:
-        raise ValueError("logits and values must be float32 (or float16 / bfloat16, widened here)")
-    f = _fields(sample_or_fields)
-    cols = {k: _column(k, f[k], rows, dev) for k in ("value_preds", "returns", "active_masks", "old_action_log_probs", "adv_targ")}
-    actions = _column("actions", f["actions"], rows, dev, (torch.float32, torch.int64))
-    avail = f["available_actions"]
-    if avail is not None:
-        if not isinstance(avail, torch.Tensor) or avail.dtype != torch.float32 or tuple(avail.shape) != (rows, K):
-            raise ValueError("available_actions must be a float32 tensor of shape (%d, %d) or None" % (rows, K))
-        if avail.device != dev:
-            raise ValueError("available_actions must be on %s (the device of logits)" % dev)
-        avail = avail.detach().contiguous()
+    logits, values, cols, actions, avail = _minibatch(logits, values, "values", sample_or_fields, rows, K, dev)
     state = None
     plan = _lib.GmpePpoLossPlan()
     if flags & _lib.PPO_VALUENORM:
@@ -189,22 +215,20 @@ def ppo_losses(logits, values, sample_or_fields, args, value_normalizer=None, wo
     else:
         plan.beta, plan.epsilon = 0.99999, 1e-5
     _need_cuda(dev)
-    nbytes = workspace_bytes(rows)
-    if workspace is None:
-        workspace = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-    elif not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous() or \
-            workspace.numel() < nbytes:
-        raise ValueError("workspace must be a contiguous uint8 tensor of at least %d bytes on %s" % (nbytes, dev))
-    plan.rows, plan.n_actions, plan.flags, plan.actions_int64 = rows, K, flags, int(actions.dtype == torch.int64)
-    plan.clip_param, plan.huber_delta, plan.entropy_coef = clip, delta, ent
-    plan.actions = actions.data_ptr()
-    plan.available_actions = None if avail is None else avail.data_ptr()
-    for k, t in cols.items():
-        setattr(plan, k, t.data_ptr())
+    workspace = _workspace(workspace_bytes(rows), workspace, dev)
+    _bind_minibatch(plan, rows, K, flags, clip, delta, ent, cols, actions, avail)
     plan.workspace, plan.workspace_bytes = workspace.data_ptr(), workspace.numel()
-    keep = (cols, actions, avail, state, workspace)
     values2 = values if values.dim() == 2 else values.reshape(rows, 1)
-    s, grad_logits, grad_values, logp, ratio = _launch(logits, values2, plan, keep)
+    lg, vl = logits.detach().contiguous(), values2.detach().contiguous()
+    out = torch.empty((_lib.PPO_NUM_OUT,), dtype=torch.float64, device=dev)
+    grad_logits, grad_values = torch.empty_like(lg), torch.empty_like(vl)
+    logp, ratio = (torch.empty((rows, 1), dtype=torch.float32, device=dev) for _ in range(2))
+    plan.logits, plan.values, plan.out = lg.data_ptr(), vl.data_ptr(), out.data_ptr()
+    plan.grad_logits, plan.grad_values = grad_logits.data_ptr(), grad_values.data_ptr()
+    plan.action_log_probs, plan.imp_weights = logp.data_ptr(), ratio.data_ptr()
+    # the inputs the plan points to (cols, actions, avail, state, workspace, lg, vl) live until the launches are enqueued on this stream
+    _lib.check(_lib.load().gmpe_ppo_loss(_ordinal(dev), C.byref(plan), _stream_of(dev)), "gmpe_ppo_loss")
+    s = out.to(torch.float32)                          # doubles are written as doubles; rounded once here
     o = _lib.PPO_OUT.index
     return PPOLosses(_Attach.apply(logits, s[o("actor_loss")], grad_logits), _Attach.apply(values2, s[o("value_loss")], grad_values),
                      s[o("policy_loss")], s[o("dist_entropy")], s[o("ratio_mean")], logp, ratio)
@@ -279,14 +303,7 @@ def ppo_losses_popart(logits, critic_features, sample_or_fields, args, popart, i
     flags, clip, delta, ent = _flags(args, popart=True)
     if install not in ("replace", "in_place"):
         raise ValueError("install must be 'replace' (the reference: new Parameters) or 'in_place', not %r" % (install,))
-    if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or not logits.is_floating_point():
-        raise ValueError("logits must be a floating-point tensor [rows, n_actions]")
-    dev = logits.device
-    rows, K = int(logits.shape[0]), int(logits.shape[1])
-    if rows < 1 or K < 1:
-        raise ValueError("logits must have at least one row and one action")
-    if K > _lib.PPO_MAX_ACTIONS:
-        raise ValueError("n_actions = %d is above the supported %d" % (K, _lib.PPO_MAX_ACTIONS))
+    dev, rows, K = _logits_shape(logits)
     if not isinstance(critic_features, torch.Tensor) or not critic_features.is_floating_point() or critic_features.dim() != 2 or \
             critic_features.shape[0] != rows or critic_features.shape[1] < 1:
         raise ValueError("critic_features must be a floating-point tensor of shape (%d, hidden)" % rows)
@@ -295,30 +312,10 @@ def ppo_losses_popart(logits, critic_features, sample_or_fields, args, popart, i
         raise ValueError("hidden = %d is above the supported %d" % (H, _lib.POPART_MAX_HIDDEN))
     if critic_features.device != dev:
         raise ValueError("critic_features must be on %s (the device of logits)" % dev)
-    if logits.dtype in (torch.float16, torch.bfloat16):
-        logits = logits.float()
-    if critic_features.dtype in (torch.float16, torch.bfloat16):
-        critic_features = critic_features.float()
-    if logits.dtype != torch.float32 or critic_features.dtype != torch.float32:
-        raise ValueError("logits and critic_features must be float32 (or float16 / bfloat16, widened here)")
-    f = _fields(sample_or_fields)
-    cols = {k: _column(k, f[k], rows, dev) for k in ("value_preds", "returns", "active_masks", "old_action_log_probs", "adv_targ")}
-    actions = _column("actions", f["actions"], rows, dev, (torch.float32, torch.int64))
-    avail = f["available_actions"]
-    if avail is not None:
-        if not isinstance(avail, torch.Tensor) or avail.dtype != torch.float32 or tuple(avail.shape) != (rows, K):
-            raise ValueError("available_actions must be a float32 tensor of shape (%d, %d) or None" % (rows, K))
-        if avail.device != dev:
-            raise ValueError("available_actions must be on %s (the device of logits)" % dev)
-        avail = avail.detach().contiguous()
+    logits, critic_features, cols, actions, avail = _minibatch(logits, critic_features, "critic_features", sample_or_fields, rows, K, dev)
     (w_obj, b_obj, s_obj, mean, mean_sq, debias), beta, epsilon = _popart_state(popart, H, dev)
     _need_cuda(dev)
-    nbytes = popart_workspace_bytes(rows, H)
-    if workspace is None:
-        workspace = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-    elif not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous() or \
-            workspace.numel() < nbytes:
-        raise ValueError("workspace must be a contiguous uint8 tensor of at least %d bytes on %s" % (nbytes, dev))
+    workspace = _workspace(popart_workspace_bytes(rows, H), workspace, dev)
     lg, ft = logits.detach().contiguous(), critic_features.detach().contiguous()
     if install == "replace":
         w_out, b_out, s_out = torch.empty_like(w_obj.detach()), torch.empty_like(b_obj.detach()), torch.empty_like(s_obj.detach())
@@ -329,12 +326,9 @@ def ppo_losses_popart(logits, critic_features, sample_or_fields, args, popart, i
     grad_weight, grad_bias = torch.empty_like(w_obj.detach()), torch.empty_like(b_obj.detach())
     logp, ratio, values = (torch.empty((rows, 1), dtype=torch.float32, device=dev) for _ in range(3))
     plan = _lib.GmpePopartLossPlan()
-    plan.rows, plan.n_actions, plan.hidden, plan.flags, plan.actions_int64 = rows, K, H, flags, int(actions.dtype == torch.int64)
-    plan.clip_param, plan.huber_delta, plan.entropy_coef, plan.beta, plan.epsilon = clip, delta, ent, beta, epsilon
-    plan.logits, plan.critic_features, plan.actions = lg.data_ptr(), ft.data_ptr(), actions.data_ptr()
-    plan.available_actions = None if avail is None else avail.data_ptr()
-    for k, t in cols.items():
-        setattr(plan, k, t.data_ptr())
+    _bind_minibatch(plan, rows, K, flags, clip, delta, ent, cols, actions, avail)
+    plan.hidden, plan.beta, plan.epsilon = H, beta, epsilon
+    plan.logits, plan.critic_features = lg.data_ptr(), ft.data_ptr()
     plan.weight, plan.bias, plan.stddev = w_obj.data_ptr(), b_obj.data_ptr(), s_obj.data_ptr()
     plan.mean, plan.mean_sq, plan.debiasing_term = mean.data_ptr(), mean_sq.data_ptr(), debias.data_ptr()
     plan.weight_out, plan.bias_out, plan.stddev_out = w_out.data_ptr(), b_out.data_ptr(), s_out.data_ptr()
@@ -342,8 +336,7 @@ def ppo_losses_popart(logits, critic_features, sample_or_fields, args, popart, i
     plan.grad_logits, plan.grad_features, plan.grad_weight, plan.grad_bias = (t.data_ptr() for t in (grad_logits, grad_features, grad_weight, grad_bias))
     plan.action_log_probs, plan.imp_weights = logp.data_ptr(), ratio.data_ptr()
     plan.workspace, plan.workspace_bytes = workspace.data_ptr(), workspace.numel()
-    _lib.check(_lib.load().gmpe_ppo_loss_popart(dev.index if dev.index is not None else torch.cuda.current_device(), C.byref(plan), _stream_of(dev)),
-               "gmpe_ppo_loss_popart")
+    _lib.check(_lib.load().gmpe_ppo_loss_popart(_ordinal(dev), C.byref(plan), _stream_of(dev)), "gmpe_ppo_loss_popart")
     s = out.to(torch.float32)
     o = _lib.PPO_OUT.index
     actor = _Attach.apply(logits, s[o("actor_loss")], grad_logits)

@@ -1,0 +1,187 @@
+"""Bit-for-bit A/B of two builds of libgmpe.so over the three entry points that share gmpe_ppo_rows.h: gmpe_ppo_loss, gmpe_ppo_loss_popart and
+gmpe_act_sample, called through their C plans on fixed inputs. The GPU suites bound the losses against float64, so they would not see a changed
+rounding; this does.
+
+    GMPE_LIB=/path/to/libgmpe_parent.so python tools/learner_ab_bits.py dump a.npz     # one process per build
+    python tools/learner_ab_bits.py dump b.npz
+    python tools/learner_ab_bits.py compare a.npz b.npz                                 # exit 1 unless every array is equal as integers
+
+Inputs: the generators of tests/ppo_loss_lib.py ("edges": +-30 logits, stop rows, rows with nothing available), tests/popart_lib.py (a layer and
+features for the values) and tests/act_lib.py ("wide", with empty rows). rows in 1, 255, 257, 600 (one lane; a tile less one; one and two tiles and a
+bit) x K in 1, 2, 5, 25, 64 (tile_copy's K == 1 branch; even: S = K + 1; odd: S = K; the 64-bit mask and the raised LDS limit) x base pointers 16-byte
+aligned / offset by one element (the 4-byte path) x actions float32 / int64 x available_actions given / absent x all flags on / off; PopArt with
+H in 1, 7, 64, 1024 laid over (rows, K) as a Latin square, so every (rows, H) and every (K, H) occurs; act with the availability from an array, from
+dones_prev and from neither x deterministic 0 / 1 x draw_dev given (the counter after the call is kept) / absent. Every call is tiny.
+Kept per call: the seven float64 scalars, every gradient, action_log_probs, imp_weights, values, the updated normaliser state and the rescaled layer;
+action_idx, both action arrays, the log-probs.
+"""
+import ctypes as C
+import itertools
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+ROWS, KS, HS = (1, 255, 257, 600), (1, 2, 5, 25, 64), (1, 7, 64, 1024)
+COLS = ("value_preds", "returns", "active_masks", "old_action_log_probs", "adv_targ")
+HYPER = dict(clip_param=0.2, huber_delta=10.0, entropy_coef=0.01, beta=0.99999, epsilon=1e-5)
+
+
+def dump(path):
+    import torch
+    import gmpe  # noqa: F401
+    from gmpe import _lib
+    import act_lib
+    import popart_lib
+    import ppo_loss_lib
+    lib = _lib.load()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    kept, keep = {}, []
+
+    def put(a, off, dtype=None):
+        """`a` on the device, its base 16-byte aligned (off 0) or one element past that (off 1)."""
+        src = torch.from_numpy(np.ascontiguousarray(a, dtype))
+        buf = torch.zeros(src.numel() + 1, dtype=src.dtype, device=dev)
+        t = buf[off:off + src.numel()].view(src.shape)
+        t.copy_(src)
+        assert t.data_ptr() % 16 == (off * src.element_size()) % 16
+        keep.append(buf)
+        return t
+
+    def blank(shape, off, dtype=np.float32):
+        return put(np.zeros(shape, dtype), off)
+
+    def ptr(t):
+        return None if t is None else t.data_ptr()
+
+    def save(tag, **arrays):
+        torch.cuda.synchronize()
+        for k, t in arrays.items():
+            kept["%s/%s" % (tag, k)] = t.cpu().numpy()
+        del keep[:]
+
+    def minibatch(plan, inp, K, off, act64, given, flags):
+        B = inp["logits"].shape[0]
+        plan.rows, plan.n_actions, plan.flags, plan.actions_int64 = B, K, flags, int(act64)
+        for k, v in HYPER.items():
+            setattr(plan, k, v)
+        plan.logits = ptr(put(inp["logits"], off))
+        plan.actions = ptr(put(inp["actions"], off, np.int64 if act64 else np.float32))
+        plan.available_actions = ptr(put(inp["available_actions"], off)) if given else None
+        for k in COLS:
+            setattr(plan, k, ptr(put(inp[k], off)))
+        out = dict(out=blank(_lib.PPO_NUM_OUT, 0, np.float64), grad_logits=blank((B, K), off), action_log_probs=blank((B, 1), off),
+                   imp_weights=blank((B, 1), off))
+        for k, t in out.items():
+            setattr(plan, k, ptr(t))
+        return out
+
+    variants = list(itertools.product((0, 1), (False, True), (True, False), (True, False)))      # off, int64 actions, avail given, flags on
+    for ri, B in enumerate(ROWS):
+        for ki, K in enumerate(KS):
+            inp = ppo_loss_lib.family("edges", B, K, masks="mixed")
+            for off, act64, given, on in variants:
+                tag = "B%d_K%d_off%d_i64%d_av%d_fl%d" % (B, K, off, act64, given, on)
+                # ---- gmpe_ppo_loss
+                plan = _lib.GmpePpoLossPlan()
+                out = minibatch(plan, inp, K, off, act64, given, 31 if on else 0)
+                plan.values = ptr(put(inp["values"], off))
+                out["grad_values"] = blank((B, 1), off)
+                plan.grad_values = ptr(out["grad_values"])
+                if on:
+                    for k, v in (("running_mean", 0.3), ("running_mean_sq", 1.7), ("debiasing_term", 0.5)):
+                        out[k] = put(np.full(1, v, np.float32), off)
+                        setattr(plan, k, ptr(out[k]))
+                n = C.c_size_t()
+                _lib.check(lib.gmpe_ppo_loss_workspace_bytes(B, C.byref(n)), "gmpe_ppo_loss_workspace_bytes")
+                ws = torch.zeros(n.value, dtype=torch.uint8, device=dev)
+                plan.workspace, plan.workspace_bytes = ws.data_ptr(), n.value
+                _lib.check(lib.gmpe_ppo_loss(dev.index, C.byref(plan), stream), "gmpe_ppo_loss")
+                save("loss/" + tag, **out)
+                # ---- gmpe_ppo_loss_popart
+                H = HS[(ri + ki) % len(HS)]
+                st = popart_lib.fresh_popart(H)
+                st.update(stddev=np.full(1, 1.5, np.float32), mean=np.full(1, 0.25, np.float32), mean_sq=np.full(1, 2.0, np.float32),
+                          debiasing_term=np.full((), 0.5, np.float32))
+                plan = _lib.GmpePopartLossPlan()
+                out = minibatch(plan, inp, K, off, act64, given, 15 if on else 0)
+                plan.hidden = H
+                plan.critic_features = ptr(put(popart_lib.features(inp["values"], st, H), off))
+                for k in popart_lib.STATE:
+                    out[k] = put(st[k].reshape(-1) if k != "weight" else st[k], off)
+                    setattr(plan, k, ptr(out[k]))
+                aliased = bool(off)                                          # the rescaled layer into new arrays, or over the old one
+                for k in ("weight", "bias", "stddev"):
+                    if not aliased:
+                        out[k + "_out"] = blank(out[k].shape, off)
+                    setattr(plan, k + "_out", ptr(out[k] if aliased else out[k + "_out"]))
+                for k, shape in (("values_out", (B, 1)), ("grad_features", (B, H)), ("grad_weight", (1, H)), ("grad_bias", (1,))):
+                    out[k] = blank(shape, off)
+                    setattr(plan, k, ptr(out[k]))
+                _lib.check(lib.gmpe_ppo_loss_popart_workspace_bytes(B, H, C.byref(n)), "gmpe_ppo_loss_popart_workspace_bytes")
+                ws = torch.zeros(n.value, dtype=torch.uint8, device=dev)
+                plan.workspace, plan.workspace_bytes = ws.data_ptr(), n.value
+                _lib.check(lib.gmpe_ppo_loss_popart(dev.index, C.byref(plan), stream), "gmpe_ppo_loss_popart")
+                save("popart_H%d/%s" % (H, tag), **out)
+            # ---- gmpe_act_sample
+            logits, av = act_lib.family("wide", B, K, avail="empty")
+            dones = (np.random.RandomState(B * 131 + K).rand(B) < 0.3).astype(np.uint8)
+            for off, source, det, counter in itertools.product((0, 1), ("array", "dones", "none"), (0, 1), (False, True)):
+                plan = _lib.GmpeActPlan()
+                plan.rows, plan.n_actions, plan.num_agents, plan.stop_action, plan.deterministic = B, K, 3, K // 2, det
+                plan.env_id_base, plan.seed, plan.draw, plan.draw_inc = 1000, act_lib.SEED, act_lib.DRAW, 5
+                plan.logits = ptr(put(logits, off))
+                plan.available_actions = ptr(put(av, off)) if source == "array" else None
+                plan.dones_prev = ptr(put(dones, off)) if source == "dones" else None
+                out = dict(action_idx=blank(B, off, np.int32), log_probs=blank((B, 1), off), actions_f32=blank((B, 1), off),
+                           actions_i64=blank((B, 1), 0, np.int64))
+                if counter:
+                    out["draw_dev"] = put(np.full(1, 7, np.int64), 0)
+                    plan.draw_dev = ptr(out["draw_dev"])
+                plan.action_idx, plan.log_probs = ptr(out["action_idx"]), ptr(out["log_probs"])
+                plan.actions_f32, plan.actions_i64 = ptr(out["actions_f32"]), ptr(out["actions_i64"])
+                _lib.check(lib.gmpe_act_sample(dev.index, C.byref(plan), stream), "gmpe_act_sample")
+                save("act/B%d_K%d_off%d_%s_det%d_ctr%d" % (B, K, off, source, det, counter), **out)
+    np.savez(path, **kept)
+    print("dump: %d arrays, %d elements (%d non-zero) from %s -> %s" % (len(kept), sum(a.size for a in kept.values()),
+                                                                       sum(int(np.count_nonzero(a)) for a in kept.values()), _lib.LIB_PATH, path))
+
+
+def compare(pa, pb):
+    a, b = np.load(pa), np.load(pb)
+    names = sorted(set(a.files) | set(b.files))
+    differing = elements = 0
+    for k in names:
+        if k not in a.files or k not in b.files:
+            print("only in one dump: %s" % k)
+            differing += 1
+            continue
+        x, y = a[k], b[k]
+        if x.dtype != y.dtype or x.shape != y.shape:
+            print("%s: %s %s against %s %s" % (k, x.dtype, x.shape, y.dtype, y.shape))
+            differing += 1
+            continue
+        bits = np.dtype("u%d" % x.dtype.itemsize)
+        d = int((x.reshape(-1).view(bits) != y.reshape(-1).view(bits)).sum())
+        elements += x.size
+        if d:
+            print("%s: %d of %d elements differ" % (k, d, x.size))
+            differing += d
+    per = {p: sum(1 for k in names if k.startswith(p)) for p in ("loss/", "popart_", "act/")}
+    print("compare: %d arrays (%s), %d elements, %d differing" % (len(names), ", ".join("%s %d" % (p.rstrip("/_"), n) for p, n in per.items()), elements,
+                                                                 differing))
+    return 1 if differing or not names else 0
+
+
+if __name__ == "__main__":
+    if len(sys.argv) == 3 and sys.argv[1] == "dump":
+        dump(sys.argv[2])
+    elif len(sys.argv) == 4 and sys.argv[1] == "compare":
+        sys.exit(compare(sys.argv[2], sys.argv[3]))
+    else:
+        sys.exit(__doc__)
