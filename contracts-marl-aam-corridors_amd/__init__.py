@@ -13,7 +13,7 @@ __all__ = ["config", "make_config", "config_from_args"]
 
 def __getattr__(name):
     # torch / HIP-dependent modules are imported on first use
-    if name in ("engine", "vec_env", "spaces", "_lib", "sharding", "rollout", "minibatch", "evaluate", "ppo_loss", "act"):
+    if name in ("engine", "vec_env", "spaces", "_lib", "sharding", "rollout", "minibatch", "evaluate", "ppo_loss", "act", "learner_shards"):
         import importlib
         return importlib.import_module("." + name, __name__)
     if name in ("BatchedGraphMPEVecEnv", "MultiDeviceGraphMPEVecEnv", "GraphMPEEnv", "make_train_env", "make_eval_env"):
@@ -22,13 +22,16 @@ def __getattr__(name):
     if name == "BatchedEvaluator":
         from . import evaluate
         return evaluate.BatchedEvaluator
-    if name in ("ppo_losses", "PPOLosses", "ppo_losses_popart", "PPOPopArtLosses"):
+    if name in ("ppo_losses", "PPOLosses", "ppo_losses_popart", "PPOPopArtLosses", "ppo_losses_begin", "ppo_losses_finish"):
         from . import ppo_loss
         return getattr(ppo_loss, name)
     if name == "sample_actions":
         from . import act
         return act.sample_actions
-    if name == "GmpeEngine":
+    if name in ("GmpeEngine", "compute_returns_begin", "compute_returns_finish"):
         from . import engine
-        return engine.GmpeEngine
+        return getattr(engine, name)
+    if name == "ProcessGroupExchange":
+        from . import learner_shards
+        return learner_shards.ProcessGroupExchange
     raise AttributeError(name)

@@ -21,7 +21,7 @@ SYMBOLS = ["gmpe_abi_version", "gmpe_last_error", "gmpe_obs_dim", "gmpe_node_fea
            "gmpe_insert_learner", "gmpe_episode_record", "gmpe_episode_metrics", "gmpe_episode_summary",
            "gmpe_minibatch_edges", "gmpe_minibatch_edges_workspace_bytes", "gmpe_episode_record_series",
            "gmpe_ppo_loss", "gmpe_ppo_loss_workspace_bytes", "gmpe_ppo_loss_popart", "gmpe_ppo_loss_popart_workspace_bytes",
-           "gmpe_act_sample"]
+           "gmpe_act_sample", "gmpe_compute_returns_shard", "gmpe_ppo_loss_shard"]
 
 
 class GmpeOutputs(C.Structure):
@@ -55,6 +55,13 @@ class GmpeReturnsPlan(C.Structure):
 
 
 RETURNS_GAE, RETURNS_PROPER_TIME_LIMITS, RETURNS_ADVANTAGES_ONLY = 1, 2, 4
+SHARD_LOCAL, SHARD_APPLY, SHARD_MAX_WORLD = 0, 1, 4096
+RETURNS_SHARD_STATS, PPO_SHARD_STATS = 3, 4
+
+
+class GmpeReturnsShardPlan(C.Structure):
+    """gmpe_returns_shard_plan (include/gmpe.h): gmpe_returns_plan in two phases around an exchange of the shards' (n, mean, M2)."""
+    _fields_ = [("base", GmpeReturnsPlan), ("phase", C.c_int32), ("world", C.c_int32), ("local", C.c_void_p), ("all", C.c_void_p)]
 
 
 class GmpeAvailPlan(C.Structure):
@@ -151,6 +158,11 @@ class GmpePpoLossPlan(C.Structure):
                 ("imp_weights", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
+class GmpePpoLossShardPlan(C.Structure):
+    """gmpe_ppo_loss_shard_plan (include/gmpe.h): gmpe_ppo_loss_plan in two phases around an exchange of the shards' sums and row counts."""
+    _fields_ = [("base", GmpePpoLossPlan), ("phase", C.c_int32), ("world", C.c_int32), ("local", C.c_void_p), ("all", C.c_void_p)]
+
+
 POPART_MAX_HIDDEN = 1024
 
 
@@ -239,6 +251,8 @@ def load():
     lib.gmpe_ppo_loss_popart.argtypes = [I, C.POINTER(GmpePopartLossPlan), P]
     lib.gmpe_ppo_loss_popart_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.POINTER(C.c_size_t)]
     lib.gmpe_act_sample.argtypes = [I, C.POINTER(GmpeActPlan), P]
+    lib.gmpe_compute_returns_shard.argtypes = [I, C.POINTER(GmpeReturnsShardPlan), P]
+    lib.gmpe_ppo_loss_shard.argtypes = [I, C.POINTER(GmpePpoLossShardPlan), P]
     from .config import ABI_VERSION
     if lib.gmpe_abi_version() != ABI_VERSION:
         raise GmpeError("libgmpe.so ABI version mismatch")

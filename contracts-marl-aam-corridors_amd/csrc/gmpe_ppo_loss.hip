@@ -10,6 +10,9 @@
 //     (onpolicy/utils/util.py:24-30).
 // Per-row arithmetic is float32 in the reference's operation order where one exists (no contraction); sums over rows are double, per-workgroup
 // partials merged in a fixed order: no atomics, the same bits for the same rows wherever they lie in memory.
+// Over several shards (gmpe_ppo_loss_shard): LOCAL stops after the merge of the statistics and writes the three sums and the row count; APPLY adds the shards'
+// rows in index order, forms the denominators, the ValueNorm update and the normalisation scalars from the global sums with the code below, and runs the same
+// row pass: a shard's scalars are its sums over the global denominators, its gradient rows those of the global loss.
 //
 // Gradients, in closed form (row r, column j, a = the action, D = the denominator of the mean: sum of active_masks or B):
 //   policy head   dlogp/dz_j = [j == a] - p_j;   dH/dz_j = -p_j * (l_j + H);   both 0 at masked entries: distributions.py:89 overwrites those logits
@@ -37,7 +40,8 @@ namespace {
 using namespace gmpe_ppo;         // gmpe_ppo_rows.h: TILE, the fixed-order sums, the tile machinery and the row arithmetic, shared with gmpe_ppo_popart.hip
 
 constexpr int NROW = 4;           // sum -min(surr1, surr2) * w, sum H * w, sum value_loss * w, sum ratio
-constexpr int HDR_DOUBLES = 4;    // D_policy, D_value, then f32 mean, std (one double), one spare
+constexpr int HDR_DOUBLES = 4;    // D_policy, D_value, then f32 mean, std (one double), then the global row count of a sharded call
+constexpr int NSHARD = GMPE_PPO_SHARD_STATS;      // the NSTAT sums and the row count
 
 struct LossArgs {
     Geom g;
@@ -56,14 +60,12 @@ __global__ __launch_bounds__(TILE) void k_loss_stats(LossArgs p) {
 }
 
 // 2: merge; ValueNorm.update (valuenorm.py:56-73), BEFORE the normalisation as cal_value_loss does (graph_mappo.py:93-97); running_mean_var (:48-54)
-__global__ __launch_bounds__(TILE) void k_loss_prepare(LossArgs p, int64_t nparts) {
-    __shared__ double sh[TILE][NSTAT];
-    merge<NSTAT>(p.stat_part, nparts, sh);
-    if (threadIdx.x != 0) return;
-    denominators(p.hdr, p.pol.flags, p.g.B, sh[0][2]);
+// sums: the merged sums of returns, returns^2, active_masks over the B rows the means are over (one thread)
+__device__ __forceinline__ void prepare_header(const LossArgs& p, const double* sums, int64_t B) {
+    denominators(p.hdr, p.pol.flags, B, sums[2]);
     float mean = 0.0f, sd = 1.0f;
     if (p.pol.flags & GMPE_PPO_VALUENORM) {
-        const Running u = running_update(p.rm, p.rms, p.db, sh[0], p.g.B, p.wbeta, p.w1beta);
+        const Running u = running_update(p.rm, p.rms, p.db, sums, B, p.wbeta, p.w1beta);
         const float dc = fmaxf(u.debias, p.eps);
         mean = __fdiv_rn(u.mean, dc);
         const float var = fmaxf(__fsub_rn(__fdiv_rn(u.mean_sq, dc), __fmul_rn(mean, mean)), 1e-2f);
@@ -71,6 +73,32 @@ __global__ __launch_bounds__(TILE) void k_loss_prepare(LossArgs p, int64_t npart
     }
     float* f = reinterpret_cast<float*>(p.hdr + 2);
     f[0] = mean; f[1] = sd;
+}
+
+__global__ __launch_bounds__(TILE) void k_loss_prepare(LossArgs p, int64_t nparts) {
+    __shared__ double sh[TILE][NSTAT];
+    merge<NSTAT>(p.stat_part, nparts, sh);
+    if (threadIdx.x == 0) prepare_header(p, sh[0], p.g.B);
+}
+
+// gmpe_ppo_loss_shard, LOCAL: the same merge, the three sums and the row count to `local`
+__global__ __launch_bounds__(TILE) void k_loss_local(LossArgs p, int64_t nparts, double* __restrict__ local) {
+    __shared__ double sh[TILE][NSTAT];
+    merge<NSTAT>(p.stat_part, nparts, sh);
+    if (threadIdx.x != 0) return;
+    for (int k = 0; k < NSTAT; ++k) local[k] = sh[0][k];
+    local[NSTAT] = (double)p.g.B;
+}
+
+// gmpe_ppo_loss_shard, APPLY: the shards' rows of `all` added in index order (one thread: the order is the result), then the header from the global sums
+__global__ __launch_bounds__(64) void k_loss_prepare_shard(LossArgs p, const double* __restrict__ all, int world) {
+    if (threadIdx.x != 0) return;
+    double s[NSHARD];
+    for (int k = 0; k < NSHARD; ++k) s[k] = all[k];
+    for (int i = 1; i < world; ++i)
+        for (int k = 0; k < NSHARD; ++k) s[k] += all[i * NSHARD + k];
+    p.hdr[3] = s[NSTAT];
+    prepare_header(p, s, (int64_t)s[NSTAT]);
 }
 
 // 3: the row pass. One lane per row; the tile's available_actions, then its logits, then its gradient pass through the same LDS rows.
@@ -107,7 +135,74 @@ __global__ __launch_bounds__(TILE) void k_loss_finish(LossArgs p, int64_t nparts
     write_scalars(p.out, sh[0], p.hdr[0], p.hdr[1], p.pol.ent_coef, p.g.B);
 }
 
+// gmpe_ppo_loss_shard, APPLY: this shard's sums over the global denominators and the global row count
+__global__ __launch_bounds__(TILE) void k_loss_finish_shard(LossArgs p, int64_t nparts) {
+    __shared__ double sh[TILE][NROW];
+    merge<NROW>(p.row_part, nparts, sh);
+    if (threadIdx.x != 0) return;
+    write_scalars(p.out, sh[0], p.hdr[0], p.hdr[1], p.pol.ent_coef, (int64_t)p.hdr[3]);
+}
+
 int fail(int code, const std::string& m) { return gmpe::report_error(code, m); }
+
+// every check of a gmpe_ppo_loss_plan, for the entry point `name`
+int check_plan(const char* name, const gmpe_ppo_loss_plan* pl) {
+    const auto bad = [&](const char* m) { return fail(GMPE_ERR_INVALID_ARG, std::string(name) + ": " + m); };
+    const int known = GMPE_PPO_POLICY_ACTIVE_MASKS | GMPE_PPO_VALUE_ACTIVE_MASKS | GMPE_PPO_CLIPPED_VALUE_LOSS | GMPE_PPO_HUBER_LOSS | GMPE_PPO_VALUENORM;
+    if (pl->flags & ~known) return bad("unknown flags");
+    const bool vn = pl->flags & GMPE_PPO_VALUENORM;
+    const char* missing = nullptr;
+    if (!pl->logits || !pl->values || !pl->actions || !pl->old_action_log_probs || !pl->adv_targ || !pl->value_preds || !pl->returns || !pl->active_masks)
+        missing = "logits, values, actions, old_action_log_probs, adv_targ, value_preds, returns and active_masks are required";
+    else if (!pl->out || !pl->grad_logits || !pl->grad_values)
+        missing = "out, grad_logits and grad_values are required";
+    else if (vn != (pl->running_mean && pl->running_mean_sq && pl->debiasing_term) || (!vn && (pl->running_mean || pl->running_mean_sq || pl->debiasing_term)))
+        missing = "the three ValueNorm scalars are given exactly with GMPE_PPO_VALUENORM";
+    if (int rc = check_loss_plan(name, pl, nullptr, missing)) return rc;
+    const uintptr_t a4 = (uintptr_t)pl->logits | (uintptr_t)pl->available_actions | (uintptr_t)pl->values | (uintptr_t)pl->old_action_log_probs |
+                         (uintptr_t)pl->adv_targ | (uintptr_t)pl->value_preds | (uintptr_t)pl->returns | (uintptr_t)pl->active_masks | (uintptr_t)pl->grad_logits |
+                         (uintptr_t)pl->grad_values | (uintptr_t)pl->action_log_probs | (uintptr_t)pl->imp_weights | (uintptr_t)pl->running_mean |
+                         (uintptr_t)pl->running_mean_sq | (uintptr_t)pl->debiasing_term;
+    if ((a4 & 3) || ((uintptr_t)pl->actions & (pl->actions_int64 ? 7 : 3)) || ((uintptr_t)pl->out & 7))
+        return bad("f32 arrays must be 4-byte aligned, int64 actions and out 8-byte aligned");
+    size_t need = 0;
+    gmpe_ppo_loss_workspace_bytes(pl->rows, &need);
+    if (!pl->workspace || pl->workspace_bytes < need || ((uintptr_t)pl->workspace & 7))
+        return bad("needs an 8-byte aligned workspace of gmpe_ppo_loss_workspace_bytes(rows)");
+    if (num_tiles(pl->rows) > 0x7fffffffLL) return bad("too many rows for one launch");
+    return GMPE_OK;
+}
+
+LossArgs loss_args(const gmpe_ppo_loss_plan* pl, int64_t nt) {
+    LossArgs a;
+    a.g = geometry(pl->rows, pl->n_actions);
+    a.pol.flags = pl->flags;
+    a.pol.logits = pl->logits; a.pol.avail = pl->available_actions; a.values = pl->values; a.pol.old_lp = pl->old_action_log_probs; a.pol.adv = pl->adv_targ;
+    a.vp = pl->value_preds; a.ret = pl->returns; a.pol.am = pl->active_masks; a.pol.actions = pl->actions;
+    a.grad_logits = pl->grad_logits; a.grad_values = pl->grad_values; a.pol.out_lp = pl->action_log_probs; a.pol.out_ratio = pl->imp_weights;
+    hyper_parameters(pl, a);
+    a.rm = pl->running_mean; a.rms = pl->running_mean_sq; a.db = pl->debiasing_term;
+    a.stat_part = static_cast<double*>(pl->workspace);
+    a.row_part = a.stat_part + nt * NSTAT;
+    a.hdr = a.row_part + nt * NROW;
+    a.out = pl->out;
+    return a;
+}
+
+// the row pass of a plan: one launch
+int launch_rows(const gmpe_ppo_loss_plan* pl, const LossArgs& a, int64_t nt, int device, hipStream_t st) {
+    const bool vec = !(((uintptr_t)pl->logits | (uintptr_t)pl->available_actions | (uintptr_t)pl->grad_logits) & 15);   // tiles start at multiples of 1 KiB
+    const size_t lds = (size_t)TILE * a.g.S * sizeof(float);
+    void (*fn)(LossArgs) = vec ? (pl->actions_int64 ? k_loss_rows<true, true> : k_loss_rows<true, false>)
+                               : (pl->actions_int64 ? k_loss_rows<false, true> : k_loss_rows<false, false>);
+    if (lds > 48 * 1024)                                                      // K = 64 only
+        if (int rc = raise_dynamic_lds_once(reinterpret_cast<const void*>(fn), device, (vec ? 2 : 0) | (pl->actions_int64 ? 1 : 0),
+                                            TILE * (GMPE_PPO_MAX_ACTIONS | 1) * sizeof(float)))
+            return rc;
+    hipLaunchKernelGGL(fn, dim3((unsigned)nt), dim3(TILE), lds, st, a);
+    GMPE_HIP_CHECK(hipGetLastError());
+    return GMPE_OK;
+}
 
 }  // namespace
 
@@ -121,59 +216,49 @@ int gmpe_ppo_loss_workspace_bytes(int64_t rows, size_t* bytes_out) {
 
 int gmpe_ppo_loss(int device, const gmpe_ppo_loss_plan* pl, void* stream) {
     if (!pl) return fail(GMPE_ERR_INVALID_ARG, "gmpe_ppo_loss: null plan");
-    const int known = GMPE_PPO_POLICY_ACTIVE_MASKS | GMPE_PPO_VALUE_ACTIVE_MASKS | GMPE_PPO_CLIPPED_VALUE_LOSS | GMPE_PPO_HUBER_LOSS | GMPE_PPO_VALUENORM;
-    if (pl->flags & ~known) return fail(GMPE_ERR_INVALID_ARG, "gmpe_ppo_loss: unknown flags");
-    const bool vn = pl->flags & GMPE_PPO_VALUENORM;
-    const char* missing = nullptr;
-    if (!pl->logits || !pl->values || !pl->actions || !pl->old_action_log_probs || !pl->adv_targ || !pl->value_preds || !pl->returns || !pl->active_masks)
-        missing = "logits, values, actions, old_action_log_probs, adv_targ, value_preds, returns and active_masks are required";
-    else if (!pl->out || !pl->grad_logits || !pl->grad_values)
-        missing = "out, grad_logits and grad_values are required";
-    else if (vn != (pl->running_mean && pl->running_mean_sq && pl->debiasing_term) || (!vn && (pl->running_mean || pl->running_mean_sq || pl->debiasing_term)))
-        missing = "the three ValueNorm scalars are given exactly with GMPE_PPO_VALUENORM";
-    if (int rc = check_loss_plan("gmpe_ppo_loss", pl, nullptr, missing)) return rc;
-    const uintptr_t a4 = (uintptr_t)pl->logits | (uintptr_t)pl->available_actions | (uintptr_t)pl->values | (uintptr_t)pl->old_action_log_probs |
-                         (uintptr_t)pl->adv_targ | (uintptr_t)pl->value_preds | (uintptr_t)pl->returns | (uintptr_t)pl->active_masks | (uintptr_t)pl->grad_logits |
-                         (uintptr_t)pl->grad_values | (uintptr_t)pl->action_log_probs | (uintptr_t)pl->imp_weights | (uintptr_t)pl->running_mean |
-                         (uintptr_t)pl->running_mean_sq | (uintptr_t)pl->debiasing_term;
-    if ((a4 & 3) || ((uintptr_t)pl->actions & (pl->actions_int64 ? 7 : 3)) || ((uintptr_t)pl->out & 7))
-        return fail(GMPE_ERR_INVALID_ARG, "gmpe_ppo_loss: f32 arrays must be 4-byte aligned, int64 actions and out 8-byte aligned");
-    size_t need = 0;
-    gmpe_ppo_loss_workspace_bytes(pl->rows, &need);
-    if (!pl->workspace || pl->workspace_bytes < need || ((uintptr_t)pl->workspace & 7))
-        return fail(GMPE_ERR_INVALID_ARG, "gmpe_ppo_loss: needs an 8-byte aligned workspace of gmpe_ppo_loss_workspace_bytes(rows)");
+    if (int rc = check_plan("gmpe_ppo_loss", pl)) return rc;
     const int64_t nt = num_tiles(pl->rows);
-    if (nt > 0x7fffffffLL) return fail(GMPE_ERR_INVALID_ARG, "gmpe_ppo_loss: too many rows for one launch");
     GMPE_HIP_CHECK(hipSetDevice(device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    LossArgs a;
-    a.g = geometry(pl->rows, pl->n_actions);
-    a.pol.flags = pl->flags;
-    a.pol.logits = pl->logits; a.pol.avail = pl->available_actions; a.values = pl->values; a.pol.old_lp = pl->old_action_log_probs; a.pol.adv = pl->adv_targ;
-    a.vp = pl->value_preds; a.ret = pl->returns; a.pol.am = pl->active_masks; a.pol.actions = pl->actions;
-    a.grad_logits = pl->grad_logits; a.grad_values = pl->grad_values; a.pol.out_lp = pl->action_log_probs; a.pol.out_ratio = pl->imp_weights;
-    hyper_parameters(pl, a);
-    a.rm = pl->running_mean; a.rms = pl->running_mean_sq; a.db = pl->debiasing_term;
-    a.stat_part = static_cast<double*>(pl->workspace);
-    a.row_part = a.stat_part + nt * NSTAT;
-    a.hdr = a.row_part + nt * NROW;
-    a.out = pl->out;
+    const LossArgs a = loss_args(pl, nt);
     const dim3 grid((unsigned)nt), block(TILE), one(1);
     hipLaunchKernelGGL(k_loss_stats, grid, block, 0, st, a);
     GMPE_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(k_loss_prepare, one, block, 0, st, a, nt);
     GMPE_HIP_CHECK(hipGetLastError());
-    const bool vec = !(((uintptr_t)pl->logits | (uintptr_t)pl->available_actions | (uintptr_t)pl->grad_logits) & 15);   // tiles start at multiples of 1 KiB
-    const size_t lds = (size_t)TILE * a.g.S * sizeof(float);
-    void (*fn)(LossArgs) = vec ? (pl->actions_int64 ? k_loss_rows<true, true> : k_loss_rows<true, false>)
-                               : (pl->actions_int64 ? k_loss_rows<false, true> : k_loss_rows<false, false>);
-    if (lds > 48 * 1024)                                                      // K = 64 only
-        if (int rc = raise_dynamic_lds_once(reinterpret_cast<const void*>(fn), device, (vec ? 2 : 0) | (pl->actions_int64 ? 1 : 0),
-                                            TILE * (GMPE_PPO_MAX_ACTIONS | 1) * sizeof(float)))
-            return rc;
-    hipLaunchKernelGGL(fn, grid, block, lds, st, a);
-    GMPE_HIP_CHECK(hipGetLastError());
+    if (int rc = launch_rows(pl, a, nt, device, st)) return rc;
     hipLaunchKernelGGL(k_loss_finish, one, block, 0, st, a, nt);
+    GMPE_HIP_CHECK(hipGetLastError());
+    return GMPE_OK;
+}
+
+int gmpe_ppo_loss_shard(int device, const gmpe_ppo_loss_shard_plan* sp, void* stream) {
+    if (!sp) return fail(GMPE_ERR_INVALID_ARG, "gmpe_ppo_loss_shard: null plan");
+    const gmpe_ppo_loss_plan* pl = &sp->base;
+    if (sp->phase != GMPE_SHARD_LOCAL && sp->phase != GMPE_SHARD_APPLY)
+        return fail(GMPE_ERR_INVALID_ARG, "gmpe_ppo_loss_shard: phase must be GMPE_SHARD_LOCAL or GMPE_SHARD_APPLY");
+    if (sp->world < 1 || sp->world > GMPE_SHARD_MAX_WORLD) return fail(GMPE_ERR_INVALID_ARG, "gmpe_ppo_loss_shard: world must be in 1 .. 4096");
+    const bool local = sp->phase == GMPE_SHARD_LOCAL;
+    const void* stat_ptr = local ? static_cast<const void*>(sp->local) : static_cast<const void*>(sp->all);
+    if (!stat_ptr || ((uintptr_t)stat_ptr & 7))
+        return fail(GMPE_ERR_INVALID_ARG, "gmpe_ppo_loss_shard: LOCAL needs `local`, APPLY needs `all`, f64 device memory, 8-byte aligned");
+    if (int rc = check_plan("gmpe_ppo_loss_shard", pl)) return rc;
+    const int64_t nt = num_tiles(pl->rows);
+    GMPE_HIP_CHECK(hipSetDevice(device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const LossArgs a = loss_args(pl, nt);
+    const dim3 grid((unsigned)nt), block(TILE), one(1);
+    if (local) {
+        hipLaunchKernelGGL(k_loss_stats, grid, block, 0, st, a);
+        GMPE_HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(k_loss_local, one, block, 0, st, a, nt, sp->local);
+        GMPE_HIP_CHECK(hipGetLastError());
+        return GMPE_OK;
+    }
+    hipLaunchKernelGGL(k_loss_prepare_shard, one, dim3(64), 0, st, a, sp->all, (int)sp->world);
+    GMPE_HIP_CHECK(hipGetLastError());
+    if (int rc = launch_rows(pl, a, nt, device, st)) return rc;
+    hipLaunchKernelGGL(k_loss_finish_shard, one, block, 0, st, a, nt);
     GMPE_HIP_CHECK(hipGetLastError());
     return GMPE_OK;
 }

@@ -12,6 +12,10 @@
 // Normalised advantages (GR_MAPPO.train, graph_mappo.py:294-304): each wave merges its lanes' (count, mean, M2) in double (Welford per
 // lane, Chan merges in a fixed butterfly order) into one partial; k_adv_stats merges the partials in a fixed order; k_adv_normalize
 // applies (adv - mean) / (std + 1e-5). No atomics: bitwise reproducible run to run.
+//
+// Over several shards (gmpe_compute_returns_shard): LOCAL stops after the fixed-order merge and writes the Stat itself; APPLY folds the shards' Stats with the
+// same chan from the left in index order, converts with the same code as k_adv_stats and normalises. The statistics are those of the whole batch, the same
+// bits on every shard; with one shard LOCAL + APPLY is gmpe_compute_returns bit for bit.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -162,9 +166,8 @@ __global__ __launch_bounds__(RET_BLOCK) void k_advantages(RetArgs p) {
     if (p.part) wave_partial(st, p.part);
 }
 
-// The partials in a fixed order -> mean, std + 1e-5 as float32 (np.nanmean / np.nanstd, ddof 0). No active entry: NaN, like NumPy.
-__global__ __launch_bounds__(STAT_BLOCK) void k_adv_stats(const Stat* __restrict__ part, int64_t nparts, float* __restrict__ out) {
-    __shared__ Stat sh[STAT_BLOCK];
+// The partials in a fixed order -> sh[0] (every thread of the workgroup calls it; thread 0 reads the result)
+__device__ __forceinline__ void merge_partials(const Stat* __restrict__ part, int64_t nparts, Stat* sh) {
     Stat s{0.0, 0.0, 0.0};
     for (int64_t i = threadIdx.x; i < nparts; i += STAT_BLOCK) s = chan(s, part[i]);
     sh[threadIdx.x] = s;
@@ -173,15 +176,39 @@ __global__ __launch_bounds__(STAT_BLOCK) void k_adv_stats(const Stat* __restrict
         if ((int)threadIdx.x < w) sh[threadIdx.x] = chan(sh[threadIdx.x], sh[threadIdx.x + w]);
         __syncthreads();
     }
-    if (threadIdx.x == 0) {
-        const Stat t = sh[0];
-        if (t.n == 0.0) {
-            out[0] = out[1] = __builtin_nanf("");
-        } else {
-            out[0] = (float)t.mean;
-            out[1] = __fadd_rn((float)sqrt(fmax(t.m2, 0.0) / t.n), 1e-5f);   // std_advantages + 1e-5 (float32 scalar arithmetic)
-        }
+}
+
+// A merged Stat -> mean, std + 1e-5 as float32 (np.nanmean / np.nanstd, ddof 0). No active entry: NaN, like NumPy.
+__device__ __forceinline__ void mean_and_denominator(const Stat& t, float* __restrict__ out) {
+    if (t.n == 0.0) {
+        out[0] = out[1] = __builtin_nanf("");
+    } else {
+        out[0] = (float)t.mean;
+        out[1] = __fadd_rn((float)sqrt(fmax(t.m2, 0.0) / t.n), 1e-5f);   // std_advantages + 1e-5 (float32 scalar arithmetic)
     }
+}
+
+__global__ __launch_bounds__(STAT_BLOCK) void k_adv_stats(const Stat* __restrict__ part, int64_t nparts, float* __restrict__ out) {
+    __shared__ Stat sh[STAT_BLOCK];
+    merge_partials(part, nparts, sh);
+    if (threadIdx.x == 0) mean_and_denominator(sh[0], out);
+}
+
+// gmpe_compute_returns_shard, LOCAL: the same merge, the Stat itself to `local` as (n, mean, M2)
+__global__ __launch_bounds__(STAT_BLOCK) void k_adv_stats_local(const Stat* __restrict__ part, int64_t nparts, double* __restrict__ local) {
+    __shared__ Stat sh[STAT_BLOCK];
+    merge_partials(part, nparts, sh);
+    if (threadIdx.x == 0) {
+        local[0] = sh[0].n; local[1] = sh[0].mean; local[2] = sh[0].m2;
+    }
+}
+
+// gmpe_compute_returns_shard, APPLY: the shards' Stats as a left fold in index order (one thread: the order is the result)
+__global__ __launch_bounds__(64) void k_adv_stats_apply(const double* __restrict__ all, int world, float* __restrict__ out) {
+    if (threadIdx.x != 0) return;
+    Stat s{all[0], all[1], all[2]};
+    for (int i = 1; i < world; ++i) s = chan(s, Stat{all[3 * i], all[3 * i + 1], all[3 * i + 2]});
+    mean_and_denominator(s, out);
 }
 
 __global__ __launch_bounds__(NORM_BLOCK) void k_adv_normalize(const float* src, float* dst, const float* __restrict__ stats, int T, int64_t lanes,
@@ -216,38 +243,26 @@ int64_t num_partials(int64_t lanes) { return (lanes + RET_BLOCK - 1) / RET_BLOCK
 
 int fail(int code, const std::string& m) { return gmpe::report_error(code, m); }
 
-}  // namespace
-
-extern "C" {
-
-int gmpe_returns_workspace_bytes(int64_t lanes, size_t* bytes_out) {
-    if (!bytes_out || lanes < 1) return fail(GMPE_ERR_INVALID_ARG, "gmpe_returns_workspace_bytes: bad arguments");
-    *bytes_out = (size_t)num_partials(lanes) * sizeof(Stat) + 2 * sizeof(float);
+// The checks of gmpe_compute_returns (stats: whether the statistics are needed, which a sharded call always does); `name` is the entry point's.
+int check_returns_plan(const char* name, const gmpe_returns_plan* pl, bool stats) {
+    const auto bad = [&](const char* m) { return fail(GMPE_ERR_INVALID_ARG, std::string(name) + ": " + m); };
+    const bool proper = pl->flags & GMPE_RETURNS_PROPER_TIME_LIMITS, only = pl->flags & GMPE_RETURNS_ADVANTAGES_ONLY;
+    if (pl->flags & ~(GMPE_RETURNS_GAE | GMPE_RETURNS_PROPER_TIME_LIMITS | GMPE_RETURNS_ADVANTAGES_ONLY)) return bad("unknown flags");
+    if (pl->num_steps < 1 || pl->lanes < 1 || pl->stride < pl->lanes) return bad("need num_steps >= 1, lanes >= 1 and stride >= lanes");
+    if (!pl->value_preds || !pl->returns) return bad("value_preds and returns are required");
+    if (!only && (!pl->rewards || !pl->masks || !pl->next_value)) return bad("rewards, masks and next_value are required");
+    if (!only && proper && !pl->bad_masks) return bad("proper time limits need bad_masks");
+    if (!pl->denorm_mean != !pl->denorm_std) return bad("denorm_mean and denorm_std go together");
+    if (only && !pl->advantages && !pl->normalized) return bad("advantages-only needs advantages or normalized");
+    size_t need = 0;
+    gmpe_returns_workspace_bytes(pl->lanes, &need);
+    if (stats && (!pl->active_masks || !pl->workspace || pl->workspace_bytes < need || ((uintptr_t)pl->workspace & 7)))
+        return bad("normalized needs active_masks and an 8-byte aligned workspace of gmpe_returns_workspace_bytes(lanes)");
+    if (num_partials(pl->lanes) > 0x7fffffffLL) return bad("too many lanes for one launch");
     return GMPE_OK;
 }
 
-int gmpe_compute_returns(int device, const gmpe_returns_plan* pl, void* stream) {
-    if (!pl) return fail(GMPE_ERR_INVALID_ARG, "gmpe_compute_returns: null plan");
-    const bool gae = pl->flags & GMPE_RETURNS_GAE, proper = pl->flags & GMPE_RETURNS_PROPER_TIME_LIMITS, only = pl->flags & GMPE_RETURNS_ADVANTAGES_ONLY;
-    if (pl->flags & ~(GMPE_RETURNS_GAE | GMPE_RETURNS_PROPER_TIME_LIMITS | GMPE_RETURNS_ADVANTAGES_ONLY))
-        return fail(GMPE_ERR_INVALID_ARG, "gmpe_compute_returns: unknown flags");
-    if (pl->num_steps < 1 || pl->lanes < 1 || pl->stride < pl->lanes)
-        return fail(GMPE_ERR_INVALID_ARG, "gmpe_compute_returns: need num_steps >= 1, lanes >= 1 and stride >= lanes");
-    if (!pl->value_preds || !pl->returns) return fail(GMPE_ERR_INVALID_ARG, "gmpe_compute_returns: value_preds and returns are required");
-    if (!only && (!pl->rewards || !pl->masks || !pl->next_value))
-        return fail(GMPE_ERR_INVALID_ARG, "gmpe_compute_returns: rewards, masks and next_value are required");
-    if (!only && proper && !pl->bad_masks) return fail(GMPE_ERR_INVALID_ARG, "gmpe_compute_returns: proper time limits need bad_masks");
-    if (!pl->denorm_mean != !pl->denorm_std) return fail(GMPE_ERR_INVALID_ARG, "gmpe_compute_returns: denorm_mean and denorm_std go together");
-    if (only && !pl->advantages && !pl->normalized)
-        return fail(GMPE_ERR_INVALID_ARG, "gmpe_compute_returns: advantages-only needs advantages or normalized");
-    const int64_t nparts = num_partials(pl->lanes);
-    size_t need = 0;
-    gmpe_returns_workspace_bytes(pl->lanes, &need);
-    if (pl->normalized && (!pl->active_masks || !pl->workspace || pl->workspace_bytes < need || ((uintptr_t)pl->workspace & 7)))
-        return fail(GMPE_ERR_INVALID_ARG, "gmpe_compute_returns: normalized needs active_masks and an 8-byte aligned workspace of gmpe_returns_workspace_bytes(lanes)");
-    if (nparts > 0x7fffffffLL) return fail(GMPE_ERR_INVALID_ARG, "gmpe_compute_returns: too many lanes for one launch");
-    GMPE_HIP_CHECK(hipSetDevice(device));
-    hipStream_t st = static_cast<hipStream_t>(stream);
+RetArgs returns_args(const gmpe_returns_plan* pl) {
     RetArgs a;
     a.T = pl->num_steps; a.lanes = pl->lanes; a.stride = pl->stride;
     a.g = (float)pl->gamma;
@@ -256,7 +271,13 @@ int gmpe_compute_returns(int device, const gmpe_returns_plan* pl, void* stream) 
     a.am = pl->active_masks; a.vp = pl->value_preds; a.ret = pl->returns;
     a.adv = pl->advantages ? pl->advantages : pl->normalized;
     a.part = pl->normalized ? static_cast<Stat*>(pl->workspace) : nullptr;
-    const dim3 grid((unsigned)nparts), block(RET_BLOCK);
+    return a;
+}
+
+// the recurrence (or the advantages alone) of a plan: one launch
+int launch_returns(const gmpe_returns_plan* pl, const RetArgs& a, hipStream_t st) {
+    const bool gae = pl->flags & GMPE_RETURNS_GAE, proper = pl->flags & GMPE_RETURNS_PROPER_TIME_LIMITS, only = pl->flags & GMPE_RETURNS_ADVANTAGES_ONLY;
+    const dim3 grid((unsigned)num_partials(pl->lanes)), block(RET_BLOCK);
     const bool dn = pl->denorm_mean != nullptr;
     if (only) {
         if (dn) hipLaunchKernelGGL((k_advantages<true>), grid, block, 0, st, a);
@@ -274,15 +295,71 @@ int gmpe_compute_returns(int device, const gmpe_returns_plan* pl, void* stream) 
         }
     }
     GMPE_HIP_CHECK(hipGetLastError());
+    return GMPE_OK;
+}
+
+// the raw advantages of a plan normalised with the (mean, std + 1e-5) at `stats`
+int launch_normalize(const gmpe_returns_plan* pl, const RetArgs& a, const float* stats, hipStream_t st) {
+    hipLaunchKernelGGL(k_adv_normalize, dim3((unsigned)((pl->lanes + NORM_BLOCK - 1) / NORM_BLOCK)), dim3(NORM_BLOCK), 0, st, a.adv, pl->normalized, stats,
+                       a.T, pl->lanes, pl->stride);
+    GMPE_HIP_CHECK(hipGetLastError());
+    return GMPE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gmpe_returns_workspace_bytes(int64_t lanes, size_t* bytes_out) {
+    if (!bytes_out || lanes < 1) return fail(GMPE_ERR_INVALID_ARG, "gmpe_returns_workspace_bytes: bad arguments");
+    *bytes_out = (size_t)num_partials(lanes) * sizeof(Stat) + 2 * sizeof(float);
+    return GMPE_OK;
+}
+
+int gmpe_compute_returns(int device, const gmpe_returns_plan* pl, void* stream) {
+    if (!pl) return fail(GMPE_ERR_INVALID_ARG, "gmpe_compute_returns: null plan");
+    if (int rc = check_returns_plan("gmpe_compute_returns", pl, pl->normalized != nullptr)) return rc;
+    const int64_t nparts = num_partials(pl->lanes);
+    GMPE_HIP_CHECK(hipSetDevice(device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const RetArgs a = returns_args(pl);
+    if (int rc = launch_returns(pl, a, st)) return rc;
     if (pl->normalized) {
         float* stats = reinterpret_cast<float*>(static_cast<Stat*>(pl->workspace) + nparts);
         hipLaunchKernelGGL(k_adv_stats, dim3(1), dim3(STAT_BLOCK), 0, st, a.part, nparts, stats);
         GMPE_HIP_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(k_adv_normalize, dim3((unsigned)((pl->lanes + NORM_BLOCK - 1) / NORM_BLOCK)), dim3(NORM_BLOCK), 0, st, a.adv, pl->normalized, stats,
-                           a.T, pl->lanes, pl->stride);
-        GMPE_HIP_CHECK(hipGetLastError());
+        if (int rc = launch_normalize(pl, a, stats, st)) return rc;
     }
     return GMPE_OK;
+}
+
+int gmpe_compute_returns_shard(int device, const gmpe_returns_shard_plan* sp, void* stream) {
+    const char* name = "gmpe_compute_returns_shard";
+    if (!sp) return fail(GMPE_ERR_INVALID_ARG, "gmpe_compute_returns_shard: null plan");
+    const gmpe_returns_plan* pl = &sp->base;
+    if (sp->phase != GMPE_SHARD_LOCAL && sp->phase != GMPE_SHARD_APPLY)
+        return fail(GMPE_ERR_INVALID_ARG, "gmpe_compute_returns_shard: phase must be GMPE_SHARD_LOCAL or GMPE_SHARD_APPLY");
+    if (sp->world < 1 || sp->world > GMPE_SHARD_MAX_WORLD) return fail(GMPE_ERR_INVALID_ARG, "gmpe_compute_returns_shard: world must be in 1 .. 4096");
+    const bool local = sp->phase == GMPE_SHARD_LOCAL;
+    const void* stat_ptr = local ? static_cast<const void*>(sp->local) : static_cast<const void*>(sp->all);
+    if (!stat_ptr || ((uintptr_t)stat_ptr & 7))
+        return fail(GMPE_ERR_INVALID_ARG, "gmpe_compute_returns_shard: LOCAL needs `local`, APPLY needs `all`, f64 device memory, 8-byte aligned");
+    if (!pl->normalized) return fail(GMPE_ERR_INVALID_ARG, "gmpe_compute_returns_shard: normalized is required");
+    if (int rc = check_returns_plan(name, pl, true)) return rc;
+    const int64_t nparts = num_partials(pl->lanes);
+    GMPE_HIP_CHECK(hipSetDevice(device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const RetArgs a = returns_args(pl);
+    if (local) {
+        if (int rc = launch_returns(pl, a, st)) return rc;
+        hipLaunchKernelGGL(k_adv_stats_local, dim3(1), dim3(STAT_BLOCK), 0, st, a.part, nparts, sp->local);
+        GMPE_HIP_CHECK(hipGetLastError());
+        return GMPE_OK;
+    }
+    float* stats = reinterpret_cast<float*>(static_cast<Stat*>(pl->workspace) + nparts);
+    hipLaunchKernelGGL(k_adv_stats_apply, dim3(1), dim3(64), 0, st, sp->all, (int)sp->world, stats);
+    GMPE_HIP_CHECK(hipGetLastError());
+    return launch_normalize(pl, a, stats, st);
 }
 
 int gmpe_available_actions_from_dones(int device, const gmpe_avail_plan* pl, void* stream) {

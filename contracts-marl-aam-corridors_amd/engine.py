@@ -465,7 +465,7 @@ def denorm_scalars(value_normalizer, device):
 
 
 def compute_returns(rewards, masks, value_preds, returns, next_value=None, gamma=0.99, gae_lambda=0.95, use_gae=True, use_proper_time_limits=False,
-                    bad_masks=None, denorm=None, advantages=None, active_masks=None, normalized=None, workspace=None, advantages_only=False):
+                    bad_masks=None, denorm=None, advantages=None, active_masks=None, normalized=None, workspace=None, advantages_only=False, shards=None):
     """GraphReplayBuffer.compute_returns (onpolicy/utils/graph_buffer.py:285-366) and the head of GR_MAPPO.train (graph_mappo.py:294-304) on the device,
     on the current stream, bit-identical to the reference's float32 NumPy for returns and raw advantages (gmpe_compute_returns).
       value_preds, returns, masks, bad_masks, active_masks: float32 [T+1, ...lane dims] (e.g. [T+1, N, A, 1]); rewards, advantages, normalized: [T, ...];
@@ -473,7 +473,26 @@ def compute_returns(rewards, masks, value_preds, returns, next_value=None, gamma
     Side effects as the reference: with use_gae value_preds[T] = next_value, without it returns[T] = next_value. advantages (optional) receives
     returns[t] - denorm(value_preds[t]); normalized (optional, may be `advantages` itself) receives (adv - mean) / (std + 1e-5) over the entries with
     active_masks[t] != 0 — which needs `workspace` (uint8, returns_workspace_bytes(lanes) bytes; allocated here when None). advantages_only=True skips
-    the recurrence and takes returns / value_preds as they stand (what train reads). Every argument is checked (ValueError) before the launch."""
+    the recurrence and takes returns / value_preds as they stand (what train reads). Every argument is checked (ValueError) before the launch.
+    shards: None, or the exchange of a data-parallel learner (gmpe.learner_shards): the arrays are this rank's lanes, and `normalized` (required then)
+    is normalised by the mean / std over the lanes of ALL ranks, the same bits on every rank: compute_returns_begin, shards.exchange(.local),
+    compute_returns_finish."""
+    if shards is not None:
+        from . import learner_shards
+        learner_shards.check_shards(shards)
+        h = compute_returns_begin(rewards, masks, value_preds, returns, next_value, gamma, gae_lambda, use_gae, use_proper_time_limits, bad_masks, denorm,
+                                  advantages, active_masks, normalized, workspace, advantages_only)
+        return compute_returns_finish(h, learner_shards.gather(shards, h.local, "compute_returns"))
+    plan, dev, _ = _returns_plan(rewards, masks, value_preds, returns, next_value, gamma, gae_lambda, use_gae, use_proper_time_limits, bad_masks, denorm,
+                                 advantages, active_masks, normalized, workspace, advantages_only)
+    _need_cuda(dev)
+    _lib.check(_lib.load().gmpe_compute_returns(dev.index, C.byref(plan), _stream_of(dev)), "gmpe_compute_returns")
+    return returns
+
+
+def _returns_plan(rewards, masks, value_preds, returns, next_value, gamma, gae_lambda, use_gae, use_proper_time_limits, bad_masks, denorm, advantages,
+                  active_masks, normalized, workspace, advantages_only):
+    """The checked arguments of compute_returns as a gmpe_returns_plan -> (plan, device, the tensors the plan points to)."""
     if not isinstance(value_preds, torch.Tensor) or value_preds.dim() < 1 or value_preds.shape[0] < 2:
         raise ValueError("value_preds must be a float32 tensor [T+1, ...] with T >= 1")
     dev = value_preds.device
@@ -520,9 +539,52 @@ def compute_returns(rewards, masks, value_preds, returns, next_value=None, gamma
         elif workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous() or workspace.numel() < nbytes:
             raise ValueError("workspace must be a contiguous uint8 tensor of at least %d bytes on %s" % (nbytes, dev))
         plan.workspace, plan.workspace_bytes = workspace.data_ptr(), workspace.numel()
+    return plan, dev, (rewards, masks, value_preds, returns, next_value, bad_masks, denorm, advantages, active_masks, normalized, workspace)
+
+
+class ReturnsShard(object):
+    """What compute_returns_begin leaves for compute_returns_finish: `.local`, this shard's (n, mean, M2) of the active raw advantages as an f64 [3]
+    device tensor (valid once the stream reaches it), and everything the plan points to, kept alive until finish has enqueued its launches."""
+
+    def __init__(self, plan, device, keep, returns, local):
+        self.plan, self.device, self.keep, self.returns, self.local, self.done = plan, device, keep, returns, local, False
+
+
+def compute_returns_begin(rewards, masks, value_preds, returns, next_value=None, gamma=0.99, gae_lambda=0.95, use_gae=True, use_proper_time_limits=False,
+                          bad_masks=None, denorm=None, advantages=None, active_masks=None, normalized=None, workspace=None, advantages_only=False):
+    """The first phase of compute_returns over one shard of a batch (gmpe_compute_returns_shard, GMPE_SHARD_LOCAL), same arguments: returns, side
+    effects and raw advantages are written as compute_returns writes them (they are lane-local), the shard's advantage statistics go to the handle's
+    `.local` in compute_returns' own merge order, and nothing is normalised yet: the raw advantages wait in `advantages` (in `normalized` when
+    advantages is None). `normalized` and `active_masks` are required. -> ReturnsShard"""
+    if normalized is None:
+        raise ValueError("a sharded compute_returns exchanges the statistics of the normalised advantages: normalized (and active_masks) are required")
+    plan, dev, keep = _returns_plan(rewards, masks, value_preds, returns, next_value, gamma, gae_lambda, use_gae, use_proper_time_limits, bad_masks, denorm,
+                                    advantages, active_masks, normalized, workspace, advantages_only)
     _need_cuda(dev)
-    _lib.check(_lib.load().gmpe_compute_returns(dev.index, C.byref(plan), _stream_of(dev)), "gmpe_compute_returns")
-    return returns
+    sp = _lib.GmpeReturnsShardPlan()
+    sp.base = plan
+    local = torch.empty((_lib.RETURNS_SHARD_STATS,), dtype=torch.float64, device=dev)
+    sp.phase, sp.world, sp.local = _lib.SHARD_LOCAL, 1, local.data_ptr()
+    _lib.check(_lib.load().gmpe_compute_returns_shard(dev.index, C.byref(sp), _stream_of(dev)), "gmpe_compute_returns_shard")
+    return ReturnsShard(sp, dev, keep, returns, local)
+
+
+def compute_returns_finish(handle, all_stats):
+    """The second phase (GMPE_SHARD_APPLY): all_stats f64 [world, 3], row r = shard r's `.local` (torch.stack of the handles' .local in one process,
+    an all-gather across ranks). The rows are merged as a left fold in index order, an empty shard (n = 0) changing nothing, and this shard's raw
+    advantages are normalised by the result — the statistics of the whole batch, the same bits on every shard. Once per handle. -> returns"""
+    from . import learner_shards
+    if not isinstance(handle, ReturnsShard):
+        raise TypeError("handle must come from compute_returns_begin")
+    if handle.done:
+        raise RuntimeError("compute_returns_finish was already called on this handle (in place it would normalise twice)")
+    world = learner_shards.check_all_stats(all_stats, handle.local, "compute_returns_finish")
+    _need_cuda(handle.device)
+    sp = handle.plan
+    sp.phase, sp.world, sp.all = _lib.SHARD_APPLY, world, all_stats.data_ptr()
+    _lib.check(_lib.load().gmpe_compute_returns_shard(handle.device.index, C.byref(sp), _stream_of(handle.device)), "gmpe_compute_returns_shard")
+    handle.done = True
+    return handle.returns
 
 
 def available_actions_from_dones(dones, out, first=0, count=None):

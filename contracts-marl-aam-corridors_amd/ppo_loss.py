@@ -190,7 +190,60 @@ class _Attach(torch.autograd.Function):
         return grad * g, None, None
 
 
-def ppo_losses(logits, values, sample_or_fields, args, value_normalizer=None, workspace=None):
+class _Call(object):
+    """One minibatch bound to a gmpe_ppo_loss_plan: the plan, the tensors it points to (kept alive with it) and what the results are made from."""
+
+    def __init__(self, logits, values, sample_or_fields, args, value_normalizer, workspace):
+        flags, clip, delta, ent = _flags(args)
+        dev, rows, K = _logits_shape(logits)
+        if not isinstance(values, torch.Tensor) or not values.is_floating_point() or tuple(values.shape) not in ((rows, 1), (rows,)):
+            raise ValueError("values must be a floating-point tensor of shape (%d, 1)" % rows)
+        if values.device != dev:
+            raise ValueError("values must be on %s (the device of logits)" % dev)
+        logits, values, cols, actions, avail = _minibatch(logits, values, "values", sample_or_fields, rows, K, dev)
+        state = None
+        plan = _lib.GmpePpoLossPlan()
+        if flags & _lib.PPO_VALUENORM:
+            state, plan.beta, plan.epsilon = _valuenorm_state(value_normalizer, dev)
+            plan.running_mean, plan.running_mean_sq, plan.debiasing_term = (t.data_ptr() for t in state)
+        else:
+            plan.beta, plan.epsilon = 0.99999, 1e-5
+        _need_cuda(dev)
+        workspace = _workspace(workspace_bytes(rows), workspace, dev)
+        _bind_minibatch(plan, rows, K, flags, clip, delta, ent, cols, actions, avail)
+        plan.workspace, plan.workspace_bytes = workspace.data_ptr(), workspace.numel()
+        values2 = values if values.dim() == 2 else values.reshape(rows, 1)
+        lg, vl = logits.detach().contiguous(), values2.detach().contiguous()
+        out = torch.empty((_lib.PPO_NUM_OUT,), dtype=torch.float64, device=dev)
+        grad_logits, grad_values = torch.empty_like(lg), torch.empty_like(vl)
+        logp, ratio = (torch.empty((rows, 1), dtype=torch.float32, device=dev) for _ in range(2))
+        plan.logits, plan.values, plan.out = lg.data_ptr(), vl.data_ptr(), out.data_ptr()
+        plan.grad_logits, plan.grad_values = grad_logits.data_ptr(), grad_values.data_ptr()
+        plan.action_log_probs, plan.imp_weights = logp.data_ptr(), ratio.data_ptr()
+        # the inputs the plan points to live until the launches are enqueued on this stream
+        self.keep = (cols, actions, avail, state, workspace, lg, vl)
+        self.plan, self.dev, self.logits, self.values2, self.out = plan, dev, logits, values2, out
+        self.grad_logits, self.grad_values, self.logp, self.ratio = grad_logits, grad_values, logp, ratio
+
+    def losses(self, scale=1):
+        """PPOLosses from `out` and the stored gradients; scale (reduce="mean"): the scalars and the gradients times the number of shards."""
+        s = self.out.to(torch.float32)                     # doubles are written as doubles; rounded once here
+        if scale != 1:
+            s = s * scale
+            self.grad_logits.mul_(scale)
+            self.grad_values.mul_(scale)
+        o = _lib.PPO_OUT.index
+        return PPOLosses(_Attach.apply(self.logits, s[o("actor_loss")], self.grad_logits), _Attach.apply(self.values2, s[o("value_loss")], self.grad_values),
+                         s[o("policy_loss")], s[o("dist_entropy")], s[o("ratio_mean")], self.logp, self.ratio)
+
+
+def _reduce(reduce):
+    if reduce not in ("sum", "mean"):
+        raise ValueError("reduce must be 'sum' (shard contributions) or 'mean' (times world, for DDP's gradient average), not %r" % (reduce,))
+    return reduce
+
+
+def ppo_losses(logits, values, sample_or_fields, args, value_normalizer=None, workspace=None, shards=None, reduce="sum"):
     """actor_loss (policy_loss - entropy_coef * dist_entropy) and value_loss of GR_MAPPO.ppo_update for one minibatch, differentiable with respect to
     `logits` [rows, n_actions] (the policy head's linear output, before masking) and `values` [rows, 1]; policy_loss, dist_entropy, ratio_mean
     (imp_weights.mean()), action_log_probs and imp_weights come detached. sample_or_fields: the generators' 16-tuple as it comes out of
@@ -199,39 +252,66 @@ def ppo_losses(logits, values, sample_or_fields, args, value_normalizer=None, wo
     use_value_active_masks, use_clipped_value_loss, use_huber_loss, use_valuenorm, use_popart; the reference's defaults where absent).
     With use_valuenorm the ValueNorm's three tensors (on the device) are updated in place before the returns are normalised, as cal_value_loss does.
     f16 / bf16 logits and values are widened to float32 first. A zero sum of active_masks gives NaN losses, like the reference's 0 / 0; nothing here
-    waits for the device. workspace: an optional uint8 device tensor of workspace_bytes(rows) to reuse between calls."""
-    flags, clip, delta, ent = _flags(args)
-    dev, rows, K = _logits_shape(logits)
-    if not isinstance(values, torch.Tensor) or not values.is_floating_point() or tuple(values.shape) not in ((rows, 1), (rows,)):
-        raise ValueError("values must be a floating-point tensor of shape (%d, 1)" % rows)
-    if values.device != dev:
-        raise ValueError("values must be on %s (the device of logits)" % dev)
-    logits, values, cols, actions, avail = _minibatch(logits, values, "values", sample_or_fields, rows, K, dev)
-    state = None
-    plan = _lib.GmpePpoLossPlan()
-    if flags & _lib.PPO_VALUENORM:
-        state, plan.beta, plan.epsilon = _valuenorm_state(value_normalizer, dev)
-        plan.running_mean, plan.running_mean_sq, plan.debiasing_term = (t.data_ptr() for t in state)
-    else:
-        plan.beta, plan.epsilon = 0.99999, 1e-5
-    _need_cuda(dev)
-    workspace = _workspace(workspace_bytes(rows), workspace, dev)
-    _bind_minibatch(plan, rows, K, flags, clip, delta, ent, cols, actions, avail)
-    plan.workspace, plan.workspace_bytes = workspace.data_ptr(), workspace.numel()
-    values2 = values if values.dim() == 2 else values.reshape(rows, 1)
-    lg, vl = logits.detach().contiguous(), values2.detach().contiguous()
-    out = torch.empty((_lib.PPO_NUM_OUT,), dtype=torch.float64, device=dev)
-    grad_logits, grad_values = torch.empty_like(lg), torch.empty_like(vl)
-    logp, ratio = (torch.empty((rows, 1), dtype=torch.float32, device=dev) for _ in range(2))
-    plan.logits, plan.values, plan.out = lg.data_ptr(), vl.data_ptr(), out.data_ptr()
-    plan.grad_logits, plan.grad_values = grad_logits.data_ptr(), grad_values.data_ptr()
-    plan.action_log_probs, plan.imp_weights = logp.data_ptr(), ratio.data_ptr()
-    # the inputs the plan points to (cols, actions, avail, state, workspace, lg, vl) live until the launches are enqueued on this stream
-    _lib.check(_lib.load().gmpe_ppo_loss(_ordinal(dev), C.byref(plan), _stream_of(dev)), "gmpe_ppo_loss")
-    s = out.to(torch.float32)                          # doubles are written as doubles; rounded once here
-    o = _lib.PPO_OUT.index
-    return PPOLosses(_Attach.apply(logits, s[o("actor_loss")], grad_logits), _Attach.apply(values2, s[o("value_loss")], grad_values),
-                     s[o("policy_loss")], s[o("dist_entropy")], s[o("ratio_mean")], logp, ratio)
+    waits for the device. workspace: an optional uint8 device tensor of workspace_bytes(rows) to reuse between calls.
+    shards: None, or the exchange of a data-parallel learner (gmpe.learner_shards): the rows are this rank's part of a minibatch whose other parts lie
+    on the other ranks, and the means, the ValueNorm update and the gradients are those of the WHOLE minibatch — ppo_losses_begin,
+    shards.exchange(.local), ppo_losses_finish(reduce=reduce). reduce is read with shards only."""
+    _reduce(reduce)
+    if shards is not None:
+        from . import learner_shards
+        learner_shards.check_shards(shards)
+        h = ppo_losses_begin(logits, values, sample_or_fields, args, value_normalizer, workspace)
+        return ppo_losses_finish(h, learner_shards.gather(shards, h.local, "ppo_losses"), reduce)
+    c = _Call(logits, values, sample_or_fields, args, value_normalizer, workspace)
+    _lib.check(_lib.load().gmpe_ppo_loss(_ordinal(c.dev), C.byref(c.plan), _stream_of(c.dev)), "gmpe_ppo_loss")
+    return c.losses()
+
+
+class PPOLossShard(object):
+    """What ppo_losses_begin leaves for ppo_losses_finish: `.local`, this shard's (sum returns, sum returns^2, sum active_masks, rows) as an f64 [4]
+    device tensor (valid once the stream reaches it), and the bound minibatch with everything its plan points to."""
+
+    def __init__(self, call, plan, local):
+        self.call, self.plan, self.local, self.done = call, plan, local, False
+
+    @property
+    def out(self):
+        """The f64 [GMPE_PPO_NUM_OUT] row of the call (_lib.PPO_OUT names the columns), written by finish: this shard's contributions before any
+        reduce="mean" scaling, and the global denominators in the two DENOM columns."""
+        return self.call.out
+
+
+def ppo_losses_begin(logits, values, sample_or_fields, args, value_normalizer=None, workspace=None):
+    """The first phase of ppo_losses over one shard of a minibatch (gmpe_ppo_loss_shard, GMPE_SHARD_LOCAL), same arguments: the shard's double sums in
+    ppo_losses' own merge order and its row count go to the handle's `.local`; the ValueNorm is not touched yet. -> PPOLossShard"""
+    c = _Call(logits, values, sample_or_fields, args, value_normalizer, workspace)
+    sp = _lib.GmpePpoLossShardPlan()
+    sp.base = c.plan
+    local = torch.empty((_lib.PPO_SHARD_STATS,), dtype=torch.float64, device=c.dev)
+    sp.phase, sp.world, sp.local = _lib.SHARD_LOCAL, 1, local.data_ptr()
+    _lib.check(_lib.load().gmpe_ppo_loss_shard(_ordinal(c.dev), C.byref(sp), _stream_of(c.dev)), "gmpe_ppo_loss_shard")
+    return PPOLossShard(c, sp, local)
+
+
+def ppo_losses_finish(handle, all_stats, reduce="sum"):
+    """The second phase (GMPE_SHARD_APPLY): all_stats f64 [world, 4], row r = shard r's `.local` (torch.stack in one process, an all-gather across
+    ranks), added in index order. The denominators, the ValueNorm update (every replica receives the same one) and the normalisation of the returns
+    come from the sums over the WHOLE minibatch. reduce="sum": the scalars are this shard's contributions — over all shards they add up to the
+    scalars of the whole minibatch — and backward() leaves the rows of the gradient of the global loss. reduce="mean": both times world, so that
+    DDP's average over ranks is the global gradient. Once per handle. -> PPOLosses"""
+    from . import learner_shards
+    _reduce(reduce)
+    if not isinstance(handle, PPOLossShard):
+        raise TypeError("handle must come from ppo_losses_begin")
+    if handle.done:
+        raise RuntimeError("ppo_losses_finish was already called on this handle (it would update the ValueNorm twice)")
+    world = learner_shards.check_all_stats(all_stats, handle.local, "ppo_losses_finish")
+    c, sp = handle.call, handle.plan
+    _need_cuda(c.dev)
+    sp.phase, sp.world, sp.all = _lib.SHARD_APPLY, world, all_stats.data_ptr()
+    _lib.check(_lib.load().gmpe_ppo_loss_shard(_ordinal(c.dev), C.byref(sp), _stream_of(c.dev)), "gmpe_ppo_loss_shard")
+    handle.done = True
+    return c.losses(world if reduce == "mean" else 1)
 
 
 def popart_workspace_bytes(rows, hidden):
@@ -286,7 +366,7 @@ class _AttachHead(torch.autograd.Function):
         return gf * g, gw * g, gb * g, None, None, None, None
 
 
-def ppo_losses_popart(logits, critic_features, sample_or_fields, args, popart, install="replace", workspace=None):
+def ppo_losses_popart(logits, critic_features, sample_or_fields, args, popart, install="replace", workspace=None, shards=None):
     """ppo_losses for --use_popart, where trainer.value_normalizer is the critic's output layer v_out = PopArt(hidden, 1) (graph_mappo.py:63-64): the
     critic is called up to `critic_features` [rows, hidden] (the input of v_out), and one call of gmpe_ppo_loss_popart (four launches) does what
     evaluate_actions' last line and cal_value_loss do, in their order: values = F.linear(critic_features, weight, bias) with the weights as they are
@@ -299,7 +379,11 @@ def ppo_losses_popart(logits, critic_features, sample_or_fields, args, popart, i
     install="in_place": the rescaled layer is written into the existing storage; the Parameters keep their identity and the optimiser trains them.
     Returns PPOPopArtLosses: the PPOLosses fields plus `values` (detached [rows, 1], what v_out gave with the pre-update weights). value_loss is one
     autograd node over (critic_features, the weight and bias objects of the call); actor_loss is as in ppo_losses. f16 / bf16 logits and features
-    are widened to float32 first. Nothing here waits for the device. workspace: an optional uint8 device tensor of popart_workspace_bytes(rows, hidden)."""
+    are widened to float32 first. Nothing here waits for the device. workspace: an optional uint8 device tensor of popart_workspace_bytes(rows, hidden).
+    shards: must be None — the sharded form (ppo_losses(..., shards=...)) does not cover PopArt."""
+    if shards is not None:
+        raise NotImplementedError("ppo_losses_popart(shards=...): the PopArt variant has no sharded form (gmpe_ppo_loss_shard covers ValueNorm or no "
+                                  "normaliser); a data-parallel learner with --use_popart is not supported")
     flags, clip, delta, ent = _flags(args, popart=True)
     if install not in ("replace", "in_place"):
         raise ValueError("install must be 'replace' (the reference: new Parameters) or 'in_place', not %r" % (install,))

@@ -378,10 +378,16 @@ class DeviceRolloutBuffer(object):
             raise ValueError("%s: args.use_valuenorm / use_popart is set, so a value_normalizer is required" % what)
         return denorm_scalars(value_normalizer, self.engine.device)
 
-    def compute_returns(self, next_value, value_normalizer=None):
+    def compute_returns(self, next_value, value_normalizer=None, shards=None):
         """GraphReplayBuffer.compute_returns (graph_buffer.py:285-366) with the runner's args, one launch on the current stream: returns[0..T-1], the
         reference's side effect (value_preds[T] = next_value with use_gae, returns[T] = next_value without), and — buffer with advantages — the raw
-        advantages returns[t] - denorm(value_preds[t]). next_value: [N, A, 1] values of the last slot (graph_mpe_runner.py:431-443)."""
+        advantages returns[t] - denorm(value_preds[t]). next_value: [N, A, 1] values of the last slot (graph_mpe_runner.py:431-443).
+        shards: the exchange of a data-parallel learner (gmpe.learner_shards) or None. Returns and raw advantages are lane-local, so this call
+        reduces over nothing and exchanges nothing: a rank's result is the unsharded one on its lanes either way; the argument is checked and
+        accepted so that the learner passes the same `shards` along its whole path (normalized_advantages is where it acts)."""
+        if shards is not None:
+            from .learner_shards import check_shards
+            check_shards(shards)
         if self.value_preds is None or self.returns is None:
             raise ValueError("compute_returns needs a buffer with value_preds and returns (policy_fields)")
         a, use_norm = self._flags("compute_returns")
@@ -394,14 +400,16 @@ class DeviceRolloutBuffer(object):
                         advantages=self.advantages)
         return self.returns
 
-    def normalized_advantages(self, value_normalizer=None):
+    def normalized_advantages(self, value_normalizer=None, shards=None):
         """The head of GR_MAPPO.train (graph_mappo.py:294-304): advantages = returns[:-1] - denorm(value_preds[:-1]), normalised by the mean / population
-        std of the entries with active_masks[:-1] != 0: (adv - mean) / (std + 1e-5), written into the buffer's advantages (three launches, no host sync)."""
+        std of the entries with active_masks[:-1] != 0: (adv - mean) / (std + 1e-5), written into the buffer's advantages (three launches, no host sync).
+        shards: the exchange of a data-parallel learner (gmpe.learner_shards) or None: the mean / std are then those over the buffers of ALL ranks, the
+        same bits on every rank (four launches around shards.exchange)."""
         if self.advantages is None or self.value_preds is None or self.returns is None:
             raise ValueError("normalized_advantages needs a buffer with value_preds, returns and advantages (policy_fields)")
         _, use_norm = self._flags("normalized_advantages")
         compute_returns(None, None, self.value_preds, self.returns, advantages_only=True, denorm=self._denorm(use_norm, value_normalizer, "normalized_advantages"),
-                        advantages=self.advantages, normalized=self.advantages, active_masks=self.active_masks, workspace=self._ws)
+                        advantages=self.advantages, normalized=self.advantages, active_masks=self.active_masks, workspace=self._ws, shards=shards)
         return self.advantages
 
     # ------------------------------------------------------------------ PPO minibatches (GraphReplayBuffer's generators, gmpe_minibatch_gather)

@@ -379,6 +379,29 @@ typedef struct gmpe_returns_plan {
 int gmpe_returns_workspace_bytes(int64_t lanes, size_t* bytes_out);
 int gmpe_compute_returns(int device, const gmpe_returns_plan* plan, void* stream);
 
+/* The same call for a learner whose batch lies in `world` shards (data-parallel ranks, or pieces of a batch inside one process): the advantage
+ * statistics are those of the WHOLE batch, the same bits on every shard. Two phases around one exchange the caller makes (an all-gather of `local`):
+ *   GMPE_SHARD_LOCAL  everything gmpe_compute_returns does up to the statistics (recurrence or advantages-only; returns, side effects, raw advantages),
+ *                     the per-wave Welford partials merged in gmpe_compute_returns' fixed order, written to `local` as (n, mean, M2). Nothing is
+ *                     normalised: the raw advantages stay in `advantages` (in `normalized` when `advantages` is NULL) until APPLY.
+ *   GMPE_SHARD_APPLY  the `world` triples of `all` merged with the same Chan merge as a left fold in index order (an empty side is skipped, so a shard
+ *                     with no active entry, n = 0, changes nothing), turned into (mean, std + 1e-5) by gmpe_compute_returns' own code, and this
+ *                     shard's raw advantages normalised with them. Run it once per LOCAL: in place it would normalise twice.
+ * `base.normalized`, `base.active_masks` and `base.workspace` are required in both phases, and both take the same `base`. Neither phase allocates, uses
+ * atomics or waits for the device; both are capturable. With world = 1 and all == local, LOCAL then APPLY gives gmpe_compute_returns' outputs bit for bit. */
+#define GMPE_SHARD_LOCAL 0
+#define GMPE_SHARD_APPLY 1
+#define GMPE_SHARD_MAX_WORLD 4096
+#define GMPE_RETURNS_SHARD_STATS 3          /* doubles per shard: n, mean, M2                                                   */
+typedef struct gmpe_returns_shard_plan {
+    gmpe_returns_plan base;     /* as for gmpe_compute_returns, with normalized, active_masks and workspace set                 */
+    int32_t phase;              /* GMPE_SHARD_LOCAL or GMPE_SHARD_APPLY                                                         */
+    int32_t world;              /* shards, 1 .. GMPE_SHARD_MAX_WORLD                                                            */
+    double* local;              /* f64 [3] device, 8-byte aligned: written by LOCAL (not read by APPLY)                         */
+    const double* all;          /* f64 [world, 3] device, 8-byte aligned: read by APPLY in index order (not read by LOCAL)      */
+} gmpe_returns_shard_plan;
+int gmpe_compute_returns_shard(int device, const gmpe_returns_shard_plan* plan, void* stream);
+
 /* available_actions of the shipped training loop (GMPERunner.run + collect_with_mask, graph_mpe_runner.py:73-141, 263-335, stored by
  * GraphReplayBuffer.insert at slot step + 1, graph_buffer.py:249-250): the availability the policy acts with at step t >= 1 is a function of
  * the dones of step t - 1 — a one-hot "stop" row at n_actions / 2 for an agent that was done, a row of ones otherwise (every agent of an env
@@ -485,6 +508,27 @@ typedef struct gmpe_ppo_loss_plan {
 } gmpe_ppo_loss_plan;
 int gmpe_ppo_loss_workspace_bytes(int64_t rows, size_t* bytes_out);
 int gmpe_ppo_loss(int device, const gmpe_ppo_loss_plan* plan, void* stream);
+
+/* The same minibatch lying in `world` shards (see gmpe_compute_returns_shard): the means are over the WHOLE minibatch and ValueNorm.update sees its
+ * returns, the same bits on every shard.
+ *   GMPE_SHARD_LOCAL  the double sums of returns, returns^2 and active_masks over this shard's rows, merged in gmpe_ppo_loss' fixed order, and the
+ *                     row count, written to `local` as four doubles. The ValueNorm scalars are not touched.
+ *   GMPE_SHARD_APPLY  the rows of `all` added sequentially in index order in double; the denominators, the ValueNorm update and the normalisation
+ *                     scalars from those GLOBAL sums and the global row count by gmpe_ppo_loss' own code; then gmpe_ppo_loss' row pass over this
+ *                     shard's rows. `out` holds this shard's sums divided by the global denominators (ratio_mean: by the global row count), so
+ *                     the rows of all shards ADD UP to the scalars of the whole minibatch; the two DENOM columns hold the global denominators;
+ *                     grad_logits / grad_values are rows of the gradient of the global loss; every replica's ValueNorm receives the same update.
+ * Both phases take the same `base`; neither allocates, uses atomics or waits for the device; both are capturable. With world = 1 and all == local,
+ * LOCAL then APPLY gives gmpe_ppo_loss' outputs and ValueNorm state bit for bit. gmpe_ppo_loss_popart has no sharded form. */
+#define GMPE_PPO_SHARD_STATS 4           /* doubles per shard: sum returns, sum returns^2, sum active_masks, rows                     */
+typedef struct gmpe_ppo_loss_shard_plan {
+    gmpe_ppo_loss_plan base;            /* as for gmpe_ppo_loss                                                                       */
+    int32_t phase;                      /* GMPE_SHARD_LOCAL or GMPE_SHARD_APPLY                                                       */
+    int32_t world;                      /* shards, 1 .. GMPE_SHARD_MAX_WORLD                                                          */
+    double* local;                      /* f64 [4] device, 8-byte aligned: written by LOCAL (not read by APPLY)                       */
+    const double* all;                  /* f64 [world, 4] device, 8-byte aligned: read by APPLY in index order (not read by LOCAL)    */
+} gmpe_ppo_loss_shard_plan;
+int gmpe_ppo_loss_shard(int device, const gmpe_ppo_loss_shard_plan* plan, void* stream);
 
 /* The same minibatch with --use_popart: the value normaliser is the critic's output layer v_out = PopArt(hidden, 1)
  * (onpolicy/algorithms/utils/popart.py, graph_mappo.py:63-64), so the line to the critic is its FEATURES [rows, hidden], not its values. In four
