@@ -1,10 +1,13 @@
-// gmpe_eval.hip — evaluation of a policy over a batch of episodes (include/gmpe.h gmpe_episode_record / gmpe_episode_metrics /
-// gmpe_episode_summary): GMPERunner.render(get_metrics=True) (onpolicy/runner/shared/graph_mpe_runner.py:526-1060) with one episode per env.
-// Handle-less: the record state and the step outputs are all it needs.
+// gmpe_eval.hip — evaluation of a policy over a batch of episodes (include/gmpe.h gmpe_episode_record / gmpe_episode_record_series /
+// gmpe_episode_metrics / gmpe_episode_summary): GMPERunner.render(get_metrics=True) (onpolicy/runner/shared/graph_mpe_runner.py:526-1060) with one
+// episode per env, or R episodes per env played back to back across the engine's auto-resets.
+// Handle-less: the record state and the step outputs are all it needs. No atomics in global memory, no allocation, no host synchronisation, capturable.
 //
-// k_episode_record: one workgroup per ER_ENVS envs. Threads 0 .. ER_ENVS-1 own one env each: they read its dones and rewards, add the rewards to
-// `ret` while the env is live, copy its info rows once when it finishes, and leave every agent's mask in LDS. Then the whole workgroup writes the
-// masks, available_actions and the zeroed RNN rows of its envs as flat loops over their contiguous ranges.
+// k_episode_record, k_episode_record_series: one workgroup per ER_ENVS envs. Threads 0 .. ER_ENVS-1 own one env each: they read its dones (record_head:
+// every agent's mask to LDS) and rewards and do the entry's own bookkeeping: one episode adds the rewards to `ret` while the env is live and copies its
+// info rows once when it finishes; the series advances the env's (episode, t_in_ep, ret). Then the whole workgroup writes the masks,
+// available_actions and the zeroed RNN rows of its envs as flat loops over their contiguous ranges (record_tail). Head and tail are one piece of
+// code; the bookkeeping is two, each measured the better on one workload.
 // k_episode_metrics: one thread per env for the columns; A extra workgroups each reduce one agent's Dists_traveled / ttg over the N envs (each
 // thread a fixed strided subset in order, then a fixed LDS tree).
 // k_episode_summary: one workgroup per column. The ranks the order statistics need are selected exactly by an 8-pass radix selection on the
@@ -35,53 +38,38 @@ constexpr int ES_RANKS = 8;        // min, p10 floor / next, median pair, p90 fl
 enum { I_DIST_TO_GOAL = 1, I_TTG = 2, I_AGENT_COLL = 3, I_OBST_COLL = 4, I_DIST_MEAN = 5, I_DIST_VAR = 6, I_MEAN_BY_VAR = 7, I_DISTS_TRAV = 8,
        I_TIME_MEAN = 10, I_TIME_STDDEV = 11, I_TIME_MEAN_BY_STDDEV = 12, I_CONFORMANCE = 13, I_DELTA_SPACING = 14, I_SPACING_VIOL = 15 };
 
-struct RecArgs {
-    int N, A, t, T, n_act, rnn_row;
+// what both record kernels read and write alike
+struct StepArgs {
+    int N, A, T, n_act, rnn_row;
     const float* reward;
     const uint8_t* done;
     const float* info;
-    uint8_t* live;
-    int32_t* steps;
-    double* ret;
     float* final_info;
     float* masks;
     float* avail;
     float* rnn;
 };
 
-__global__ __launch_bounds__(ER_BLOCK) void k_episode_record(RecArgs p) {
-    __shared__ uint8_t mask_sh[ER_ENVS * GMPE_MAX_AGENTS];
-    __shared__ uint8_t done_sh[ER_ENVS * GMPE_MAX_AGENTS];
+// The head of a record kernel, for the thread that owns env n (slot tid of its workgroup): its dones to done_sh, every agent's mask to mask_sh;
+// returns whether all its agents are done.
+__device__ __forceinline__ bool record_head(const StepArgs& p, int64_t n, int tid, uint8_t* done_sh, uint8_t* mask_sh) {
     const int A = p.A;
-    const int64_t env0 = (int64_t)blockIdx.x * ER_ENVS;
-    const int ne = (int)(p.N - env0 < ER_ENVS ? p.N - env0 : ER_ENVS);
-    const int tid = threadIdx.x;
-    if (tid < ne) {
-        const int64_t n = env0 + tid;
-        const uint8_t* d = p.done + n * A;
-        bool all = true;
-        for (int a = 0; a < A; ++a) {
-            const uint8_t v = d[a] != 0;
-            done_sh[tid * A + a] = v;
-            all = all && v;
-        }
-        for (int a = 0; a < A; ++a) mask_sh[tid * A + a] = all || !done_sh[tid * A + a];     // dones_env rows: all ones
-        if (p.live[n]) {
-            const float* r = p.reward + n * A;
-            double* acc = p.ret + n * A;
-            for (int a = 0; a < A; ++a) acc[a] = acc[a] + (double)r[a];
-            if (all || p.t == p.T - 1) {
-                const float* s = p.info + n * A * K;
-                float* o = p.final_info + n * A * K;
-                for (int i = 0; i < A * K; ++i) o[i] = s[i];
-                p.steps[n] = p.t + 1;
-                p.live[n] = 0;
-            }
-        }
+    const uint8_t* d = p.done + n * A;
+    bool all = true;
+    for (int a = 0; a < A; ++a) {
+        const uint8_t v = d[a] != 0;
+        done_sh[tid * A + a] = v;
+        all = all && v;
     }
-    __syncthreads();
-    const int lanes = ne * A;
-    const int64_t lane0 = env0 * A;
+    for (int a = 0; a < A; ++a) mask_sh[tid * A + a] = all || !done_sh[tid * A + a];     // dones_env rows: all ones
+    return all;
+}
+
+// The tail of a record kernel, by the whole workgroup after the barrier: the masks, the stop rows of available_actions and the zeroed RNN rows of its
+// ne envs from env0 on, as flat loops over their contiguous ranges.
+__device__ __forceinline__ void record_tail(const StepArgs& p, int64_t env0, int ne, int tid, const uint8_t* done_sh, const uint8_t* mask_sh) {
+    const int lanes = ne * p.A;
+    const int64_t lane0 = env0 * p.A;
     for (int i = tid; i < lanes; i += ER_BLOCK) p.masks[lane0 + i] = mask_sh[i] ? 1.0f : 0.0f;
     // 32-bit index math: a workgroup's ranges are below 2^32 elements (n_actions <= 4096, rnn_row <= 2^20)
     const uint32_t na = (uint32_t)p.n_act, stop = na / 2;
@@ -96,6 +84,104 @@ __global__ __launch_bounds__(ER_BLOCK) void k_episode_record(RecArgs p) {
     float* rs = p.rnn + lane0 * row;
     for (uint32_t i = tid; i < nr; i += ER_BLOCK)
         if (done_sh[i / row]) rs[i] = 0.0f;
+}
+
+struct RecArgs {
+    StepArgs s;
+    int t;
+    uint8_t* live;
+    int32_t* steps;
+    double* ret;
+};
+
+__global__ __launch_bounds__(ER_BLOCK) void k_episode_record(RecArgs p) {
+    __shared__ uint8_t mask_sh[ER_ENVS * GMPE_MAX_AGENTS];
+    __shared__ uint8_t done_sh[ER_ENVS * GMPE_MAX_AGENTS];
+    const int A = p.s.A;
+    const int64_t env0 = (int64_t)blockIdx.x * ER_ENVS;
+    const int ne = (int)(p.s.N - env0 < ER_ENVS ? p.s.N - env0 : ER_ENVS);
+    const int tid = threadIdx.x;
+    if (tid < ne) {
+        const int64_t n = env0 + tid;
+        const bool all = record_head(p.s, n, tid, done_sh, mask_sh);
+        if (p.live[n]) {
+            const float* r = p.s.reward + n * A;
+            double* acc = p.ret + n * A;
+            for (int a = 0; a < A; ++a) acc[a] = acc[a] + (double)r[a];
+            if (all || p.t == p.s.T - 1) {
+                const float* s = p.s.info + n * A * K;
+                float* o = p.s.final_info + n * A * K;
+                for (int i = 0; i < A * K; ++i) o[i] = s[i];
+                p.steps[n] = p.t + 1;
+                p.live[n] = 0;
+            }
+        }
+    }
+    __syncthreads();
+    record_tail(p.s, env0, ne, tid, done_sh, mask_sh);
+}
+
+// The record for R episodes per env played back to back across the engine's auto-resets. The env threads advance their env's own (episode, t_in_ep, ret)
+// state, write the episode's length and returns when it ends at this step and leave the episode index in LDS (-1: no end); the whole workgroup copies the
+// info rows of the envs that ended an episode into row e * N + n of final_info.
+// Offsets into the [R, N, ...] arrays are 64-bit: R * N * A * 18 passes 2^31 at sizes the summary accepts.
+struct SeriesArgs {
+    StepArgs s;
+    int R;
+    int32_t* episode;
+    int32_t* t_in_ep;
+    double* ret;
+    int32_t* steps;
+    double* ret_out;
+};
+
+__global__ __launch_bounds__(ER_BLOCK) void k_episode_record_series(SeriesArgs p) {
+    __shared__ uint8_t mask_sh[ER_ENVS * GMPE_MAX_AGENTS];
+    __shared__ uint8_t done_sh[ER_ENVS * GMPE_MAX_AGENTS];
+    __shared__ int32_t end_sh[ER_ENVS];                       // the episode index an env ends at this step, or -1
+    const int A = p.s.A;
+    const int64_t env0 = (int64_t)blockIdx.x * ER_ENVS;
+    const int ne = (int)(p.s.N - env0 < ER_ENVS ? p.s.N - env0 : ER_ENVS);
+    const int tid = threadIdx.x;
+    if (tid < ne) {
+        const int64_t n = env0 + tid;
+        const bool all = record_head(p.s, n, tid, done_sh, mask_sh);
+        int32_t ended = -1;
+        const int32_t e = p.episode[n];
+        if (e < p.R) {
+            const float* r = p.s.reward + n * A;
+            double* acc = p.ret + n * A;
+            const int32_t t = p.t_in_ep[n] + 1;
+            if (all || t == p.s.T) {
+                const int64_t row = (int64_t)e * p.s.N + n;
+                double* o = p.ret_out + row * A;
+                for (int a = 0; a < A; ++a) {
+                    o[a] = acc[a] + (double)r[a];
+                    acc[a] = 0.0;
+                }
+                p.steps[row] = t;
+                p.episode[n] = e + 1;
+                p.t_in_ep[n] = 0;
+                ended = e;
+            } else {
+                for (int a = 0; a < A; ++a) acc[a] = acc[a] + (double)r[a];
+                p.t_in_ep[n] = t;
+            }
+        }
+        end_sh[tid] = ended;
+    }
+    __syncthreads();
+    // the info rows of the envs that ended an episode: A * K contiguous floats per env, to row e * N + n. The branch is uniform over the
+    // workgroup, so a step at which no env of the block ends costs ER_ENVS LDS reads here.
+    const int per = A * K;
+    for (int w = 0; w < ne; ++w) {
+        const int32_t e = end_sh[w];
+        if (e < 0) continue;
+        const float* src = p.s.info + (env0 + w) * per;
+        float* dst = p.s.final_info + ((int64_t)e * p.s.N + env0 + w) * per;
+        for (int i = tid; i < per; i += ER_BLOCK) dst[i] = src[i];
+    }
+    record_tail(p.s, env0, ne, tid, done_sh, mask_sh);
 }
 
 // NumPy's pairwise_sum (numpy/_core/src/umath/loops_utils.h.src) for n <= 128, on values produced by f(i)
@@ -359,6 +445,31 @@ bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0;
 
 int fail(const char* fn, const std::string& m) { return gmpe::report_error(GMPE_ERR_INVALID_ARG, std::string(fn) + ": " + m); }
 
+// The checks the two record entry points make alike, in the order both make them. `dims`, `missing`, `a4` and `mis8` are the entry point's own findings:
+// its steps and further dimensions (a message, or null), whether a required pointer is null, its 4-byte arrays' addresses or-ed together, and its 8-byte arrays
+// (a message, or null), reported at their place in that order.
+template <class Plan>
+int check_record_plan(const char* fn, const Plan* pl, const char* dims, bool missing, uintptr_t a4, const char* mis8) {
+    if (pl->num_envs < 1 || pl->num_agents < 1 || pl->num_agents > GMPE_MAX_AGENTS) return fail(fn, "need num_envs >= 1 and 1 <= num_agents <= 64");
+    if (dims) return fail(fn, dims);
+    if (pl->n_actions < 1 || pl->n_actions > 4096) return fail(fn, "n_actions must be in 1 .. 4096");
+    if (pl->rnn_states && (pl->rnn_row < 1 || pl->rnn_row > (1 << 20))) return fail(fn, "rnn_row must be in 1 .. 2^20 with rnn_states");
+    if (missing) return fail(fn, "null pointer: only rnn_states may be NULL");
+    if (a4 & 3) return fail(fn, "misaligned pointer: 4-byte arrays need 4-byte alignment");
+    if (mis8) return fail(fn, mis8);
+    const int64_t lanes = (int64_t)pl->num_envs * pl->num_agents;
+    if (lanes * pl->n_actions > (int64_t)1 << 40 || (pl->rnn_states && lanes * pl->rnn_row > (int64_t)1 << 40)) return fail(fn, "arrays too large");
+    return GMPE_OK;
+}
+
+template <class Plan>
+StepArgs step_args(const Plan* pl) {
+    return StepArgs{pl->num_envs, pl->num_agents, pl->num_steps, pl->n_actions, pl->rnn_states ? pl->rnn_row : 0, pl->reward, pl->done, pl->info,
+                    pl->final_info, pl->masks, pl->available_actions, pl->rnn_states};
+}
+
+unsigned record_blocks(int num_envs) { return (unsigned)(((int64_t)num_envs + ER_ENVS - 1) / ER_ENVS); }
+
 }  // namespace
 
 extern "C" {
@@ -366,23 +477,36 @@ extern "C" {
 int gmpe_episode_record(int device, const gmpe_episode_record_plan* pl, void* stream) {
     const char* fn = "gmpe_episode_record";
     if (!pl) return fail(fn, "null plan");
-    if (pl->num_envs < 1 || pl->num_agents < 1 || pl->num_agents > GMPE_MAX_AGENTS) return fail(fn, "need num_envs >= 1 and 1 <= num_agents <= 64");
-    if (pl->num_steps < 1 || pl->t < 0 || pl->t >= pl->num_steps) return fail(fn, "need num_steps >= 1 and 0 <= t < num_steps");
-    if (pl->n_actions < 1 || pl->n_actions > 4096) return fail(fn, "n_actions must be in 1 .. 4096");
-    if (pl->rnn_states && (pl->rnn_row < 1 || pl->rnn_row > (1 << 20))) return fail(fn, "rnn_row must be in 1 .. 2^20 with rnn_states");
-    if (!pl->reward || !pl->done || !pl->info || !pl->live || !pl->steps || !pl->ret || !pl->final_info || !pl->masks || !pl->available_actions)
-        return fail(fn, "null pointer: only rnn_states may be NULL");
-    const void* f4[] = {pl->reward, pl->info, pl->steps, pl->final_info, pl->masks, pl->available_actions, pl->rnn_states};
-    for (const void* q : f4)
-        if (!aligned(q, 4)) return fail(fn, "misaligned pointer: 4-byte arrays need 4-byte alignment");
-    if (!aligned(pl->ret, 8)) return fail(fn, "misaligned pointer: ret needs 8-byte alignment");
-    const int64_t lanes = (int64_t)pl->num_envs * pl->num_agents;
-    if (lanes * pl->n_actions > (int64_t)1 << 40 || (pl->rnn_states && lanes * pl->rnn_row > (int64_t)1 << 40)) return fail(fn, "arrays too large");
-    RecArgs a{pl->num_envs, pl->num_agents, pl->t, pl->num_steps, pl->n_actions, pl->rnn_states ? pl->rnn_row : 0, pl->reward, pl->done, pl->info,
-              pl->live, pl->steps, pl->ret, pl->final_info, pl->masks, pl->available_actions, pl->rnn_states};
-    const int64_t blocks = ((int64_t)pl->num_envs + ER_ENVS - 1) / ER_ENVS;
+    const bool missing = !pl->reward || !pl->done || !pl->info || !pl->live || !pl->steps || !pl->ret || !pl->final_info || !pl->masks || !pl->available_actions;
+    const uintptr_t a4 = (uintptr_t)pl->reward | (uintptr_t)pl->info | (uintptr_t)pl->steps | (uintptr_t)pl->final_info | (uintptr_t)pl->masks |
+                         (uintptr_t)pl->available_actions | (uintptr_t)pl->rnn_states;
+    if (int rc = check_record_plan(fn, pl, pl->num_steps < 1 || pl->t < 0 || pl->t >= pl->num_steps ? "need num_steps >= 1 and 0 <= t < num_steps" : nullptr, missing, a4,
+                                   aligned(pl->ret, 8) ? nullptr : "misaligned pointer: ret needs 8-byte alignment"))
+        return rc;
+    RecArgs a{step_args(pl), pl->t, pl->live, pl->steps, pl->ret};
     GMPE_HIP_CHECK(hipSetDevice(device));
-    hipLaunchKernelGGL(k_episode_record, dim3((unsigned)blocks), dim3(ER_BLOCK), 0, static_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL(k_episode_record, dim3(record_blocks(pl->num_envs)), dim3(ER_BLOCK), 0, static_cast<hipStream_t>(stream), a);
+    GMPE_HIP_CHECK(hipGetLastError());
+    return GMPE_OK;
+}
+
+int gmpe_episode_record_series(int device, const gmpe_episode_series_plan* pl, void* stream) {
+    const char* fn = "gmpe_episode_record_series";
+    if (!pl) return fail(fn, "null plan");
+    const char* dims = nullptr;
+    if (pl->num_steps < 1) dims = "need num_steps >= 1";
+    else if (pl->num_episodes < 1) dims = "need num_episodes >= 1";
+    else if ((int64_t)pl->num_episodes * pl->num_envs > 0x7fffffffLL) dims = "num_episodes * num_envs must be at most 2^31 - 1";
+    const bool missing = !pl->reward || !pl->done || !pl->info || !pl->episode || !pl->t_in_ep || !pl->ret || !pl->steps || !pl->ret_out || !pl->final_info ||
+                         !pl->masks || !pl->available_actions;
+    const uintptr_t a4 = (uintptr_t)pl->reward | (uintptr_t)pl->info | (uintptr_t)pl->episode | (uintptr_t)pl->t_in_ep | (uintptr_t)pl->steps |
+                         (uintptr_t)pl->final_info | (uintptr_t)pl->masks | (uintptr_t)pl->available_actions | (uintptr_t)pl->rnn_states;
+    if (int rc = check_record_plan(fn, pl, dims, missing, a4, aligned(pl->ret, 8) && aligned(pl->ret_out, 8) ? nullptr
+                                   : "misaligned pointer: ret and ret_out need 8-byte alignment"))
+        return rc;
+    SeriesArgs a{step_args(pl), pl->num_episodes, pl->episode, pl->t_in_ep, pl->ret, pl->steps, pl->ret_out};
+    GMPE_HIP_CHECK(hipSetDevice(device));
+    hipLaunchKernelGGL(k_episode_record_series, dim3(record_blocks(pl->num_envs)), dim3(ER_BLOCK), 0, static_cast<hipStream_t>(stream), a);
     GMPE_HIP_CHECK(hipGetLastError());
     return GMPE_OK;
 }

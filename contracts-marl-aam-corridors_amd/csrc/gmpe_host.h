@@ -1,5 +1,6 @@
 // gmpe_host.h — what the host halves of the learner-side files share (internal: not installed, nothing here has external linkage).
 //   * every file: the library's error text and the one HIP-check macro;
+//   * the two sharded entry points (gmpe_compute_returns_shard, gmpe_ppo_loss_shard): the checks of their phase, world, `local` and `all`;
 //   * the three entry points over gmpe_ppo_rows.h (gmpe_ppo_loss, gmpe_ppo_loss_popart, gmpe_act_sample): the tile geometry the host fills and the row
 //     kernels read, the checks and the float hyper-parameters the two loss entry points have in common, and the once-per-device raise of the dynamic LDS limit.
 #pragma once
@@ -13,6 +14,16 @@
 
 namespace gmpe {
 int report_error(int code, const std::string& m);   // gmpe_step.hip: the library's gmpe_last_error text
+
+// What the two sharded entry points (`name`: gmpe_compute_returns_shard, gmpe_ppo_loss_shard) check of their own fields, before their base plan's checks.
+static int check_shard_args(const char* name, int phase, int world, const double* local, const double* all) {
+    const auto bad = [&](const char* m) { return report_error(GMPE_ERR_INVALID_ARG, std::string(name) + ": " + m); };
+    if (phase != GMPE_SHARD_LOCAL && phase != GMPE_SHARD_APPLY) return bad("phase must be GMPE_SHARD_LOCAL or GMPE_SHARD_APPLY");
+    if (world < 1 || world > GMPE_SHARD_MAX_WORLD) return bad("world must be in 1 .. 4096");
+    const double* stat_ptr = phase == GMPE_SHARD_LOCAL ? local : all;
+    if (!stat_ptr || ((uintptr_t)stat_ptr & 7)) return bad("LOCAL needs `local`, APPLY needs `all`, f64 device memory, 8-byte aligned");
+    return GMPE_OK;
+}
 }
 
 #define GMPE_HIP_CHECK(x) \

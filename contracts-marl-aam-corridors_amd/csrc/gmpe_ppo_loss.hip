@@ -10,9 +10,10 @@
 //     (onpolicy/utils/util.py:24-30).
 // Per-row arithmetic is float32 in the reference's operation order where one exists (no contraction); sums over rows are double, per-workgroup
 // partials merged in a fixed order: no atomics, the same bits for the same rows wherever they lie in memory.
-// Over several shards (gmpe_ppo_loss_shard): LOCAL stops after the merge of the statistics and writes the three sums and the row count; APPLY adds the shards'
-// rows in index order, forms the denominators, the ValueNorm update and the normalisation scalars from the global sums with the code below, and runs the same
-// row pass: a shard's scalars are its sums over the global denominators, its gradient rows those of the global loss.
+// Over several shards (gmpe_ppo_loss_shard): the same kernels and the same host path (run_plan). LOCAL is the call up to k_loss_prepare, which writes the three
+// sums and the row count to `local` instead of the header; APPLY starts at k_loss_prepare, which adds the shards' rows of `all` in index order instead of
+// merging partials, and forms the denominators, the ValueNorm update and the normalisation scalars from the global sums: a shard's scalars are its sums over
+// the global denominators, its gradient rows those of the global loss.
 //
 // Gradients, in closed form (row r, column j, a = the action, D = the denominator of the mean: sum of active_masks or B):
 //   policy head   dlogp/dz_j = [j == a] - p_j;   dH/dz_j = -p_j * (l_j + H);   both 0 at masked entries: distributions.py:89 overwrites those logits
@@ -75,28 +76,28 @@ __device__ __forceinline__ void prepare_header(const LossArgs& p, const double* 
     f[0] = mean; f[1] = sd;
 }
 
-__global__ __launch_bounds__(TILE) void k_loss_prepare(LossArgs p, int64_t nparts) {
+// One kernel for the three callers. Source of the sums: `all` (gmpe_ppo_loss_shard, APPLY) = the shards' rows of NSHARD doubles added in index order by one
+// thread (the order is the result), the row count with them; otherwise the merged partials of this call's rows and B. Sink: `local` (LOCAL) = the sums and the
+// row count, and the kernel stops; otherwise hdr[3] = the row count, which k_loss_finish reads, and the header. The branch on `all` is uniform over the
+// workgroup, so the barriers inside merge are reached by all of it or by none.
+__global__ __launch_bounds__(TILE) void k_loss_prepare(LossArgs p, int64_t nparts, const double* __restrict__ all, int world, double* __restrict__ local) {
     __shared__ double sh[TILE][NSTAT];
-    merge<NSTAT>(p.stat_part, nparts, sh);
-    if (threadIdx.x == 0) prepare_header(p, sh[0], p.g.B);
-}
-
-// gmpe_ppo_loss_shard, LOCAL: the same merge, the three sums and the row count to `local`
-__global__ __launch_bounds__(TILE) void k_loss_local(LossArgs p, int64_t nparts, double* __restrict__ local) {
-    __shared__ double sh[TILE][NSTAT];
-    merge<NSTAT>(p.stat_part, nparts, sh);
-    if (threadIdx.x != 0) return;
-    for (int k = 0; k < NSTAT; ++k) local[k] = sh[0][k];
-    local[NSTAT] = (double)p.g.B;
-}
-
-// gmpe_ppo_loss_shard, APPLY: the shards' rows of `all` added in index order (one thread: the order is the result), then the header from the global sums
-__global__ __launch_bounds__(64) void k_loss_prepare_shard(LossArgs p, const double* __restrict__ all, int world) {
-    if (threadIdx.x != 0) return;
     double s[NSHARD];
-    for (int k = 0; k < NSHARD; ++k) s[k] = all[k];
-    for (int i = 1; i < world; ++i)
-        for (int k = 0; k < NSHARD; ++k) s[k] += all[i * NSHARD + k];
+    if (all) {
+        if (threadIdx.x != 0) return;
+        for (int k = 0; k < NSHARD; ++k) s[k] = all[k];
+        for (int i = 1; i < world; ++i)
+            for (int k = 0; k < NSHARD; ++k) s[k] += all[i * NSHARD + k];
+    } else {
+        merge<NSTAT>(p.stat_part, nparts, sh);
+        if (threadIdx.x != 0) return;
+        for (int k = 0; k < NSTAT; ++k) s[k] = sh[0][k];
+        s[NSTAT] = (double)p.g.B;
+    }
+    if (local) {
+        for (int k = 0; k < NSHARD; ++k) local[k] = s[k];
+        return;
+    }
     p.hdr[3] = s[NSTAT];
     prepare_header(p, s, (int64_t)s[NSTAT]);
 }
@@ -127,16 +128,8 @@ __global__ __launch_bounds__(TILE) void k_loss_rows(LossArgs p) {
     tile_copy<VEC, false>(p.grad_logits + t.g0, sh, t.n, p.g.K, p.g.S, p.g.magic);
 }
 
-// 4: the partials -> the scalar row
+// 4: the partials -> the scalar row: this call's sums over the denominators and the row count of the header (a shard's: the global ones)
 __global__ __launch_bounds__(TILE) void k_loss_finish(LossArgs p, int64_t nparts) {
-    __shared__ double sh[TILE][NROW];
-    merge<NROW>(p.row_part, nparts, sh);
-    if (threadIdx.x != 0) return;
-    write_scalars(p.out, sh[0], p.hdr[0], p.hdr[1], p.pol.ent_coef, p.g.B);
-}
-
-// gmpe_ppo_loss_shard, APPLY: this shard's sums over the global denominators and the global row count
-__global__ __launch_bounds__(TILE) void k_loss_finish_shard(LossArgs p, int64_t nparts) {
     __shared__ double sh[TILE][NROW];
     merge<NROW>(p.row_part, nparts, sh);
     if (threadIdx.x != 0) return;
@@ -204,6 +197,27 @@ int launch_rows(const gmpe_ppo_loss_plan* pl, const LossArgs& a, int64_t nt, int
     return GMPE_OK;
 }
 
+// A checked plan, for both entry points: the statistics unless the shards' are given (`all`), prepare, and the row pass with the scalars unless the
+// statistics are all that is asked for (`local`). (null, 0, null) is the unsharded call: 4 launches; LOCAL 2, APPLY 3.
+int run_plan(int device, const gmpe_ppo_loss_plan* pl, void* stream, const double* all, int world, double* local) {
+    const int64_t nt = num_tiles(pl->rows);
+    GMPE_HIP_CHECK(hipSetDevice(device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const LossArgs a = loss_args(pl, nt);
+    const dim3 grid((unsigned)nt), block(TILE), one(1);
+    if (!all) {
+        hipLaunchKernelGGL(k_loss_stats, grid, block, 0, st, a);
+        GMPE_HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_loss_prepare, one, block, 0, st, a, nt, all, world, local);
+    GMPE_HIP_CHECK(hipGetLastError());
+    if (local) return GMPE_OK;
+    if (int rc = launch_rows(pl, a, nt, device, st)) return rc;
+    hipLaunchKernelGGL(k_loss_finish, one, block, 0, st, a, nt);
+    GMPE_HIP_CHECK(hipGetLastError());
+    return GMPE_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -217,50 +231,15 @@ int gmpe_ppo_loss_workspace_bytes(int64_t rows, size_t* bytes_out) {
 int gmpe_ppo_loss(int device, const gmpe_ppo_loss_plan* pl, void* stream) {
     if (!pl) return fail(GMPE_ERR_INVALID_ARG, "gmpe_ppo_loss: null plan");
     if (int rc = check_plan("gmpe_ppo_loss", pl)) return rc;
-    const int64_t nt = num_tiles(pl->rows);
-    GMPE_HIP_CHECK(hipSetDevice(device));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const LossArgs a = loss_args(pl, nt);
-    const dim3 grid((unsigned)nt), block(TILE), one(1);
-    hipLaunchKernelGGL(k_loss_stats, grid, block, 0, st, a);
-    GMPE_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(k_loss_prepare, one, block, 0, st, a, nt);
-    GMPE_HIP_CHECK(hipGetLastError());
-    if (int rc = launch_rows(pl, a, nt, device, st)) return rc;
-    hipLaunchKernelGGL(k_loss_finish, one, block, 0, st, a, nt);
-    GMPE_HIP_CHECK(hipGetLastError());
-    return GMPE_OK;
+    return run_plan(device, pl, stream, nullptr, 0, nullptr);
 }
 
 int gmpe_ppo_loss_shard(int device, const gmpe_ppo_loss_shard_plan* sp, void* stream) {
     if (!sp) return fail(GMPE_ERR_INVALID_ARG, "gmpe_ppo_loss_shard: null plan");
-    const gmpe_ppo_loss_plan* pl = &sp->base;
-    if (sp->phase != GMPE_SHARD_LOCAL && sp->phase != GMPE_SHARD_APPLY)
-        return fail(GMPE_ERR_INVALID_ARG, "gmpe_ppo_loss_shard: phase must be GMPE_SHARD_LOCAL or GMPE_SHARD_APPLY");
-    if (sp->world < 1 || sp->world > GMPE_SHARD_MAX_WORLD) return fail(GMPE_ERR_INVALID_ARG, "gmpe_ppo_loss_shard: world must be in 1 .. 4096");
+    if (int rc = gmpe::check_shard_args("gmpe_ppo_loss_shard", sp->phase, sp->world, sp->local, sp->all)) return rc;
+    if (int rc = check_plan("gmpe_ppo_loss_shard", &sp->base)) return rc;
     const bool local = sp->phase == GMPE_SHARD_LOCAL;
-    const void* stat_ptr = local ? static_cast<const void*>(sp->local) : static_cast<const void*>(sp->all);
-    if (!stat_ptr || ((uintptr_t)stat_ptr & 7))
-        return fail(GMPE_ERR_INVALID_ARG, "gmpe_ppo_loss_shard: LOCAL needs `local`, APPLY needs `all`, f64 device memory, 8-byte aligned");
-    if (int rc = check_plan("gmpe_ppo_loss_shard", pl)) return rc;
-    const int64_t nt = num_tiles(pl->rows);
-    GMPE_HIP_CHECK(hipSetDevice(device));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const LossArgs a = loss_args(pl, nt);
-    const dim3 grid((unsigned)nt), block(TILE), one(1);
-    if (local) {
-        hipLaunchKernelGGL(k_loss_stats, grid, block, 0, st, a);
-        GMPE_HIP_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(k_loss_local, one, block, 0, st, a, nt, sp->local);
-        GMPE_HIP_CHECK(hipGetLastError());
-        return GMPE_OK;
-    }
-    hipLaunchKernelGGL(k_loss_prepare_shard, one, dim3(64), 0, st, a, sp->all, (int)sp->world);
-    GMPE_HIP_CHECK(hipGetLastError());
-    if (int rc = launch_rows(pl, a, nt, device, st)) return rc;
-    hipLaunchKernelGGL(k_loss_finish_shard, one, block, 0, st, a, nt);
-    GMPE_HIP_CHECK(hipGetLastError());
-    return GMPE_OK;
+    return run_plan(device, &sp->base, stream, local ? nullptr : sp->all, (int)sp->world, local ? sp->local : nullptr);
 }
 
 }  // extern "C"

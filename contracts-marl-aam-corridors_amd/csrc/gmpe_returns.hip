@@ -13,9 +13,10 @@
 // lane, Chan merges in a fixed butterfly order) into one partial; k_adv_stats merges the partials in a fixed order; k_adv_normalize
 // applies (adv - mean) / (std + 1e-5). No atomics: bitwise reproducible run to run.
 //
-// Over several shards (gmpe_compute_returns_shard): LOCAL stops after the fixed-order merge and writes the Stat itself; APPLY folds the shards' Stats with the
-// same chan from the left in index order, converts with the same code as k_adv_stats and normalises. The statistics are those of the whole batch, the same
-// bits on every shard; with one shard LOCAL + APPLY is gmpe_compute_returns bit for bit.
+// Over several shards (gmpe_compute_returns_shard): the same kernels and the same host path (run_plan). LOCAL is the call up to k_adv_stats, which writes the
+// merged Stat itself to `local`; APPLY starts at k_adv_stats, which folds the shards' Stats of `all` with the same chan from the left in index order instead of
+// merging partials, and normalises. The statistics are those of the whole batch, the same bits on every shard; with one shard LOCAL + APPLY is
+// gmpe_compute_returns bit for bit.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -188,27 +189,27 @@ __device__ __forceinline__ void mean_and_denominator(const Stat& t, float* __res
     }
 }
 
-__global__ __launch_bounds__(STAT_BLOCK) void k_adv_stats(const Stat* __restrict__ part, int64_t nparts, float* __restrict__ out) {
+// One kernel for the three callers. Source of the Stat: `all` (gmpe_compute_returns_shard, APPLY) = the shards' (n, mean, M2) as a left fold in index order
+// by one thread (the order is the result); otherwise this call's partials. Sink: `local` (LOCAL) = the Stat itself; otherwise (mean, std + 1e-5) to `out`.
+// The branch on `all` is uniform over the workgroup, so the barriers inside merge_partials are reached by all of it or by none.
+__global__ __launch_bounds__(STAT_BLOCK) void k_adv_stats(const Stat* __restrict__ part, int64_t nparts, const double* __restrict__ all, int world,
+                                                          double* __restrict__ local, float* __restrict__ out) {
     __shared__ Stat sh[STAT_BLOCK];
-    merge_partials(part, nparts, sh);
-    if (threadIdx.x == 0) mean_and_denominator(sh[0], out);
-}
-
-// gmpe_compute_returns_shard, LOCAL: the same merge, the Stat itself to `local` as (n, mean, M2)
-__global__ __launch_bounds__(STAT_BLOCK) void k_adv_stats_local(const Stat* __restrict__ part, int64_t nparts, double* __restrict__ local) {
-    __shared__ Stat sh[STAT_BLOCK];
-    merge_partials(part, nparts, sh);
-    if (threadIdx.x == 0) {
-        local[0] = sh[0].n; local[1] = sh[0].mean; local[2] = sh[0].m2;
+    Stat s;
+    if (all) {
+        if (threadIdx.x != 0) return;
+        s = Stat{all[0], all[1], all[2]};
+        for (int i = 1; i < world; ++i) s = chan(s, Stat{all[3 * i], all[3 * i + 1], all[3 * i + 2]});
+    } else {
+        merge_partials(part, nparts, sh);
+        if (threadIdx.x != 0) return;
+        s = sh[0];
     }
-}
-
-// gmpe_compute_returns_shard, APPLY: the shards' Stats as a left fold in index order (one thread: the order is the result)
-__global__ __launch_bounds__(64) void k_adv_stats_apply(const double* __restrict__ all, int world, float* __restrict__ out) {
-    if (threadIdx.x != 0) return;
-    Stat s{all[0], all[1], all[2]};
-    for (int i = 1; i < world; ++i) s = chan(s, Stat{all[3 * i], all[3 * i + 1], all[3 * i + 2]});
-    mean_and_denominator(s, out);
+    if (local) {
+        local[0] = s.n; local[1] = s.mean; local[2] = s.m2;
+    } else {
+        mean_and_denominator(s, out);
+    }
 }
 
 __global__ __launch_bounds__(NORM_BLOCK) void k_adv_normalize(const float* src, float* dst, const float* __restrict__ stats, int T, int64_t lanes,
@@ -298,8 +299,21 @@ int launch_returns(const gmpe_returns_plan* pl, const RetArgs& a, hipStream_t st
     return GMPE_OK;
 }
 
-// the raw advantages of a plan normalised with the (mean, std + 1e-5) at `stats`
-int launch_normalize(const gmpe_returns_plan* pl, const RetArgs& a, const float* stats, hipStream_t st) {
+// A checked plan, for both entry points: the recurrence (or the advantages alone) unless the shards' statistics are given (`all`), the statistics when
+// they are wanted, the normalisation unless the statistics are all that is asked for (`local`). (null, 0, null) is the unsharded call: 3 launches with
+// statistics, 1 without; LOCAL 2, APPLY 2.
+int run_plan(int device, const gmpe_returns_plan* pl, void* stream, const double* all, int world, double* local) {
+    const int64_t nparts = num_partials(pl->lanes);
+    GMPE_HIP_CHECK(hipSetDevice(device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const RetArgs a = returns_args(pl);
+    if (!all)
+        if (int rc = launch_returns(pl, a, st)) return rc;
+    if (!pl->normalized) return GMPE_OK;
+    float* stats = reinterpret_cast<float*>(static_cast<Stat*>(pl->workspace) + nparts);
+    hipLaunchKernelGGL(k_adv_stats, dim3(1), dim3(STAT_BLOCK), 0, st, a.part, nparts, all, world, local, stats);
+    GMPE_HIP_CHECK(hipGetLastError());
+    if (local) return GMPE_OK;
     hipLaunchKernelGGL(k_adv_normalize, dim3((unsigned)((pl->lanes + NORM_BLOCK - 1) / NORM_BLOCK)), dim3(NORM_BLOCK), 0, st, a.adv, pl->normalized, stats,
                        a.T, pl->lanes, pl->stride);
     GMPE_HIP_CHECK(hipGetLastError());
@@ -319,47 +333,17 @@ int gmpe_returns_workspace_bytes(int64_t lanes, size_t* bytes_out) {
 int gmpe_compute_returns(int device, const gmpe_returns_plan* pl, void* stream) {
     if (!pl) return fail(GMPE_ERR_INVALID_ARG, "gmpe_compute_returns: null plan");
     if (int rc = check_returns_plan("gmpe_compute_returns", pl, pl->normalized != nullptr)) return rc;
-    const int64_t nparts = num_partials(pl->lanes);
-    GMPE_HIP_CHECK(hipSetDevice(device));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const RetArgs a = returns_args(pl);
-    if (int rc = launch_returns(pl, a, st)) return rc;
-    if (pl->normalized) {
-        float* stats = reinterpret_cast<float*>(static_cast<Stat*>(pl->workspace) + nparts);
-        hipLaunchKernelGGL(k_adv_stats, dim3(1), dim3(STAT_BLOCK), 0, st, a.part, nparts, stats);
-        GMPE_HIP_CHECK(hipGetLastError());
-        if (int rc = launch_normalize(pl, a, stats, st)) return rc;
-    }
-    return GMPE_OK;
+    return run_plan(device, pl, stream, nullptr, 0, nullptr);
 }
 
 int gmpe_compute_returns_shard(int device, const gmpe_returns_shard_plan* sp, void* stream) {
     const char* name = "gmpe_compute_returns_shard";
     if (!sp) return fail(GMPE_ERR_INVALID_ARG, "gmpe_compute_returns_shard: null plan");
-    const gmpe_returns_plan* pl = &sp->base;
-    if (sp->phase != GMPE_SHARD_LOCAL && sp->phase != GMPE_SHARD_APPLY)
-        return fail(GMPE_ERR_INVALID_ARG, "gmpe_compute_returns_shard: phase must be GMPE_SHARD_LOCAL or GMPE_SHARD_APPLY");
-    if (sp->world < 1 || sp->world > GMPE_SHARD_MAX_WORLD) return fail(GMPE_ERR_INVALID_ARG, "gmpe_compute_returns_shard: world must be in 1 .. 4096");
+    if (int rc = gmpe::check_shard_args(name, sp->phase, sp->world, sp->local, sp->all)) return rc;
+    if (!sp->base.normalized) return fail(GMPE_ERR_INVALID_ARG, "gmpe_compute_returns_shard: normalized is required");
+    if (int rc = check_returns_plan(name, &sp->base, true)) return rc;
     const bool local = sp->phase == GMPE_SHARD_LOCAL;
-    const void* stat_ptr = local ? static_cast<const void*>(sp->local) : static_cast<const void*>(sp->all);
-    if (!stat_ptr || ((uintptr_t)stat_ptr & 7))
-        return fail(GMPE_ERR_INVALID_ARG, "gmpe_compute_returns_shard: LOCAL needs `local`, APPLY needs `all`, f64 device memory, 8-byte aligned");
-    if (!pl->normalized) return fail(GMPE_ERR_INVALID_ARG, "gmpe_compute_returns_shard: normalized is required");
-    if (int rc = check_returns_plan(name, pl, true)) return rc;
-    const int64_t nparts = num_partials(pl->lanes);
-    GMPE_HIP_CHECK(hipSetDevice(device));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const RetArgs a = returns_args(pl);
-    if (local) {
-        if (int rc = launch_returns(pl, a, st)) return rc;
-        hipLaunchKernelGGL(k_adv_stats_local, dim3(1), dim3(STAT_BLOCK), 0, st, a.part, nparts, sp->local);
-        GMPE_HIP_CHECK(hipGetLastError());
-        return GMPE_OK;
-    }
-    float* stats = reinterpret_cast<float*>(static_cast<Stat*>(pl->workspace) + nparts);
-    hipLaunchKernelGGL(k_adv_stats_apply, dim3(1), dim3(64), 0, st, sp->all, (int)sp->world, stats);
-    GMPE_HIP_CHECK(hipGetLastError());
-    return launch_normalize(pl, a, stats, st);
+    return run_plan(device, &sp->base, stream, local ? nullptr : sp->all, (int)sp->world, local ? sp->local : nullptr);
 }
 
 int gmpe_available_actions_from_dones(int device, const gmpe_avail_plan* pl, void* stream) {

@@ -436,6 +436,16 @@ def _dev_f32(name, t, shape, device, dtype=torch.float32):
     return t.data_ptr()
 
 
+def _workspace(nbytes, workspace, dev):
+    """`workspace` checked, or a fresh one of nbytes when None"""
+    if workspace is None:
+        return torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    if not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous() or \
+            workspace.numel() < nbytes:
+        raise ValueError("workspace must be a contiguous uint8 tensor of at least %d bytes on %s" % (nbytes, dev))
+    return workspace
+
+
 def _need_cuda(device):
     if device.type != "cuda":
         raise ValueError("the arrays must be CUDA (HIP) device tensors: these kernels have no CPU fallback")
@@ -533,11 +543,7 @@ def _returns_plan(rewards, masks, value_preds, returns, next_value, gamma, gae_l
     if normalized is not None:
         plan.normalized = ptr("normalized", normalized, half)
         plan.active_masks = ptr("active_masks", active_masks, full)
-        nbytes = returns_workspace_bytes(lanes)
-        if workspace is None:
-            workspace = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        elif workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous() or workspace.numel() < nbytes:
-            raise ValueError("workspace must be a contiguous uint8 tensor of at least %d bytes on %s" % (nbytes, dev))
+        workspace = _workspace(returns_workspace_bytes(lanes), workspace, dev)
         plan.workspace, plan.workspace_bytes = workspace.data_ptr(), workspace.numel()
     return plan, dev, (rewards, masks, value_preds, returns, next_value, bad_masks, denorm, advantages, active_masks, normalized, workspace)
 
@@ -560,12 +566,9 @@ def compute_returns_begin(rewards, masks, value_preds, returns, next_value=None,
         raise ValueError("a sharded compute_returns exchanges the statistics of the normalised advantages: normalized (and active_masks) are required")
     plan, dev, keep = _returns_plan(rewards, masks, value_preds, returns, next_value, gamma, gae_lambda, use_gae, use_proper_time_limits, bad_masks, denorm,
                                     advantages, active_masks, normalized, workspace, advantages_only)
-    _need_cuda(dev)
+    from . import learner_shards
     sp = _lib.GmpeReturnsShardPlan()
-    sp.base = plan
-    local = torch.empty((_lib.RETURNS_SHARD_STATS,), dtype=torch.float64, device=dev)
-    sp.phase, sp.world, sp.local = _lib.SHARD_LOCAL, 1, local.data_ptr()
-    _lib.check(_lib.load().gmpe_compute_returns_shard(dev.index, C.byref(sp), _stream_of(dev)), "gmpe_compute_returns_shard")
+    local = learner_shards.begin("gmpe_compute_returns_shard", sp, plan, _lib.RETURNS_SHARD_STATS, dev)
     return ReturnsShard(sp, dev, keep, returns, local)
 
 
@@ -576,14 +579,8 @@ def compute_returns_finish(handle, all_stats):
     from . import learner_shards
     if not isinstance(handle, ReturnsShard):
         raise TypeError("handle must come from compute_returns_begin")
-    if handle.done:
-        raise RuntimeError("compute_returns_finish was already called on this handle (in place it would normalise twice)")
-    world = learner_shards.check_all_stats(all_stats, handle.local, "compute_returns_finish")
-    _need_cuda(handle.device)
-    sp = handle.plan
-    sp.phase, sp.world, sp.all = _lib.SHARD_APPLY, world, all_stats.data_ptr()
-    _lib.check(_lib.load().gmpe_compute_returns_shard(handle.device.index, C.byref(sp), _stream_of(handle.device)), "gmpe_compute_returns_shard")
-    handle.done = True
+    learner_shards.finish("gmpe_compute_returns_shard", handle, handle.device, all_stats, "compute_returns_finish",
+                          "compute_returns_finish was already called on this handle (in place it would normalise twice)")
     return handle.returns
 
 

@@ -75,3 +75,41 @@ def gather(shards, local, what):
     if check_all_stats(all_stats, local, what) != world:
         raise ValueError("%s: shards.exchange returned %d rows, shards.world is %d" % (what, all_stats.shape[0], world))
     return all_stats
+
+
+# ------------------------------------------------------ the two-phase protocol of compute_returns_begin / _finish and ppo_losses_begin / _finish
+# Their handles (engine.ReturnsShard, ppo_loss.PPOLossShard) carry `.plan` (the shard plan), `.local` and `.done`. engine and ppo_loss import this
+# module inside their functions and this one imports them inside its own: neither import is at module level.
+def _launch(entry, sp, dev):
+    import ctypes as C
+    from . import _lib
+    from .engine import _stream_of
+    ordinal = dev.index if dev.index is not None else torch.cuda.current_device()
+    _lib.check(getattr(_lib.load(), entry)(ordinal, C.byref(sp), _stream_of(dev)), entry)
+
+
+def begin(entry, sp, base, k, dev):
+    """GMPE_SHARD_LOCAL of the C entry point `entry`: sp, its fresh shard plan, around the checked plan `base` -> `.local`, f64 [k] on dev"""
+    from . import _lib
+    from .engine import _need_cuda
+    _need_cuda(dev)
+    sp.base = base
+    local = torch.empty((k,), dtype=torch.float64, device=dev)
+    sp.phase, sp.world, sp.local = _lib.SHARD_LOCAL, 1, local.data_ptr()
+    _launch(entry, sp, dev)
+    return local
+
+
+def finish(entry, handle, dev, all_stats, what, again):
+    """GMPE_SHARD_APPLY on a handle of begin, once: `again` is the caller's RuntimeError text for a second call, `what` its name -> world"""
+    from . import _lib
+    from .engine import _need_cuda
+    if handle.done:
+        raise RuntimeError(again)
+    world = check_all_stats(all_stats, handle.local, what)
+    _need_cuda(dev)
+    sp = handle.plan
+    sp.phase, sp.world, sp.all = _lib.SHARD_APPLY, world, all_stats.data_ptr()
+    _launch(entry, sp, dev)
+    handle.done = True
+    return world

@@ -22,7 +22,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .engine import _need_cuda, _stream_of
+from .engine import _need_cuda, _stream_of, _workspace
 
 PPOPopArtLosses = collections.namedtuple("PPOPopArtLosses", ["actor_loss", "value_loss", "policy_loss", "dist_entropy", "ratio_mean", "action_log_probs",
                                                              "imp_weights", "values"])
@@ -166,15 +166,6 @@ def _bind_minibatch(plan, rows, K, flags, clip, delta, ent, cols, actions, avail
         setattr(plan, k, t.data_ptr())
 
 
-def _workspace(nbytes, workspace, dev):
-    if workspace is None:
-        return torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-    if not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous() or \
-            workspace.numel() < nbytes:
-        raise ValueError("workspace must be a contiguous uint8 tensor of at least %d bytes on %s" % (nbytes, dev))
-    return workspace
-
-
 class _Attach(torch.autograd.Function):
     """A scalar the kernel computed from `x`, with its gradient d scalar / d x already known: backward multiplies it by the incoming scalar. The two
     losses are two such nodes, so each is backpropagated on its own, as ppo_update does."""
@@ -285,11 +276,9 @@ def ppo_losses_begin(logits, values, sample_or_fields, args, value_normalizer=No
     """The first phase of ppo_losses over one shard of a minibatch (gmpe_ppo_loss_shard, GMPE_SHARD_LOCAL), same arguments: the shard's double sums in
     ppo_losses' own merge order and its row count go to the handle's `.local`; the ValueNorm is not touched yet. -> PPOLossShard"""
     c = _Call(logits, values, sample_or_fields, args, value_normalizer, workspace)
+    from . import learner_shards
     sp = _lib.GmpePpoLossShardPlan()
-    sp.base = c.plan
-    local = torch.empty((_lib.PPO_SHARD_STATS,), dtype=torch.float64, device=c.dev)
-    sp.phase, sp.world, sp.local = _lib.SHARD_LOCAL, 1, local.data_ptr()
-    _lib.check(_lib.load().gmpe_ppo_loss_shard(_ordinal(c.dev), C.byref(sp), _stream_of(c.dev)), "gmpe_ppo_loss_shard")
+    local = learner_shards.begin("gmpe_ppo_loss_shard", sp, c.plan, _lib.PPO_SHARD_STATS, c.dev)
     return PPOLossShard(c, sp, local)
 
 
@@ -303,14 +292,9 @@ def ppo_losses_finish(handle, all_stats, reduce="sum"):
     _reduce(reduce)
     if not isinstance(handle, PPOLossShard):
         raise TypeError("handle must come from ppo_losses_begin")
-    if handle.done:
-        raise RuntimeError("ppo_losses_finish was already called on this handle (it would update the ValueNorm twice)")
-    world = learner_shards.check_all_stats(all_stats, handle.local, "ppo_losses_finish")
-    c, sp = handle.call, handle.plan
-    _need_cuda(c.dev)
-    sp.phase, sp.world, sp.all = _lib.SHARD_APPLY, world, all_stats.data_ptr()
-    _lib.check(_lib.load().gmpe_ppo_loss_shard(_ordinal(c.dev), C.byref(sp), _stream_of(c.dev)), "gmpe_ppo_loss_shard")
-    handle.done = True
+    c = handle.call
+    world = learner_shards.finish("gmpe_ppo_loss_shard", handle, c.dev, all_stats, "ppo_losses_finish",
+                                  "ppo_losses_finish was already called on this handle (it would update the ValueNorm twice)")
     return c.losses(world if reduce == "mean" else 1)
 
 

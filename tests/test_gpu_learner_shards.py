@@ -308,6 +308,35 @@ def test_loss_world_1_is_the_existing_call_bit_for_bit(fam, K):
         gmpe.ppo_losses_finish(one["handle"], torch.zeros((1, 4), dtype=torch.float64, device="cuda"))
 
 
+def test_plain_call_after_a_sharded_one_in_the_same_workspace_is_the_fresh_call_bit_for_bit():
+    """The unsharded finish reads its row count from the header word the sharded APPLY also writes (there: the global count, 1030). One workspace
+    tensor through both shards of 257 + 773, then through a plain call over the 257 rows: that call must leave what it leaves in a fresh workspace."""
+    import torch
+    case = ("off_vn", 5, LS.LOSS_SPLITS[0], None)
+    inp, c, st, ref = LS.loss_case(case)
+    bounds = LS.bounds(case[2])
+    ws = torch.zeros(gmpe.ppo_loss.workspace_bytes(max(case[2])), dtype=torch.uint8, device="cuda")
+    rows = torch.as_tensor(np.stack([LS.shard_sums(LS.rows_of(inp, lo, hi)) for lo, hi in bounds]), device="cuda")
+    for rank, (lo, hi) in enumerate(bounds):
+        lg, vl, f, vn = _shard_tensors(torch, LS.rows_of(inp, lo, hi), c, st)
+        res = gmpe.ppo_losses(lg, vl, f, _args(c), vn, workspace=ws, shards=_Rows(rows, rank))
+        assert float(res.ratio_mean) != 0.0
+    got = []
+    for workspace in (ws, None):
+        lg, vl, f, vn = _shard_tensors(torch, LS.rows_of(inp, *bounds[0]), c, st)
+        res = gmpe.ppo_losses(lg, vl, f, _args(c), vn, workspace=workspace)
+        res.actor_loss.backward()
+        res.value_loss.backward()
+        g = {k: getattr(res, k).detach().cpu().numpy() for k in res._fields}
+        g.update(grad_logits=lg.grad.cpu().numpy(), grad_values=vl.grad.cpu().numpy(), **vn.state())
+        got.append(g)
+    used, fresh = got
+    assert sorted(used) == sorted(fresh) and len(used) == len(SCALARS) + 2 + 2 + 3
+    for k, v in fresh.items():
+        assert np.isfinite(v).all(), k
+        assert np.array_equal(_bits(used[k]), _bits(v)), k
+
+
 def test_reduce_mean_is_sum_times_world_bit_for_bit():
     import torch
     case = ("on_vn", 25, (257, 773), None)

@@ -1,6 +1,6 @@
 """Bit-for-bit A/B of two builds of libgmpe.so over the three entry points that share gmpe_ppo_rows.h: gmpe_ppo_loss, gmpe_ppo_loss_popart and
-gmpe_act_sample, called through their C plans on fixed inputs. The GPU suites bound the losses against float64, so they would not see a changed
-rounding; this does.
+gmpe_act_sample, and over gmpe_compute_returns and the two sharded entry points, called through their C plans on fixed inputs. The GPU suites bound
+the losses against float64, so they would not see a changed rounding; this does.
 
     GMPE_LIB=/path/to/libgmpe_parent.so python tools/learner_ab_bits.py dump a.npz     # one process per build
     python tools/learner_ab_bits.py dump b.npz
@@ -14,6 +14,11 @@ H in 1, 7, 64, 1024 laid over (rows, K) as a Latin square, so every (rows, H) an
 dones_prev and from neither x deterministic 0 / 1 x draw_dev given (the counter after the call is kept) / absent. Every call is tiny.
 Kept per call: the seven float64 scalars, every gradient, action_log_probs, imp_weights, values, the updated normaliser state and the rescaled layer;
 action_idx, both action arrays, the log-probs.
+returns/: gmpe_compute_returns with normalised advantages on tests/returns_lib.py's branch_inputs (T in 8, 9, 17, 65 at 65 lanes; the recurrence in its
+eight branches and the advantages alone with and without a denormaliser) and on every tests/learner_shards_lib.py RETURNS_CASES x both paths; the same
+inputs through gmpe_compute_returns_shard LOCAL then APPLY at world 1, and the cases at their own split with `all` stacked from the shards' `local`.
+shard/: gmpe_ppo_loss_shard LOCAL then APPLY for rows in 1, 257, 600 x K in 1, 5, 64 x all flags on / off at world 1, and 1030 rows split 1 + 256 + 773.
+Kept: returns, value_preds, raw and normalised advantages, `local`; the loss call's outputs as above with `local`.
 """
 import ctypes as C
 import itertools
@@ -45,7 +50,7 @@ def dump(path):
 
     def put(a, off, dtype=None):
         """`a` on the device, its base 16-byte aligned (off 0) or one element past that (off 1)."""
-        src = torch.from_numpy(np.ascontiguousarray(a, dtype))
+        src = torch.from_numpy(np.array(a, dtype=dtype, order="C"))      # a copy: the cases are read-only arrays
         buf = torch.zeros(src.numel() + 1, dtype=src.dtype, device=dev)
         t = buf[off:off + src.numel()].view(src.shape)
         t.copy_(src)
@@ -147,6 +152,97 @@ def dump(path):
                 plan.actions_f32, plan.actions_i64 = ptr(out["actions_f32"]), ptr(out["actions_i64"])
                 _lib.check(lib.gmpe_act_sample(dev.index, C.byref(plan), stream), "gmpe_act_sample")
                 save("act/B%d_K%d_off%d_%s_det%d_ctr%d" % (B, K, off, source, det, counter), **out)
+    # ---- gmpe_compute_returns and gmpe_compute_returns_shard
+    import learner_shards_lib as LS
+    import returns_lib
+
+    def returns_plan(d, flags, denorm):
+        """d: float32 arrays [T(+1), lanes, 1] -> (plan, the arrays it writes)"""
+        T, L = d["value_preds"].shape[0] - 1, d["value_preds"].shape[1]
+        plan = _lib.GmpeReturnsPlan()
+        plan.num_steps, plan.flags, plan.lanes, plan.stride, plan.gamma, plan.gae_lambda = T, flags, L, L, 0.99, 0.95
+        out = dict(value_preds=put(d["value_preds"], 0), returns=put(d["returns"], 0), advantages=blank((T, L, 1), 0), normalized=blank((T, L, 1), 0))
+        for k, t in out.items():
+            setattr(plan, k, ptr(t))
+        for k in ("rewards", "masks", "bad_masks", "next_value", "active_masks"):
+            if k in d and not (flags & _lib.RETURNS_ADVANTAGES_ONLY and k != "active_masks"):
+                setattr(plan, k, ptr(put(d[k], 0)))
+        if denorm:
+            plan.denorm_mean, plan.denorm_std = (ptr(put(np.full(1, v, np.float32), 0)) for v in returns_lib.DENORM)
+        n = C.c_size_t()
+        _lib.check(lib.gmpe_returns_workspace_bytes(L, C.byref(n)), "gmpe_returns_workspace_bytes")
+        ws = torch.zeros(n.value, dtype=torch.uint8, device=dev)
+        keep.append(ws)
+        plan.workspace, plan.workspace_bytes = ws.data_ptr(), n.value
+        return plan, out
+
+    def shard_call(entry, sp, phase, world, local, all_stats):
+        sp.phase, sp.world, sp.local, sp.all = phase, world, ptr(local), ptr(all_stats)
+        _lib.check(getattr(lib, entry)(dev.index, C.byref(sp), stream), entry)
+
+    def two_phase(entry, Shard, k, plans):
+        """LOCAL on every shard's plan, `all` stacked from their `local`, APPLY on every shard -> the [world, k] tensor"""
+        sps, locs = [], []
+        for plan in plans:
+            sp = Shard()
+            sp.base = plan
+            locs.append(torch.zeros(k, dtype=torch.float64, device=dev))
+            shard_call(entry, sp, _lib.SHARD_LOCAL, 1, locs[-1], None)
+            sps.append(sp)
+        all_stats = torch.stack(locs).contiguous()
+        for sp in sps:
+            shard_call(entry, sp, _lib.SHARD_APPLY, len(plans), None, all_stats)
+        return all_stats
+
+    def returns_group(tag, d, flags, denorm, split):
+        plan, out = returns_plan(d, flags, denorm)
+        _lib.check(lib.gmpe_compute_returns(dev.index, C.byref(plan), stream), "gmpe_compute_returns")
+        save("returns/%s/plain" % tag, **out)
+        for name, bounds in (("world1", [(0, d["value_preds"].shape[1])]),) + ((("split", LS.bounds(split)),) if split else ()):
+            made = [returns_plan({k: np.ascontiguousarray(v[:, lo:hi] if k != "next_value" else v[lo:hi]) for k, v in d.items()}, flags, denorm)
+                    for lo, hi in bounds]
+            all_stats = two_phase("gmpe_compute_returns_shard", _lib.GmpeReturnsShardPlan, _lib.RETURNS_SHARD_STATS, [m[0] for m in made])
+            outs = {"%s_s%d" % (k, i): t for i, m in enumerate(made) for k, t in m[1].items()}
+            save("returns/%s/%s" % (tag, name), local=all_stats, **outs)
+
+    for T in (8, 9, 17, 65):
+        d = returns_lib.branch_inputs(T)
+        for gae, proper, dn in itertools.product((0, 1), repeat=3):
+            returns_group("branch_T%d_gae%d_proper%d_dn%d" % (T, gae, proper, dn), d, gae * _lib.RETURNS_GAE | proper * _lib.RETURNS_PROPER_TIME_LIMITS, dn, None)
+        for dn in (0, 1):
+            returns_group("branch_T%d_only_dn%d" % (T, dn), d, _lib.RETURNS_ADVANTAGES_ONLY, dn, None)
+    for name in LS.RETURNS_CASES:
+        adv, am, split = LS.returns_case(name)
+        for which in LS.PATHS:
+            d = dict(returns_lib.prescribed_inputs(adv, which), active_masks=am.reshape(am.shape + (1,)))
+            returns_group("%s_%s" % (name, which), d, _lib.RETURNS_ADVANTAGES_ONLY if which == "advantages" else 0, 0, split)
+
+    # ---- gmpe_ppo_loss_shard
+    def loss_plan(inp, K, on):
+        B = inp["logits"].shape[0]
+        plan = _lib.GmpePpoLossPlan()
+        out = minibatch(plan, inp, K, 0, False, True, 31 if on else 0)
+        plan.values = ptr(put(inp["values"], 0))
+        out["grad_values"] = blank((B, 1), 0)
+        plan.grad_values = ptr(out["grad_values"])
+        if on:
+            for k, v in (("running_mean", 0.3), ("running_mean_sq", 1.7), ("debiasing_term", 0.5)):
+                out[k] = put(np.full(1, v, np.float32), 0)
+                setattr(plan, k, ptr(out[k]))
+        n = C.c_size_t()
+        _lib.check(lib.gmpe_ppo_loss_workspace_bytes(B, C.byref(n)), "gmpe_ppo_loss_workspace_bytes")
+        ws = torch.zeros(n.value, dtype=torch.uint8, device=dev)
+        keep.append(ws)
+        plan.workspace, plan.workspace_bytes = ws.data_ptr(), n.value
+        return plan, out
+
+    for B, split in [(B, (B,)) for B in (1, 257, 600)] + [(LS.ROWS, LS.LOSS_SPLITS[1])]:
+        for K, on in itertools.product((1, 5, 64), (True, False)):
+            inp = ppo_loss_lib.family("edges", B, K, masks="mixed")
+            made = [loss_plan(LS.rows_of(inp, lo, hi), K, on) for lo, hi in LS.bounds(split)]
+            all_stats = two_phase("gmpe_ppo_loss_shard", _lib.GmpePpoLossShardPlan, _lib.PPO_SHARD_STATS, [m[0] for m in made])
+            outs = {"%s_s%d" % (k, i): t for i, m in enumerate(made) for k, t in m[1].items()}
+            save("shard/B%d_K%d_fl%d_%s" % (B, K, on, "+".join(str(x) for x in split)), local=all_stats, **outs)
     np.savez(path, **kept)
     print("dump: %d arrays, %d elements (%d non-zero) from %s -> %s" % (len(kept), sum(a.size for a in kept.values()),
                                                                        sum(int(np.count_nonzero(a)) for a in kept.values()), _lib.LIB_PATH, path))
@@ -172,7 +268,7 @@ def compare(pa, pb):
         if d:
             print("%s: %d of %d elements differ" % (k, d, x.size))
             differing += d
-    per = {p: sum(1 for k in names if k.startswith(p)) for p in ("loss/", "popart_", "act/")}
+    per = {p: sum(1 for k in names if k.startswith(p)) for p in ("loss/", "popart_", "act/", "returns/", "shard/")}
     print("compare: %d arrays (%s), %d elements, %d differing" % (len(names), ", ".join("%s %d" % (p.rstrip("/_"), n) for p, n in per.items()), elements,
                                                                  differing))
     return 1 if differing or not names else 0
