@@ -13,7 +13,7 @@ __all__ = ["config", "make_config", "config_from_args"]
 
 def __getattr__(name):
     # torch / HIP-dependent modules are imported on first use
-    if name in ("engine", "vec_env", "spaces", "_lib", "sharding", "rollout", "minibatch", "evaluate", "ppo_loss", "act", "learner_shards"):
+    if name in ("engine", "vec_env", "spaces", "_lib", "sharding", "rollout", "minibatch", "evaluate", "ppo_loss", "act", "learner_shards", "gru"):
         import importlib
         return importlib.import_module("." + name, __name__)
     if name in ("BatchedGraphMPEVecEnv", "MultiDeviceGraphMPEVecEnv", "GraphMPEEnv", "make_train_env", "make_eval_env"):
@@ -28,6 +28,9 @@ def __getattr__(name):
     if name == "sample_actions":
         from . import act
         return act.sample_actions
+    if name in ("rnn_layer", "rnn_workspace_bytes"):
+        from . import gru
+        return getattr(gru, name)
     if name in ("GmpeEngine", "compute_returns_begin", "compute_returns_finish"):
         from . import engine
         return getattr(engine, name)

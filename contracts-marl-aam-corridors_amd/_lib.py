@@ -21,7 +21,8 @@ SYMBOLS = ["gmpe_abi_version", "gmpe_last_error", "gmpe_obs_dim", "gmpe_node_fea
            "gmpe_insert_learner", "gmpe_episode_record", "gmpe_episode_metrics", "gmpe_episode_summary",
            "gmpe_minibatch_edges", "gmpe_minibatch_edges_workspace_bytes", "gmpe_episode_record_series",
            "gmpe_ppo_loss", "gmpe_ppo_loss_workspace_bytes", "gmpe_ppo_loss_popart", "gmpe_ppo_loss_popart_workspace_bytes",
-           "gmpe_act_sample", "gmpe_compute_returns_shard", "gmpe_ppo_loss_shard"]
+           "gmpe_act_sample", "gmpe_compute_returns_shard", "gmpe_ppo_loss_shard",
+           "gmpe_gru_workspace_bytes", "gmpe_gru_forward", "gmpe_gru_backward"]
 
 
 class GmpeOutputs(C.Structure):
@@ -187,6 +188,19 @@ class GmpeActPlan(C.Structure):
                 ("action_idx", C.c_void_p), ("log_probs", C.c_void_p), ("actions_f32", C.c_void_p), ("actions_i64", C.c_void_p)]
 
 
+GRU_ROW_TILE = 32        # GMPE_GRU_ROW_TILE of include/gmpe.h; tests/gru_lib.py TILE is the third copy — tests/test_gru_host.py compiles against the header and ties the three together
+
+
+class GmpeGruPlan(C.Structure):
+    """gmpe_gru_plan (include/gmpe.h): the policy's masked GRU layer with its LayerNorm, forward and backward."""
+    _fields_ = [("steps", C.c_int64), ("rows", C.c_int64), ("in_dim", C.c_int32), ("hidden", C.c_int32), ("eps", C.c_double),
+                ("x", C.c_void_p), ("hxs", C.c_void_p), ("masks", C.c_void_p), ("weight_ih", C.c_void_p), ("weight_hh", C.c_void_p),
+                ("bias_ih", C.c_void_p), ("bias_hh", C.c_void_p), ("ln_weight", C.c_void_p), ("ln_bias", C.c_void_p), ("features", C.c_void_p),
+                ("hxs_out", C.c_void_p), ("grad_features", C.c_void_p), ("grad_hxs_out", C.c_void_p), ("grad_x", C.c_void_p), ("grad_hxs", C.c_void_p),
+                ("grad_weight_ih", C.c_void_p), ("grad_weight_hh", C.c_void_p), ("grad_bias_ih", C.c_void_p), ("grad_bias_hh", C.c_void_p),
+                ("grad_ln_weight", C.c_void_p), ("grad_ln_bias", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
 class GmpeError(RuntimeError):
     pass
 
@@ -253,6 +267,9 @@ def load():
     lib.gmpe_act_sample.argtypes = [I, C.POINTER(GmpeActPlan), P]
     lib.gmpe_compute_returns_shard.argtypes = [I, C.POINTER(GmpeReturnsShardPlan), P]
     lib.gmpe_ppo_loss_shard.argtypes = [I, C.POINTER(GmpePpoLossShardPlan), P]
+    lib.gmpe_gru_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]
+    lib.gmpe_gru_forward.argtypes = [I, C.POINTER(GmpeGruPlan), P]
+    lib.gmpe_gru_backward.argtypes = [I, C.POINTER(GmpeGruPlan), P]
     from .config import ABI_VERSION
     if lib.gmpe_abi_version() != ABI_VERSION:
         raise GmpeError("libgmpe.so ABI version mismatch")

@@ -627,6 +627,71 @@ typedef struct gmpe_act_plan {
 } gmpe_act_plan;
 int gmpe_act_sample(int device, const gmpe_act_plan* plan, void* stream);
 
+/* ---- The policy's masked GRU layer (handle-less): RNNLayer.forward (onpolicy/algorithms/utils/rnn.py:23-79) with recurrent_N == 1 ----
+ * The layer in front of the action head (GR_Actor) and of the value head (GR_Critic): nn.GRU(D, H) driven step by step with the state multiplied by
+ * the step's mask, then nn.LayerNorm(H). All arrays float32, contiguous. For every row k of `rows` independently, t = 0 .. steps-1 (x, masks, features
+ * and grad_* of the [steps * rows] arrays are time-major: row t * rows + k):
+ *     h <- h * masks[t, k]
+ *     r = sigmoid(W_ir x_t + b_ir + W_hr h + b_hr),  z = sigmoid(W_iz x_t + b_iz + W_hz h + b_hz),  n = tanh(W_in x_t + b_in + r * (W_hn h + b_hn))
+ *     h <- (1 - z) * n + z * h
+ *     features[t, k] = LayerNorm(h)            biased variance, eps inside the square root
+ * and hxs_out[k] = the last h, not normalised. For masks in {0, 1} this is the reference's segment loop (it splits the sequence at every step at which
+ * ANY row has a zero and multiplies every row by its own mask there; a row whose mask is 1 is untouched) and, with steps == 1, its rollout branch.
+ * Masks outside {0, 1} are undefined here (in the reference their effect depends on the other rows of the batch) and are not checked.
+ * Supported: in_dim == hidden == 64 (every shipped checkpoint); anything else is refused before any launch.
+ * Arithmetic of one row (float32, a function of (in_dim, hidden) alone — not of steps, rows, the row's place in a tile or its neighbours): every
+ * pre-activation is one fmaf chain in ascending k, r and z from b_i + b_h over x then over h, the two n terms from b_in over x and from b_hn over h;
+ * sigmoid = 1 / (1 + expf(-a)), tanhf; the LayerNorm sums are xor trees over the 64 columns (offsets 32, 16, .. 1).
+ * gmpe_gru_forward: ONE launch. With a workspace (a training plan) it keeps r, z, n, W_hn h + b_hn, h and the LayerNorm mean / rstd of every (t, k) in
+ * it; with workspace == NULL (the rollout step, under no_grad) it writes nothing but features and hxs_out, and the gradient pointers may be NULL.
+ * hxs_out may be hxs itself in a forward-only plan; any other overlap of hxs_out with an input, a parameter, features or the workspace is refused.
+ * gmpe_gru_backward (after gmpe_gru_forward on the same plan's inputs and workspace; may be repeated): THREE launches whatever steps, rows and masks.
+ *   1 back-propagation through time, per tile of GMPE_GRU_ROW_TILE rows, t descending: LayerNorm backward, the gate gradients (kept in the workspace),
+ *     grad_x[t, k] and the state gradient, multiplied by masks[t, k] on its way to step t-1 — so nothing flows across a step whose mask is 0 and
+ *     grad_hxs of a row with masks[0] == 0 is 0; and the tile's double sums of the bias and LayerNorm gradients (t descending, the rows of a wave
+ *     ascending, then the four waves in wave order);
+ *   2 the weight gradients as double sums of exact products over P = min(128, ceil(steps * rows / 32)) contiguous parts of the steps * rows rows, in
+ *     ascending row order inside a part;
+ *   3 the parts added in ascending part order (weights), the tiles as 16 interleaved slices in ascending order and the slices in slice order (biases,
+ *     LayerNorm), each rounded to float32 once.
+ *   So a parameter gradient's summation order is a function of (steps, rows) alone. grad_hxs_out == NULL stands for zeros.
+ * No atomics, no allocation, no host synchronisation; capturable. */
+#define GMPE_GRU_ROW_TILE 32
+typedef struct gmpe_gru_plan {
+    int64_t steps;                      /* L >= 1                                                                                     */
+    int64_t rows;                       /* Nb >= 1: the rows of hxs (chunks of a recurrent minibatch, or N*A of a rollout step)       */
+    int32_t in_dim;                     /* D = 64                                                                                     */
+    int32_t hidden;                     /* H = 64                                                                                     */
+    double eps;                         /* LayerNorm.eps > 0                                                                          */
+    const float* x;                     /* [steps * rows, D]                                                                          */
+    const float* hxs;                   /* [rows, H] (the [rows, 1, H] state)                                                         */
+    const float* masks;                 /* [steps * rows]                                                                             */
+    const float* weight_ih;             /* [3H, D] gate order r, z, n                                                                 */
+    const float* weight_hh;             /* [3H, H]                                                                                    */
+    const float* bias_ih;               /* [3H]                                                                                       */
+    const float* bias_hh;               /* [3H]                                                                                       */
+    const float* ln_weight;             /* [H]                                                                                        */
+    const float* ln_bias;               /* [H]                                                                                        */
+    float* features;                    /* [steps * rows, H]                                                                          */
+    float* hxs_out;                     /* [rows, H]                                                                                  */
+    const float* grad_features;         /* [steps * rows, H]; backward                                                                */
+    const float* grad_hxs_out;          /* [rows, H] or NULL (zeros); backward                                                        */
+    float* grad_x;                      /* [steps * rows, D]; backward, like every grad_* below                                       */
+    float* grad_hxs;                    /* [rows, H]                                                                                  */
+    float* grad_weight_ih;              /* [3H, D]                                                                                    */
+    float* grad_weight_hh;              /* [3H, H]                                                                                    */
+    float* grad_bias_ih;                /* [3H]                                                                                       */
+    float* grad_bias_hh;                /* [3H]                                                                                       */
+    float* grad_ln_weight;              /* [H]                                                                                        */
+    float* grad_ln_bias;                /* [H]                                                                                        */
+    void* workspace;                    /* gmpe_gru_workspace_bytes(steps, rows, hidden, 1) bytes, 8-byte aligned; NULL: forward only */
+    size_t workspace_bytes;
+} gmpe_gru_plan;
+/* want_backward == 0: 0 bytes (the forward-only plan takes no workspace). */
+int gmpe_gru_workspace_bytes(int64_t steps, int64_t rows, int32_t hidden, int32_t want_backward, size_t* bytes_out);
+int gmpe_gru_forward(int device, const gmpe_gru_plan* plan, void* stream);
+int gmpe_gru_backward(int device, const gmpe_gru_plan* plan, void* stream);
+
 /* ---- Evaluation of a policy over a batch of episodes (handle-less): GMPERunner.render(get_metrics=True) as one episode per env ----
  * (onpolicy/runner/shared/graph_mpe_runner.py:526-1060, base_runner.py:194-574). Every env plays one episode from a reset; the caller's policy acts,
  * the engine steps, gmpe_episode_record books the step. No allocation, no host synchronisation, every launch on `stream`.
