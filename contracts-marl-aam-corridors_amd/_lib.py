@@ -22,7 +22,8 @@ SYMBOLS = ["gmpe_abi_version", "gmpe_last_error", "gmpe_obs_dim", "gmpe_node_fea
            "gmpe_minibatch_edges", "gmpe_minibatch_edges_workspace_bytes", "gmpe_episode_record_series",
            "gmpe_ppo_loss", "gmpe_ppo_loss_workspace_bytes", "gmpe_ppo_loss_popart", "gmpe_ppo_loss_popart_workspace_bytes",
            "gmpe_act_sample", "gmpe_compute_returns_shard", "gmpe_ppo_loss_shard",
-           "gmpe_gru_workspace_bytes", "gmpe_gru_forward", "gmpe_gru_backward"]
+           "gmpe_gru_workspace_bytes", "gmpe_gru_forward", "gmpe_gru_backward",
+           "gmpe_mlp_workspace_bytes", "gmpe_mlp_forward", "gmpe_mlp_backward"]
 
 
 class GmpeOutputs(C.Structure):
@@ -201,6 +202,25 @@ class GmpeGruPlan(C.Structure):
                 ("grad_ln_weight", C.c_void_p), ("grad_ln_bias", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
+MLP_ROW_TILE, MLP_MAX_PARTS, MLP_MAX_IN, MLP_MAX_LAYERS = 32, 4, 256, 3      # GMPE_MLP_* of include/gmpe.h; tests/test_mlp_host.py compiles against the header
+MLP_RELU, MLP_TANH = 0, 1
+
+
+class GmpeMlpLayer(C.Structure):
+    """gmpe_mlp_layer (include/gmpe.h): one Linear -> activation -> LayerNorm of the MLPBase, with its gradients."""
+    _fields_ = [("weight", C.c_void_p), ("bias", C.c_void_p), ("ln_weight", C.c_void_p), ("ln_bias", C.c_void_p), ("eps", C.c_double),
+                ("grad_weight", C.c_void_p), ("grad_bias", C.c_void_p), ("grad_ln_weight", C.c_void_p), ("grad_ln_bias", C.c_void_p)]
+
+
+class GmpeMlpPlan(C.Structure):
+    """gmpe_mlp_plan (include/gmpe.h): the policy's MLPBase over the parts of its input, forward and backward."""
+    _fields_ = [("rows", C.c_int64), ("hidden", C.c_int32), ("layer_n", C.c_int32), ("activation", C.c_int32), ("feature_norm", C.c_int32),
+                ("n_parts", C.c_int32), ("reserved", C.c_int32), ("part", C.c_void_p * MLP_MAX_PARTS), ("part_dim", C.c_int32 * MLP_MAX_PARTS),
+                ("grad_part", C.c_void_p * MLP_MAX_PARTS), ("fn_weight", C.c_void_p), ("fn_bias", C.c_void_p), ("fn_eps", C.c_double),
+                ("grad_fn_weight", C.c_void_p), ("grad_fn_bias", C.c_void_p), ("layer", GmpeMlpLayer * MLP_MAX_LAYERS), ("features", C.c_void_p),
+                ("grad_features", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
 class GmpeError(RuntimeError):
     pass
 
@@ -270,6 +290,9 @@ def load():
     lib.gmpe_gru_workspace_bytes.argtypes = [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]
     lib.gmpe_gru_forward.argtypes = [I, C.POINTER(GmpeGruPlan), P]
     lib.gmpe_gru_backward.argtypes = [I, C.POINTER(GmpeGruPlan), P]
+    lib.gmpe_mlp_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]
+    lib.gmpe_mlp_forward.argtypes = [I, C.POINTER(GmpeMlpPlan), P]
+    lib.gmpe_mlp_backward.argtypes = [I, C.POINTER(GmpeMlpPlan), P]
     from .config import ABI_VERSION
     if lib.gmpe_abi_version() != ABI_VERSION:
         raise GmpeError("libgmpe.so ABI version mismatch")

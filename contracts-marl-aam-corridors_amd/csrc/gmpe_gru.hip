@@ -33,6 +33,7 @@
 #include <string>
 
 #include "gmpe_host.h"          // include/gmpe.h, the error text, GMPE_HIP_CHECK, raise_dynamic_lds_once
+#include "gmpe_wgrad.h"         // the weight-gradient parts and the ordered finish sums, shared with gmpe_mlp.hip
 
 #pragma clang fp contract(off)
 
@@ -43,8 +44,9 @@ constexpr int G3 = 3 * H, G4 = 4 * H;
 constexpr int TILE = GMPE_GRU_ROW_TILE, BLOCK = 256, NW = BLOCK / 64, R = TILE / NW;     // R rows per wave
 constexpr int WS = G3 + 1;                              // row stride of the transposed weights in LDS
 constexpr int NCOL = 6 * H;                             // dr, dz, dn, dhn (the bias gradients), LayerNorm weight, bias
-constexpr int MAX_PARTS = 128, PART_ROWS = 32;          // k_gru_wgrad: parts, and rows per LDS stage
-constexpr int FIN_COLS = 16, FIN_SLICES = BLOCK / FIN_COLS;
+using gmpe_wgrad::FIN_COLS;                             // k_gru_wgrad's parts and k_gru_finish's slices: gmpe_wgrad.h
+using gmpe_wgrad::FIN_SLICES;
+static_assert(H == gmpe_wgrad::H && BLOCK == gmpe_wgrad::BLOCK, "gmpe_wgrad.h's workgroup");
 constexpr int MAX_GRID = 256;                           // one workgroup per CU fits (LDS); tiles beyond that are looped over
 static_assert(R == 8 && TILE == NW * R, "eight rows per wave");
 constexpr size_t FWD_LDS = (size_t)(2 * H * WS + 2 * NW * R * H) * sizeof(float);
@@ -264,42 +266,16 @@ __global__ __launch_bounds__(BLOCK) void k_gru_bptt(GruArgs p) {
 // backward 2: part blockIdx.x of the rows, matrix blockIdx.y (0 .. 2: W_ih gates r, z, n; 3 .. 5: W_hh): out[j][d] = sum over the part's rows of
 // dG[m][gate][j] * B[m][d], B = x or the masked previous state. Thread: j = tid / 4, d = 16 * (tid % 4) .. + 15.
 __global__ __launch_bounds__(BLOCK) void k_gru_wgrad(GruArgs p) {
-    __shared__ __attribute__((aligned(16))) float As[PART_ROWS][H];
-    __shared__ __attribute__((aligned(16))) float Bs[PART_ROWS][H];
-    const int tid = threadIdx.x, y = blockIdx.y, j = tid >> 2, d0 = (tid & 3) * 16;
+    const int y = blockIdx.y;
     const int col = y < 3 ? y * H : (y == 5 ? 3 * H : (y - 3) * H);             // column block of dG
     const int64_t m0 = (int64_t)blockIdx.x * p.part_rows, m1 = m0 + p.part_rows < p.M ? m0 + p.part_rows : p.M;
-    double acc[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.0;
-    for (int64_t ms = m0; ms < m1; ms += PART_ROWS) {
-        for (int i = tid; i < PART_ROWS * H; i += BLOCK) {
-            const int mm = i >> 6, k = i & 63;
-            const int64_t m = ms + mm;
-            float a = 0.0f, b = 0.0f;
-            if (m < m1) {
-                a = p.dG[m * G4 + col + k];
-                if (y < 3) b = p.x[m * H + k];
-                else b = __fmul_rn(m >= p.Nb ? p.sH[(m - p.Nb) * H + k] : p.hxs[m * H + k], p.masks[m]);
-            }
-            As[mm][k] = a; Bs[mm][k] = b;
-        }
-        __syncthreads();
-#pragma unroll 2
-        for (int mm = 0; mm < PART_ROWS; ++mm) {
-            const double a = (double)As[mm][j];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float4 b = *reinterpret_cast<const float4*>(&Bs[mm][d0 + 4 * q]);
-                acc[4 * q + 0] = fma(a, (double)b.x, acc[4 * q + 0]); acc[4 * q + 1] = fma(a, (double)b.y, acc[4 * q + 1]);
-                acc[4 * q + 2] = fma(a, (double)b.z, acc[4 * q + 2]); acc[4 * q + 3] = fma(a, (double)b.w, acc[4 * q + 3]);
-            }
-        }
-        __syncthreads();
-    }
-    double* o = p.partW + (((int64_t)blockIdx.x * 6 + y) * H + j) * H + d0;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) o[i] = acc[i];
+    gmpe_wgrad::part_products(
+        m0, m1, [&](int64_t m, int k) { return p.dG[m * G4 + col + k]; },
+        [&](int64_t m, int k) {
+            if (y < 3) return p.x[m * H + k];
+            return __fmul_rn(m >= p.Nb ? p.sH[(m - p.Nb) * H + k] : p.hxs[m * H + k], p.masks[m]);
+        },
+        p.partW + ((int64_t)blockIdx.x * 6 + y) * H * H);
 }
 
 // backward 3: the partial sums in their fixed order, rounded once. Workgroups 0 .. 95: one weight element per thread; 96 .. 119: 16 columns of partC each.
@@ -309,19 +285,13 @@ __global__ __launch_bounds__(BLOCK) void k_gru_finish(GruArgs p) {
     const int tid = threadIdx.x;
     if (blockIdx.x < FIN_W_BLOCKS) {
         const int e = blockIdx.x * BLOCK + tid;         // (matrix 0 .. 5, j, d) as in partW
-        double s = 0.0;
-        for (int q = 0; q < p.nparts; ++q) s += p.partW[(int64_t)q * (2 * G3 * H) + e];
+        const double s = gmpe_wgrad::sum_parts(p.partW, p.nparts, 2 * G3 * H, e);
         if (e < G3 * H) p.gwih[e] = (float)s; else p.gwhh[e - G3 * H] = (float)s;
         return;
     }
-    const int jc = tid % FIN_COLS, s = tid / FIN_COLS, col = ((int)blockIdx.x - FIN_W_BLOCKS) * FIN_COLS + jc;
-    double sum = 0.0;
-    for (int64_t i = s; i < p.ntiles; i += FIN_SLICES) sum += p.partC[i * NCOL + col];
-    cs[s][jc] = sum;
-    __syncthreads();
-    if (s != 0) return;
-    double tot = cs[0][jc];
-    for (int q = 1; q < FIN_SLICES; ++q) tot += cs[q][jc];
+    const int col = ((int)blockIdx.x - FIN_W_BLOCKS) * FIN_COLS + tid % FIN_COLS;
+    const double tot = gmpe_wgrad::sum_slices(p.partC, p.ntiles, NCOL, col - tid % FIN_COLS, cs);
+    if (tid >= FIN_COLS) return;
     const float v = (float)tot;
     const int q = col / H, jj = col % H;
     if (q == 0 || q == 1) { p.gbih[q * H + jj] = v; p.gbhh[q * H + jj] = v; }
@@ -339,9 +309,8 @@ bool layout(int64_t L, int64_t Nb, Layout& y) {
     if (L < 1 || Nb < 1 || L > (int64_t)1 << 40 || Nb > ((int64_t)1 << 40) / L) return false;      // M * 4H * 4 bytes stays far inside int64
     const int64_t M = L * Nb;
     y.ntiles = (Nb + TILE - 1) / TILE;
-    const int64_t want = (M + PART_ROWS - 1) / PART_ROWS;
-    y.nparts = (int)(want < MAX_PARTS ? want : MAX_PARTS);
-    y.part_rows = (M + y.nparts - 1) / y.nparts;
+    const gmpe_wgrad::Parts parts = gmpe_wgrad::partition(M);
+    y.nparts = parts.nparts; y.part_rows = parts.part_rows;
     size_t o = 0;
     y.partC = o; o += (size_t)y.ntiles * NCOL * sizeof(double);
     y.partW = o; o += (size_t)y.nparts * 2 * G3 * H * sizeof(double);

@@ -692,6 +692,82 @@ int gmpe_gru_workspace_bytes(int64_t steps, int64_t rows, int32_t hidden, int32_
 int gmpe_gru_forward(int device, const gmpe_gru_plan* plan, void* stream);
 int gmpe_gru_backward(int device, const gmpe_gru_plan* plan, void* stream);
 
+/* ---- The policy's MLPBase (handle-less): MLPBase.forward (onpolicy/algorithms/utils/mlp.py:44-76), the stage in front of the GRU layer ----
+ * GR_Actor runs it on torch.cat([obs, nbd_features]), GR_Critic on nbd_features or torch.cat([cent_obs, nbd_features]). Here the input is n_parts
+ * (1 .. GMPE_MLP_MAX_PARTS) float32 arrays part[i] of [rows, part_dim[i]], contiguous, whose columns are read as if concatenated: D = sum of part_dim,
+ * 1 <= D <= GMPE_MLP_MAX_IN. The concatenation is never written anywhere, and every part has a gradient array of its own. For every row independently:
+ *     x <- LayerNorm_D(x)                          if feature_norm (fn_weight, fn_bias [D], fn_eps); biased variance, eps inside the square root
+ *     x <- LayerNorm_64(act(W_l x + b_l))          for l = 0 .. layer_n: layer[0].weight is [64, D], layer[l > 0].weight [64, 64]; act = ReLU or Tanh
+ *     features = x                                 [rows, 64]
+ * Supported: hidden == 64, layer_n in 0 .. 2, float32; anything else is refused before any launch, with the field named.
+ * Arithmetic of one row (a function of (D, layer_n, activation, feature_norm) alone — not of rows, of the row's place, of how the columns are split into
+ * parts): every dot product is one fmaf chain from the bias in ascending k (layer 0 over D rounded up to a multiple of 4, the padding being zeros); every
+ * other operation is rounded on its own; a LayerNorm sum is an xor tree over the 64 lanes (offsets 32, 16, .. 1), mean and variance multiplied by 1 / 64,
+ * rstd = 1 / sqrt(var + eps). The feature norm's statistics are formed in double (lane j adds its columns j, j + 64, .. ascending, then the xor tree;
+ * mean, (x - mean), the variance / D and rstd in double; (x - mean) * rstd rounded to float32 once): a row of 2 or 3 observations that lie close together
+ * would lose in x - mean the digits a float32 mean does not have.
+ * D == 1 with feature_norm is legal and degenerate: the normalised input is 0 for every row.
+ * gmpe_mlp_forward: ONE launch; it reads the parts and the parameters, writes features, and neither reads nor writes the workspace: the forward-only plan
+ * (workspace == NULL, gradient pointers NULL) and the training plan run the same kernel and give the same bits.
+ * gmpe_mlp_backward (may be repeated; it needs no gmpe_mlp_forward before it — it recomputes a tile's forward, the same code and bits): THREE launches
+ * whatever rows, D, layer_n and n_parts.
+ *   1 per tile of GMPE_MLP_ROW_TILE rows: forward again, then LayerNorm, activation and Linear backward layer by layer and the feature norm's backward;
+ *     grad_part[i] written; the workgroup's double sums of the bias, LayerNorm and feature-norm gradients (its tiles ascending, a wave's rows ascending,
+ *     then the four waves in wave order);
+ *   2 the weight gradients as double sums of exact products over P = min(128, ceil(rows / 32)) contiguous parts of the rows, ascending inside a part;
+ *   3 the parts added in ascending order (weights), the workgroups of launch 1 as 16 interleaved slices in ascending order and the slices in slice order
+ *     (everything else), each rounded to float32 once. So a parameter gradient's summation order is a function of (rows, D, layer_n) alone.
+ * Workspace (training only; gmpe_mlp_workspace_bytes is the single source of its size; its contents before the call do not matter), in this order:
+ *     double partC[G][(3 * 3 + 2 * 4) * 64]      G = the workgroups of launch 1: column (3 l + {0 bias, 1 ln_weight, 2 ln_bias}) * 64 + j, then fn_weight, fn_bias
+ *     double partW[P][ceil(D / 64) + layer_n][64][64]
+ *     double stats[rows][2]                      the feature norm's mean and rstd
+ *     float  dpre[layer_n + 1][rows][64]         the gradients of the pre-activations
+ *     float  out[layer_n][rows][64]              the outputs of layers 0 .. layer_n - 1 (the inputs of the hidden layers' weight gradients)
+ * Outputs must not overlap inputs. No atomics, no allocation, no host synchronisation; capturable. */
+#define GMPE_MLP_ROW_TILE 32
+#define GMPE_MLP_MAX_PARTS 4
+#define GMPE_MLP_MAX_IN 256
+#define GMPE_MLP_MAX_LAYERS 3           /* fc1 and layer_n <= 2 copies of fc_h                                                        */
+#define GMPE_MLP_RELU 0
+#define GMPE_MLP_TANH 1
+typedef struct gmpe_mlp_layer {
+    const float* weight;                /* [64, D] (layer 0) or [64, 64]                                                              */
+    const float* bias;                  /* [64]                                                                                       */
+    const float* ln_weight;             /* [64]                                                                                       */
+    const float* ln_bias;               /* [64]                                                                                       */
+    double eps;                         /* this LayerNorm's eps > 0                                                                   */
+    float* grad_weight;                 /* backward, like every grad_* here                                                           */
+    float* grad_bias;
+    float* grad_ln_weight;
+    float* grad_ln_bias;
+} gmpe_mlp_layer;
+typedef struct gmpe_mlp_plan {
+    int64_t rows;                       /* >= 1                                                                                       */
+    int32_t hidden;                     /* 64                                                                                         */
+    int32_t layer_n;                    /* 0 .. 2: MLPLayer._layer_N                                                                  */
+    int32_t activation;                 /* GMPE_MLP_RELU or GMPE_MLP_TANH                                                             */
+    int32_t feature_norm;               /* 0 or 1: MLPBase._use_feature_normalization                                                 */
+    int32_t n_parts;                    /* 1 .. GMPE_MLP_MAX_PARTS                                                                    */
+    int32_t reserved;
+    const float* part[GMPE_MLP_MAX_PARTS];      /* [rows, part_dim[i]]                                                                */
+    int32_t part_dim[GMPE_MLP_MAX_PARTS];       /* >= 1, their sum D <= GMPE_MLP_MAX_IN                                               */
+    float* grad_part[GMPE_MLP_MAX_PARTS];       /* [rows, part_dim[i]]; backward                                                      */
+    const float* fn_weight;             /* [D]; with feature_norm, like the four fields below                                         */
+    const float* fn_bias;               /* [D]                                                                                        */
+    double fn_eps;                      /* > 0                                                                                        */
+    float* grad_fn_weight;              /* [D]; backward                                                                              */
+    float* grad_fn_bias;                /* [D]; backward                                                                              */
+    gmpe_mlp_layer layer[GMPE_MLP_MAX_LAYERS];  /* layer[0 .. layer_n] are read                                                       */
+    float* features;                    /* [rows, 64]; forward (backward does not need it)                                            */
+    const float* grad_features;         /* [rows, 64]; backward                                                                       */
+    void* workspace;                    /* gmpe_mlp_workspace_bytes(rows, D, hidden, layer_n, 1) bytes, 8-byte aligned; backward only */
+    size_t workspace_bytes;
+} gmpe_mlp_plan;
+/* want_backward == 0: 0 bytes (the forward-only plan takes no workspace). */
+int gmpe_mlp_workspace_bytes(int64_t rows, int32_t in_dim, int32_t hidden, int32_t layer_n, int32_t want_backward, size_t* bytes_out);
+int gmpe_mlp_forward(int device, const gmpe_mlp_plan* plan, void* stream);
+int gmpe_mlp_backward(int device, const gmpe_mlp_plan* plan, void* stream);
+
 /* ---- Evaluation of a policy over a batch of episodes (handle-less): GMPERunner.render(get_metrics=True) as one episode per env ----
  * (onpolicy/runner/shared/graph_mpe_runner.py:526-1060, base_runner.py:194-574). Every env plays one episode from a reset; the caller's policy acts,
  * the engine steps, gmpe_episode_record books the step. No allocation, no host synchronisation, every launch on `stream`.
