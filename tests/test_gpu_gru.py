@@ -112,13 +112,19 @@ def test_the_shapes_the_fixture_does_not_hold(L, Nb):
 
 
 # ---------------------------------------------------------------------------------------------- 2
+GUARD = 3                                               # rows behind every output, which the kernels must leave alone
+
+
 def c_call(I, m, P, backward=True, fill=None, gh=True):
-    """gmpe_gru_forward (+ gmpe_gru_backward) through ctypes -> {name: array}; fill: the byte the workspace holds before forward"""
+    """gmpe_gru_forward (+ gmpe_gru_backward) through ctypes -> {name: array}; fill: the byte the workspace holds before forward. Every output has GUARD
+    rows of NaN behind it and the workspace 64 bytes of `fill`, which must be intact afterwards."""
     lib = _lib.load()
     Nb = I["hxs"].shape[0]
     L = I["x"].shape[0] // Nb
     ins = [dev(I["x"]), dev(I["hxs"]), dev(m)] + [dev(P[k]) for k in G.PARAMS]
-    f, ho = torch.empty((L * Nb, G.H), device=DEV), torch.empty((Nb, 1, G.H), device=DEV)
+    nan = float("nan")
+    guarded = lambda shape: torch.full((shape[0] + GUARD,) + tuple(shape[1:]), nan, device=DEV)
+    f, ho = guarded((L * Nb, G.H)), guarded((Nb, 1, G.H))
     p = _lib.GmpeGruPlan()
     p.steps, p.rows, p.in_dim, p.hidden, p.eps = L, Nb, G.D, G.H, G.EPS
     for k, t in zip(("x", "hxs", "masks") + G.PARAMS, ins):
@@ -127,14 +133,16 @@ def c_call(I, m, P, backward=True, fill=None, gh=True):
     ws = None
     if backward:
         n = gmpe.rnn_workspace_bytes(L, Nb, G.H)
-        ws = torch.full((n,), 0 if fill is None else fill, dtype=torch.uint8, device=DEV)
+        fill = 0 if fill is None else fill
+        ws = torch.full((n + 64,), fill, dtype=torch.uint8, device=DEV)
         p.workspace, p.workspace_bytes = ws.data_ptr(), n
     st = C.c_void_p(torch.cuda.current_stream(torch.device(DEV)).cuda_stream)
     _lib.check(lib.gmpe_gru_forward(0, C.byref(p), st), "gmpe_gru_forward")
-    out = [f, ho]
+    out, like = [f, ho], [(L * Nb, G.H), (Nb, 1, G.H)]
     if backward:
         gf, ghx = dev(I["gf"]), dev(I["gh"])
-        grads = [torch.empty_like(t) for t in ins[:2] + ins[3:]]
+        grads = [guarded(t.shape) for t in ins[:2] + ins[3:]]
+        like += [tuple(t.shape) for t in ins[:2] + ins[3:]]
         p.grad_features = gf.data_ptr()
         p.grad_hxs_out = ghx.data_ptr() if gh else None
         for k, t in zip(G.GRADS, grads):
@@ -148,9 +156,15 @@ def c_call(I, m, P, backward=True, fill=None, gh=True):
         torch.cuda.synchronize()
         for a, b, k in zip(first, grads, G.GRADS):
             assert same(a.cpu().numpy(), b.cpu().numpy()), "the second backward call differs: " + k
+        assert bool((ws[n:] == fill).all()), "bytes past gmpe_gru_workspace_bytes were written"
         out += grads
     torch.cuda.synchronize()
-    return {k: v.cpu().numpy() for k, v in zip(OUT, out)}
+    res = {}
+    for k, t, shape in zip(OUT, out, like):
+        a = t.cpu().numpy()
+        assert np.isnan(a[shape[0]:]).all(), "rows past the end of %s were written" % k
+        res[k] = a[:shape[0]]
+    return res
 
 
 @pytest.mark.parametrize("L,Nb", [(2, 3), (10, 2 * G.TILE + 1)])
