@@ -23,7 +23,8 @@ SYMBOLS = ["gmpe_abi_version", "gmpe_last_error", "gmpe_obs_dim", "gmpe_node_fea
            "gmpe_ppo_loss", "gmpe_ppo_loss_workspace_bytes", "gmpe_ppo_loss_popart", "gmpe_ppo_loss_popart_workspace_bytes",
            "gmpe_act_sample", "gmpe_compute_returns_shard", "gmpe_ppo_loss_shard",
            "gmpe_gru_workspace_bytes", "gmpe_gru_forward", "gmpe_gru_backward",
-           "gmpe_mlp_workspace_bytes", "gmpe_mlp_forward", "gmpe_mlp_backward"]
+           "gmpe_mlp_workspace_bytes", "gmpe_mlp_forward", "gmpe_mlp_backward",
+           "gmpe_gnn_workspace_bytes", "gmpe_gnn_forward", "gmpe_gnn_backward"]
 
 
 class GmpeOutputs(C.Structure):
@@ -221,6 +222,33 @@ class GmpeMlpPlan(C.Structure):
                 ("grad_features", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
+# GMPE_GNN_* of include/gmpe.h; tests/test_gnn_host.py compiles against the header
+GNN_HIDDEN, GNN_MAX_NODES, GNN_MAX_HEADS, GNN_MAX_CONVS, GNN_MAX_EMBED_LAYERS = 16, 64, 4, 3, 2
+GNN_MAX_FEATS, GNN_MAX_EMBEDDINGS, GNN_MAX_EMBEDDING_SIZE = 16, 16, 8
+GNN_RELU, GNN_TANH = 0, 1
+GNN_NODE, GNN_MEAN, GNN_MAX, GNN_ADD = 0, 1, 2, 3
+GNN_CONV_PARAMS = ("query_weight", "query_bias", "key_weight", "key_bias", "value_weight", "value_bias", "edge_weight", "skip_weight", "skip_bias")
+
+
+class GmpeGnnConv(C.Structure):
+    """gmpe_gnn_conv (include/gmpe.h): one TransformerConv of the GNNBase, with its gradients."""
+    _fields_ = [(k, C.c_void_p) for k in GNN_CONV_PARAMS] + [("grad_" + k, C.c_void_p) for k in GNN_CONV_PARAMS]
+
+
+class GmpeGnnPlan(C.Structure):
+    """gmpe_gnn_plan (include/gmpe.h): the policy's GNNBase from the dense adjacency, forward and backward."""
+    _fields_ = [("rows", C.c_int64)] + [(k, C.c_int32) for k in (
+        "num_nodes", "node_feats", "adj_share", "hidden", "heads", "concat", "beta", "edge_dim", "gnn_layer_n", "embed_layer_n", "embed_activation",
+        "conv_activation", "embed_layer_norm", "aggregate", "num_embeddings", "embedding_size")] + [
+        ("max_edge_dist", C.c_double), ("ln_eps", C.c_double), ("node_obs", C.c_void_p), ("adj", C.c_void_p), ("agent_id", C.c_void_p),
+        ("entity_embed", C.c_void_p), ("lin1_weight", C.c_void_p), ("lin1_bias", C.c_void_p), ("ln_weight", C.c_void_p), ("ln_bias", C.c_void_p),
+        ("embed_weight", C.c_void_p * GNN_MAX_EMBED_LAYERS), ("embed_bias", C.c_void_p * GNN_MAX_EMBED_LAYERS),
+        ("grad_entity_embed", C.c_void_p), ("grad_lin1_weight", C.c_void_p), ("grad_lin1_bias", C.c_void_p), ("grad_ln_weight", C.c_void_p),
+        ("grad_ln_bias", C.c_void_p), ("grad_embed_weight", C.c_void_p * GNN_MAX_EMBED_LAYERS), ("grad_embed_bias", C.c_void_p * GNN_MAX_EMBED_LAYERS),
+        ("conv", GmpeGnnConv * GNN_MAX_CONVS), ("features", C.c_void_p), ("grad_features", C.c_void_p), ("workspace", C.c_void_p),
+        ("workspace_bytes", C.c_size_t)]
+
+
 class GmpeError(RuntimeError):
     pass
 
@@ -293,6 +321,9 @@ def load():
     lib.gmpe_mlp_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]
     lib.gmpe_mlp_forward.argtypes = [I, C.POINTER(GmpeMlpPlan), P]
     lib.gmpe_mlp_backward.argtypes = [I, C.POINTER(GmpeMlpPlan), P]
+    lib.gmpe_gnn_workspace_bytes.argtypes = [C.POINTER(GmpeGnnPlan), C.c_int32, C.POINTER(C.c_size_t)]
+    lib.gmpe_gnn_forward.argtypes = [I, C.POINTER(GmpeGnnPlan), P]
+    lib.gmpe_gnn_backward.argtypes = [I, C.POINTER(GmpeGnnPlan), P]
     from .config import ABI_VERSION
     if lib.gmpe_abi_version() != ABI_VERSION:
         raise GmpeError("libgmpe.so ABI version mismatch")

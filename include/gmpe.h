@@ -768,6 +768,137 @@ int gmpe_mlp_workspace_bytes(int64_t rows, int32_t in_dim, int32_t hidden, int32
 int gmpe_mlp_forward(int device, const gmpe_mlp_plan* plan, void* stream);
 int gmpe_mlp_backward(int device, const gmpe_mlp_plan* plan, void* stream);
 
+/* ---- The policy's GNNBase (handle-less): GNNBase.forward (onpolicy/algorithms/utils/gnn_new.py:492-510), the first stage of GR_Actor / GR_Critic ----
+ * One module per call: nbd_features [rows, 16] from node_obs [rows, E, F], the dense adjacency and agent_id [rows]. Row g is one graph of E nodes.
+ *   edges      j -> i exists iff 0 < adj[j, i] < max_edge_dist (float32 compares, strict), e = adj[j, i]; the matrix is read as it is (no symmetry assumed)
+ *              and no edge list is ever built. adj is [rows / adj_share, E, E]: matrix g / adj_share serves row g (adj_share = 1: one matrix per row;
+ *              adj_share = A: the compact adjacency of a rollout step). rows must be a multiple of adj_share; the result has the bits of the materialised form.
+ *   EmbedConv  per edge m = [x_j[0 .. F-2], entity_embed[int(x_j[F-1])], e]; y = LN(act(lin1 m)); embed_layer_n times y = LN(act(W_l y + b_l)) with the SAME
+ *              LayerNorm parameters (embed_layer_norm = 0: no LayerNorm at all); x_i = sum over the incoming edges of i (none: zeros).
+ *              An entity type outside [0, num_embeddings) is clamped into it, and that row's value is then unspecified; nothing is read out of bounds.
+ *   conv[0 .. gnn_layer_n] (TransformerConv, heads H of 16 channels, averaged, no beta, no dropout): q, k, v = lin_query / lin_key / lin_value (x) as
+ *              [E, H, 16]; ee = lin_edge_weight * e; alpha_ji = softmax over the incoming edges of i of q_i . (k_j + ee_ji) / 4;
+ *              out_i = (sum over heads of sum_j alpha_ji (v_j + ee_ji)) / H + lin_skip(x_i); x = act(out). A node without incoming edge keeps the skip term.
+ *   output     GMPE_GNN_NODE: the row of node agent_id[g] (clamped into [0, E): a bad id reads nothing out of bounds, its row is unspecified);
+ *              GMPE_GNN_MEAN / _MAX / _ADD: the pool over all E nodes, isolated ones included.
+ * Supported: float32, hidden == 16, heads 1 .. 4, gnn_layer_n 0 .. 2, embed_layer_n 0 .. 2, edge_dim == 1, 2 <= F <= 16, num_embeddings 1 .. 16,
+ * embedding_size 1 .. 8, 1 <= E <= 64, concat == 0, beta == 0. Anything else is refused before any launch, with the field named.
+ * Arithmetic of one graph (a function of E and the configuration alone — not of rows, of the graph's place in the call, of adj_share). One lane owns one
+ * node; every sum over nodes or edges runs in ascending node index; contraction is off and every operation not named here is rounded on its own.
+ *   P_j   = fmaf chain from lin1_bias over lin1_weight[:, k] * m[k], k = 0 .. F + embedding_size - 2 ascending (the node's part of lin1);
+ *   edge  pre = fmaf(lin1_weight[:, last], e, P_j); a = max(pre, 0) or float(tanh(double(pre))); LayerNorm over the 16 values with its statistics in
+ *         double (sums ascending from 0, mean and variance times 1 / 16, rstd = 1 / sqrt(var + eps), (a - mean) * rstd rounded to float32 once), then
+ *         xh * w + b in float32; a 16 x 16 Linear is an fmaf chain from the bias, k ascending; x_i = the double sum of the edges' outputs, j ascending
+ *         from 0, rounded to float32 once;
+ *   conv  logit = (fmaf chain from 0 over c of q_i[c] * fmaf(we[c], e, k_j[c])) * 0.25; m = max over j; p = expf(logit - m); s = sum of p (j ascending);
+ *         acc[c] = fmaf chain over j of p * fmaf(we[c], e, v_j[c]); head = acc / s; heads added in ascending order from 0, divided by H, plus the skip
+ *         Linear; the 1e-16 of the reference's softmax denominator is below one ulp of s >= 1 and is dropped;
+ *   pools sums and maxima over i ascending; the mean is the sum divided by E.
+ *   backward: every difference that cancels is formed in double from the float32 values of the forward and rounded once — the dot products dout . v of
+ *         the softmax backward (exact products, c ascending), its own softmax (the sum of p in double, alpha = p / sum in double, so that the logit
+ *         gradients of a target add up to zero to double precision), the LayerNorm's backward means; Tanh's derivative is (1 - y) (1 + y).
+ * gmpe_gnn_forward: ONE launch; it reads the inputs and the parameters, writes features, and neither reads nor writes the workspace: the forward-only
+ * plan (workspace == NULL, gradient pointers NULL) and the training plan run the same kernel and give the same bits.
+ * gmpe_gnn_backward (may be repeated; it needs no gmpe_gnn_forward before it — it recomputes a graph's forward, the same code and bits): THREE launches
+ * whatever rows, E and the data. The inputs get no gradient.
+ *   1 a workgroup of 256 threads owns tiles of W graphs (W = 1 .. 4 graphs side by side, a function of E and the configuration: what fits the LDS),
+ *     tile blockIdx.x, blockIdx.x + gridDim.x, ...: forward again, then the pool and the convs backward; the gradient of the EmbedConv's output is
+ *     written to the workspace. A parameter-gradient element belongs to one thread of the workgroup. A tile's contribution to it is a double sum from 0
+ *     of exact products over the tile's graphs in ascending order and a graph's nodes in ascending order (a per-edge term first summed over
+ *     a source node's targets, ascending, in double, and rounded once when staged); it is added to the workgroup's running double sum. A conv's input
+ *     gradient (the skip's and every head's three Linears, transposed) is one double sum of exact products, rounded to float32 once.
+ *   2 the same tiles: the EmbedConv backward, every edge's MLP recomputed; its parameters' sums as in 1, the per-edge layers' once per target node.
+ *   3 the workgroups' double sums added in ascending workgroup order and rounded to float32 once.
+ *   So a parameter gradient's summation order is a function of (rows, E, configuration) alone, and two calls give the same bits.
+ * Workspace (training only; gmpe_gnn_workspace_bytes is the single source of its size; its contents before the call do not matter):
+ *     double part[G][NP]      G = min(ceil(rows / W), 256) workgroups of launches 1 and 2; NP = the parameters in the order entity_embed (rounded up to 4 floats),
+ *                             lin1 weight, lin1 bias, LayerNorm weight, bias (16 + 16, reserved also without LayerNorm), (weight, bias) per embed layer,
+ *                             then per conv (query weight, bias, key weight, bias, value weight, bias, edge weight, skip weight, bias)
+ *     float  dX[rows][E][16]  the gradient of the EmbedConv's output, from launch 1 to launch 2
+ * Outputs must not overlap inputs. No atomics, no allocation, no host synchronisation; capturable. */
+#define GMPE_GNN_HIDDEN 16
+#define GMPE_GNN_MAX_NODES 64
+#define GMPE_GNN_MAX_HEADS 4
+#define GMPE_GNN_MAX_CONVS 3            /* gnn1 and gnn_layer_n <= 2 of gnn2                                                          */
+#define GMPE_GNN_MAX_EMBED_LAYERS 2
+#define GMPE_GNN_MAX_FEATS 16
+#define GMPE_GNN_MAX_EMBEDDINGS 16
+#define GMPE_GNN_MAX_EMBEDDING_SIZE 8
+#define GMPE_GNN_RELU 0
+#define GMPE_GNN_TANH 1
+#define GMPE_GNN_NODE 0
+#define GMPE_GNN_MEAN 1
+#define GMPE_GNN_MAX 2
+#define GMPE_GNN_ADD 3
+typedef struct gmpe_gnn_conv {          /* one TransformerConv; H = heads                                                             */
+    const float* query_weight;          /* [16 H, 16]                                                                                 */
+    const float* query_bias;            /* [16 H]                                                                                     */
+    const float* key_weight;
+    const float* key_bias;
+    const float* value_weight;
+    const float* value_bias;
+    const float* edge_weight;           /* [16 H, 1], no bias                                                                         */
+    const float* skip_weight;           /* [16, 16]                                                                                   */
+    const float* skip_bias;             /* [16]                                                                                       */
+    float* grad_query_weight;           /* backward, like every grad_* here                                                           */
+    float* grad_query_bias;
+    float* grad_key_weight;
+    float* grad_key_bias;
+    float* grad_value_weight;
+    float* grad_value_bias;
+    float* grad_edge_weight;
+    float* grad_skip_weight;
+    float* grad_skip_bias;
+} gmpe_gnn_conv;
+typedef struct gmpe_gnn_plan {
+    int64_t rows;                       /* >= 1, a multiple of adj_share                                                              */
+    int32_t num_nodes;                  /* E: 1 .. 64                                                                                 */
+    int32_t node_feats;                 /* F: 2 .. 16, the last column is the entity type                                             */
+    int32_t adj_share;                  /* >= 1: consecutive rows served by one adjacency matrix                                      */
+    int32_t hidden;                     /* 16: embed_hidden_size and gnn_hidden_size                                                  */
+    int32_t heads;                      /* 1 .. 4                                                                                     */
+    int32_t concat;                     /* 0                                                                                          */
+    int32_t beta;                       /* 0                                                                                          */
+    int32_t edge_dim;                   /* 1                                                                                          */
+    int32_t gnn_layer_n;                /* 0 .. 2                                                                                     */
+    int32_t embed_layer_n;              /* 0 .. 2                                                                                     */
+    int32_t embed_activation;           /* GMPE_GNN_RELU or GMPE_GNN_TANH                                                             */
+    int32_t conv_activation;
+    int32_t embed_layer_norm;           /* 0 or 1                                                                                     */
+    int32_t aggregate;                  /* GMPE_GNN_NODE, _MEAN, _MAX or _ADD                                                         */
+    int32_t num_embeddings;             /* 1 .. 16                                                                                    */
+    int32_t embedding_size;             /* 1 .. 8                                                                                     */
+    double max_edge_dist;               /* compared as float32                                                                        */
+    double ln_eps;                      /* > 0 with embed_layer_norm                                                                  */
+    const float* node_obs;              /* [rows, E, F]                                                                               */
+    const float* adj;                   /* [rows / adj_share, E, E]                                                                   */
+    const int32_t* agent_id;            /* [rows]; read with GMPE_GNN_NODE only                                                       */
+    const float* entity_embed;          /* [num_embeddings, embedding_size]                                                           */
+    const float* lin1_weight;           /* [16, F - 1 + embedding_size + 1]                                                           */
+    const float* lin1_bias;             /* [16]                                                                                       */
+    const float* ln_weight;             /* [16]; with embed_layer_norm, like ln_bias and their gradients                              */
+    const float* ln_bias;
+    const float* embed_weight[GMPE_GNN_MAX_EMBED_LAYERS];       /* [16, 16]                                                           */
+    const float* embed_bias[GMPE_GNN_MAX_EMBED_LAYERS];         /* [16]                                                               */
+    float* grad_entity_embed;
+    float* grad_lin1_weight;
+    float* grad_lin1_bias;
+    float* grad_ln_weight;              /* the sum over every use of the one LayerNorm                                                */
+    float* grad_ln_bias;
+    float* grad_embed_weight[GMPE_GNN_MAX_EMBED_LAYERS];
+    float* grad_embed_bias[GMPE_GNN_MAX_EMBED_LAYERS];
+    gmpe_gnn_conv conv[GMPE_GNN_MAX_CONVS];                     /* conv[0 .. gnn_layer_n] are read                                    */
+    float* features;                    /* [rows, 16]; forward (backward does not need it)                                            */
+    const float* grad_features;         /* [rows, 16]; backward                                                                       */
+    void* workspace;                    /* gmpe_gnn_workspace_bytes(plan, 1) bytes, 8-byte aligned; backward only                     */
+    size_t workspace_bytes;
+} gmpe_gnn_plan;
+/* The size depends on rows, num_nodes, node_feats, heads, gnn_layer_n, embed_layer_n, num_embeddings and embedding_size only (no pointer is read).
+ * want_backward == 0: 0 bytes (the forward-only plan takes no workspace). */
+int gmpe_gnn_workspace_bytes(const gmpe_gnn_plan* plan, int32_t want_backward, size_t* bytes_out);
+int gmpe_gnn_forward(int device, const gmpe_gnn_plan* plan, void* stream);
+int gmpe_gnn_backward(int device, const gmpe_gnn_plan* plan, void* stream);
+
 /* ---- Evaluation of a policy over a batch of episodes (handle-less): GMPERunner.render(get_metrics=True) as one episode per env ----
  * (onpolicy/runner/shared/graph_mpe_runner.py:526-1060, base_runner.py:194-574). Every env plays one episode from a reset; the caller's policy acts,
  * the engine steps, gmpe_episode_record books the step. No allocation, no host synchronisation, every launch on `stream`.
