@@ -17,8 +17,8 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .engine import _need_cuda, _stream_of
-from .ppo_loss import _available, _logits_shape, _ordinal, _widened
+from .engine import _need_cuda, _ordinal, _stream_of
+from .ppo_loss import _available, _logits_shape, _widened
 
 OUT_KEYS = ("action_idx", "actions", "actions_f32", "action_log_probs")
 _OUT_DTYPES = dict(action_idx=torch.int32, actions=torch.int64, actions_f32=torch.float32, action_log_probs=torch.float32)

@@ -128,7 +128,7 @@ int gmpe_act_sample(int device, const gmpe_act_plan* pl, void* stream) {
     const size_t lds = (size_t)TILE * a.g.S * sizeof(float);
     void (*fn)(ActArgs) = vec ? k_act_rows<true> : k_act_rows<false>;
     if (lds > 48 * 1024)                                                      // K = 64 only
-        if (int rc = raise_dynamic_lds_once(reinterpret_cast<const void*>(fn), device, vec, TILE * (GMPE_PPO_MAX_ACTIONS | 1) * sizeof(float)))
+        if (int rc = gmpe::raise_dynamic_lds_once(reinterpret_cast<const void*>(fn), device, vec, TILE * (GMPE_PPO_MAX_ACTIONS | 1) * sizeof(float)))
             return rc;
     hipLaunchKernelGGL(fn, dim3((unsigned)nt), dim3(TILE), lds, st, a);
     GMPE_HIP_CHECK(hipGetLastError());

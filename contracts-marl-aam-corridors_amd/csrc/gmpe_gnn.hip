@@ -29,7 +29,7 @@
 
 #include <string>
 
-#include "gmpe_host.h"          // include/gmpe.h, the error text, GMPE_HIP_CHECK, raise_dynamic_lds_once
+#include "gmpe_host.h"          // include/gmpe.h, the error text, GMPE_HIP_CHECK, the layer files' shared host half
 
 #pragma clang fp contract(off)
 
@@ -40,7 +40,7 @@ constexpr int MAXE = GMPE_GNN_MAX_NODES, MAXH = GMPE_GNN_MAX_HEADS, MAXC = GMPE_
 constexpr int NINS = 32;                                // row stride of a node's lin1 input in LDS: F - 1 + embedding_size <= 23 columns, zeros behind
 constexpr int QDS = 40;                                 // backward's per-node row: q [16], the head's output gradient [16], max, -, 1 / sum and D (doubles), -
 constexpr int LIN = C * C + C;                          // a 16 x 16 Linear with its bias
-constexpr int MAX_CU = 256, LDS_CU = 160 * 1024;
+using gmpe::LDS_CU;
 static_assert(C == 16 && NW == 4 && MAXH == 4 && MAXC == 3 && MAXL == 2, "16 channels, four waves");
 static_assert(GMPE_GNN_MAX_FEATS - 1 + GMPE_GNN_MAX_EMBEDDING_SIZE <= NINS, "a node's lin1 input fits its LDS row");
 
@@ -912,7 +912,7 @@ __global__ __launch_bounds__(BLOCK) void k_gnn_finish(GnnArgs p) {
     *dst = (float)s;
 }
 
-int fail(const char* fn, const std::string& m) { return gmpe::report_error(GMPE_ERR_INVALID_ARG, std::string(fn) + ": " + m); }
+using gmpe::fail;
 
 struct Layout {
     Lay L;
@@ -958,11 +958,8 @@ int check_shape(const char* fn, const gmpe_gnn_plan* pl, Layout& y) {
     if (y.lds_fwd > (size_t)LDS_CU || y.lds_bwd > (size_t)LDS_CU) return fail(fn, "internal: the LDS layout does not fit");
     y.ntiles_fwd = (pl->rows + y.W_fwd - 1) / y.W_fwd;
     y.ntiles_bwd = (pl->rows + y.W_bwd - 1) / y.W_bwd;
-    int per_cu = (int)(LDS_CU / y.lds_fwd);
-    per_cu = per_cu < 1 ? 1 : (per_cu > 4 ? 4 : per_cu);
-    const int64_t gf = (int64_t)MAX_CU * per_cu;
-    y.nblocks_fwd = (int)(y.ntiles_fwd < gf ? y.ntiles_fwd : gf);
-    y.nblocks_bwd = (int)(y.ntiles_bwd < MAX_CU ? y.ntiles_bwd : MAX_CU);           // the backward kernels keep a thread's sums in registers: one wave per SIMD
+    y.nblocks_fwd = gmpe::resident_grid(y.ntiles_fwd, y.lds_fwd, 4);
+    y.nblocks_bwd = gmpe::resident_grid(y.ntiles_bwd, y.lds_bwd, 1);        // the backward kernels keep a thread's sums in registers: one wave per SIMD
     y.dX = (size_t)y.nblocks_bwd * y.L.np * sizeof(double);
     y.total = y.dX + (size_t)pl->rows * E * C * sizeof(float);
     return GMPE_OK;
@@ -979,34 +976,27 @@ int check_plan(const char* fn, const gmpe_gnn_plan* pl, bool backward, Layout& y
     if (pl->aggregate < GMPE_GNN_NODE || pl->aggregate > GMPE_GNN_ADD) return fail(fn, "aggregate must be GMPE_GNN_NODE, _MEAN, _MAX or _ADD");
     if (!(pl->max_edge_dist == pl->max_edge_dist)) return fail(fn, "max_edge_dist must be a number");
     if (pl->embed_layer_norm && !(pl->ln_eps > 0.0)) return fail(fn, "ln_eps must be > 0");
-    const auto ptr = [&](const void* q, const std::string& name, bool need) {
-        if (need && !q) return fail(fn, name + " is required");
-        if ((uintptr_t)q & 3) return fail(fn, name + " must be 4-byte aligned");
-        return (int)GMPE_OK;
-    };
-    struct Field { const void* p; const char* name; bool need; };
     const bool ln = pl->embed_layer_norm != 0;
-    const Field top[] = {
+    const gmpe::PtrField top[] = {
         {pl->node_obs, "node_obs", true}, {pl->adj, "adj", true}, {pl->agent_id, "agent_id", pl->aggregate == GMPE_GNN_NODE},
         {pl->entity_embed, "entity_embed", true}, {pl->lin1_weight, "lin1_weight", true}, {pl->lin1_bias, "lin1_bias", true},
         {pl->ln_weight, "ln_weight", ln}, {pl->ln_bias, "ln_bias", ln},
         {pl->grad_entity_embed, "grad_entity_embed", backward}, {pl->grad_lin1_weight, "grad_lin1_weight", backward},
         {pl->grad_lin1_bias, "grad_lin1_bias", backward}, {pl->grad_ln_weight, "grad_ln_weight", backward && ln}, {pl->grad_ln_bias, "grad_ln_bias", backward && ln},
         {pl->features, "features", !backward}, {pl->grad_features, "grad_features", backward}};
-    for (const auto& q : top)
-        if (int rc = ptr(q.p, q.name, q.need)) return rc;
+    if (int rc = gmpe::check_ptrs(fn, top)) return rc;
     if (((uintptr_t)pl->grad_features & 15) && backward) return fail(fn, "grad_features must be 16-byte aligned");
     for (int l = 0; l < pl->embed_layer_n; ++l) {
         const std::string n = "[" + std::to_string(l) + "]";
-        if (int rc = ptr(pl->embed_weight[l], "embed_weight" + n, true)) return rc;
-        if (int rc = ptr(pl->embed_bias[l], "embed_bias" + n, true)) return rc;
-        if (int rc = ptr(pl->grad_embed_weight[l], "grad_embed_weight" + n, backward)) return rc;
-        if (int rc = ptr(pl->grad_embed_bias[l], "grad_embed_bias" + n, backward)) return rc;
+        if (int rc = gmpe::check_ptr(fn, pl->embed_weight[l], "embed_weight" + n, true)) return rc;
+        if (int rc = gmpe::check_ptr(fn, pl->embed_bias[l], "embed_bias" + n, true)) return rc;
+        if (int rc = gmpe::check_ptr(fn, pl->grad_embed_weight[l], "grad_embed_weight" + n, backward)) return rc;
+        if (int rc = gmpe::check_ptr(fn, pl->grad_embed_bias[l], "grad_embed_bias" + n, backward)) return rc;
     }
     for (int c = 0; c <= pl->gnn_layer_n; ++c) {
         const gmpe_gnn_conv& v = pl->conv[c];
         const std::string n = "conv[" + std::to_string(c) + "].";
-        const Field fs[] = {
+        const gmpe::PtrField fs[] = {
             {v.query_weight, "query_weight", true}, {v.query_bias, "query_bias", true}, {v.key_weight, "key_weight", true}, {v.key_bias, "key_bias", true},
             {v.value_weight, "value_weight", true}, {v.value_bias, "value_bias", true}, {v.edge_weight, "edge_weight", true},
             {v.skip_weight, "skip_weight", true}, {v.skip_bias, "skip_bias", true},
@@ -1014,15 +1004,9 @@ int check_plan(const char* fn, const gmpe_gnn_plan* pl, bool backward, Layout& y
             {v.grad_key_weight, "grad_key_weight", backward}, {v.grad_key_bias, "grad_key_bias", backward},
             {v.grad_value_weight, "grad_value_weight", backward}, {v.grad_value_bias, "grad_value_bias", backward},
             {v.grad_edge_weight, "grad_edge_weight", backward}, {v.grad_skip_weight, "grad_skip_weight", backward}, {v.grad_skip_bias, "grad_skip_bias", backward}};
-        for (const auto& q : fs)
-            if (int rc = ptr(q.p, n + q.name, q.need)) return rc;
+        if (int rc = gmpe::check_ptrs(fn, fs, n)) return rc;
     }
-    if (backward && !pl->workspace) return fail(fn, "workspace is required");
-    if (pl->workspace) {
-        if ((uintptr_t)pl->workspace & 7) return fail(fn, "workspace must be 8-byte aligned");
-        if (pl->workspace_bytes < y.total) return fail(fn, "workspace_bytes is below gmpe_gnn_workspace_bytes(plan, 1) = " + std::to_string(y.total));
-    }
-    return GMPE_OK;
+    return gmpe::check_workspace(fn, pl->workspace, pl->workspace_bytes, y.total, backward, "workspace is required", "gmpe_gnn_workspace_bytes(plan, 1)");
 }
 
 GnnArgs bind(const gmpe_gnn_plan* pl, const Layout& y, bool backward) {
@@ -1046,7 +1030,7 @@ GnnArgs bind(const gmpe_gnn_plan* pl, const Layout& y, bool backward) {
     }
     a.out = pl->features; a.gout = pl->grad_features;
     a.part = static_cast<double*>(pl->workspace);
-    a.dX = pl->workspace ? reinterpret_cast<float*>(static_cast<char*>(pl->workspace) + y.dX) : nullptr;
+    a.dX = gmpe::at<float>(pl->workspace, y.dX);
     return a;
 }
 
@@ -1057,8 +1041,7 @@ extern "C" {
 int gmpe_gnn_workspace_bytes(const gmpe_gnn_plan* plan, int32_t want_backward, size_t* bytes_out) {
     const char* fn = "gmpe_gnn_workspace_bytes";
     Layout y;
-    if (!bytes_out) return fail(fn, "bytes_out is null");
-    if (want_backward != 0 && want_backward != 1) return fail(fn, "want_backward must be 0 or 1");
+    if (int rc = gmpe::check_workspace_query(fn, bytes_out, std::string(), want_backward)) return rc;
     if (int rc = check_shape(fn, plan, y)) return rc;
     *bytes_out = want_backward ? y.total : 0;
     return GMPE_OK;
@@ -1068,10 +1051,9 @@ int gmpe_gnn_forward(int device, const gmpe_gnn_plan* pl, void* stream) {
     Layout y;
     if (int rc = check_plan("gmpe_gnn_forward", pl, false, y)) return rc;
     GMPE_HIP_CHECK(hipSetDevice(device));
-    if (int rc = gmpe_ppo::raise_dynamic_lds_once(reinterpret_cast<const void*>(k_gnn_fwd), device, 0, LDS_CU)) return rc;
+    if (int rc = gmpe::raise_dynamic_lds_once(reinterpret_cast<const void*>(k_gnn_fwd), device, 0, LDS_CU)) return rc;
     const GnnArgs a = bind(pl, y, false);
-    hipLaunchKernelGGL(k_gnn_fwd, dim3((unsigned)y.nblocks_fwd), dim3(BLOCK), y.lds_fwd, static_cast<hipStream_t>(stream), a);
-    GMPE_HIP_CHECK(hipGetLastError());
+    GMPE_LAUNCH(k_gnn_fwd, dim3((unsigned)y.nblocks_fwd), dim3(BLOCK), y.lds_fwd, static_cast<hipStream_t>(stream), a);
     return GMPE_OK;
 }
 
@@ -1079,16 +1061,13 @@ int gmpe_gnn_backward(int device, const gmpe_gnn_plan* pl, void* stream) {
     Layout y;
     if (int rc = check_plan("gmpe_gnn_backward", pl, true, y)) return rc;
     GMPE_HIP_CHECK(hipSetDevice(device));
-    if (int rc = gmpe_ppo::raise_dynamic_lds_once(reinterpret_cast<const void*>(k_gnn_bwd_conv), device, 1, LDS_CU)) return rc;
-    if (int rc = gmpe_ppo::raise_dynamic_lds_once(reinterpret_cast<const void*>(k_gnn_bwd_embed), device, 2, LDS_CU)) return rc;
+    if (int rc = gmpe::raise_dynamic_lds_once(reinterpret_cast<const void*>(k_gnn_bwd_conv), device, 1, LDS_CU)) return rc;
+    if (int rc = gmpe::raise_dynamic_lds_once(reinterpret_cast<const void*>(k_gnn_bwd_embed), device, 2, LDS_CU)) return rc;
     const GnnArgs a = bind(pl, y, true);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(k_gnn_bwd_conv, dim3((unsigned)y.nblocks_bwd), dim3(BLOCK), y.lds_bwd, st, a);
-    GMPE_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(k_gnn_bwd_embed, dim3((unsigned)y.nblocks_bwd), dim3(BLOCK), y.lds_bwd, st, a);
-    GMPE_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(k_gnn_finish, dim3((unsigned)((y.L.np + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, a);
-    GMPE_HIP_CHECK(hipGetLastError());
+    GMPE_LAUNCH(k_gnn_bwd_conv, dim3((unsigned)y.nblocks_bwd), dim3(BLOCK), y.lds_bwd, st, a);
+    GMPE_LAUNCH(k_gnn_bwd_embed, dim3((unsigned)y.nblocks_bwd), dim3(BLOCK), y.lds_bwd, st, a);
+    GMPE_LAUNCH(k_gnn_finish, dim3((unsigned)((y.L.np + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, st, a);
     return GMPE_OK;
 }
 

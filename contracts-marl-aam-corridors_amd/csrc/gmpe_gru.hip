@@ -32,8 +32,8 @@
 
 #include <string>
 
-#include "gmpe_host.h"          // include/gmpe.h, the error text, GMPE_HIP_CHECK, raise_dynamic_lds_once
-#include "gmpe_wgrad.h"         // the weight-gradient parts and the ordered finish sums, shared with gmpe_mlp.hip
+#include "gmpe_host.h"          // include/gmpe.h, the error text, GMPE_HIP_CHECK, the layer files' shared host half
+#include "gmpe_wgrad.h"         // the weight-gradient parts, the ordered finish sums, wave_sum and the 64-wide LayerNorm, shared with gmpe_mlp.hip
 
 #pragma clang fp contract(off)
 
@@ -47,12 +47,11 @@ constexpr int NCOL = 6 * H;                             // dr, dz, dn, dhn (the 
 using gmpe_wgrad::FIN_COLS;                             // k_gru_wgrad's parts and k_gru_finish's slices: gmpe_wgrad.h
 using gmpe_wgrad::FIN_SLICES;
 static_assert(H == gmpe_wgrad::H && BLOCK == gmpe_wgrad::BLOCK, "gmpe_wgrad.h's workgroup");
-constexpr int MAX_GRID = 256;                           // one workgroup per CU fits (LDS); tiles beyond that are looped over
 static_assert(R == 8 && TILE == NW * R, "eight rows per wave");
 constexpr size_t FWD_LDS = (size_t)(2 * H * WS + 2 * NW * R * H) * sizeof(float);
 constexpr size_t BPTT_LDS = (size_t)(2 * G3 * H + NW * R * G4) * sizeof(float) + (size_t)NW * NCOL * sizeof(double);
 static_assert((2 * H * WS) % 4 == 0, "the broadcast vectors start at a 16-byte boundary");
-static_assert(FWD_LDS <= 160 * 1024 && BPTT_LDS <= 160 * 1024, "one workgroup's LDS");
+static_assert(FWD_LDS <= gmpe::LDS_CU && BPTT_LDS <= gmpe::LDS_CU, "one workgroup's LDS");      // one per CU fits; tiles beyond that are looped over
 
 struct GruArgs {
     int64_t L, Nb, M, ntiles, part_rows;
@@ -65,12 +64,6 @@ struct GruArgs {
     const float *gf, *gho;
     float *gx, *ghxs, *gwih, *gwhh, *gbih, *gbhh, *glnw, *glnb;
 };
-
-__device__ __forceinline__ float wave_sum(float v) {    // the same bits in every lane: a + b == b + a
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = __fadd_rn(v, __shfl_xor(v, off));
-    return v;
-}
 
 __device__ __forceinline__ float sigmoid(float a) { return __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-a))); }
 
@@ -146,10 +139,8 @@ __global__ __launch_bounds__(BLOCK) void k_gru_fwd(GruArgs p) {
                 const float nn = tanhf(__fadd_rn(a3[2][r], __fmul_rn(rr, a1[0][r])));
                 const float hn = __fadd_rn(__fmul_rn(__fsub_rn(1.0f, zz), nn), __fmul_rn(zz, h[r]));
                 h[r] = hn;
-                const float mean = __fmul_rn(wave_sum(hn), 1.0f / H);
-                const float d = __fsub_rn(hn, mean);
-                const float var = __fmul_rn(wave_sum(__fmul_rn(d, d)), 1.0f / H);
-                const float rstd = __fdiv_rn(1.0f, __fsqrt_rn(__fadd_rn(var, p.eps)));
+                float mean, rstd;
+                const float d = gmpe_wgrad::layer_norm_64(hn, p.eps, mean, rstd);
                 if (ok) {
                     p.feat[m * H + lane] = __fadd_rn(__fmul_rn(__fmul_rn(d, rstd), lw), lb);
                     if (SAVE) {
@@ -203,8 +194,7 @@ __global__ __launch_bounds__(BLOCK) void k_gru_bptt(GruArgs p) {
                 }
                 const float xh = __fmul_rn(__fsub_rn(hc, mean), rstd);
                 const float dxh = __fmul_rn(g, lw);
-                const float s1 = __fmul_rn(wave_sum(dxh), 1.0f / H), s2 = __fmul_rn(wave_sum(__fmul_rn(dxh, xh)), 1.0f / H);
-                const float dln = __fmul_rn(rstd, __fsub_rn(__fsub_rn(dxh, s1), __fmul_rn(xh, s2)));
+                const float dln = gmpe_wgrad::layer_norm_64_backward(dxh, xh, rstd);
                 const float dt = __fadd_rn(dh[r], dln);
                 const float dz = __fmul_rn(dt, __fsub_rn(hp, nn)), dn = __fmul_rn(dt, __fsub_rn(1.0f, zz));
                 dtz[r] = __fmul_rn(dt, zz);
@@ -301,7 +291,7 @@ __global__ __launch_bounds__(BLOCK) void k_gru_finish(GruArgs p) {
     else p.glnb[jj] = v;
 }
 
-int fail(const char* fn, const std::string& m) { return gmpe::report_error(GMPE_ERR_INVALID_ARG, std::string(fn) + ": " + m); }
+using gmpe::fail;
 
 struct Layout { size_t sG, sH, sS, dG, partC, partW, total; int64_t ntiles; int nparts; int64_t part_rows; };
 
@@ -311,14 +301,14 @@ bool layout(int64_t L, int64_t Nb, Layout& y) {
     y.ntiles = (Nb + TILE - 1) / TILE;
     const gmpe_wgrad::Parts parts = gmpe_wgrad::partition(M);
     y.nparts = parts.nparts; y.part_rows = parts.part_rows;
-    size_t o = 0;
-    y.partC = o; o += (size_t)y.ntiles * NCOL * sizeof(double);
-    y.partW = o; o += (size_t)y.nparts * 2 * G3 * H * sizeof(double);
-    y.sG = o; o += (size_t)M * G4 * sizeof(float);
-    y.dG = o; o += (size_t)M * G4 * sizeof(float);
-    y.sH = o; o += (size_t)M * H * sizeof(float);
-    y.sS = o; o += (size_t)M * 2 * sizeof(float);
-    y.total = (o + 7) & ~(size_t)7;
+    gmpe::Carver c;
+    y.partC = c.take((size_t)y.ntiles * NCOL * sizeof(double));
+    y.partW = c.take((size_t)y.nparts * 2 * G3 * H * sizeof(double));
+    y.sG = c.take((size_t)M * G4 * sizeof(float));
+    y.dG = c.take((size_t)M * G4 * sizeof(float));
+    y.sH = c.take((size_t)M * H * sizeof(float));
+    y.sS = c.take((size_t)M * 2 * sizeof(float));
+    y.total = c.total();
     return true;
 }
 
@@ -332,23 +322,17 @@ int check_plan(const char* fn, const gmpe_gru_plan* pl, bool backward, Layout& y
     if (!(pl->eps > 0.0)) return fail(fn, "eps must be > 0");
     if (!layout(pl->steps, pl->rows, y)) return fail(fn, "steps * rows is too large");
     if (y.ntiles > 0x7fffffffLL) return fail(fn, "rows: too many for one launch");
-    const struct { const void* ptr; const char* name; bool need; } ptrs[] = {
+    const gmpe::PtrField ptrs[] = {
         {pl->x, "x", true}, {pl->hxs, "hxs", true}, {pl->masks, "masks", true}, {pl->weight_ih, "weight_ih", true}, {pl->weight_hh, "weight_hh", true},
         {pl->bias_ih, "bias_ih", true}, {pl->bias_hh, "bias_hh", true}, {pl->ln_weight, "ln_weight", true}, {pl->ln_bias, "ln_bias", true},
         {pl->features, "features", !backward}, {pl->hxs_out, "hxs_out", !backward}, {pl->grad_features, "grad_features", backward},
         {pl->grad_hxs_out, "grad_hxs_out", false}, {pl->grad_x, "grad_x", backward}, {pl->grad_hxs, "grad_hxs", backward},
         {pl->grad_weight_ih, "grad_weight_ih", backward}, {pl->grad_weight_hh, "grad_weight_hh", backward}, {pl->grad_bias_ih, "grad_bias_ih", backward},
         {pl->grad_bias_hh, "grad_bias_hh", backward}, {pl->grad_ln_weight, "grad_ln_weight", backward}, {pl->grad_ln_bias, "grad_ln_bias", backward}};
-    for (const auto& q : ptrs) {
-        if (q.need && !q.ptr) return fail(fn, std::string(q.name) + " is required");
-        if ((uintptr_t)q.ptr & 3) return fail(fn, std::string(q.name) + " must be 4-byte aligned");
-    }
-    if (backward && !pl->workspace) return fail(fn, "workspace is required (the one gmpe_gru_forward filled)");
-    if (pl->workspace) {
-        if ((uintptr_t)pl->workspace & 7) return fail(fn, "workspace must be 8-byte aligned");
-        if (pl->workspace_bytes < y.total)
-            return fail(fn, "workspace_bytes is below gmpe_gru_workspace_bytes(steps, rows, hidden, 1) = " + std::to_string(y.total));
-    }
+    if (int rc = gmpe::check_ptrs(fn, ptrs)) return rc;
+    if (int rc = gmpe::check_workspace(fn, pl->workspace, pl->workspace_bytes, y.total, backward, "workspace is required (the one gmpe_gru_forward filled)",
+                                       "gmpe_gru_workspace_bytes(steps, rows, hidden, 1)"))
+        return rc;
     if (!backward) {                                    // hxs_out against everything the launch reads or writes
         const size_t M = (size_t)pl->steps * (size_t)pl->rows, fb = sizeof(float);
         const uintptr_t a0 = (uintptr_t)pl->hxs_out, a1 = a0 + (size_t)pl->rows * H * fb;
@@ -376,10 +360,9 @@ GruArgs bind(const gmpe_gru_plan* pl, const Layout& y) {
     a.eps = (float)pl->eps;
     a.x = pl->x; a.hxs = pl->hxs; a.masks = pl->masks; a.wih = pl->weight_ih; a.whh = pl->weight_hh; a.bih = pl->bias_ih; a.bhh = pl->bias_hh;
     a.lnw = pl->ln_weight; a.lnb = pl->ln_bias; a.feat = pl->features; a.hout = pl->hxs_out;
-    char* w = static_cast<char*>(pl->workspace);
-    const auto at = [&](size_t off) { return w ? w + off : nullptr; };
-    a.sG = reinterpret_cast<float*>(at(y.sG)); a.sH = reinterpret_cast<float*>(at(y.sH)); a.sS = reinterpret_cast<float*>(at(y.sS));
-    a.dG = reinterpret_cast<float*>(at(y.dG)); a.partC = reinterpret_cast<double*>(at(y.partC)); a.partW = reinterpret_cast<double*>(at(y.partW));
+    void* w = pl->workspace;
+    a.sG = gmpe::at<float>(w, y.sG); a.sH = gmpe::at<float>(w, y.sH); a.sS = gmpe::at<float>(w, y.sS);
+    a.dG = gmpe::at<float>(w, y.dG); a.partC = gmpe::at<double>(w, y.partC); a.partW = gmpe::at<double>(w, y.partW);
     a.gf = pl->grad_features; a.gho = pl->grad_hxs_out; a.gx = pl->grad_x; a.ghxs = pl->grad_hxs; a.gwih = pl->grad_weight_ih; a.gwhh = pl->grad_weight_hh;
     a.gbih = pl->grad_bias_ih; a.gbhh = pl->grad_bias_hh; a.glnw = pl->grad_ln_weight; a.glnb = pl->grad_ln_bias;
     return a;
@@ -392,9 +375,8 @@ extern "C" {
 int gmpe_gru_workspace_bytes(int64_t steps, int64_t rows, int32_t hidden, int32_t want_backward, size_t* bytes_out) {
     const char* fn = "gmpe_gru_workspace_bytes";
     Layout y;
-    if (!bytes_out) return fail(fn, "bytes_out is null");
-    if (hidden != H) return fail(fn, "unsupported hidden = " + std::to_string(hidden) + ": only 64 is built");
-    if (want_backward != 0 && want_backward != 1) return fail(fn, "want_backward must be 0 or 1");
+    const std::string dims = hidden != H ? "unsupported hidden = " + std::to_string(hidden) + ": only 64 is built" : std::string();
+    if (int rc = gmpe::check_workspace_query(fn, bytes_out, dims, want_backward)) return rc;
     if (!layout(steps, rows, y)) return fail(fn, "steps and rows must be >= 1 (and their product not absurd)");
     *bytes_out = want_backward ? y.total : 0;
     return GMPE_OK;
@@ -406,11 +388,9 @@ int gmpe_gru_forward(int device, const gmpe_gru_plan* pl, void* stream) {
     GMPE_HIP_CHECK(hipSetDevice(device));
     const bool save = pl->workspace != nullptr;
     void (*fn)(GruArgs) = save ? k_gru_fwd<true> : k_gru_fwd<false>;
-    if (int rc = gmpe_ppo::raise_dynamic_lds_once(reinterpret_cast<const void*>(fn), device, save ? 1 : 0, FWD_LDS)) return rc;
+    if (int rc = gmpe::raise_dynamic_lds_once(reinterpret_cast<const void*>(fn), device, save ? 1 : 0, FWD_LDS)) return rc;
     const GruArgs a = bind(pl, y);
-    const dim3 grid((unsigned)(y.ntiles < MAX_GRID ? y.ntiles : MAX_GRID)), block(BLOCK);
-    hipLaunchKernelGGL(fn, grid, block, FWD_LDS, static_cast<hipStream_t>(stream), a);
-    GMPE_HIP_CHECK(hipGetLastError());
+    GMPE_LAUNCH(fn, dim3((unsigned)gmpe::resident_grid(y.ntiles, FWD_LDS, 1)), dim3(BLOCK), FWD_LDS, static_cast<hipStream_t>(stream), a);
     return GMPE_OK;
 }
 
@@ -418,16 +398,12 @@ int gmpe_gru_backward(int device, const gmpe_gru_plan* pl, void* stream) {
     Layout y;
     if (int rc = check_plan("gmpe_gru_backward", pl, true, y)) return rc;
     GMPE_HIP_CHECK(hipSetDevice(device));
-    if (int rc = gmpe_ppo::raise_dynamic_lds_once(reinterpret_cast<const void*>(k_gru_bptt), device, 2, BPTT_LDS)) return rc;
+    if (int rc = gmpe::raise_dynamic_lds_once(reinterpret_cast<const void*>(k_gru_bptt), device, 2, BPTT_LDS)) return rc;
     const GruArgs a = bind(pl, y);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const dim3 grid((unsigned)(y.ntiles < MAX_GRID ? y.ntiles : MAX_GRID)), block(BLOCK);
-    hipLaunchKernelGGL(k_gru_bptt, grid, block, BPTT_LDS, st, a);
-    GMPE_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(k_gru_wgrad, dim3((unsigned)y.nparts, 6), block, 0, st, a);
-    GMPE_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(k_gru_finish, dim3(FIN_W_BLOCKS + FIN_C_BLOCKS), block, 0, st, a);
-    GMPE_HIP_CHECK(hipGetLastError());
+    GMPE_LAUNCH(k_gru_bptt, dim3((unsigned)gmpe::resident_grid(y.ntiles, BPTT_LDS, 1)), dim3(BLOCK), BPTT_LDS, st, a);
+    GMPE_LAUNCH(k_gru_wgrad, dim3((unsigned)y.nparts, 6), dim3(BLOCK), 0, st, a);
+    GMPE_LAUNCH(k_gru_finish, dim3(FIN_W_BLOCKS + FIN_C_BLOCKS), dim3(BLOCK), 0, st, a);
     return GMPE_OK;
 }
 

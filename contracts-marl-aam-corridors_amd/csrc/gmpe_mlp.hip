@@ -34,8 +34,8 @@
 
 #include <string>
 
-#include "gmpe_host.h"          // include/gmpe.h, the error text, GMPE_HIP_CHECK, raise_dynamic_lds_once
-#include "gmpe_wgrad.h"         // the weight-gradient parts and the ordered finish sums, shared with gmpe_gru.hip
+#include "gmpe_host.h"          // include/gmpe.h, the error text, GMPE_HIP_CHECK, the layer files' shared host half
+#include "gmpe_wgrad.h"         // the weight-gradient parts, the ordered finish sums, wave_sum and the 64-wide LayerNorm, shared with gmpe_gru.hip
 
 #pragma clang fp contract(off)
 
@@ -47,9 +47,9 @@ constexpr int WS = H + 1;                               // row stride of the tra
 constexpr int MAXD = GMPE_MLP_MAX_IN, MAXL = GMPE_MLP_MAX_LAYERS, MAXP = GMPE_MLP_MAX_PARTS, NI = MAXD / 64;
 constexpr int NQ = 3 * MAXL + 2 * NI;                   // column sums per lane: (bias, LayerNorm weight, bias) per layer, feature-norm weight and bias per 64 columns
 constexpr int NCOL = NQ * H;                            // ... and per workgroup: column q * 64 + lane
-constexpr int MAX_CU = 256, LDS_CU = 160 * 1024;
 using gmpe_wgrad::FIN_COLS;
 using gmpe_wgrad::FIN_SLICES;
+using gmpe_wgrad::wave_sum;
 static_assert(R == 8 && TILE == NW * R && NI == 4 && MAXL == 3 && MAXP == 4, "eight rows per wave, four column groups, three layers, four parts");
 static_assert(H == gmpe_wgrad::H && BLOCK == gmpe_wgrad::BLOCK, "gmpe_wgrad.h's workgroup");
 constexpr size_t CS_LDS = (size_t)NW * NCOL * sizeof(double);
@@ -73,13 +73,6 @@ struct MlpArgs {
 
 template <class T>
 __device__ __forceinline__ T pick(T const (&a)[MAXL], int i) { return i == 0 ? a[0] : (i == 1 ? a[1] : a[2]); }
-
-template <class T>
-__device__ __forceinline__ T wave_sum(T v) {            // the same bits in every lane: a + b == b + a
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = v + __shfl_xor(v, off);
-    return v;
-}
 
 __device__ __forceinline__ float activate(int act, float a) { return act == GMPE_MLP_RELU ? (a > 0.0f ? a : 0.0f) : tanhf(a); }
 
@@ -228,11 +221,8 @@ __device__ __forceinline__ void tile_forward(const MlpArgs& p, const Lane& c, co
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 const float av = activate(p.act, acc[r]);
-                const float mean = wave_sum(av) * (1.0f / H);
-                const float d = av - mean;
-                const float var = wave_sum(d * d) * (1.0f / H);
-                const float rstd = __fdiv_rn(1.0f, __fsqrt_rn(var + p.eps[l]));
-                const float xh = d * rstd;
+                float mean, rstd;
+                const float xh = gmpe_wgrad::layer_norm_64(av, p.eps[l], mean, rstd) * rstd;
                 y[r] = xh * c.lw[l] + c.lb[l];
                 if (KEEP) { kp->a[l][r] = av; kp->xh[l][r] = xh; kp->rs[l][r] = rstd; }
                 if (more) {
@@ -295,8 +285,7 @@ __global__ __launch_bounds__(BLOCK) void k_mlp_bprop(MlpArgs p) {
                 for (int r = 0; r < R; ++r) {
                     const float g = dy[r], xh = kp.xh[l][r], av = kp.a[l][r];
                     const float dxh = g * c.lw[l];
-                    const float s1 = wave_sum(dxh) * (1.0f / H), s2 = wave_sum(dxh * xh) * (1.0f / H);
-                    const float dact = kp.rs[l][r] * ((dxh - s1) - xh * s2);
+                    const float dact = gmpe_wgrad::layer_norm_64_backward(dxh, xh, kp.rs[l][r]);
                     dp[r] = p.act == GMPE_MLP_RELU ? (av > 0.0f ? dact : 0.0f) : dact * (1.0f - av * av);
                     if (r < nvalid) {
                         cq[3 * l] += (double)dp[r]; cq[3 * l + 1] += (double)g * (double)xh; cq[3 * l + 2] += (double)g;
@@ -423,7 +412,7 @@ __global__ __launch_bounds__(BLOCK) void k_mlp_finish(MlpArgs p) {
     }
 }
 
-int fail(const char* fn, const std::string& m) { return gmpe::report_error(GMPE_ERR_INVALID_ARG, std::string(fn) + ": " + m); }
+using gmpe::fail;
 
 struct Layout {
     size_t partC, partW, dP, Y, S, total;
@@ -442,21 +431,15 @@ bool layout(int64_t rows, int D, int layer_n, Layout& y) {
     y.DS = y.DP > H ? y.DP : H;
     y.lds_fwd = (size_t)(y.DP * WS + layer_n * H * WS + NW * R * y.DS) * sizeof(float);
     y.lds_bwd = y.lds_fwd > CS_LDS ? y.lds_fwd : CS_LDS;
-    const auto blocks = [&](size_t lds, int cap) {      // as many workgroups as the CUs hold at once, by LDS and at most `cap` per CU
-        int per = (int)(LDS_CU / lds);
-        per = per < 1 ? 1 : (per > cap ? cap : per);
-        const int64_t g = (int64_t)MAX_CU * per;
-        return (int)(y.ntiles < g ? y.ntiles : g);
-    };
-    y.nblocks_fwd = blocks(y.lds_fwd, 4);
-    y.nblocks_bwd = blocks(y.lds_bwd, 1);          // k_mlp_bprop keeps a tile's forward in registers: one wave per SIMD
-    size_t o = 0;
-    y.partC = o; o += (size_t)y.nblocks_bwd * NCOL * sizeof(double);
-    y.partW = o; o += (size_t)y.nparts * (y.nblk1 + layer_n) * H * H * sizeof(double);
-    y.S = o; o += (size_t)rows * 2 * sizeof(double);
-    y.dP = o; o += (size_t)rows * (layer_n + 1) * H * sizeof(float);
-    y.Y = o; o += (size_t)rows * layer_n * H * sizeof(float);
-    y.total = (o + 7) & ~(size_t)7;
+    y.nblocks_fwd = gmpe::resident_grid(y.ntiles, y.lds_fwd, 4);
+    y.nblocks_bwd = gmpe::resident_grid(y.ntiles, y.lds_bwd, 1);           // k_mlp_bprop keeps a tile's forward in registers: one wave per SIMD
+    gmpe::Carver c;
+    y.partC = c.take((size_t)y.nblocks_bwd * NCOL * sizeof(double));
+    y.partW = c.take((size_t)y.nparts * (y.nblk1 + layer_n) * H * H * sizeof(double));
+    y.S = c.take((size_t)rows * 2 * sizeof(double));
+    y.dP = c.take((size_t)rows * (layer_n + 1) * H * sizeof(float));
+    y.Y = c.take((size_t)rows * layer_n * H * sizeof(float));
+    y.total = c.total();
     return true;
 }
 
@@ -482,38 +465,27 @@ int check_plan(const char* fn, const gmpe_mlp_plan* pl, bool backward, Layout& y
     if (D > MAXD) return fail(fn, "unsupported sum of part_dim = " + std::to_string(D) + ": at most " + std::to_string(MAXD) + " input columns are built");
     if (!layout(pl->rows, D, pl->layer_n, y)) return fail(fn, "rows is too large");
     if (y.ntiles > 0x7fffffffLL) return fail(fn, "rows: too many for one launch");
-    const auto ptr = [&](const void* q, const std::string& name, bool need) {
-        if (need && !q) return fail(fn, name + " is required");
-        if ((uintptr_t)q & 3) return fail(fn, name + " must be 4-byte aligned");
-        return (int)GMPE_OK;
-    };
     if (pl->feature_norm) {
         if (!(pl->fn_eps > 0.0)) return fail(fn, "fn_eps must be > 0");
-        if (int rc = ptr(pl->fn_weight, "fn_weight", true)) return rc;
-        if (int rc = ptr(pl->fn_bias, "fn_bias", true)) return rc;
-        if (int rc = ptr(pl->grad_fn_weight, "grad_fn_weight", backward)) return rc;
-        if (int rc = ptr(pl->grad_fn_bias, "grad_fn_bias", backward)) return rc;
+        const gmpe::PtrField ps[] = {
+            {pl->fn_weight, "fn_weight", true}, {pl->fn_bias, "fn_bias", true}, {pl->grad_fn_weight, "grad_fn_weight", backward},
+            {pl->grad_fn_bias, "grad_fn_bias", backward}};
+        if (int rc = gmpe::check_ptrs(fn, ps)) return rc;
     }
     for (int l = 0; l <= pl->layer_n; ++l) {
         const gmpe_mlp_layer& L = pl->layer[l];
         const std::string n = "layer[" + std::to_string(l) + "].";
         if (!(L.eps > 0.0)) return fail(fn, n + "eps must be > 0");
-        const struct { const void* p; const char* name; bool need; } ps[] = {
+        const gmpe::PtrField ps[] = {
             {L.weight, "weight", true}, {L.bias, "bias", true}, {L.ln_weight, "ln_weight", true}, {L.ln_bias, "ln_bias", true},
             {L.grad_weight, "grad_weight", backward}, {L.grad_bias, "grad_bias", backward}, {L.grad_ln_weight, "grad_ln_weight", backward},
             {L.grad_ln_bias, "grad_ln_bias", backward}};
-        for (const auto& q : ps)
-            if (int rc = ptr(q.p, n + q.name, q.need)) return rc;
+        if (int rc = gmpe::check_ptrs(fn, ps, n)) return rc;
     }
-    if (int rc = ptr(pl->features, "features", !backward)) return rc;
-    if (int rc = ptr(pl->grad_features, "grad_features", backward)) return rc;
-    if (backward && !pl->workspace) return fail(fn, "workspace is required");
-    if (pl->workspace) {
-        if ((uintptr_t)pl->workspace & 7) return fail(fn, "workspace must be 8-byte aligned");
-        if (pl->workspace_bytes < y.total)
-            return fail(fn, "workspace_bytes is below gmpe_mlp_workspace_bytes(rows, in_dim, hidden, layer_n, 1) = " + std::to_string(y.total));
-    }
-    return GMPE_OK;
+    if (int rc = gmpe::check_ptr(fn, pl->features, "features", !backward)) return rc;
+    if (int rc = gmpe::check_ptr(fn, pl->grad_features, "grad_features", backward)) return rc;
+    return gmpe::check_workspace(fn, pl->workspace, pl->workspace_bytes, y.total, backward, "workspace is required",
+                                 "gmpe_mlp_workspace_bytes(rows, in_dim, hidden, layer_n, 1)");
 }
 
 MlpArgs bind(const gmpe_mlp_plan* pl, const Layout& y, int D) {
@@ -536,10 +508,9 @@ MlpArgs bind(const gmpe_mlp_plan* pl, const Layout& y, int D) {
         a.gw[l] = L.grad_weight; a.gb[l] = L.grad_bias; a.glw[l] = L.grad_ln_weight; a.glb[l] = L.grad_ln_bias;
     }
     a.feat = pl->features; a.gf = pl->grad_features;
-    char* w = static_cast<char*>(pl->workspace);
-    const auto at = [&](size_t o) { return w ? w + o : nullptr; };
-    a.dP = reinterpret_cast<float*>(at(y.dP)); a.Y = reinterpret_cast<float*>(at(y.Y)); a.S = reinterpret_cast<double*>(at(y.S));
-    a.partC = reinterpret_cast<double*>(at(y.partC)); a.partW = reinterpret_cast<double*>(at(y.partW));
+    void* w = pl->workspace;
+    a.dP = gmpe::at<float>(w, y.dP); a.Y = gmpe::at<float>(w, y.Y); a.S = gmpe::at<double>(w, y.S);
+    a.partC = gmpe::at<double>(w, y.partC); a.partW = gmpe::at<double>(w, y.partW);
     return a;
 }
 
@@ -550,11 +521,13 @@ extern "C" {
 int gmpe_mlp_workspace_bytes(int64_t rows, int32_t in_dim, int32_t hidden, int32_t layer_n, int32_t want_backward, size_t* bytes_out) {
     const char* fn = "gmpe_mlp_workspace_bytes";
     Layout y;
-    if (!bytes_out) return fail(fn, "bytes_out is null");
-    if (hidden != H) return fail(fn, "unsupported hidden = " + std::to_string(hidden) + ": only 64 is built");
-    if (layer_n < 0 || layer_n >= MAXL) return fail(fn, "unsupported layer_n = " + std::to_string(layer_n) + ": 0 .. 2 are built");
-    if (in_dim < 1 || in_dim > MAXD) return fail(fn, "in_dim must be in 1 .. " + std::to_string(MAXD));
-    if (want_backward != 0 && want_backward != 1) return fail(fn, "want_backward must be 0 or 1");
+    const auto dims = [&]() -> std::string {
+        if (hidden != H) return "unsupported hidden = " + std::to_string(hidden) + ": only 64 is built";
+        if (layer_n < 0 || layer_n >= MAXL) return "unsupported layer_n = " + std::to_string(layer_n) + ": 0 .. 2 are built";
+        if (in_dim < 1 || in_dim > MAXD) return "in_dim must be in 1 .. " + std::to_string(MAXD);
+        return std::string();
+    };
+    if (int rc = gmpe::check_workspace_query(fn, bytes_out, dims(), want_backward)) return rc;
     if (!layout(rows, in_dim, layer_n, y)) return fail(fn, "rows must be >= 1 (and not absurd)");
     *bytes_out = want_backward ? y.total : 0;
     return GMPE_OK;
@@ -565,10 +538,9 @@ int gmpe_mlp_forward(int device, const gmpe_mlp_plan* pl, void* stream) {
     int D;
     if (int rc = check_plan("gmpe_mlp_forward", pl, false, y, D)) return rc;
     GMPE_HIP_CHECK(hipSetDevice(device));
-    if (int rc = gmpe_ppo::raise_dynamic_lds_once(reinterpret_cast<const void*>(k_mlp_fwd), device, 0, LDS_CU)) return rc;
+    if (int rc = gmpe::raise_dynamic_lds_once(reinterpret_cast<const void*>(k_mlp_fwd), device, 0, gmpe::LDS_CU)) return rc;
     const MlpArgs a = bind(pl, y, D);
-    hipLaunchKernelGGL(k_mlp_fwd, dim3((unsigned)y.nblocks_fwd), dim3(BLOCK), y.lds_fwd, static_cast<hipStream_t>(stream), a);
-    GMPE_HIP_CHECK(hipGetLastError());
+    GMPE_LAUNCH(k_mlp_fwd, dim3((unsigned)y.nblocks_fwd), dim3(BLOCK), y.lds_fwd, static_cast<hipStream_t>(stream), a);
     return GMPE_OK;
 }
 
@@ -577,16 +549,13 @@ int gmpe_mlp_backward(int device, const gmpe_mlp_plan* pl, void* stream) {
     int D;
     if (int rc = check_plan("gmpe_mlp_backward", pl, true, y, D)) return rc;
     GMPE_HIP_CHECK(hipSetDevice(device));
-    if (int rc = gmpe_ppo::raise_dynamic_lds_once(reinterpret_cast<const void*>(k_mlp_bprop), device, 1, LDS_CU)) return rc;
+    if (int rc = gmpe::raise_dynamic_lds_once(reinterpret_cast<const void*>(k_mlp_bprop), device, 1, gmpe::LDS_CU)) return rc;
     const MlpArgs a = bind(pl, y, D);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int nmat = y.nblk1 + pl->layer_n;
-    hipLaunchKernelGGL(k_mlp_bprop, dim3((unsigned)y.nblocks_bwd), dim3(BLOCK), y.lds_bwd, st, a);
-    GMPE_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(k_mlp_wgrad, dim3((unsigned)y.nparts, (unsigned)nmat), dim3(BLOCK), 0, st, a);
-    GMPE_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(k_mlp_finish, dim3((unsigned)(nmat * (H * H / BLOCK) + NCOL / FIN_COLS)), dim3(BLOCK), 0, st, a);
-    GMPE_HIP_CHECK(hipGetLastError());
+    GMPE_LAUNCH(k_mlp_bprop, dim3((unsigned)y.nblocks_bwd), dim3(BLOCK), y.lds_bwd, st, a);
+    GMPE_LAUNCH(k_mlp_wgrad, dim3((unsigned)y.nparts, (unsigned)nmat), dim3(BLOCK), 0, st, a);
+    GMPE_LAUNCH(k_mlp_finish, dim3((unsigned)(nmat * (H * H / BLOCK) + NCOL / FIN_COLS)), dim3(BLOCK), 0, st, a);
     return GMPE_OK;
 }
 

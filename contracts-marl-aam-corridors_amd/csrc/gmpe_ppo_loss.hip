@@ -189,7 +189,7 @@ int launch_rows(const gmpe_ppo_loss_plan* pl, const LossArgs& a, int64_t nt, int
     void (*fn)(LossArgs) = vec ? (pl->actions_int64 ? k_loss_rows<true, true> : k_loss_rows<true, false>)
                                : (pl->actions_int64 ? k_loss_rows<false, true> : k_loss_rows<false, false>);
     if (lds > 48 * 1024)                                                      // K = 64 only
-        if (int rc = raise_dynamic_lds_once(reinterpret_cast<const void*>(fn), device, (vec ? 2 : 0) | (pl->actions_int64 ? 1 : 0),
+        if (int rc = gmpe::raise_dynamic_lds_once(reinterpret_cast<const void*>(fn), device, (vec ? 2 : 0) | (pl->actions_int64 ? 1 : 0),
                                             TILE * (GMPE_PPO_MAX_ACTIONS | 1) * sizeof(float)))
             return rc;
     hipLaunchKernelGGL(fn, dim3((unsigned)nt), dim3(TILE), lds, st, a);

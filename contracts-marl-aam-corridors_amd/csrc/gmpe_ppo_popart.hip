@@ -323,7 +323,7 @@ int gmpe_ppo_loss_popart(int device, const gmpe_popart_loss_plan* pl, void* stre
     void (*fn)(PopArgs) = vec ? (pl->actions_int64 ? k_pop_rows<true, true> : k_pop_rows<true, false>)
                               : (pl->actions_int64 ? k_pop_rows<false, true> : k_pop_rows<false, false>);
     if (lds > 48 * 1024)                                                      // large K or H
-        if (int rc = raise_dynamic_lds_once(reinterpret_cast<const void*>(fn), device, (vec ? 2 : 0) | (pl->actions_int64 ? 1 : 0),
+        if (int rc = gmpe::raise_dynamic_lds_once(reinterpret_cast<const void*>(fn), device, (vec ? 2 : 0) | (pl->actions_int64 ? 1 : 0),
                                             ((TILE * (GMPE_PPO_MAX_ACTIONS | 1) + 3) & ~3) * sizeof(float) + 4 * 64 * MAXQ * sizeof(double)))
             return rc;
     hipLaunchKernelGGL(fn, grid, block, lds, st, a);

@@ -6,6 +6,8 @@
 //   columns: n partial rows of doubles are added as 16 interleaved slices (slice s: rows s, s + 16, ... ascending), then the slices in slice order
 //     (sum_slices).
 // So a sum's order is a function of M (and of n) alone.
+// And the device pieces both files' kernels hold alike: the xor-tree sum over a wave, the float32 LayerNorm over the 64 columns a wave's lanes hold,
+// forward and backward.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -15,6 +17,29 @@ namespace gmpe_wgrad {
 constexpr int H = 64, BLOCK = 256;
 constexpr int MAX_PARTS = 128, PART_ROWS = 32;          // parts, and rows per LDS stage
 constexpr int FIN_COLS = 16, FIN_SLICES = BLOCK / FIN_COLS;
+
+template <class T>
+__device__ __forceinline__ T wave_sum(T v) {            // the same bits in every lane: a + b == b + a
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = v + __shfl_xor(v, off);
+    return v;
+}
+
+// LayerNorm over the 64 columns of a row, lane j holding column j's v: -> v - mean; the normalised value is that times rstd. Every operation is rounded
+// on its own (the files compile with contraction off).
+__device__ __forceinline__ float layer_norm_64(float v, float eps, float& mean, float& rstd) {
+    mean = wave_sum(v) * (1.0f / H);
+    const float d = v - mean;
+    const float var = wave_sum(d * d) * (1.0f / H);
+    rstd = __fdiv_rn(1.0f, __fsqrt_rn(var + eps));
+    return d;
+}
+
+// ... and its backward: dxh = the output's gradient times the LayerNorm weight, xh the normalised value -> the gradient of v
+__device__ __forceinline__ float layer_norm_64_backward(float dxh, float xh, float rstd) {
+    const float s1 = wave_sum(dxh) * (1.0f / H), s2 = wave_sum(dxh * xh) * (1.0f / H);
+    return rstd * ((dxh - s1) - xh * s2);
+}
 
 struct Parts { int nparts; int64_t part_rows; };
 static inline Parts partition(int64_t M) {

@@ -427,6 +427,10 @@ def _stream_of(device):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+def _ordinal(dev):                                     # what the C entry points take
+    return dev.index if dev.index is not None else torch.cuda.current_device()
+
+
 def _dev_f32(name, t, shape, device, dtype=torch.float32):
     """`t` must be a contiguous `dtype` tensor of `shape` on `device`, else ValueError — checked before anything is launched (layout first, then device)."""
     if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != tuple(shape):

@@ -10,9 +10,8 @@ import ctypes as C
 
 import torch
 
-from . import _lib
-from .engine import _need_cuda, _stream_of, _workspace
-from .ppo_loss import _ordinal
+from . import _layers, _lib
+from .engine import _need_cuda
 
 HIDDEN = _lib.GNN_HIDDEN                                # embed_hidden_size and gnn_hidden_size the library is built for
 MAX_NODES, MAX_HEADS, MAX_GNN_LAYER_N, MAX_EMBED_LAYER_N = _lib.GNN_MAX_NODES, _lib.GNN_MAX_HEADS, _lib.GNN_MAX_CONVS - 1, _lib.GNN_MAX_EMBED_LAYERS
@@ -23,10 +22,7 @@ _CONV_LINEARS = (("lin_query", "query"), ("lin_key", "key"), ("lin_value", "valu
 
 
 def _tensor(obj, path, attr):
-    t = getattr(obj, attr, None)
-    if not isinstance(t, torch.Tensor):
-        raise ValueError("base.%s.%s is missing or no tensor" % (path, attr))
-    return t
+    return _layers.tensor_attr(obj, "base." + path, attr)
 
 
 def _activation(obj, path):
@@ -127,11 +123,7 @@ def _check(node_obs, adj, agent_id, names, ps, meta):
         if not isinstance(t, torch.Tensor):
             raise ValueError("%s must be a tensor" % name)
     tensors = [("node_obs", node_obs), ("adj", adj)] + [("base.gnn." + n, t) for n, t in zip(names, ps)]
-    for name, t in tensors:
-        if t.dtype in (torch.float16, torch.bfloat16):
-            raise NotImplementedError("%s is %s: gnn_base is float32 only (half precision is not supported)" % (name, t.dtype))
-        if t.dtype != torch.float32:
-            raise ValueError("%s must be float32, not %s" % (name, t.dtype))
+    _layers.need_float32("gnn_base", tensors)
     if agent_id.dtype not in (torch.int32, torch.int64, torch.float32):
         raise ValueError("agent_id must be int32, int64 or float32, not %s" % agent_id.dtype)
     if node_obs.dim() != 3 or min(node_obs.shape) < 1:
@@ -169,9 +161,7 @@ def _check(node_obs, adj, agent_id, names, ps, meta):
             raise ValueError("base.gnn.%s must have shape %s (F = %d, %d heads of %d, averaged), not %s" % (name, s, F, heads, HIDDEN, tuple(t.shape)))
     dev = node_obs.device
     _need_cuda(dev)
-    for name, t in tensors + [("agent_id", agent_id)]:
-        if t.device != dev:
-            raise ValueError("%s must be on %s (the device of node_obs)" % (name, dev))
+    _layers.need_device(tensors + [("agent_id", agent_id)], dev, "node_obs")
     return dev, rows, E, F, share, nemb, esz
 
 
@@ -231,7 +221,7 @@ class _Base(torch.autograd.Function):
         features = torch.empty((shape[0], HIDDEN), dtype=torch.float32, device=dev)
         plan = _plan(shape, meta, cs[0], cs[1], cs[2], cs[3:])
         plan.features = features.data_ptr()
-        _lib.check(_lib.load().gmpe_gnn_forward(_ordinal(dev), C.byref(plan), _stream_of(dev)), "gmpe_gnn_forward")
+        _layers.run("gmpe_gnn_forward", dev, plan)
         if workspace is not None:
             ctx.save_for_backward(*cs)
         ctx.meta, ctx.shape, ctx.workspace = meta, shape, workspace
@@ -248,7 +238,7 @@ class _Base(torch.autograd.Function):
         plan.grad_features = gf.data_ptr()
         plan.workspace, plan.workspace_bytes = ctx.workspace.data_ptr(), ctx.workspace.numel()
         _fill(plan, ctx.meta, ctx.meta[5], ctx.meta[2], ctx.meta[1], grads, "grad_")
-        _lib.check(_lib.load().gmpe_gnn_backward(_ordinal(dev), C.byref(plan), _stream_of(dev)), "gmpe_gnn_backward")
+        _layers.run("gmpe_gnn_backward", dev, plan)
         return (None, None, None, None, None, None) + tuple(grads)
 
 
@@ -273,9 +263,5 @@ def gnn_base(node_obs, adj, agent_id, base, workspace=None):
     dev, rows, E, F, share, nemb, esz = _check(node_obs, adj, agent_id, names, ps, meta)
     ids = agent_id.detach().reshape(rows).to(torch.int32)
     train = torch.is_grad_enabled() and any(t.requires_grad for t in ps)
-    if train:
-        workspace = _workspace(gnn_workspace_bytes(rows, E, F, meta[0], meta[1], meta[2], nemb, esz), workspace, dev)
-    elif workspace is not None:
-        _workspace(0, workspace, dev)
-        workspace = None
+    workspace = _layers.backward_workspace(train, lambda: gnn_workspace_bytes(rows, E, F, meta[0], meta[1], meta[2], nemb, esz), workspace, dev)
     return _Base.apply(meta, (rows, E, F, share, nemb, esz), workspace, node_obs, adj, ids, *ps)

@@ -10,9 +10,8 @@ import ctypes as C
 
 import torch
 
-from . import _lib
-from .engine import _need_cuda, _stream_of, _workspace
-from .ppo_loss import _ordinal
+from . import _layers, _lib
+from .engine import _need_cuda
 
 SUPPORTED = ((64, 64),)                                 # (in_dim, hidden) the library is built for
 _PARAMS = ("weight_ih", "weight_hh", "bias_ih", "bias_hh", "ln_weight", "ln_bias")
@@ -39,11 +38,7 @@ def _layer_params(layer):
         raise NotImplementedError("layer.rnn has more than one layer or direction: rnn_layer supports recurrent_N == 1, one direction")
     ps = []
     for owner, obj, names in (("rnn", rnn, ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")), ("norm", norm, ("weight", "bias"))):
-        for k in names:
-            t = getattr(obj, k, None)
-            if not isinstance(t, torch.Tensor):
-                raise ValueError("layer.%s.%s is missing or no tensor" % (owner, k))
-            ps.append(t)
+        ps += [_layers.tensor_attr(obj, "layer." + owner, k) for k in names]
     return ps, float(getattr(norm, "eps", 1e-5))
 
 
@@ -53,11 +48,7 @@ def _check(x, hxs, masks, ps):
         if not isinstance(t, torch.Tensor):
             raise ValueError("%s must be a tensor" % name)
     tensors = (("x", x), ("hxs", hxs), ("masks", masks)) + tuple(zip(_PARAMS, ps))
-    for name, t in tensors:
-        if t.dtype in (torch.float16, torch.bfloat16):
-            raise NotImplementedError("%s is %s: rnn_layer is float32 only (half precision is not supported)" % (name, t.dtype))
-        if t.dtype != torch.float32:
-            raise ValueError("%s must be float32, not %s" % (name, t.dtype))
+    _layers.need_float32("rnn_layer", tensors)
     if x.dim() != 2 or hxs.dim() != 3 or hxs.shape[0] < 1 or x.shape[0] < 1:
         raise ValueError("x must have shape (L * Nb, D) and hxs (Nb, recurrent_N, H), not %s and %s" % (tuple(x.shape), tuple(hxs.shape)))
     if hxs.shape[1] != 1:
@@ -76,9 +67,7 @@ def _check(x, hxs, masks, ps):
         raise NotImplementedError("(in_dim, hidden) = (%d, %d): rnn_layer is built for %s" % (D, H, list(SUPPORTED)))
     dev = x.device
     _need_cuda(dev)
-    for name, t in tensors:
-        if t.device != dev:
-            raise ValueError("%s must be on %s (the device of x)" % (name, dev))
+    _layers.need_device(tensors, dev, "x")
     return dev, L, Nb, D, H
 
 
@@ -108,7 +97,7 @@ class _Layer(torch.autograd.Function):
         features = torch.empty((L * Nb, H), dtype=torch.float32, device=dev)
         hxs_out = torch.empty((Nb, 1, H), dtype=torch.float32, device=dev)
         plan = _plan(L, Nb, D, H, eps, xc, hc, mc, ps, features, hxs_out, workspace)
-        _lib.check(_lib.load().gmpe_gru_forward(_ordinal(dev), C.byref(plan), _stream_of(dev)), "gmpe_gru_forward")
+        _layers.run("gmpe_gru_forward", dev, plan)
         ctx.save_for_backward(xc, hc, mc, *ps)
         ctx.workspace, ctx.eps, ctx.dims = workspace, eps, dims
         return features, hxs_out
@@ -129,7 +118,7 @@ class _Layer(torch.autograd.Function):
             plan.grad_hxs_out = gh.data_ptr()
         for k, t in zip(("grad_x", "grad_hxs") + tuple("grad_" + n for n in _PARAMS), grads):
             setattr(plan, k, t.data_ptr())
-        _lib.check(_lib.load().gmpe_gru_backward(_ordinal(dev), C.byref(plan), _stream_of(dev)), "gmpe_gru_backward")
+        _layers.run("gmpe_gru_backward", dev, plan)
         return tuple(grads) + (None, None, None, None)
 
 
@@ -147,9 +136,5 @@ def rnn_layer(x, hxs, masks, layer, workspace=None):
     ps, eps = _layer_params(layer)
     dev, L, Nb, D, H = _check(x, hxs, masks, ps)
     train = torch.is_grad_enabled() and any(t.requires_grad for t in [x, hxs] + ps)
-    if train:
-        workspace = _workspace(rnn_workspace_bytes(L, Nb, H), workspace, dev)
-    elif workspace is not None:
-        _workspace(0, workspace, dev)
-        workspace = None
+    workspace = _layers.backward_workspace(train, lambda: rnn_workspace_bytes(L, Nb, H), workspace, dev)
     return _Layer.apply(x, hxs, *ps, masks, eps, (L, Nb, D, H), workspace)

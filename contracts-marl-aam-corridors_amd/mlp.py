@@ -10,9 +10,8 @@ import ctypes as C
 
 import torch
 
-from . import _lib
-from .engine import _need_cuda, _stream_of, _workspace
-from .ppo_loss import _ordinal
+from . import _layers, _lib
+from .engine import _need_cuda
 
 HIDDEN = 64                                             # the hidden size the library is built for
 MAX_LAYER_N, MAX_IN, MAX_PARTS = _lib.MLP_MAX_LAYERS - 1, _lib.MLP_MAX_IN, _lib.MLP_MAX_PARTS
@@ -41,10 +40,7 @@ def _block(owner, seq, names, ps, epss):
     except (TypeError, IndexError, KeyError):
         raise ValueError("base.mlp.%s must hold [0] the Linear, [1] the activation and [2] the LayerNorm" % owner)
     for obj, what, k in ((lin, "[0]", "weight"), (lin, "[0]", "bias"), (norm, "[2]", "weight"), (norm, "[2]", "bias")):
-        t = getattr(obj, k, None)
-        if not isinstance(t, torch.Tensor):
-            raise ValueError("base.mlp.%s%s.%s is missing or no tensor" % (owner, what, k))
-        ps.append(t)
+        ps.append(_layers.tensor_attr(obj, "base.mlp." + owner + what, k))
     names += ["%s.%s" % (owner, k) for k in _LAYER]
     epss.append(float(getattr(norm, "eps", 1e-5)))
     return type(act).__name__
@@ -69,10 +65,7 @@ def _base_params(base):
     if fnorm:
         norm = getattr(base, "feature_norm", None)
         for k in ("weight", "bias"):
-            t = getattr(norm, k, None)
-            if not isinstance(t, torch.Tensor):
-                raise ValueError("base.feature_norm.%s is missing or no tensor (base._use_feature_normalization is set)" % k)
-            ps.append(t)
+            ps.append(_layers.tensor_attr(norm, "base.feature_norm", k, " (base._use_feature_normalization is set)"))
             names.append("feature_norm." + k)
         fn_eps = float(getattr(norm, "eps", 1e-5))
     acts = [_block("fc1", mlp.fc1, names, ps, epss)] + [_block("fc2[%d]" % i, fc2[i], names, ps, epss) for i in range(layer_n)]
@@ -94,11 +87,7 @@ def _check(parts, names, ps, meta):
         if not isinstance(t, torch.Tensor):
             raise ValueError("parts[%d] must be a tensor" % i)
     tensors = [("parts[%d]" % i, t) for i, t in enumerate(parts)] + list(zip(names, ps))
-    for name, t in tensors:
-        if t.dtype in (torch.float16, torch.bfloat16):
-            raise NotImplementedError("%s is %s: mlp_base is float32 only (half precision is not supported)" % (name, t.dtype))
-        if t.dtype != torch.float32:
-            raise ValueError("%s must be float32, not %s" % (name, t.dtype))
+    _layers.need_float32("mlp_base", tensors)
     for i, t in enumerate(parts):
         if t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
             raise ValueError("parts[%d] must have shape (rows, d) with rows, d >= 1, not %s" % (i, tuple(t.shape)))
@@ -117,9 +106,7 @@ def _check(parts, names, ps, meta):
             raise ValueError("base's %s must have shape %s (the parts have %d columns), not %s" % (name, s, D, tuple(t.shape)))
     dev = parts[0].device
     _need_cuda(dev)
-    for name, t in tensors:
-        if t.device != dev:
-            raise ValueError("%s must be on %s (the device of parts[0])" % (name, dev))
+    _layers.need_device(tensors, dev, "parts[0]")
     return dev, rows, dims
 
 
@@ -161,7 +148,7 @@ class _Base(torch.autograd.Function):
         features = torch.empty((rows, HIDDEN), dtype=torch.float32, device=dev)
         plan = _plan(rows, dims, meta, cs[:n], cs[n:])
         plan.features = features.data_ptr()
-        _lib.check(_lib.load().gmpe_mlp_forward(_ordinal(dev), C.byref(plan), _stream_of(dev)), "gmpe_mlp_forward")
+        _layers.run("gmpe_mlp_forward", dev, plan)
         if workspace is not None:
             ctx.save_for_backward(*cs)
         ctx.meta, ctx.rows, ctx.dims, ctx.workspace = meta, rows, dims, workspace
@@ -178,7 +165,7 @@ class _Base(torch.autograd.Function):
         plan.grad_features = gf.data_ptr()
         plan.workspace, plan.workspace_bytes = ctx.workspace.data_ptr(), ctx.workspace.numel()
         _grads_into(plan, ctx.meta, grads[:n], grads[n:])
-        _lib.check(_lib.load().gmpe_mlp_backward(_ordinal(dev), C.byref(plan), _stream_of(dev)), "gmpe_mlp_backward")
+        _layers.run("gmpe_mlp_backward", dev, plan)
         return (None, None, None, None) + tuple(grads)
 
 
@@ -203,9 +190,5 @@ def mlp_base(parts, base, workspace=None):
     names, ps, meta = _base_params(base)
     dev, rows, dims = _check(parts, names, ps, meta)
     train = torch.is_grad_enabled() and any(t.requires_grad for t in parts + tuple(ps))
-    if train:
-        workspace = _workspace(mlp_workspace_bytes(rows, sum(dims), meta[0]), workspace, dev)
-    elif workspace is not None:
-        _workspace(0, workspace, dev)
-        workspace = None
+    workspace = _layers.backward_workspace(train, lambda: mlp_workspace_bytes(rows, sum(dims), meta[0]), workspace, dev)
     return _Base.apply(meta, rows, dims, workspace, *parts, *ps)

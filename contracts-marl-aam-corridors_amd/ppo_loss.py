@@ -22,7 +22,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .engine import _need_cuda, _stream_of, _workspace
+from .engine import _need_cuda, _ordinal, _stream_of, _workspace
 
 PPOPopArtLosses = collections.namedtuple("PPOPopArtLosses", ["actor_loss", "value_loss", "policy_loss", "dist_entropy", "ratio_mean", "action_log_probs",
                                                              "imp_weights", "values"])
@@ -108,10 +108,6 @@ def _column(name, t, rows, dev, dtypes=(torch.float32,)):
     if t.device != dev:
         raise ValueError("%s must be on %s (the device of logits)" % (name, dev))
     return t.detach().contiguous()
-
-
-def _ordinal(dev):                                     # what the C entry points take
-    return dev.index if dev.index is not None else torch.cuda.current_device()
 
 
 def _logits_shape(logits):

@@ -43,16 +43,15 @@ def test_gru_workspace_is_exactly_the_documented_layout(L, Nb):
 
 
 def test_the_restated_constants_are_the_sources():
-    src = {f: open(os.path.join(CSRC, f)).read() for f in ("gmpe_gru.hip", "gmpe_mlp.hip", "gmpe_wgrad.h")}
+    src = {f: open(os.path.join(CSRC, f)).read() for f in ("gmpe_host.h", "gmpe_wgrad.h")}
     hdr = open(os.path.join(ROOT, "include", "gmpe.h")).read()
 
     def const(text, name):
         m = re.search(r"\b%s\s*=\s*([^,;]+)[,;]" % name, text)
         assert m, name
         return m.group(1).strip()
-    assert int(const(src["gmpe_gru.hip"], "MAX_GRID")) == S.MAX_GRID
-    assert int(const(src["gmpe_mlp.hip"], "MAX_CU")) == S.MAX_CU
-    assert const(src["gmpe_mlp.hip"], "LDS_CU") == "160 * 1024" and S.LDS_CU == 160 * 1024
+    assert int(const(src["gmpe_host.h"], "MAX_CU")) == S.MAX_CU == S.MAX_GRID         # the GRU's grids are the one rule's, at one workgroup per CU
+    assert const(src["gmpe_host.h"], "LDS_CU") == "160 * 1024" and S.LDS_CU == 160 * 1024
     assert int(const(src["gmpe_wgrad.h"], "MAX_PARTS")) == S.MAX_PARTS and int(const(src["gmpe_wgrad.h"], "PART_ROWS")) == S.PART_ROWS
     assert const(src["gmpe_wgrad.h"], "FIN_SLICES") == "BLOCK / FIN_COLS"
     assert int(const(src["gmpe_wgrad.h"], "BLOCK")) // int(const(src["gmpe_wgrad.h"], "FIN_COLS")) == S.FIN_SLICES

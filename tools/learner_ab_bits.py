@@ -1,6 +1,7 @@
 """Bit-for-bit A/B of two builds of libgmpe.so over the three entry points that share gmpe_ppo_rows.h: gmpe_ppo_loss, gmpe_ppo_loss_popart and
-gmpe_act_sample, and over gmpe_compute_returns and the two sharded entry points, called through their C plans on fixed inputs. The GPU suites bound
-the losses against float64, so they would not see a changed rounding; this does.
+gmpe_act_sample, over gmpe_compute_returns and the two sharded entry points, and over the nine entry points of the three layer kernels (gmpe_gru_*,
+gmpe_mlp_*, gmpe_gnn_*), called through their C plans on fixed inputs. The GPU suites bound the losses and the layers against float64, so they would
+not see a changed rounding or a changed order of the finish sums; this does.
 
     GMPE_LIB=/path/to/libgmpe_parent.so python tools/learner_ab_bits.py dump a.npz     # one process per build
     python tools/learner_ab_bits.py dump b.npz
@@ -19,6 +20,12 @@ eight branches and the advantages alone with and without a denormaliser) and on 
 inputs through gmpe_compute_returns_shard LOCAL then APPLY at world 1, and the cases at their own split with `all` stacked from the shards' `local`.
 shard/: gmpe_ppo_loss_shard LOCAL then APPLY for rows in 1, 257, 600 x K in 1, 5, 64 x all flags on / off at world 1, and 1030 rows split 1 + 256 + 773.
 Kept: returns, value_preds, raw and normalised advantages, `local`; the loss call's outputs as above with `local`.
+layers/: every case once through its forward-only plan and once through its training plan (forward with the workspace, then backward), the workspace
+of the size its *_workspace_bytes entry gives. gru/: tests/gru_lib.py's CASES x PATTERNS, and (1, 8257) (259 tiles on 256 workgroups) and (17, 241)
+(ragged and empty parts, tests/layer_scale_lib.py's GRU_SIZE_SHAPES) with random masks. mlp/: tests/mlp_lib.py's CASES and layer_scale_lib's 545-,
+8257- and 32801-row cases, at mlp_lib's seed 0. gnn/: tests/gnn_lib.py's CASES, and 5005 graphs of E = 6 (the 65 of the actor's case repeated: every
+workgroup of backward owns several tiles, the finish adds 256 partial rows) with a dense adjacency and with one matrix shared by five rows.
+Kept: features (and hxs_out) of both plans, every input gradient, every parameter gradient, the workspace size.
 """
 import ctypes as C
 import itertools
@@ -243,6 +250,113 @@ def dump(path):
             all_stats = two_phase("gmpe_ppo_loss_shard", _lib.GmpePpoLossShardPlan, _lib.PPO_SHARD_STATS, [m[0] for m in made])
             outs = {"%s_s%d" % (k, i): t for i, m in enumerate(made) for k, t in m[1].items()}
             save("shard/B%d_K%d_fl%d_%s" % (B, K, on, "+".join(str(x) for x in split)), local=all_stats, **outs)
+    # ---- the three layer kernels, each through its three entry points
+    import gnn_lib
+    import gru_lib
+    import layer_scale_lib
+    import mlp_lib
+    from gmpe import gnn, gru, mlp
+
+    def on_dev(a):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+    def zeros(shape):
+        return torch.zeros(tuple(shape), dtype=torch.float32, device=dev)
+
+    def with_workspace(plan, ws):
+        if ws is not None:
+            plan.workspace, plan.workspace_bytes = ws.data_ptr(), ws.numel()
+        return plan
+
+    def layer(tag, name, nbytes, forward_plan, backward_plan):
+        """forward_plan(workspace or None) -> (plan, its outputs), backward_plan(workspace) -> (plan, its gradients)"""
+        plan, out = forward_plan(None)
+        _lib.check(getattr(lib, name + "_forward")(dev.index, C.byref(plan), stream), name + "_forward")
+        save("layers/%s/eval" % tag, **out)
+        ws = torch.zeros(nbytes.value, dtype=torch.uint8, device=dev)
+        plan, out = forward_plan(ws)
+        _lib.check(getattr(lib, name + "_forward")(dev.index, C.byref(plan), stream), name + "_forward")
+        plan, grads = backward_plan(ws)
+        _lib.check(getattr(lib, name + "_backward")(dev.index, C.byref(plan), stream), name + "_backward")
+        save("layers/%s/train" % tag, workspace_bytes=torch.tensor([nbytes.value]), **out, **grads)
+
+    def gru_case(L, Nb, pattern):
+        P, I, H = gru_lib.params(), gru_lib.inputs(L, Nb), gru_lib.H
+        ps = [on_dev(P[k]) for k in gru_lib.PARAMS]
+        x, hxs, gf, gh, m = (on_dev(a) for a in (I["x"], I["hxs"], I["gf"], I["gh"], gru_lib.masks(L, Nb, pattern)))
+        n = C.c_size_t()
+        _lib.check(lib.gmpe_gru_workspace_bytes(L, Nb, H, 1, C.byref(n)), "gmpe_gru_workspace_bytes")
+
+        def forward_plan(ws):
+            out = dict(features=zeros((L * Nb, H)), hxs_out=zeros((Nb, 1, H)))
+            return gru._plan(L, Nb, gru_lib.D, H, gru_lib.EPS, x, hxs, m, ps, out["features"], out["hxs_out"], ws), out
+
+        def backward_plan(ws):
+            grads = {k: torch.zeros_like(t) for k, t in zip(gru_lib.GRADS, [x, hxs] + ps)}
+            plan = gru._plan(L, Nb, gru_lib.D, H, gru_lib.EPS, x, hxs, m, ps, None, None, ws)
+            plan.grad_features, plan.grad_hxs_out = ptr(gf), ptr(gh)
+            for k, t in grads.items():
+                setattr(plan, k, ptr(t))
+            return plan, grads
+        layer("gru/" + gru_lib.key(L, Nb, pattern), "gmpe_gru", n, forward_plan, backward_plan)
+
+    def mlp_case(case):
+        rows, dims, layer_n, act, fnorm = case
+        P, I = mlp_lib.params(case), mlp_lib.inputs(case)
+        ps = [on_dev(P[k]) for k in mlp_lib.param_names(case)]
+        parts, gf = [on_dev(a) for a in mlp_lib.split(I["x"], dims)], on_dev(I["gf"])
+        meta = (layer_n, mlp._ACTIVATIONS[act], fnorm, mlp_lib.EPS, (mlp_lib.EPS,) * (layer_n + 1))
+        n = C.c_size_t()
+        _lib.check(lib.gmpe_mlp_workspace_bytes(rows, sum(dims), mlp_lib.H, layer_n, 1, C.byref(n)), "gmpe_mlp_workspace_bytes")
+
+        def forward_plan(ws):
+            out = dict(features=zeros((rows, mlp_lib.H)))
+            plan = with_workspace(mlp._plan(rows, dims, meta, parts, ps), ws)
+            plan.features = ptr(out["features"])
+            return plan, out
+
+        def backward_plan(ws):
+            grads = [torch.zeros_like(t) for t in parts + ps]
+            plan = with_workspace(mlp._plan(rows, dims, meta, parts, ps), ws)
+            plan.grad_features = ptr(gf)
+            mlp._grads_into(plan, meta, grads[:len(parts)], grads[len(parts):])
+            return plan, dict(zip(mlp_lib.out_names(case)[1:], grads))
+        layer("mlp/" + mlp_lib.key(case), "gmpe_mlp", n, forward_plan, backward_plan)
+
+    def gnn_case(tag, key, x, adj, ids, gf):
+        names, ps, meta = gnn._base_params(gnn_lib.build(gnn_lib.CONFIGS[key]).to(dev))
+        ps = [t.detach().contiguous() for t in ps]
+        x, adj, ids, gf = x.to(dev).contiguous(), adj.to(dev).contiguous(), ids.to(device=dev, dtype=torch.int32), gf.to(dev).contiguous()
+        (rows, E, F), (nemb, esz) = x.shape, ps[0].shape
+        shape = (rows, E, F, rows // adj.shape[0], nemb, esz)
+        n = C.c_size_t()
+        _lib.check(lib.gmpe_gnn_workspace_bytes(C.byref(gnn._shape_plan(rows, E, F, shape[3], meta[0], meta[1], meta[2], nemb, esz)), 1, C.byref(n)),
+                   "gmpe_gnn_workspace_bytes")
+
+        def forward_plan(ws):
+            out = dict(features=zeros((rows, gnn_lib.C)))
+            plan = with_workspace(gnn._plan(shape, meta, x, adj, ids, ps), ws)
+            plan.features = ptr(out["features"])
+            return plan, out
+
+        def backward_plan(ws):
+            grads = [torch.zeros_like(t) for t in ps]
+            plan = with_workspace(gnn._plan(shape, meta, x, adj, ids, ps), ws)
+            plan.grad_features = ptr(gf)
+            gnn._fill(plan, meta, meta[5], meta[2], meta[1], grads, "grad_")
+            return plan, {"grad_" + k: t for k, t in zip(names, grads)}
+        layer("gnn/" + tag, "gmpe_gnn", n, forward_plan, backward_plan)
+
+    for (L, Nb), pattern in list(itertools.product(gru_lib.CASES, gru_lib.PATTERNS)) + [((1, 8257), "random"), ((17, 241), "random")]:
+        gru_case(L, Nb, pattern)
+    for case in mlp_lib.CASES + tuple(c for c in layer_scale_lib.MLP_CASES if c[0] in (545, 8257, 32801)):
+        mlp_case(case)
+    for case in gnn_lib.CASES:
+        gnn_case(gnn_lib.case_id(case), case[2], *gnn_lib.inputs(*case)[:4])
+    many, share = 5005, 5
+    X, A, I, W = (t.repeat((many // 65,) + (1,) * (t.dim() - 1)) for t in gnn_lib.inputs(65, 6, gnn_lib.ACTOR)[:4])
+    gnn_case("%dx6_dense" % many, gnn_lib.ACTOR, X, A, I, W)
+    gnn_case("%dx6_shared%d" % (many, share), gnn_lib.ACTOR, X, A[:many // share], I, W)
     np.savez(path, **kept)
     print("dump: %d arrays, %d elements (%d non-zero) from %s -> %s" % (len(kept), sum(a.size for a in kept.values()),
                                                                        sum(int(np.count_nonzero(a)) for a in kept.values()), _lib.LIB_PATH, path))
@@ -268,7 +382,7 @@ def compare(pa, pb):
         if d:
             print("%s: %d of %d elements differ" % (k, d, x.size))
             differing += d
-    per = {p: sum(1 for k in names if k.startswith(p)) for p in ("loss/", "popart_", "act/", "returns/", "shard/")}
+    per = {p: sum(1 for k in names if k.startswith(p)) for p in ("loss/", "popart_", "act/", "returns/", "shard/", "layers/")}
     print("compare: %d arrays (%s), %d elements, %d differing" % (len(names), ", ".join("%s %d" % (p.rstrip("/_"), n) for p, n in per.items()), elements,
                                                                  differing))
     return 1 if differing or not names else 0
