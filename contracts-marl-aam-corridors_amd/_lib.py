@@ -24,7 +24,8 @@ SYMBOLS = ["gmpe_abi_version", "gmpe_last_error", "gmpe_obs_dim", "gmpe_node_fea
            "gmpe_act_sample", "gmpe_compute_returns_shard", "gmpe_ppo_loss_shard",
            "gmpe_gru_workspace_bytes", "gmpe_gru_forward", "gmpe_gru_backward",
            "gmpe_mlp_workspace_bytes", "gmpe_mlp_forward", "gmpe_mlp_backward",
-           "gmpe_gnn_workspace_bytes", "gmpe_gnn_forward", "gmpe_gnn_backward"]
+           "gmpe_gnn_workspace_bytes", "gmpe_gnn_forward", "gmpe_gnn_backward",
+           "gmpe_head_workspace_bytes", "gmpe_head_forward", "gmpe_head_backward", "gmpe_act_head"]
 
 
 class GmpeOutputs(C.Structure):
@@ -190,6 +191,13 @@ class GmpeActPlan(C.Structure):
                 ("action_idx", C.c_void_p), ("log_probs", C.c_void_p), ("actions_f32", C.c_void_p), ("actions_i64", C.c_void_p)]
 
 
+class GmpeHeadPlan(C.Structure):
+    """gmpe_head_plan (include/gmpe.h): the Linear of the policy's action head, forward, backward and inside the rollout's sampling launch."""
+    _fields_ = [("rows", C.c_int64), ("n_actions", C.c_int32), ("hidden", C.c_int32), ("features", C.c_void_p), ("weight", C.c_void_p),
+                ("bias", C.c_void_p), ("logits_out", C.c_void_p), ("grad_logits", C.c_void_p), ("grad_features", C.c_void_p),
+                ("grad_weight", C.c_void_p), ("grad_bias", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
 GRU_ROW_TILE = 32        # GMPE_GRU_ROW_TILE of include/gmpe.h; tests/gru_lib.py TILE is the third copy — tests/test_gru_host.py compiles against the header and ties the three together
 
 
@@ -324,6 +332,10 @@ def load():
     lib.gmpe_gnn_workspace_bytes.argtypes = [C.POINTER(GmpeGnnPlan), C.c_int32, C.POINTER(C.c_size_t)]
     lib.gmpe_gnn_forward.argtypes = [I, C.POINTER(GmpeGnnPlan), P]
     lib.gmpe_gnn_backward.argtypes = [I, C.POINTER(GmpeGnnPlan), P]
+    lib.gmpe_head_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]
+    lib.gmpe_head_forward.argtypes = [I, C.POINTER(GmpeHeadPlan), P]
+    lib.gmpe_head_backward.argtypes = [I, C.POINTER(GmpeHeadPlan), P]
+    lib.gmpe_act_head.argtypes = [I, C.POINTER(GmpeActPlan), C.POINTER(GmpeHeadPlan), P]
     from .config import ABI_VERSION
     if lib.gmpe_abi_version() != ABI_VERSION:
         raise GmpeError("libgmpe.so ABI version mismatch")

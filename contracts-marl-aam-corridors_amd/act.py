@@ -24,12 +24,73 @@ OUT_KEYS = ("action_idx", "actions", "actions_f32", "action_log_probs")
 _OUT_DTYPES = dict(action_idx=torch.int32, actions=torch.int64, actions_f32=torch.float32, action_log_probs=torch.float32)
 
 
-def _rows_tensor(name, t, rows, dev, dtypes):
+def _rows_tensor(name, t, rows, dev, dtypes, anchor="logits"):
     if not isinstance(t, torch.Tensor) or t.dtype not in dtypes or t.numel() != rows or not t.is_contiguous():
         raise ValueError("%s must be a contiguous %s tensor with %d elements" % (name, " or ".join(str(d) for d in dtypes), rows))
     if t.device != dev:
-        raise ValueError("%s must be on %s (the device of logits)" % (name, dev))
+        raise ValueError("%s must be on %s (the device of %s)" % (name, dev, anchor))
     return t
+
+
+def _plan(rows, K, dev, anchor, available_actions, dones_prev, stop_action, seed, env_id_base, num_agents, draw, draw_dev, draw_inc, deterministic, out,
+          more_out=()):
+    """What sample_actions and head.act_head share: every argument besides the logits (or the features in their place; `anchor` names them in a
+    complaint) checked, the outputs taken from `out` or allocated -> (the plan without its logits, (action_idx, actions, action_log_probs), out as a
+    dict, the availability the plan points to: keep it until the launch is queued). more_out: {key: (dtype, elements)} of further entries `out` may hold; they are checked and left to the caller."""
+    if available_actions is not None and dones_prev is not None:
+        raise ValueError("available_actions and dones_prev are two sources of the availability: give at most one")
+    if available_actions is not None:
+        available_actions = _available(available_actions, rows, K, dev, contiguous=True)
+    if dones_prev is not None:
+        _rows_tensor("dones_prev", dones_prev, rows, dev, (torch.uint8, torch.bool), anchor)
+    elif stop_action is not None:
+        raise ValueError("stop_action is read with dones_prev only")
+    stop = K // 2 if stop_action is None else int(stop_action)          # available_actions[int(n / 2)] = 1 (graph_mpe_runner.py:283)
+    if not 0 <= stop < K:
+        raise ValueError("stop_action must lie in [0, %d)" % K)
+    num_agents = int(num_agents)
+    if num_agents < 1:
+        raise ValueError("num_agents must be >= 1")
+    if not -2 ** 31 <= int(env_id_base) < 2 ** 31:
+        raise ValueError("env_id_base must fit 32 bits")
+    if int(draw) < 0 or int(draw_inc) < 0:
+        raise ValueError("draw and draw_inc must be >= 0")
+    if draw_dev is not None:
+        if not isinstance(draw_dev, torch.Tensor) or draw_dev.dtype not in (torch.int64, torch.uint64) or draw_dev.numel() != 1 or \
+                not draw_dev.is_contiguous():
+            raise ValueError("draw_dev must be a contiguous int64 tensor with one element")
+        if draw_dev.device != dev:
+            raise ValueError("draw_dev must be on %s (the device of %s)" % (dev, anchor))
+    given = dict(out or {})
+    keys = OUT_KEYS + tuple(more_out)
+    unknown = set(given) - set(keys)
+    if unknown:
+        raise ValueError("unknown out entries: %s (expected some of %s)" % (sorted(unknown), list(keys)))
+    for k, t in given.items():
+        dtype, n = more_out[k] if k in more_out else (_OUT_DTYPES[k], rows)
+        _rows_tensor("out[%r]" % k, t, n, dev, (dtype,), anchor)
+    _need_cuda(dev)
+    idx = given.get("action_idx")
+    if idx is None:
+        idx = torch.empty((rows,), dtype=torch.int32, device=dev)
+    logp = given.get("action_log_probs")
+    if logp is None:
+        logp = torch.empty((rows, 1), dtype=torch.float32, device=dev)
+    act64 = given.get("actions")
+    if act64 is None and out is None:
+        act64 = torch.empty((rows, 1), dtype=torch.int64, device=dev)
+    actf = given.get("actions_f32")
+    plan = _lib.GmpeActPlan()
+    plan.rows, plan.n_actions, plan.num_agents, plan.stop_action, plan.deterministic = rows, K, num_agents, stop, int(bool(deterministic))
+    plan.env_id_base, plan.seed = int(env_id_base), int(seed) & 0xFFFFFFFFFFFFFFFF
+    plan.draw, plan.draw_inc = int(draw) & 0xFFFFFFFFFFFFFFFF, int(draw_inc) & 0xFFFFFFFFFFFFFFFF
+    plan.draw_dev = None if draw_dev is None else draw_dev.data_ptr()
+    plan.available_actions = None if available_actions is None else available_actions.data_ptr()
+    plan.dones_prev = None if dones_prev is None else dones_prev.data_ptr()
+    plan.action_idx, plan.log_probs = idx.data_ptr(), logp.data_ptr()
+    plan.actions_f32 = None if actf is None else actf.data_ptr()
+    plan.actions_i64 = None if act64 is None else act64.data_ptr()
+    return plan, (idx, act64, logp), given, available_actions
 
 
 def sample_actions(logits, available_actions=None, *, dones_prev=None, stop_action=None, seed, env_id_base=0, num_agents, draw, draw_dev=None,
@@ -58,58 +119,10 @@ def sample_actions(logits, available_actions=None, *, dones_prev=None, stop_acti
     logits = _widened(logits)
     if logits.dtype != torch.float32:
         raise ValueError("logits must be float32 (or float16 / bfloat16, widened here)")
-    if available_actions is not None and dones_prev is not None:
-        raise ValueError("available_actions and dones_prev are two sources of the availability: give at most one")
-    if available_actions is not None:
-        available_actions = _available(available_actions, rows, K, dev, contiguous=True)
-    if dones_prev is not None:
-        _rows_tensor("dones_prev", dones_prev, rows, dev, (torch.uint8, torch.bool))
-    elif stop_action is not None:
-        raise ValueError("stop_action is read with dones_prev only")
-    stop = K // 2 if stop_action is None else int(stop_action)          # available_actions[int(n / 2)] = 1 (graph_mpe_runner.py:283)
-    if not 0 <= stop < K:
-        raise ValueError("stop_action must lie in [0, %d)" % K)
-    num_agents = int(num_agents)
-    if num_agents < 1:
-        raise ValueError("num_agents must be >= 1")
-    if not -2 ** 31 <= int(env_id_base) < 2 ** 31:
-        raise ValueError("env_id_base must fit 32 bits")
-    if int(draw) < 0 or int(draw_inc) < 0:
-        raise ValueError("draw and draw_inc must be >= 0")
-    if draw_dev is not None:
-        if not isinstance(draw_dev, torch.Tensor) or draw_dev.dtype not in (torch.int64, torch.uint64) or draw_dev.numel() != 1 or \
-                not draw_dev.is_contiguous():
-            raise ValueError("draw_dev must be a contiguous int64 tensor with one element")
-        if draw_dev.device != dev:
-            raise ValueError("draw_dev must be on %s (the device of logits)" % dev)
-    given = dict(out or {})
-    unknown = set(given) - set(OUT_KEYS)
-    if unknown:
-        raise ValueError("unknown out entries: %s (expected some of %s)" % (sorted(unknown), list(OUT_KEYS)))
-    for k, t in given.items():
-        _rows_tensor("out[%r]" % k, t, rows, dev, (_OUT_DTYPES[k],))
-    _need_cuda(dev)
-    idx = given.get("action_idx")
-    if idx is None:
-        idx = torch.empty((rows,), dtype=torch.int32, device=dev)
-    logp = given.get("action_log_probs")
-    if logp is None:
-        logp = torch.empty((rows, 1), dtype=torch.float32, device=dev)
-    act64 = given.get("actions")
-    if act64 is None and out is None:
-        act64 = torch.empty((rows, 1), dtype=torch.int64, device=dev)
-    actf = given.get("actions_f32")
-    plan = _lib.GmpeActPlan()
-    plan.rows, plan.n_actions, plan.num_agents, plan.stop_action, plan.deterministic = rows, K, num_agents, stop, int(bool(deterministic))
-    plan.env_id_base, plan.seed = int(env_id_base), int(seed) & 0xFFFFFFFFFFFFFFFF
-    plan.draw, plan.draw_inc = int(draw) & 0xFFFFFFFFFFFFFFFF, int(draw_inc) & 0xFFFFFFFFFFFFFFFF
-    plan.draw_dev = None if draw_dev is None else draw_dev.data_ptr()
+    plan, outs, _, keep = _plan(rows, K, dev, "logits", available_actions, dones_prev, stop_action, seed, env_id_base, num_agents, draw, draw_dev, draw_inc,
+                                deterministic, out)
     plan.logits = logits.data_ptr()
-    plan.available_actions = None if available_actions is None else available_actions.data_ptr()
-    plan.dones_prev = None if dones_prev is None else dones_prev.data_ptr()
-    plan.action_idx, plan.log_probs = idx.data_ptr(), logp.data_ptr()
-    plan.actions_f32 = None if actf is None else actf.data_ptr()
-    plan.actions_i64 = None if act64 is None else act64.data_ptr()
     st = C.c_void_p(stream.cuda_stream) if stream is not None else _stream_of(dev)
     _lib.check(_lib.load().gmpe_act_sample(_ordinal(dev), C.byref(plan), st), "gmpe_act_sample")
-    return idx, act64, logp
+    del keep                                            # the availability as the launch reads it lives until the launch is queued
+    return outs

@@ -22,9 +22,7 @@
 
 #include <string>
 
-#include "gmpe_device.h"
-#include "gmpe_host.h"          // include/gmpe.h, the error text, GMPE_HIP_CHECK
-#include "gmpe_ppo_rows.h"
+#include "gmpe_act_rows.h"       // gmpe_device.h, gmpe_host.h (include/gmpe.h, the error text, GMPE_HIP_CHECK), gmpe_ppo_rows.h; the row's routine, shared with gmpe_head.hip
 
 #pragma clang fp contract(off)
 
@@ -32,110 +30,66 @@ namespace {
 
 using namespace gmpe_ppo;         // gmpe_ppo_rows.h: TILE, the tile machinery and the masked categorical
 
-struct ActArgs {
-    Geom g;
-    int A, stop, det;
-    uint32_t env_base;
-    uint64_t seed, draw;
-    const uint64_t* draw_dev;
-    const float *logits, *avail;
-    const uint8_t* dones;
-    int32_t* idx;
-    float *lp, *af;
-    int64_t* ai;
-};
-
 // One lane per row; the tile's available_actions (when given), then its logits, pass through the same LDS rows.
 template <bool VEC>
 __global__ __launch_bounds__(TILE) void k_act_rows(ActArgs p) {
     extern __shared__ __attribute__((aligned(16))) float sh[];
-    const int K = p.g.K;
     const Tile t = tile_of(p.g, sh);
-    const int64_t r = t.r;
-    float* row = t.row;
-    const uint64_t all = K == 64 ? ~0ull : (1ull << K) - 1ull;
-
-    uint64_t avail = all;
-    if (!p.avail && p.dones && t.live && p.dones[r]) avail = 1ull << p.stop;         // collect_with_mask: a done agent may only stop
-    avail = tile_in<VEC>(p.g, t, p.avail, p.logits, sh, avail);
+    const uint64_t avail = tile_in<VEC>(p.g, t, p.avail, p.logits, sh, act_avail0(p, t));
     if (!t.live) return;
-
-    // ---- the masked categorical, as policy_row forms it; the mode is taken while the row still holds the logits (rounding x - lse can make ties)
-    const float m = masked_max(row, K, avail);
-    const uint64_t set = avail ? avail : all;                                       // nothing available: the uniform row over all K
-    int mode = __builtin_ctzll(set);
-    for (int j = K - 1; j >= 0; --j)
-        if ((set >> j & 1) && masked_logit(row, avail, j) == m) mode = j;           // the first index of the largest masked logit
-    float ml, s2;
-    normalise_row(row, K, avail, m, &ml, &s2);
-    int a = mode;
-    if (!p.det) {
-        const int64_t env = r / p.A;
-        const uint64_t agent = (uint64_t)(r - env * p.A);
-        const uint64_t d = p.draw + (p.draw_dev ? *p.draw_dev : 0ull);
-        const double u = gmpe::philox_uniform(p.seed, p.env_base + (uint32_t)env, 0x8000000000000000ull | (d * (uint64_t)p.A + agent));
-        float c = 0.0f;
-        for (int j = 0; j < K; ++j) {
-            if (!(set >> j & 1)) continue;
-            c = __fadd_rn(c, prob(row[j], ml, s2));
-            if ((double)c > u) { a = j; break; }
-        }
-    }
-    p.idx[r] = a;
-    p.lp[r] = row[a];
-    if (p.af) p.af[r] = (float)a;
-    if (p.ai) p.ai[r] = (int64_t)a;
+    act_row(p, t.r, t.row, avail);
 }
 
 // after the rows of this call have read the counter (same stream): the next replay of a captured graph draws fresh numbers
 __global__ void k_act_advance(uint64_t* draw_dev, uint64_t inc) { *draw_dev += inc; }
 
-int fail(int code, const std::string& m) { return gmpe::report_error(code, m); }
-
 }  // namespace
+
+namespace gmpe {
+
+int check_act_plan(const char* fn, const gmpe_act_plan* pl, bool given_logits) {
+    if (!pl) return fail(fn, "null plan");
+    if (pl->rows < 1) return fail(fn, "need rows >= 1");
+    if (pl->n_actions < 1 || pl->n_actions > GMPE_PPO_MAX_ACTIONS) return fail(fn, "n_actions must be in 1 .. " + std::to_string(GMPE_PPO_MAX_ACTIONS));
+    if (pl->num_agents < 1) return fail(fn, "need num_agents >= 1");
+    if (pl->stop_action < 0 || pl->stop_action >= pl->n_actions) return fail(fn, "stop_action must be in 0 .. n_actions - 1");
+    if (pl->deterministic != 0 && pl->deterministic != 1) return fail(fn, "deterministic must be 0 or 1");
+    if (pl->reserved != 0) return fail(fn, "reserved must be 0");
+    if (pl->available_actions && pl->dones_prev)
+        return fail(fn, "available_actions and dones_prev are two sources of the availability: give at most one");
+    if (given_logits && !pl->logits) return fail(fn, "logits is required");
+    if (!given_logits && pl->logits) return fail(fn, "act_plan->logits must be NULL: the logits are formed from head_plan->features");
+    if (!pl->action_idx) return fail(fn, "action_idx is required");
+    if (!pl->log_probs) return fail(fn, "log_probs is required");
+    const uintptr_t a4 = (uintptr_t)pl->logits | (uintptr_t)pl->available_actions | (uintptr_t)pl->action_idx | (uintptr_t)pl->log_probs | (uintptr_t)pl->actions_f32;
+    if ((a4 & 3) || (((uintptr_t)pl->actions_i64 | (uintptr_t)pl->draw_dev) & 7))
+        return fail(fn, "f32 / int32 arrays must be 4-byte aligned, actions_i64 and draw_dev 8-byte aligned");
+    if (gmpe_ppo::num_tiles(pl->rows) > 0x7fffffffLL) return fail(fn, "too many rows for one launch");
+    return GMPE_OK;
+}
+
+int act_advance(uint64_t* draw_dev, uint64_t inc, hipStream_t stream) {
+    GMPE_LAUNCH(k_act_advance, dim3(1), dim3(1), 0, stream, draw_dev, inc);
+    return GMPE_OK;
+}
+
+}  // namespace gmpe
 
 extern "C" {
 
 int gmpe_act_sample(int device, const gmpe_act_plan* pl, void* stream) {
-    if (!pl) return fail(GMPE_ERR_INVALID_ARG, "gmpe_act_sample: null plan");
-    if (pl->rows < 1) return fail(GMPE_ERR_INVALID_ARG, "gmpe_act_sample: need rows >= 1");
-    if (pl->n_actions < 1 || pl->n_actions > GMPE_PPO_MAX_ACTIONS)
-        return fail(GMPE_ERR_INVALID_ARG, "gmpe_act_sample: n_actions must be in 1 .. " + std::to_string(GMPE_PPO_MAX_ACTIONS));
-    if (pl->num_agents < 1) return fail(GMPE_ERR_INVALID_ARG, "gmpe_act_sample: need num_agents >= 1");
-    if (pl->stop_action < 0 || pl->stop_action >= pl->n_actions) return fail(GMPE_ERR_INVALID_ARG, "gmpe_act_sample: stop_action must be in 0 .. n_actions - 1");
-    if (pl->deterministic != 0 && pl->deterministic != 1) return fail(GMPE_ERR_INVALID_ARG, "gmpe_act_sample: deterministic must be 0 or 1");
-    if (pl->reserved != 0) return fail(GMPE_ERR_INVALID_ARG, "gmpe_act_sample: reserved must be 0");
-    if (pl->available_actions && pl->dones_prev)
-        return fail(GMPE_ERR_INVALID_ARG, "gmpe_act_sample: available_actions and dones_prev are two sources of the availability: give at most one");
-    if (!pl->logits) return fail(GMPE_ERR_INVALID_ARG, "gmpe_act_sample: logits is required");
-    if (!pl->action_idx) return fail(GMPE_ERR_INVALID_ARG, "gmpe_act_sample: action_idx is required");
-    if (!pl->log_probs) return fail(GMPE_ERR_INVALID_ARG, "gmpe_act_sample: log_probs is required");
-    const uintptr_t a4 = (uintptr_t)pl->logits | (uintptr_t)pl->available_actions | (uintptr_t)pl->action_idx | (uintptr_t)pl->log_probs | (uintptr_t)pl->actions_f32;
-    if ((a4 & 3) || (((uintptr_t)pl->actions_i64 | (uintptr_t)pl->draw_dev) & 7))
-        return fail(GMPE_ERR_INVALID_ARG, "gmpe_act_sample: f32 / int32 arrays must be 4-byte aligned, actions_i64 and draw_dev 8-byte aligned");
-    const int64_t nt = num_tiles(pl->rows);
-    if (nt > 0x7fffffffLL) return fail(GMPE_ERR_INVALID_ARG, "gmpe_act_sample: too many rows for one launch");
+    if (int rc = gmpe::check_act_plan("gmpe_act_sample", pl, true)) return rc;
     GMPE_HIP_CHECK(hipSetDevice(device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    ActArgs a;
-    a.g = geometry(pl->rows, pl->n_actions);
-    a.A = pl->num_agents; a.stop = pl->stop_action; a.det = pl->deterministic;
-    a.env_base = (uint32_t)pl->env_id_base;
-    a.seed = pl->seed; a.draw = pl->draw; a.draw_dev = pl->draw_dev;
-    a.logits = pl->logits; a.avail = pl->available_actions; a.dones = pl->dones_prev;
-    a.idx = pl->action_idx; a.lp = pl->log_probs; a.af = pl->actions_f32; a.ai = pl->actions_i64;
+    const ActArgs a = act_args(pl);
     const bool vec = !(((uintptr_t)pl->logits | (uintptr_t)pl->available_actions) & 15);        // tiles start at multiples of 1 KiB
     const size_t lds = (size_t)TILE * a.g.S * sizeof(float);
     void (*fn)(ActArgs) = vec ? k_act_rows<true> : k_act_rows<false>;
     if (lds > 48 * 1024)                                                      // K = 64 only
         if (int rc = gmpe::raise_dynamic_lds_once(reinterpret_cast<const void*>(fn), device, vec, TILE * (GMPE_PPO_MAX_ACTIONS | 1) * sizeof(float)))
             return rc;
-    hipLaunchKernelGGL(fn, dim3((unsigned)nt), dim3(TILE), lds, st, a);
-    GMPE_HIP_CHECK(hipGetLastError());
-    if (pl->draw_dev) {
-        hipLaunchKernelGGL(k_act_advance, dim3(1), dim3(1), 0, st, pl->draw_dev, pl->draw_inc);
-        GMPE_HIP_CHECK(hipGetLastError());
-    }
+    GMPE_LAUNCH(fn, dim3((unsigned)num_tiles(pl->rows)), dim3(TILE), lds, st, a);
+    if (pl->draw_dev) return gmpe::act_advance(pl->draw_dev, pl->draw_inc, st);
     return GMPE_OK;
 }
 

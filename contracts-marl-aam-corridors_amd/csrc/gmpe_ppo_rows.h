@@ -1,6 +1,6 @@
 // gmpe_ppo_rows.h — the per-row arithmetic, the tile machinery and the fixed-order reductions of the row kernels over a policy head's logits, shared by
-// gmpe_ppo_loss.hip (values in), gmpe_ppo_popart.hip (critic features in, PopArt) and gmpe_act.hip (the rollout's action and log-prob): one text, so the
-// three entry points cannot drift apart — the log-prob the act kernel stores is the one the loss kernels recompute because both run the masked
+// gmpe_ppo_loss.hip (values in), gmpe_ppo_popart.hip (critic features in, PopArt), gmpe_act.hip (the rollout's action and log-prob) and gmpe_head.hip (the
+// head's Linear in front of either): one text, so the entry points cannot drift apart — the log-prob the act kernel stores is the one the loss kernels recompute because both run the masked
 // categorical below. Everything here is float32 per row in the reference's operation order (no contraction) and double across rows; the derivations of
 // the gradients are at the head of gmpe_ppo_loss.hip.
 #pragma once

@@ -1,0 +1,108 @@
+"""The reference's actor and critic composed from the device layers: composition only, no arithmetic of its own.
+
+    GR_Actor.forward      ->  actor_forward(actor, ...)    = gnn_base -> mlp_base((obs, nbd)) -> rnn_layer -> act_head
+    GR_Critic.forward     ->  critic_forward(critic, ...)  = gnn_base -> mlp_base((cent_obs, nbd)) -> rnn_layer -> F.linear(v_out)
+    evaluate_actions + the loss arithmetic of ppo_update  ->  minibatch_losses(actor, critic, sample, args, ...)
+    the evaluator's act callable                          ->  evaluator_act(actor, evaluator)
+
+The modules are the caller's unchanged GR_Actor / GR_Critic (onpolicy/algorithms/graph_actor_critic.py), read by their attribute names (.gnn_base, .base,
+.rnn, .act, .v_out, .args); the parameters stay where they are, so the optimisers and the checkpoints do not change. Everything a layer refuses is
+refused here by that layer, in its words. v_out stays torch's F.linear on the caller's weight and bias (with --use_popart in training, ppo_losses_popart
+evaluates it). There is no torch fallback: the arrays must be on a HIP device.
+"""
+import torch
+import torch.nn.functional as F
+
+from .gnn import gnn_base
+from .gru import rnn_layer
+from .head import act_head, action_logits
+from .mlp import mlp_base
+from .ppo_loss import ppo_losses, ppo_losses_popart
+
+
+def _recurrent(net):
+    """whether the module runs its RNNLayer: the reference's two flags where it has them, else whether there is an .rnn"""
+    if hasattr(net, "_use_recurrent_policy") or hasattr(net, "_use_naive_recurrent_policy"):
+        return bool(getattr(net, "_use_recurrent_policy", False) or getattr(net, "_use_naive_recurrent_policy", False))
+    return getattr(net, "rnn", None) is not None
+
+
+def _features(net, own_obs, node_obs, adj, agent_id, rnn_states, masks):
+    """(features [rows, 64], rnn_states) of an actor or a critic in front of its head; own_obs None: the graph features alone enter the MLPBase"""
+    nbd = gnn_base(node_obs, adj, agent_id, net.gnn_base)
+    features = mlp_base(nbd if own_obs is None else (own_obs, nbd), net.base)
+    if _recurrent(net):
+        features, rnn_states = rnn_layer(features, rnn_states, masks, net.rnn)
+    return features, rnn_states
+
+
+def actor_forward(actor, obs, node_obs, adj, agent_id, rnn_states, masks, available_actions=None, deterministic=False, *, dones_prev=None, seed,
+                  env_id_base=0, num_agents, draw, draw_dev=None, out=None):
+    """GR_Actor.forward (graph_actor_critic.py:162-173) -> (actions, action_log_probs, rnn_states), under torch.no_grad().
+    obs [rows, obs_dim], node_obs [rows, E, F], adj [rows, E, E] or [rows / S, E, E], agent_id [rows] or [rows, 1], rnn_states [rows, 1, 64],
+    masks [rows, 1]: float32 device tensors as the layers take them. available_actions / dones_prev, seed, env_id_base, num_agents, draw, draw_dev,
+    out: as for act_head (out may hold "logits"). actions is the int64 [rows, 1] tensor the reference returns; with `out` given and no "actions" in
+    it, it is the int32 action_idx [rows] instead (what GmpeEngine.step takes). rnn_states comes back unchanged when the actor has no RNN."""
+    with torch.no_grad():
+        features, rnn_states = _features(actor, obs, node_obs, adj, agent_id, rnn_states, masks)
+        idx, actions, logp = act_head(features, actor.act, available_actions, dones_prev=dones_prev, seed=seed, env_id_base=env_id_base,
+                                      num_agents=num_agents, draw=draw, draw_dev=draw_dev, deterministic=deterministic, out=out)
+    return (idx if actions is None else actions), logp, rnn_states
+
+
+def _cent(critic, cent_obs):
+    return cent_obs if bool(getattr(getattr(critic, "args", None), "use_cent_obs", True)) else None
+
+
+def critic_forward(critic, cent_obs, node_obs, adj, agent_id, rnn_states_critic, masks):
+    """GR_Critic.forward (graph_actor_critic.py:385-397) -> (values [rows, 1], rnn_states_critic); differentiable where gradients are enabled.
+    critic.args.use_cent_obs (default True) decides whether cent_obs enters the MLPBase. v_out is F.linear on the caller's weight and bias — for a
+    PopArt v_out that is PopArt.forward. critic_graph_aggr == "node" hands the GNNBase several ids per row, which gnn_base refuses by name."""
+    features, rnn_states_critic = _features(critic, _cent(critic, cent_obs), node_obs, adj, agent_id, rnn_states_critic, masks)
+    return F.linear(features, critic.v_out.weight, critic.v_out.bias), rnn_states_critic
+
+
+def minibatch_losses(actor, critic, sample, args, value_normalizer=None, install="replace", workspace=None, shards=None):
+    """evaluate_actions and the loss arithmetic of GR_MAPPO.ppo_update (graph_mappo.py:147-245) for the generators' 16-tuple `sample`: the actor chain up to
+    action_logits, the critic chain up to its values — up to its features with args.use_popart —, then ppo_losses (value_normalizer, shards) or
+    ppo_losses_popart (critic.v_out, install). Returns their result object unchanged; backward() of its two losses reaches every parameter of the actor
+    and of the critic. workspace: the loss call's (ppo_loss.workspace_bytes / popart_workspace_bytes)."""
+    if not isinstance(sample, (tuple, list)) or len(sample) != 16:
+        raise ValueError("sample must be the generators' 16-tuple")
+    share_obs, obs, node_obs, adj, agent_id, share_agent_id, rnn_states, rnn_states_critic = sample[:8]
+    masks = sample[11]
+    actor_features, _ = _features(actor, obs, node_obs, adj, agent_id, rnn_states, masks)
+    logits = action_logits(actor_features, actor.act)
+    critic_features, _ = _features(critic, _cent(critic, share_obs), node_obs, adj, share_agent_id, rnn_states_critic, masks)
+    if getattr(args, "use_popart", False):
+        return ppo_losses_popart(logits, critic_features, sample, args, critic.v_out, install=install, workspace=workspace, shards=shards)
+    values = F.linear(critic_features, critic.v_out.weight, critic.v_out.bias)
+    return ppo_losses(logits, values, sample, args, value_normalizer, workspace=workspace, shards=shards)
+
+
+def evaluator_act(actor, evaluator, deterministic=True, seed=0, draw0=0):
+    """The act(obs, node_obs, adj, agent_id, masks, available_actions) -> int32 [N, A] callable BatchedEvaluator documents, from `actor`:
+    [N, A, ...] flattened to rows, evaluator.rnn_states (when the evaluator carries them, [N, A, 1, 64]) read and written in place, `draw` advanced by one
+    per call from draw0, the adjacency in either form the engine hands out ([N, E, E] or [N, A, E, E]). It always runs under torch.no_grad()."""
+    cfg = evaluator.engine.cfg
+    N, A = evaluator.N, evaluator.A
+    rows = N * A
+    state = {"draw": int(draw0)}
+    if _recurrent(actor) and evaluator.rnn_states is None:
+        raise ValueError("the actor has an RNN: build the evaluator with rnn_states=[N, A, 1, 64] so that record() resets them")
+
+    def act(obs, node_obs, adj, agent_id, masks, available_actions):
+        if adj is None:
+            raise ValueError("the engine hands out no adjacency (adj_form='none'): evaluator_act needs one")
+        E = int(node_obs.shape[-2])
+        hxs = evaluator.rnn_states
+        flat_h = None if hxs is None else hxs.reshape(rows, hxs.shape[2], hxs.shape[3])
+        idx, _, h = actor_forward(actor, obs.reshape(rows, -1), node_obs.reshape(rows, E, -1), adj.reshape(-1, E, E), agent_id.reshape(rows),
+                                  flat_h, masks.reshape(rows, 1), available_actions.reshape(rows, -1), deterministic, seed=seed,
+                                  env_id_base=int(cfg.env_id_base), num_agents=A, draw=state["draw"], out={})
+        state["draw"] += 1
+        if hxs is not None and h is not flat_h:
+            hxs.copy_(h.reshape(hxs.shape))
+        return idx.view(N, A)
+
+    return act

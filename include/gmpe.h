@@ -627,6 +627,53 @@ typedef struct gmpe_act_plan {
 } gmpe_act_plan;
 int gmpe_act_sample(int device, const gmpe_act_plan* plan, void* stream);
 
+/* ---- The policy's action head (handle-less): the Linear in front of the masked categorical above ----
+ * Categorical.linear of a single Discrete ACTLayer (onpolicy/algorithms/utils/act.py:27-29, distributions.py:72-91): logits = features W^T + b with
+ * weight [K, hidden], bias [K], float32, contiguous, hidden == 64 and 1 <= K <= GMPE_PPO_MAX_ACTIONS; everything else is GMPE_ERR_INVALID_ARG with the
+ * function and the field in gmpe_last_error, before any launch. No allocation, no atomics, no host synchronisation; every launch on `stream`; capturable.
+ *
+ * gmpe_head_forward, ONE launch:
+ *   logits_out[r, k] = the fmaf chain that starts at bias[k] and runs over h = 0 .. 63 ascending of features[r, h] * weight[k, h].
+ *   A row's bits are a function of that row and the parameters alone: not of rows, not of the row's place in the call, not of the width of the loads
+ *   (16-byte units where an array is 16-byte aligned, 4-byte units otherwise).
+ * gmpe_head_backward, at most THREE launches, from grad_logits [rows, K] (features and weight as in forward; bias and logits_out are not read):
+ *   grad_features[r, h] = the fmaf chain from 0.0f over k = 0 .. K-1 ascending of grad_logits[r, k] * weight[k, h]: a function of the row alone;
+ *   grad_weight[k, h]   = sum over r of grad_logits[r, k] * features[r, h]: the rows are cut into P = min(128, ceil(rows / 32)) contiguous parts of
+ *                         ceil(rows / P) rows; a part's exact double products are added in ascending row order, the parts in ascending part order, and
+ *                         the sum is rounded to float32 once;
+ *   grad_bias[k]        = sum over r of grad_logits[r, k] in double: within a tile of 256 rows four runs of 64 rows, each ascending, added in run order;
+ *                         the tiles as 16 interleaved slices (slice s: tiles s, s + 16, ... ascending), the slices in slice order; rounded once.
+ *   So the order is a function of rows alone and two calls give the same bits. Each of the three outputs may be NULL and is then not formed.
+ * Workspace (backward only; gmpe_head_workspace_bytes is the single source of its size; its contents before the call do not matter), in this order:
+ *   f64 [P][64][64] the parts' blocks, f64 [ceil(rows / 256)][64] the tiles' column sums. A forward-only plan needs none.
+ *
+ * gmpe_act_head, the rollout form: gmpe_act_sample with act_plan->logits == NULL (anything else is refused) and the logits formed in the launch from
+ * head_plan->features, weight and bias (rows and n_actions of the two plans must agree; the head plan's gradient fields and workspace are not read).
+ * Exactly ONE launch, plus gmpe_act_sample's one-thread counter launch when draw_dev is given. The logits are the dot product of gmpe_head_forward (one
+ * device function) and the row's routine is gmpe_act_sample's (one device function): action_idx, log_probs, actions_f32, actions_i64 — and logits_out,
+ * written when it is not NULL — are bit for bit what gmpe_head_forward followed by gmpe_act_sample gives. With gmpe_ppo_loss recomputing log_probs from
+ * gmpe_head_forward's logits, an unchanged policy has importance weights of exactly 1 whatever the two batch shapes. */
+typedef struct gmpe_head_plan {
+    int64_t rows;                       /* >= 1                                                                                       */
+    int32_t n_actions;                  /* K, 1 .. GMPE_PPO_MAX_ACTIONS                                                               */
+    int32_t hidden;                     /* 64                                                                                         */
+    const float* features;              /* [rows, 64] the actor features                                                              */
+    const float* weight;                /* [K, 64]                                                                                    */
+    const float* bias;                  /* [K]; forward and gmpe_act_head                                                             */
+    float* logits_out;                  /* [rows, K]; forward: required; gmpe_act_head: or NULL; backward: not read                   */
+    const float* grad_logits;           /* [rows, K]; backward only                                                                   */
+    float* grad_features;               /* [rows, 64] or NULL; backward only                                                          */
+    float* grad_weight;                 /* [K, 64] or NULL; backward only                                                             */
+    float* grad_bias;                   /* [K] or NULL; backward only                                                                 */
+    void* workspace;                    /* gmpe_head_workspace_bytes(rows, K, 1) bytes, 8-byte aligned; backward only                 */
+    size_t workspace_bytes;
+} gmpe_head_plan;
+/* want_backward == 0: 0 bytes. The size depends on rows alone; n_actions is checked. */
+int gmpe_head_workspace_bytes(int64_t rows, int32_t n_actions, int32_t want_backward, size_t* bytes_out);
+int gmpe_head_forward(int device, const gmpe_head_plan* plan, void* stream);
+int gmpe_head_backward(int device, const gmpe_head_plan* plan, void* stream);
+int gmpe_act_head(int device, const gmpe_act_plan* act_plan, const gmpe_head_plan* head_plan, void* stream);
+
 /* ---- The policy's masked GRU layer (handle-less): RNNLayer.forward (onpolicy/algorithms/utils/rnn.py:23-79) with recurrent_N == 1 ----
  * The layer in front of the action head (GR_Actor) and of the value head (GR_Critic): nn.GRU(D, H) driven step by step with the state multiplied by
  * the step's mask, then nn.LayerNorm(H). All arrays float32, contiguous. For every row k of `rows` independently, t = 0 .. steps-1 (x, masks, features
