@@ -25,7 +25,8 @@ SYMBOLS = ["gmpe_abi_version", "gmpe_last_error", "gmpe_obs_dim", "gmpe_node_fea
            "gmpe_gru_workspace_bytes", "gmpe_gru_forward", "gmpe_gru_backward",
            "gmpe_mlp_workspace_bytes", "gmpe_mlp_forward", "gmpe_mlp_backward",
            "gmpe_gnn_workspace_bytes", "gmpe_gnn_forward", "gmpe_gnn_backward",
-           "gmpe_head_workspace_bytes", "gmpe_head_forward", "gmpe_head_backward", "gmpe_act_head"]
+           "gmpe_head_workspace_bytes", "gmpe_head_forward", "gmpe_head_backward", "gmpe_act_head",
+           "gmpe_optim_workspace_bytes", "gmpe_optim_step"]
 
 
 class GmpeOutputs(C.Structure):
@@ -257,6 +258,30 @@ class GmpeGnnPlan(C.Structure):
         ("workspace_bytes", C.c_size_t)]
 
 
+# GMPE_OPT_* of include/gmpe.h; tests/test_optim_host.py compiles against the header
+OPT_MAX_TENSORS, OPT_MAX_HYPERS, OPT_CHUNK, OPT_MAX_PLAN_TENSORS, OPT_MAX_NUMEL = 64, 8, 1024, 4096, 1 << 30
+OPT_CLIP, OPT_STEP = 1, 2
+OPT_T_IN_NORM, OPT_T_STEP = 1, 2
+
+
+class GmpeOptimTensor(C.Structure):
+    """gmpe_optim_tensor (include/gmpe.h): one tensor of the clip-and-step table."""
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("numel", C.c_int64),
+                ("flags", C.c_int32), ("hyper", C.c_int32)]
+
+
+class GmpeOptimHyper(C.Structure):
+    """gmpe_optim_hyper (include/gmpe.h): one torch param_group at one step count."""
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double), ("t", C.c_int64)]
+
+
+class GmpeOptimPlan(C.Structure):
+    """gmpe_optim_plan (include/gmpe.h): clip_grad_norm_ and Adam.step over a table of tensors."""
+    _fields_ = [("n_tensors", C.c_int32), ("n_hypers", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32),
+                ("tensors", C.POINTER(GmpeOptimTensor)), ("hypers", C.POINTER(GmpeOptimHyper)), ("max_norm", C.c_double), ("out", C.c_void_p),
+                ("grad_norm_f32", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
 class GmpeError(RuntimeError):
     pass
 
@@ -336,6 +361,8 @@ def load():
     lib.gmpe_head_forward.argtypes = [I, C.POINTER(GmpeHeadPlan), P]
     lib.gmpe_head_backward.argtypes = [I, C.POINTER(GmpeHeadPlan), P]
     lib.gmpe_act_head.argtypes = [I, C.POINTER(GmpeActPlan), C.POINTER(GmpeHeadPlan), P]
+    lib.gmpe_optim_workspace_bytes.argtypes = [C.POINTER(GmpeOptimPlan), C.POINTER(C.c_size_t)]
+    lib.gmpe_optim_step.argtypes = [I, C.POINTER(GmpeOptimPlan), P]
     from .config import ABI_VERSION
     if lib.gmpe_abi_version() != ABI_VERSION:
         raise GmpeError("libgmpe.so ABI version mismatch")

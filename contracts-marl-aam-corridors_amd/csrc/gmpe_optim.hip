@@ -1,0 +1,256 @@
+// gmpe_optim.hip — the gradient clip and the Adam step of GR_MAPPO.ppo_update over a table of tensors (include/gmpe.h gmpe_optim_step): the numeric
+// contract, the geometry and the launch order are stated there, line by line. Two kernels per launch group of at most 64 tensors:
+//   k_opt_norm  a chunk's double sum of exact squares -> part[chunk];
+//   k_opt_step  every workgroup adds part[] itself in one fixed order (no finish kernel, no atomics: the list is a few hundred doubles at most for the
+//               shipped networks and the sum costs less than a launch), then clips and steps its own chunk.
+// The table is a kernel argument (64 descriptors of 40 bytes + 8 hyper-parameter sets of 28 bytes: under the 4 KB of a kernel's arguments), so a call
+// uploads nothing, allocates nothing and waits for nothing. Sizes are tiny (about 41 000 elements for the shipped actor): the job is few launches, not
+// bandwidth, which is why a lane finds its tensor by a binary search over the prefix sums rather than through a precomputed map in device memory.
+#include <math.h>
+
+#include <vector>
+
+#include "gmpe_host.h"
+
+namespace {
+
+constexpr int BLOCK = 256, CHUNK = GMPE_OPT_CHUNK, PER_THREAD = CHUNK / BLOCK, MAXT = GMPE_OPT_MAX_TENSORS, MAXH = GMPE_OPT_MAX_HYPERS;
+constexpr uint32_t GROUP_LIMIT = 0x7fffffffu - (uint32_t)CHUNK;     // a group's elements: every chunk's last index stays below 2^31
+
+struct Desc {
+    float* p; float* g; float* m; float* v;
+    uint32_t start;                // the tensor's first element in the group's concatenation
+    uint16_t flags, hyper;         // GMPE_OPT_T_*; index into Table::h
+};
+static_assert(sizeof(Desc) == 40, "a descriptor is 40 bytes");
+
+struct Hyper { float wd, w1, b2, w2, a, s2, eps; };
+
+struct Table {
+    Desc d[MAXT];
+    Hyper h[MAXH];
+    uint32_t total;                // the group's elements
+    int32_t n;                     // its tensors
+};
+static_assert(sizeof(Table) <= 3072, "the table and the other arguments stay under the 4 KB of kernel arguments");
+
+// the tensor that holds element e < total: the last i with d[i].start <= e (the starts ascend strictly: empty tensors are not in the table)
+__device__ __forceinline__ int find_tensor(const Table& tb, uint32_t e) {
+    int lo = 0, hi = tb.n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (tb.d[mid].start <= e) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// the 256 sums of a workgroup added pairwise by halving; every thread returns the total
+__device__ __forceinline__ double block_sum(double s, double* red) {
+    const int tid = threadIdx.x;
+    red[tid] = s;
+    __syncthreads();
+    for (int w = BLOCK / 2; w > 0; w >>= 1) {
+        if (tid < w) red[tid] += red[tid + w];
+        __syncthreads();
+    }
+    const double tot = red[0];
+    __syncthreads();
+    return tot;
+}
+
+__global__ __launch_bounds__(BLOCK) void k_opt_norm(const Table tb, double* __restrict__ part) {
+    __shared__ double red[BLOCK];
+    const uint32_t e0 = blockIdx.x * (uint32_t)CHUNK + threadIdx.x;
+    double s = 0.0;
+    for (int k = 0; k < PER_THREAD; ++k) {
+        const uint32_t e = e0 + (uint32_t)k * BLOCK;
+        if (e >= tb.total) break;
+        const Desc& d = tb.d[find_tensor(tb, e)];
+        if (d.flags & GMPE_OPT_T_IN_NORM) {
+            const double g = (double)d.g[e - d.start];
+            s += g * g;
+        }
+    }
+    const double tot = block_sum(s, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = tot;
+}
+
+struct StepArgs {
+    const double* part;            // the chunks' sums of ALL groups
+    int32_t n_parts;
+    int32_t clip, step, first;     // plan flags; first: this launch's workgroup 0 writes out
+    double max_norm;
+    double* out;
+    float* norm_f32;
+};
+
+__global__ __launch_bounds__(BLOCK) void k_opt_step(const Table tb, const StepArgs a) {
+    __shared__ double red[BLOCK];
+    double s = 0.0;
+    for (int j = threadIdx.x; j < a.n_parts; j += BLOCK) s += a.part[j];
+    const double norm = sqrt(block_sum(s, red));
+    float coef = 1.0f;
+    if (a.clip) {
+        const double c = a.max_norm / (norm + 1e-6);
+        coef = (float)(c > 1.0 ? 1.0 : c);                           // NaN stays NaN, as torch.clamp keeps it
+    }
+    if (a.first && blockIdx.x == 0 && threadIdx.x == 0) {
+        a.out[0] = norm; a.out[1] = (double)coef;
+        if (a.norm_f32) a.norm_f32[0] = (float)norm;
+    }
+    const uint32_t e0 = blockIdx.x * (uint32_t)CHUNK + threadIdx.x;
+    for (int k = 0; k < PER_THREAD; ++k) {
+        const uint32_t e = e0 + (uint32_t)k * BLOCK;
+        if (e >= tb.total) break;
+        const Desc& d = tb.d[find_tensor(tb, e)];
+        const uint32_t o = e - d.start;
+        const bool scale = a.clip && (d.flags & GMPE_OPT_T_IN_NORM), step = a.step && (d.flags & GMPE_OPT_T_STEP);
+        if (!scale && !step) continue;
+        float g = d.g[o];
+        if (scale) { g = g * coef; d.g[o] = g; }
+        if (step) {
+            const Hyper& h = tb.h[d.hyper];
+            float p = d.p[o], m = d.m[o], v = d.v[o];
+            if (h.wd != 0.0f) g = g + h.wd * p;
+            m = m + (g - m) * h.w1;
+            v = h.b2 * v + (h.w2 * g) * g;
+            const float denom = sqrtf(v) / h.s2 + h.eps;
+            p = p - h.a * (m / denom);
+            d.m[o] = m; d.v[o] = v; d.p[o] = p;
+        }
+    }
+}
+
+using gmpe::fail;
+
+struct Layout {
+    std::vector<Table> groups;     // at least one: a table without elements still writes `out`
+    std::vector<int64_t> chunks;   // per group
+    int64_t n_chunks = 0;
+    size_t total = 0;              // workspace bytes
+};
+
+// what both entry points check of the geometry: counts, numel, flags, hyper indices
+int check_geometry(const char* fn, const gmpe_optim_plan* pl) {
+    if (!pl) return fail(fn, "null plan");
+    if (pl->n_tensors < 1 || pl->n_tensors > GMPE_OPT_MAX_PLAN_TENSORS) return fail(fn, "n_tensors must be in 1 .. " + std::to_string(GMPE_OPT_MAX_PLAN_TENSORS));
+    if (pl->n_hypers < 0 || pl->n_hypers > GMPE_OPT_MAX_PLAN_TENSORS) return fail(fn, "n_hypers must be in 0 .. " + std::to_string(GMPE_OPT_MAX_PLAN_TENSORS));
+    if (!pl->tensors) return fail(fn, "tensors is null");
+    if (pl->n_hypers > 0 && !pl->hypers) return fail(fn, "hypers is null");
+    for (int i = 0; i < pl->n_tensors; ++i) {
+        const gmpe_optim_tensor& t = pl->tensors[i];
+        const std::string at = "tensors[" + std::to_string(i) + "].";
+        if (t.numel < 0 || t.numel > GMPE_OPT_MAX_NUMEL) return fail(fn, at + "numel must be in 0 .. 2^30");
+        if (!(t.flags & (GMPE_OPT_T_IN_NORM | GMPE_OPT_T_STEP)) || (t.flags & ~(GMPE_OPT_T_IN_NORM | GMPE_OPT_T_STEP)))
+            return fail(fn, at + "flags must be GMPE_OPT_T_IN_NORM, GMPE_OPT_T_STEP or both");
+        if ((t.flags & GMPE_OPT_T_STEP) ? (t.hyper < 0 || t.hyper >= pl->n_hypers) : t.hyper != 0)
+            return fail(fn, at + "hyper must index hypers with GMPE_OPT_T_STEP and be 0 without");
+    }
+    return GMPE_OK;
+}
+
+// The launch groups of a checked plan. `fill`: with the pointers and the float32 hyper-parameters (gmpe_optim_step), else the geometry alone.
+void layout(const gmpe_optim_plan* pl, bool fill, Layout& y) {
+    int slot_of[MAXH];             // the plan's hyper index in each of the current group's slots
+    int n_slots = 0;
+    y.groups.emplace_back();
+    Table* tb = &y.groups.back();
+    tb->total = 0; tb->n = 0;
+    for (int i = 0; i < pl->n_tensors; ++i) {
+        const gmpe_optim_tensor& t = pl->tensors[i];
+        if (t.numel == 0) continue;
+        const bool steps = t.flags & GMPE_OPT_T_STEP;
+        int slot = 0;
+        if (steps) for (slot = 0; slot < n_slots && slot_of[slot] != t.hyper; ++slot) {}
+        if (tb->n == MAXT || (steps && slot == MAXH) || (uint64_t)tb->total + (uint64_t)t.numel > GROUP_LIMIT) {
+            y.groups.emplace_back();
+            tb = &y.groups.back();
+            tb->total = 0; tb->n = 0; n_slots = 0; slot = 0;
+        }
+        if (steps && slot == n_slots) {
+            slot_of[n_slots++] = t.hyper;
+            if (fill) {
+                const gmpe_optim_hyper& h = pl->hypers[t.hyper];
+                const double bc1 = 1.0 - pow(h.beta1, (double)h.t), bc2 = 1.0 - pow(h.beta2, (double)h.t);
+                tb->h[slot] = Hyper{(float)h.weight_decay, (float)(1.0 - h.beta1), (float)h.beta2, (float)(1.0 - h.beta2), (float)(h.lr / bc1),
+                                    (float)sqrt(bc2), (float)h.eps};
+            }
+        }
+        Desc& d = tb->d[tb->n++];
+        d.start = tb->total; d.flags = (uint16_t)t.flags; d.hyper = (uint16_t)slot;
+        if (fill) { d.p = t.param; d.g = t.grad; d.m = t.exp_avg; d.v = t.exp_avg_sq; }
+        tb->total += (uint32_t)t.numel;
+    }
+    for (const Table& g : y.groups) {
+        y.chunks.push_back(((int64_t)g.total + CHUNK - 1) / CHUNK);
+        y.n_chunks += y.chunks.back();
+    }
+    gmpe::Carver c;
+    c.take((size_t)y.n_chunks * sizeof(double));
+    y.total = c.total();
+}
+
+}  // namespace
+
+extern "C" {
+
+int gmpe_optim_workspace_bytes(const gmpe_optim_plan* pl, size_t* bytes_out) {
+    const char* fn = "gmpe_optim_workspace_bytes";
+    if (!bytes_out) return fail(fn, "bytes_out is null");
+    if (int rc = check_geometry(fn, pl)) return rc;
+    Layout y;
+    layout(pl, false, y);
+    if (y.n_chunks > 0x7fffffffLL) return fail(fn, "tensors: too many elements for one call");
+    *bytes_out = y.total;
+    return GMPE_OK;
+}
+
+int gmpe_optim_step(int device, const gmpe_optim_plan* pl, void* stream) {
+    const char* fn = "gmpe_optim_step";
+    if (int rc = check_geometry(fn, pl)) return rc;
+    if (pl->flags & ~(GMPE_OPT_CLIP | GMPE_OPT_STEP)) return fail(fn, "flags must be GMPE_OPT_CLIP, GMPE_OPT_STEP, both or 0");
+    if (pl->reserved != 0) return fail(fn, "reserved must be 0");
+    const bool clip = pl->flags & GMPE_OPT_CLIP, step = pl->flags & GMPE_OPT_STEP;
+    for (int i = 0; i < pl->n_hypers; ++i) {
+        const gmpe_optim_hyper& h = pl->hypers[i];
+        const std::string at = "hypers[" + std::to_string(i) + "].";
+        if (!(h.lr >= 0.0)) return fail(fn, at + "lr must be >= 0");
+        if (!(h.beta1 >= 0.0 && h.beta1 < 1.0)) return fail(fn, at + "beta1 must be in [0, 1)");
+        if (!(h.beta2 >= 0.0 && h.beta2 < 1.0)) return fail(fn, at + "beta2 must be in [0, 1)");
+        if (!(h.eps >= 0.0)) return fail(fn, at + "eps must be >= 0");
+        if (!(h.weight_decay >= 0.0)) return fail(fn, at + "weight_decay must be >= 0");
+        if (h.t < 1) return fail(fn, at + "t must be >= 1");
+    }
+    if (clip && !(pl->max_norm > 0.0)) return fail(fn, "max_norm must be > 0 with GMPE_OPT_CLIP");
+    for (int i = 0; i < pl->n_tensors; ++i) {
+        const gmpe_optim_tensor& t = pl->tensors[i];
+        const bool steps = step && (t.flags & GMPE_OPT_T_STEP) && t.numel > 0;          // an empty tensor has no address
+        const gmpe::PtrField ps[] = {{t.param, "param", steps}, {t.grad, "grad", t.numel > 0}, {t.exp_avg, "exp_avg", steps}, {t.exp_avg_sq, "exp_avg_sq", steps}};
+        if (int rc = gmpe::check_ptrs(fn, ps, "tensors[" + std::to_string(i) + "].")) return rc;
+    }
+    if (!pl->out) return fail(fn, "out is required");
+    if ((uintptr_t)pl->out & 7) return fail(fn, "out must be 8-byte aligned");
+    if (int rc = gmpe::check_ptr(fn, pl->grad_norm_f32, "grad_norm_f32", false)) return rc;
+    Layout y;
+    layout(pl, true, y);
+    if (y.n_chunks > 0x7fffffffLL) return fail(fn, "tensors: too many elements for one call");
+    if (int rc = gmpe::check_workspace(fn, pl->workspace, pl->workspace_bytes, y.total, y.total > 0, "workspace is required", "gmpe_optim_workspace_bytes(plan)"))
+        return rc;
+    GMPE_HIP_CHECK(hipSetDevice(device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    double* part = static_cast<double*>(pl->workspace);
+    int64_t base = 0;
+    for (size_t g = 0; g < y.groups.size(); ++g) {
+        if (y.chunks[g] > 0) GMPE_LAUNCH(k_opt_norm, dim3((unsigned)y.chunks[g]), dim3(BLOCK), 0, st, y.groups[g], part + base);
+        base += y.chunks[g];
+    }
+    StepArgs a = {part, (int32_t)y.n_chunks, clip, step, 0, pl->max_norm, pl->out, pl->grad_norm_f32};
+    for (size_t g = 0; g < y.groups.size(); ++g) {
+        a.first = g == 0;
+        const int64_t grid = y.chunks[g] > 0 ? y.chunks[g] : (g == 0 ? 1 : 0);
+        if (grid > 0) GMPE_LAUNCH(k_opt_step, dim3((unsigned)grid), dim3(BLOCK), 0, st, y.groups[g], a);
+    }
+    return GMPE_OK;
+}
+
+}  // extern "C"

@@ -3,6 +3,8 @@
     GR_Actor.forward      ->  actor_forward(actor, ...)    = gnn_base -> mlp_base((obs, nbd)) -> rnn_layer -> act_head
     GR_Critic.forward     ->  critic_forward(critic, ...)  = gnn_base -> mlp_base((cent_obs, nbd)) -> rnn_layer -> F.linear(v_out)
     evaluate_actions + the loss arithmetic of ppo_update  ->  minibatch_losses(actor, critic, sample, args, ...)
+    GR_MAPPO.ppo_update                                   ->  ppo_update(actor, critic, actor_optimizer, critic_optimizer, sample, args, ...)
+    GR_MAPPO.train                                        ->  train(actor, critic, actor_optimizer, critic_optimizer, buffer, args, ...)
     the evaluator's act callable                          ->  evaluator_act(actor, evaluator)
 
 The modules are the caller's unchanged GR_Actor / GR_Critic (onpolicy/algorithms/graph_actor_critic.py), read by their attribute names (.gnn_base, .base,
@@ -10,6 +12,8 @@ The modules are the caller's unchanged GR_Actor / GR_Critic (onpolicy/algorithms
 refused here by that layer, in its words. v_out stays torch's F.linear on the caller's weight and bias (with --use_popart in training, ppo_losses_popart
 evaluates it). There is no torch fallback: the arrays must be on a HIP device.
 """
+import collections
+
 import torch
 import torch.nn.functional as F
 
@@ -17,6 +21,7 @@ from .gnn import gnn_base
 from .gru import rnn_layer
 from .head import act_head, action_logits
 from .mlp import mlp_base
+from .optim import clip_and_step
 from .ppo_loss import ppo_losses, ppo_losses_popart
 
 
@@ -78,6 +83,79 @@ def minibatch_losses(actor, critic, sample, args, value_normalizer=None, install
         return ppo_losses_popart(logits, critic_features, sample, args, critic.v_out, install=install, workspace=workspace, shards=shards)
     values = F.linear(critic_features, critic.v_out.weight, critic.v_out.bias)
     return ppo_losses(logits, values, sample, args, value_normalizer, workspace=workspace, shards=shards)
+
+
+PPOUpdate = collections.namedtuple("PPOUpdate", ["value_loss", "critic_grad_norm", "policy_loss", "dist_entropy", "actor_grad_norm", "ratio_mean",
+                                                  "imp_weights"])
+TRAIN_INFO = ("value_loss", "policy_loss", "dist_entropy", "actor_grad_norm", "critic_grad_norm", "ratio")      # graph_mappo.py:309-314
+
+
+def _no_accumulation(fn, accumulation_steps, shards=None):
+    if accumulation_steps != 1:
+        raise NotImplementedError("accumulation_steps = %r: %s steps at every minibatch (gradient accumulation is not supported)" % (accumulation_steps, fn))
+    if shards is not None:
+        raise NotImplementedError("shards: %s clips and steps one learner's gradients; the gradient all-reduce of a data-parallel learner stays "
+                                  "DistributedDataParallel's (a norm across ranks is not supported)" % fn)
+
+
+def ppo_update(actor, critic, actor_optimizer, critic_optimizer, sample, args, value_normalizer=None, update_actor=True, install="replace", workspace=None,
+               *, accumulation_steps=1, shards=None):
+    """GR_MAPPO.ppo_update (graph_mappo.py:147-278) in the reference's order: minibatch_losses; actor_optimizer.zero_grad(); with update_actor the actor
+    loss's backward(); clip_and_step over actor.parameters() (step only with update_actor); critic_optimizer.zero_grad(); (value_loss *
+    args.value_loss_coef).backward(); clip_and_step over critic.parameters(). With args.use_max_grad_norm (default True) the gradients are clipped to
+    args.max_grad_norm (default 10.0), else their norm is only reported (the reference's get_grad_norm); args.value_loss_coef defaults to 1.
+    The norm and the clip run over net.parameters(), the step over the optimiser's own list, as in the reference: after a PopArt update with
+    install="replace" the critic holds new v_out Parameters, which have no gradient, and the optimiser the old ones, which are stepped unclipped.
+    Returns PPOUpdate(value_loss, critic_grad_norm, policy_loss, dist_entropy, actor_grad_norm, ratio_mean, imp_weights): detached device scalars and
+    the [rows, 1] importance weights; actor_grad_norm is 0 without update_actor. workspace: minibatch_losses' own.
+    The reference's GradScaler is not reproduced: with float32 losses it changes no value unless a gradient overflows, and its step() waits for the
+    device. accumulation_steps != 1 and shards raise NotImplementedError. Nothing here waits for the device."""
+    _no_accumulation("ppo_update", accumulation_steps, shards)
+    res = minibatch_losses(actor, critic, sample, args, value_normalizer, install=install, workspace=workspace)
+    max_norm = getattr(args, "max_grad_norm", 10.0) if getattr(args, "use_max_grad_norm", True) else None
+    actor_optimizer.zero_grad()
+    if update_actor:
+        res.actor_loss.backward()
+    actor_grad_norm = clip_and_step(actor_optimizer, max_norm, parameters=actor.parameters(), step=bool(update_actor))
+    critic_optimizer.zero_grad()
+    (res.value_loss * getattr(args, "value_loss_coef", 1)).backward()
+    critic_grad_norm = clip_and_step(critic_optimizer, max_norm, parameters=critic.parameters())
+    return PPOUpdate(res.value_loss.detach(), critic_grad_norm, res.policy_loss.detach(), res.dist_entropy.detach(), actor_grad_norm,
+                     res.ratio_mean.detach(), res.imp_weights.detach())
+
+
+def train(actor, critic, actor_optimizer, critic_optimizer, buffer, args, value_normalizer=None, update_actor=True, perms=None, *, install="replace",
+          accumulation_steps=1):
+    """GR_MAPPO.train (graph_mappo.py:294-359) over a DeviceRolloutBuffer: buffer.normalized_advantages(value_normalizer), then args.ppo_epoch (15) passes
+    of the generator the reference chooses — recurrent_generator with args.data_chunk_length (10) under args.use_recurrent_policy (True), else
+    naive_recurrent_generator under args.use_naive_recurrent_policy, else feed_forward_generator, each with args.num_mini_batch (1) — and ppo_update
+    per sample. perms: None, or one permutation per epoch, handed to the generator's perm= (None: the reference's CPU randperm, uploaded from pinned
+    memory; "device": drawn on the device; an int64 tensor is range-checked by the generator, which reads it back: the one wait on this path).
+    Returns the reference's train_info: the six sums as float32 device adds in its order (value_loss, policy_loss, dist_entropy, actor_grad_norm,
+    critic_grad_norm, ratio = imp_weights.mean()), each divided by ppo_epoch * num_mini_batch — a dict of 0-dim device tensors where the reference
+    calls .item() three times per minibatch. Between call and return nothing is copied to the host (a tensor in perms excepted, see above)."""
+    _no_accumulation("train", accumulation_steps)
+    ppo_epoch, num_mini_batch = int(getattr(args, "ppo_epoch", 15)), int(getattr(args, "num_mini_batch", 1))
+    if perms is not None and len(perms) != ppo_epoch:
+        raise ValueError("perms must hold one permutation per epoch: %d, not %d" % (ppo_epoch, len(perms)))
+    advantages = buffer.normalized_advantages(value_normalizer)
+    info = None
+    for epoch in range(ppo_epoch):
+        perm = None if perms is None else perms[epoch]
+        if getattr(args, "use_recurrent_policy", True):
+            generator = buffer.recurrent_generator(advantages, num_mini_batch, int(getattr(args, "data_chunk_length", 10)), perm=perm)
+        elif getattr(args, "use_naive_recurrent_policy", False):
+            generator = buffer.naive_recurrent_generator(advantages, num_mini_batch)
+        else:
+            generator = buffer.feed_forward_generator(advantages, num_mini_batch, perm=perm)
+        for sample in generator:
+            u = ppo_update(actor, critic, actor_optimizer, critic_optimizer, sample, args, value_normalizer, update_actor, install)
+            terms = (u.value_loss, u.policy_loss, u.dist_entropy, u.actor_grad_norm, u.critic_grad_norm, u.imp_weights.mean())
+            info = terms if info is None else tuple(a + b for a, b in zip(info, terms))
+    if info is None:
+        raise ValueError("train needs at least one minibatch: ppo_epoch = %d" % ppo_epoch)
+    num_updates = ppo_epoch * num_mini_batch
+    return {k: v / num_updates for k, v in zip(TRAIN_INFO, info)}
 
 
 def evaluator_act(actor, evaluator, deterministic=True, seed=0, draw0=0):

@@ -674,6 +674,83 @@ int gmpe_head_forward(int device, const gmpe_head_plan* plan, void* stream);
 int gmpe_head_backward(int device, const gmpe_head_plan* plan, void* stream);
 int gmpe_act_head(int device, const gmpe_act_plan* act_plan, const gmpe_head_plan* head_plan, void* stream);
 
+/* ---- The gradient clip and the Adam step of GR_MAPPO.ppo_update (handle-less) ----
+ * nn.utils.clip_grad_norm_ followed by torch.optim.Adam.step (onpolicy/algorithms/graph_mappo.py:212-227 and :254-265) over a table of float32 tensors:
+ * the 2-norm of the gradients flagged GMPE_OPT_T_IN_NORM, those gradients scaled by the clip coefficient, and torch's single-tensor Adam on the tensors
+ * flagged GMPE_OPT_T_STEP. The two sets may differ (after a PopArt update that installs new Parameters the reference clips critic.parameters() and steps
+ * the optimiser's own list). All arrays contiguous, 4-byte aligned (views at odd float offsets are fine: every access is one dword), none overlapping
+ * another; a tensor appears once in the table. Tensors with numel == 0 are skipped. Everything the host can see is checked before any launch; a refusal
+ * is GMPE_ERR_INVALID_ARG with the function and the field in gmpe_last_error.
+ *
+ * Geometry. The tensors with numel > 0 are cut, in table order, into launch groups: a group ends before the tensor that would be its
+ * (GMPE_OPT_MAX_TENSORS + 1)-th, that would bring a (GMPE_OPT_MAX_HYPERS + 1)-th distinct `hyper` index into it, or that would take its elements past
+ * 2^31 - 1 - GMPE_OPT_CHUNK. A group's elements are concatenated in table order and cut into chunks of GMPE_OPT_CHUNK elements, one workgroup of 256
+ * threads per chunk (thread i owns elements i, i + 256, i + 512, i + 768 of its chunk); the group's table (pointers, prefix sums, flags, and the float32
+ * hyper-parameters) travels as kernel arguments, so nothing is uploaded, allocated or cached between calls: gradient addresses may change every call.
+ * The chunks of all groups are numbered in group order: n_chunks = sum over groups of ceil(group elements / GMPE_OPT_CHUNK).
+ *
+ * Launches on `stream`, 2 per group, every group's k_opt_norm before any group's k_opt_step (a table without elements: one k_opt_step that writes `out`):
+ *   k_opt_norm   part[c] = the sum over chunk c of (double)g * (double)g for the elements of GMPE_OPT_T_IN_NORM tensors (exact products; 0 for the
+ *                others): each thread adds its four in ascending order, then the 256 sums are added pairwise by halving (i += i + 128, then + 64, ..., + 1).
+ *   k_opt_step   every workgroup forms total = sum of part[0 .. n_chunks) itself — thread i adds part[i], part[i + 256], ... ascending, then the same
+ *                halving — so every workgroup holds the same bits, a function of the shapes, the flags and the data. No atomics.
+ *     total_norm = sqrt(total)                                                            (double)
+ *     coef       = (float)min(1.0, max_norm / (total_norm + 1e-6))                        formed in double, rounded once; NaN stays NaN; GMPE_OPT_CLIP only
+ *     out[0] = total_norm, out[1] = coef (1.0 without GMPE_OPT_CLIP), grad_norm_f32[0] = (float)total_norm: written by the first workgroup
+ *     per element of a GMPE_OPT_T_IN_NORM tensor, GMPE_OPT_CLIP only:   g = g * coef, written back to grad (also when coef == 1, as torch multiplies)
+ *     per element of a GMPE_OPT_T_STEP tensor, GMPE_OPT_STEP only, all float32, no fused multiply-add, g as it stands after the clip (the gradient of a
+ *     tensor that is not GMPE_OPT_T_IN_NORM is used unscaled; the decayed g is not written back):
+ *       g     = g + wd * p                       when wd != 0
+ *       m     = m + (g - m) * w1                 w1 = (float)(1 - beta1)                  exp_avg.lerp_(grad, 1 - beta1)
+ *       v     = b2 * v + (w2 * g) * g            b2 = (float)beta2, w2 = (float)(1 - beta2)   exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
+ *       denom = sqrtf(v) / s2 + eps              s2 = (float)sqrt(1 - beta2^t)            correctly rounded sqrt and divide
+ *       p     = p - a * (m / denom)              a  = (float)(lr / (1 - beta1^t))         param.addcdiv_(exp_avg, denom, value=-step_size)
+ *     The host forms w1, w2, a and s2 in double from the plan's doubles and t and rounds each to float32 once, as a Python float is when it meets a
+ *     float32 tensor. Non-finite values propagate as the formulas say and nothing is skipped: an infinite gradient entry gives total_norm = inf and
+ *     coef = 0, so that entry becomes NaN and the other clipped gradients 0.
+ * Two calls from the same state give the same bits. Workspace: f64 part[n_chunks]; its contents before the call do not matter. */
+#define GMPE_OPT_MAX_TENSORS 64        /* tensors per launch group                                                                      */
+#define GMPE_OPT_MAX_HYPERS 8          /* distinct hyper-parameter sets per launch group                                                 */
+#define GMPE_OPT_CHUNK 1024            /* elements per workgroup: 256 threads x 4 dwords, every access coalesced                          */
+#define GMPE_OPT_MAX_PLAN_TENSORS 4096 /* tensors per call                                                                               */
+#define GMPE_OPT_MAX_NUMEL (1LL << 30) /* elements per tensor                                                                            */
+#define GMPE_OPT_CLIP 1                /* plan flag: scale the GMPE_OPT_T_IN_NORM gradients by coef                                       */
+#define GMPE_OPT_STEP 2                /* plan flag: step the GMPE_OPT_T_STEP tensors                                                     */
+#define GMPE_OPT_T_IN_NORM 1           /* tensor flag: its gradient enters the norm and is scaled                                         */
+#define GMPE_OPT_T_STEP 2              /* tensor flag: Adam steps it, with hypers[hyper]                                                  */
+typedef struct gmpe_optim_tensor {
+    float* param;                       /* [numel]; read and written with GMPE_OPT_T_STEP, else not read (may be NULL)                 */
+    float* grad;                        /* [numel]; required                                                                           */
+    float* exp_avg;                     /* [numel]; GMPE_OPT_T_STEP                                                                    */
+    float* exp_avg_sq;                  /* [numel]; GMPE_OPT_T_STEP                                                                    */
+    int64_t numel;                      /* 0 .. GMPE_OPT_MAX_NUMEL; 0: the tensor is skipped                                           */
+    int32_t flags;                      /* GMPE_OPT_T_*, at least one                                                                  */
+    int32_t hyper;                      /* index into hypers with GMPE_OPT_T_STEP, else 0                                              */
+} gmpe_optim_tensor;
+typedef struct gmpe_optim_hyper {       /* one torch param_group at one step count                                                     */
+    double lr;                          /* >= 0                                                                                        */
+    double beta1, beta2;                /* in [0, 1)                                                                                   */
+    double eps;                         /* >= 0                                                                                        */
+    double weight_decay;                /* >= 0 (torch's coupled weight decay: added to the gradient)                                  */
+    int64_t t;                          /* the step count AFTER this step, >= 1                                                        */
+} gmpe_optim_hyper;
+typedef struct gmpe_optim_plan {
+    int32_t n_tensors;                  /* 1 .. GMPE_OPT_MAX_PLAN_TENSORS                                                              */
+    int32_t n_hypers;                   /* 0 .. GMPE_OPT_MAX_PLAN_TENSORS                                                              */
+    int32_t flags;                      /* GMPE_OPT_CLIP | GMPE_OPT_STEP, or 0: the norm is only reported                              */
+    int32_t reserved;                   /* 0                                                                                           */
+    const gmpe_optim_tensor* tensors;   /* HOST array [n_tensors]                                                                      */
+    const gmpe_optim_hyper* hypers;     /* HOST array [n_hypers]                                                                       */
+    double max_norm;                    /* > 0 with GMPE_OPT_CLIP (inf allowed), else not read                                         */
+    double* out;                        /* f64 [2] device: total_norm, coef; 8-byte aligned                                            */
+    float* grad_norm_f32;               /* f32 [1] device or NULL: total_norm rounded once                                             */
+    void* workspace;                    /* gmpe_optim_workspace_bytes(plan) bytes, 8-byte aligned; may be NULL when that is 0          */
+    size_t workspace_bytes;
+} gmpe_optim_plan;
+/* bytes of workspace for this plan's geometry: reads n_tensors, n_hypers and the tensors' numel, flags and hyper; no pointer into device memory */
+int gmpe_optim_workspace_bytes(const gmpe_optim_plan* plan, size_t* bytes_out);
+int gmpe_optim_step(int device, const gmpe_optim_plan* plan, void* stream);
+
 /* ---- The policy's masked GRU layer (handle-less): RNNLayer.forward (onpolicy/algorithms/utils/rnn.py:23-79) with recurrent_N == 1 ----
  * The layer in front of the action head (GR_Actor) and of the value head (GR_Critic): nn.GRU(D, H) driven step by step with the state multiplied by
  * the step's mask, then nn.LayerNorm(H). All arrays float32, contiguous. For every row k of `rows` independently, t = 0 .. steps-1 (x, masks, features
