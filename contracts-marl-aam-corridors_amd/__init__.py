@@ -40,9 +40,9 @@ def __getattr__(name):
     if name in ("action_logits", "act_head", "head_workspace_bytes"):
         from . import head
         return getattr(head, name)
-    if name == "clip_and_step":
+    if name in ("clip_and_step", "clip_and_step_begin", "clip_and_step_finish"):
         from . import optim
-        return optim.clip_and_step
+        return getattr(optim, name)
     if name in ("GmpeEngine", "compute_returns_begin", "compute_returns_finish"):
         from . import engine
         return getattr(engine, name)

@@ -26,7 +26,7 @@ SYMBOLS = ["gmpe_abi_version", "gmpe_last_error", "gmpe_obs_dim", "gmpe_node_fea
            "gmpe_mlp_workspace_bytes", "gmpe_mlp_forward", "gmpe_mlp_backward",
            "gmpe_gnn_workspace_bytes", "gmpe_gnn_forward", "gmpe_gnn_backward",
            "gmpe_head_workspace_bytes", "gmpe_head_forward", "gmpe_head_backward", "gmpe_act_head",
-           "gmpe_optim_workspace_bytes", "gmpe_optim_step"]
+           "gmpe_optim_workspace_bytes", "gmpe_optim_step", "gmpe_optim_shard_elems", "gmpe_optim_step_shard"]
 
 
 class GmpeOutputs(C.Structure):
@@ -282,6 +282,12 @@ class GmpeOptimPlan(C.Structure):
                 ("grad_norm_f32", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
+class GmpeOptimShardPlan(C.Structure):
+    """gmpe_optim_shard_plan (include/gmpe.h): gmpe_optim_plan in two phases around an all-gather of the shards' packed gradients."""
+    _fields_ = [("base", GmpeOptimPlan), ("phase", C.c_int32), ("world", C.c_int32), ("local", C.c_void_p), ("all", C.c_void_p),
+                ("local_elems", C.c_int64)]
+
+
 class GmpeError(RuntimeError):
     pass
 
@@ -363,6 +369,8 @@ def load():
     lib.gmpe_act_head.argtypes = [I, C.POINTER(GmpeActPlan), C.POINTER(GmpeHeadPlan), P]
     lib.gmpe_optim_workspace_bytes.argtypes = [C.POINTER(GmpeOptimPlan), C.POINTER(C.c_size_t)]
     lib.gmpe_optim_step.argtypes = [I, C.POINTER(GmpeOptimPlan), P]
+    lib.gmpe_optim_shard_elems.argtypes = [C.POINTER(GmpeOptimPlan), C.POINTER(C.c_int64)]
+    lib.gmpe_optim_step_shard.argtypes = [I, C.POINTER(GmpeOptimShardPlan), P]
     from .config import ABI_VERSION
     if lib.gmpe_abi_version() != ABI_VERSION:
         raise GmpeError("libgmpe.so ABI version mismatch")

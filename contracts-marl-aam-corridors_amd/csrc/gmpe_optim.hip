@@ -6,57 +6,15 @@
 // The table is a kernel argument (64 descriptors of 40 bytes + 8 hyper-parameter sets of 28 bytes: under the 4 KB of a kernel's arguments), so a call
 // uploads nothing, allocates nothing and waits for nothing. Sizes are tiny (about 41 000 elements for the shipped actor): the job is few launches, not
 // bandwidth, which is why a lane finds its tensor by a binary search over the prefix sums rather than through a precomputed map in device memory.
+// The table, the search and the workgroup sum are gmpe_optim_table.h's, shared with gmpe_optim_shard.hip (gmpe_optim_step_shard), which launches this file's
+// k_opt_step through launch_steps() behind its own sum kernel.
 #include <math.h>
 
-#include <vector>
+#include "gmpe_optim_table.h"
 
-#include "gmpe_host.h"
+using namespace gmpe_opt;
 
 namespace {
-
-constexpr int BLOCK = 256, CHUNK = GMPE_OPT_CHUNK, PER_THREAD = CHUNK / BLOCK, MAXT = GMPE_OPT_MAX_TENSORS, MAXH = GMPE_OPT_MAX_HYPERS;
-constexpr uint32_t GROUP_LIMIT = 0x7fffffffu - (uint32_t)CHUNK;     // a group's elements: every chunk's last index stays below 2^31
-
-struct Desc {
-    float* p; float* g; float* m; float* v;
-    uint32_t start;                // the tensor's first element in the group's concatenation
-    uint16_t flags, hyper;         // GMPE_OPT_T_*; index into Table::h
-};
-static_assert(sizeof(Desc) == 40, "a descriptor is 40 bytes");
-
-struct Hyper { float wd, w1, b2, w2, a, s2, eps; };
-
-struct Table {
-    Desc d[MAXT];
-    Hyper h[MAXH];
-    uint32_t total;                // the group's elements
-    int32_t n;                     // its tensors
-};
-static_assert(sizeof(Table) <= 3072, "the table and the other arguments stay under the 4 KB of kernel arguments");
-
-// the tensor that holds element e < total: the last i with d[i].start <= e (the starts ascend strictly: empty tensors are not in the table)
-__device__ __forceinline__ int find_tensor(const Table& tb, uint32_t e) {
-    int lo = 0, hi = tb.n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (tb.d[mid].start <= e) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
-// the 256 sums of a workgroup added pairwise by halving; every thread returns the total
-__device__ __forceinline__ double block_sum(double s, double* red) {
-    const int tid = threadIdx.x;
-    red[tid] = s;
-    __syncthreads();
-    for (int w = BLOCK / 2; w > 0; w >>= 1) {
-        if (tid < w) red[tid] += red[tid + w];
-        __syncthreads();
-    }
-    const double tot = red[0];
-    __syncthreads();
-    return tot;
-}
 
 __global__ __launch_bounds__(BLOCK) void k_opt_norm(const Table tb, double* __restrict__ part) {
     __shared__ double red[BLOCK];
@@ -123,14 +81,7 @@ __global__ __launch_bounds__(BLOCK) void k_opt_step(const Table tb, const StepAr
 
 using gmpe::fail;
 
-struct Layout {
-    std::vector<Table> groups;     // at least one: a table without elements still writes `out`
-    std::vector<int64_t> chunks;   // per group
-    int64_t n_chunks = 0;
-    size_t total = 0;              // workspace bytes
-};
-
-// what both entry points check of the geometry: counts, numel, flags, hyper indices
+// what every entry point checks of the geometry: counts, numel, flags, hyper indices
 int check_geometry(const char* fn, const gmpe_optim_plan* pl) {
     if (!pl) return fail(fn, "null plan");
     if (pl->n_tensors < 1 || pl->n_tensors > GMPE_OPT_MAX_PLAN_TENSORS) return fail(fn, "n_tensors must be in 1 .. " + std::to_string(GMPE_OPT_MAX_PLAN_TENSORS));
@@ -149,8 +100,9 @@ int check_geometry(const char* fn, const gmpe_optim_plan* pl) {
     return GMPE_OK;
 }
 
-// The launch groups of a checked plan. `fill`: with the pointers and the float32 hyper-parameters (gmpe_optim_step), else the geometry alone.
-void layout(const gmpe_optim_plan* pl, bool fill, Layout& y) {
+// The launch groups of a checked plan, filled as far as `depth` says: the geometry alone, with the pointers (GRADS), or with the pointers and the float32
+// hyper-parameters (STEP).
+void layout(const gmpe_optim_plan* pl, Depth depth, Layout& y) {
     int slot_of[MAXH];             // the plan's hyper index in each of the current group's slots
     int n_slots = 0;
     y.groups.emplace_back();
@@ -169,7 +121,7 @@ void layout(const gmpe_optim_plan* pl, bool fill, Layout& y) {
         }
         if (steps && slot == n_slots) {
             slot_of[n_slots++] = t.hyper;
-            if (fill) {
+            if (depth == STEP) {
                 const gmpe_optim_hyper& h = pl->hypers[t.hyper];
                 const double bc1 = 1.0 - pow(h.beta1, (double)h.t), bc2 = 1.0 - pow(h.beta2, (double)h.t);
                 tb->h[slot] = Hyper{(float)h.weight_decay, (float)(1.0 - h.beta1), (float)h.beta2, (float)(1.0 - h.beta2), (float)(h.lr / bc1),
@@ -178,12 +130,13 @@ void layout(const gmpe_optim_plan* pl, bool fill, Layout& y) {
         }
         Desc& d = tb->d[tb->n++];
         d.start = tb->total; d.flags = (uint16_t)t.flags; d.hyper = (uint16_t)slot;
-        if (fill) { d.p = t.param; d.g = t.grad; d.m = t.exp_avg; d.v = t.exp_avg_sq; }
+        if (depth != GEOMETRY) { d.p = t.param; d.g = t.grad; d.m = t.exp_avg; d.v = t.exp_avg_sq; }
         tb->total += (uint32_t)t.numel;
     }
     for (const Table& g : y.groups) {
         y.chunks.push_back(((int64_t)g.total + CHUNK - 1) / CHUNK);
         y.n_chunks += y.chunks.back();
+        y.elems += (int64_t)g.total;
     }
     gmpe::Carver c;
     c.take((size_t)y.n_chunks * sizeof(double));
@@ -192,50 +145,68 @@ void layout(const gmpe_optim_plan* pl, bool fill, Layout& y) {
 
 }  // namespace
 
+int gmpe_opt::prepare(const char* fn, const gmpe_optim_plan* pl, Depth depth, Layout& y) {
+    if (int rc = check_geometry(fn, pl)) return rc;
+    if (depth == GRADS) {
+        for (int i = 0; i < pl->n_tensors; ++i)
+            if (int rc = gmpe::check_ptr(fn, pl->tensors[i].grad, "tensors[" + std::to_string(i) + "].grad", pl->tensors[i].numel > 0)) return rc;
+    } else if (depth == STEP) {
+        if (pl->flags & ~(GMPE_OPT_CLIP | GMPE_OPT_STEP)) return fail(fn, "flags must be GMPE_OPT_CLIP, GMPE_OPT_STEP, both or 0");
+        if (pl->reserved != 0) return fail(fn, "reserved must be 0");
+        const bool clip = pl->flags & GMPE_OPT_CLIP, step = pl->flags & GMPE_OPT_STEP;
+        for (int i = 0; i < pl->n_hypers; ++i) {
+            const gmpe_optim_hyper& h = pl->hypers[i];
+            const std::string at = "hypers[" + std::to_string(i) + "].";
+            if (!(h.lr >= 0.0)) return fail(fn, at + "lr must be >= 0");
+            if (!(h.beta1 >= 0.0 && h.beta1 < 1.0)) return fail(fn, at + "beta1 must be in [0, 1)");
+            if (!(h.beta2 >= 0.0 && h.beta2 < 1.0)) return fail(fn, at + "beta2 must be in [0, 1)");
+            if (!(h.eps >= 0.0)) return fail(fn, at + "eps must be >= 0");
+            if (!(h.weight_decay >= 0.0)) return fail(fn, at + "weight_decay must be >= 0");
+            if (h.t < 1) return fail(fn, at + "t must be >= 1");
+        }
+        if (clip && !(pl->max_norm > 0.0)) return fail(fn, "max_norm must be > 0 with GMPE_OPT_CLIP");
+        for (int i = 0; i < pl->n_tensors; ++i) {
+            const gmpe_optim_tensor& t = pl->tensors[i];
+            const bool steps = step && (t.flags & GMPE_OPT_T_STEP) && t.numel > 0;          // an empty tensor has no address
+            const gmpe::PtrField ps[] = {{t.param, "param", steps}, {t.grad, "grad", t.numel > 0}, {t.exp_avg, "exp_avg", steps}, {t.exp_avg_sq, "exp_avg_sq", steps}};
+            if (int rc = gmpe::check_ptrs(fn, ps, "tensors[" + std::to_string(i) + "].")) return rc;
+        }
+        if (!pl->out) return fail(fn, "out is required");
+        if ((uintptr_t)pl->out & 7) return fail(fn, "out must be 8-byte aligned");
+        if (int rc = gmpe::check_ptr(fn, pl->grad_norm_f32, "grad_norm_f32", false)) return rc;
+    }
+    layout(pl, depth, y);
+    if (y.n_chunks > 0x7fffffffLL) return fail(fn, "tensors: too many elements for one call");
+    if (depth == STEP)
+        return gmpe::check_workspace(fn, pl->workspace, pl->workspace_bytes, y.total, y.total > 0, "workspace is required", "gmpe_optim_workspace_bytes(plan)");
+    return GMPE_OK;
+}
+
+int gmpe_opt::launch_steps(const gmpe_optim_plan* pl, const Layout& y, hipStream_t st) {
+    StepArgs a = {static_cast<const double*>(pl->workspace), (int32_t)y.n_chunks, (pl->flags & GMPE_OPT_CLIP) != 0, (pl->flags & GMPE_OPT_STEP) != 0, 0,
+                  pl->max_norm, pl->out, pl->grad_norm_f32};
+    for (size_t g = 0; g < y.groups.size(); ++g) {
+        a.first = g == 0;
+        const int64_t grid = y.chunks[g] > 0 ? y.chunks[g] : (g == 0 ? 1 : 0);
+        if (grid > 0) GMPE_LAUNCH(k_opt_step, dim3((unsigned)grid), dim3(BLOCK), 0, st, y.groups[g], a);
+    }
+    return GMPE_OK;
+}
+
 extern "C" {
 
 int gmpe_optim_workspace_bytes(const gmpe_optim_plan* pl, size_t* bytes_out) {
     const char* fn = "gmpe_optim_workspace_bytes";
     if (!bytes_out) return fail(fn, "bytes_out is null");
-    if (int rc = check_geometry(fn, pl)) return rc;
     Layout y;
-    layout(pl, false, y);
-    if (y.n_chunks > 0x7fffffffLL) return fail(fn, "tensors: too many elements for one call");
+    if (int rc = prepare(fn, pl, GEOMETRY, y)) return rc;
     *bytes_out = y.total;
     return GMPE_OK;
 }
 
 int gmpe_optim_step(int device, const gmpe_optim_plan* pl, void* stream) {
-    const char* fn = "gmpe_optim_step";
-    if (int rc = check_geometry(fn, pl)) return rc;
-    if (pl->flags & ~(GMPE_OPT_CLIP | GMPE_OPT_STEP)) return fail(fn, "flags must be GMPE_OPT_CLIP, GMPE_OPT_STEP, both or 0");
-    if (pl->reserved != 0) return fail(fn, "reserved must be 0");
-    const bool clip = pl->flags & GMPE_OPT_CLIP, step = pl->flags & GMPE_OPT_STEP;
-    for (int i = 0; i < pl->n_hypers; ++i) {
-        const gmpe_optim_hyper& h = pl->hypers[i];
-        const std::string at = "hypers[" + std::to_string(i) + "].";
-        if (!(h.lr >= 0.0)) return fail(fn, at + "lr must be >= 0");
-        if (!(h.beta1 >= 0.0 && h.beta1 < 1.0)) return fail(fn, at + "beta1 must be in [0, 1)");
-        if (!(h.beta2 >= 0.0 && h.beta2 < 1.0)) return fail(fn, at + "beta2 must be in [0, 1)");
-        if (!(h.eps >= 0.0)) return fail(fn, at + "eps must be >= 0");
-        if (!(h.weight_decay >= 0.0)) return fail(fn, at + "weight_decay must be >= 0");
-        if (h.t < 1) return fail(fn, at + "t must be >= 1");
-    }
-    if (clip && !(pl->max_norm > 0.0)) return fail(fn, "max_norm must be > 0 with GMPE_OPT_CLIP");
-    for (int i = 0; i < pl->n_tensors; ++i) {
-        const gmpe_optim_tensor& t = pl->tensors[i];
-        const bool steps = step && (t.flags & GMPE_OPT_T_STEP) && t.numel > 0;          // an empty tensor has no address
-        const gmpe::PtrField ps[] = {{t.param, "param", steps}, {t.grad, "grad", t.numel > 0}, {t.exp_avg, "exp_avg", steps}, {t.exp_avg_sq, "exp_avg_sq", steps}};
-        if (int rc = gmpe::check_ptrs(fn, ps, "tensors[" + std::to_string(i) + "].")) return rc;
-    }
-    if (!pl->out) return fail(fn, "out is required");
-    if ((uintptr_t)pl->out & 7) return fail(fn, "out must be 8-byte aligned");
-    if (int rc = gmpe::check_ptr(fn, pl->grad_norm_f32, "grad_norm_f32", false)) return rc;
     Layout y;
-    layout(pl, true, y);
-    if (y.n_chunks > 0x7fffffffLL) return fail(fn, "tensors: too many elements for one call");
-    if (int rc = gmpe::check_workspace(fn, pl->workspace, pl->workspace_bytes, y.total, y.total > 0, "workspace is required", "gmpe_optim_workspace_bytes(plan)"))
-        return rc;
+    if (int rc = prepare("gmpe_optim_step", pl, STEP, y)) return rc;
     GMPE_HIP_CHECK(hipSetDevice(device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     double* part = static_cast<double*>(pl->workspace);
@@ -244,13 +215,7 @@ int gmpe_optim_step(int device, const gmpe_optim_plan* pl, void* stream) {
         if (y.chunks[g] > 0) GMPE_LAUNCH(k_opt_norm, dim3((unsigned)y.chunks[g]), dim3(BLOCK), 0, st, y.groups[g], part + base);
         base += y.chunks[g];
     }
-    StepArgs a = {part, (int32_t)y.n_chunks, clip, step, 0, pl->max_norm, pl->out, pl->grad_norm_f32};
-    for (size_t g = 0; g < y.groups.size(); ++g) {
-        a.first = g == 0;
-        const int64_t grid = y.chunks[g] > 0 ? y.chunks[g] : (g == 0 ? 1 : 0);
-        if (grid > 0) GMPE_LAUNCH(k_opt_step, dim3((unsigned)grid), dim3(BLOCK), 0, st, y.groups[g], a);
-    }
-    return GMPE_OK;
+    return launch_steps(pl, y, st);
 }
 
 }  // extern "C"

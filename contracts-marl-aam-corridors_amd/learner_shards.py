@@ -1,7 +1,7 @@
 """The exchange of a data-parallel learner's batch statistics (include/gmpe.h gmpe_compute_returns_shard, gmpe_ppo_loss_shard).
 
-Every rank keeps its DeviceRolloutBuffer where its rollout was produced and only gradients are all-reduced. The three reductions of the learner path
-that are over "the batch" — the mean / std of the advantages, ValueNorm.update's batch means, the denominators of the loss means — run in two phases:
+Every rank keeps its DeviceRolloutBuffer where its rollout was produced and only gradients cross ranks (clip_and_step(..., shards=x) gathers and sums
+them through the same object: see optim.py). The three reductions of the learner path that are over "the batch" — the mean / std of the advantages, ValueNorm.update's batch means, the denominators of the loss means — run in two phases:
 LOCAL leaves a few doubles per shard (`local`: f64 [3] or [4] on the device), the caller gathers them into `all` ([world, k], rank order = row order),
 APPLY merges the rows in index order. The result is the statistic of the whole batch, the same bits on every shard.
 
@@ -51,13 +51,14 @@ def check_shards(shards):
     return world
 
 
-def check_all_stats(all_stats, local, what):
-    """all_stats: the gathered [world, k] of `local` [k] -> world. Checked before anything is launched."""
+def check_all_stats(all_stats, local, what, dtype=torch.float64):
+    """all_stats: the gathered [world, k] of `local` [k] -> world. Checked before anything is launched. dtype: float64 for the statistics, float32 for
+    clip_and_step's packed gradients."""
     k = int(local.numel())
     if not isinstance(all_stats, torch.Tensor) or all_stats.dim() != 2 or all_stats.shape[1] != k:
         raise ValueError("%s: all_stats must be a tensor of shape (world, %d)" % (what, k))
-    if all_stats.dtype != torch.float64:
-        raise ValueError("%s: all_stats must be float64, not %s" % (what, all_stats.dtype))
+    if all_stats.dtype != dtype:
+        raise ValueError("%s: all_stats must be %s, not %s" % (what, str(dtype).replace("torch.", ""), all_stats.dtype))
     world = int(all_stats.shape[0])
     if not 1 <= world <= MAX_WORLD:
         raise ValueError("%s: world = %d is outside 1 .. %d" % (what, world, MAX_WORLD))
@@ -68,11 +69,11 @@ def check_all_stats(all_stats, local, what):
     return world
 
 
-def gather(shards, local, what):
+def gather(shards, local, what, dtype=torch.float64):
     """shards.exchange(local), checked -> all_stats"""
     world = check_shards(shards)
     all_stats = shards.exchange(local)
-    if check_all_stats(all_stats, local, what) != world:
+    if check_all_stats(all_stats, local, what, dtype) != world:
         raise ValueError("%s: shards.exchange returned %d rows, shards.world is %d" % (what, all_stats.shape[0], world))
     return all_stats
 

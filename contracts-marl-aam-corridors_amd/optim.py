@@ -4,6 +4,10 @@ torch.optim.Adam.step (onpolicy/algorithms/graph_mappo.py:212-227, :254-265) as 
     grad_norm = gmpe.clip_and_step(optimizer, max_grad_norm, parameters=net.parameters())
     # was: grad_norm = nn.utils.clip_grad_norm_(net.parameters(), max_grad_norm); optimizer.step()
 
+For a data-parallel learner (include/gmpe.h gmpe_optim_step_shard) the same call with shards=x works on the sum over the ranks of their gradients, taken in
+rank order in double and rounded once — clip_and_step_begin, x.exchange(.local), clip_and_step_finish: one launch per 64 tensors before the all-gather
+and two after it. No DistributedDataParallel is involved, and the replicas stay bit-identical.
+
 The optimiser stays the caller's unchanged torch.optim.Adam: its param_groups are read at every call, its state holds torch's own keys, so
 optimizer.state_dict(), load_state_dict and a later optimizer.step() by torch keep working, in either order. There is no torch fallback: the tensors must
 be on a HIP device.
@@ -150,8 +154,84 @@ def workspace_bytes(optimizer, parameters=None):
     return 8 * (sum(sizes) // CHUNK + len(sizes))
 
 
+def _max_norm(max_grad_norm):
+    """-> (clip, max_grad_norm as a float)"""
+    if max_grad_norm is None:
+        return False, 0.0
+    max_grad_norm = float(max_grad_norm)
+    if not max_grad_norm > 0.0:
+        raise ValueError("max_grad_norm must be positive (or None: the norm is only reported), not %r" % (max_grad_norm,))
+    return True, max_grad_norm
+
+
+_NO_GROUP = (0.0, 0.0, 0.0, 1.0, 0.0)                # the hyper-parameters of a table that steps nothing but carries `extra`: any valid set will do
+
+
+def _bind(hypers, rows, clip, max_grad_norm, step, create=True, carry=None):
+    """The gmpe_optim_plan over _table's rows, without outputs and workspace -> (plan, what it points to, the states' step counts).
+    create False (clip_and_step_begin): missing state is not created — such a tensor has null pointers and the step count 1 it will have.
+    carry: (total [k], scratch [3k]) of clip_and_step_begin's `extra`, the table's last tensor: stepped only, so that it is packed and summed like a
+    gradient and never scaled; its parameter and its state are scratch."""
+    n = len(rows) + (carry is not None)
+    table = bytearray(n * _TENSOR.size)                 # gmpe_optim_tensor[n], one pack per tensor: field by field through ctypes costs several times that
+    keys, steps = {}, []
+    for i, (p, flags, gi, st) in enumerate(rows):
+        if st is None:
+            _TENSOR.pack_into(table, i * _TENSOR.size, 0, p.grad.data_ptr(), 0, 0, p.numel(), flags, 0)
+            continue
+        if not st:
+            if not create:
+                _TENSOR.pack_into(table, i * _TENSOR.size, 0, p.grad.data_ptr(), 0, 0, p.numel(), flags, keys.setdefault((gi, 1), len(keys)))
+                continue
+            _new_state(st, p)
+        t = st["step"]
+        steps.append(t)
+        _TENSOR.pack_into(table, i * _TENSOR.size, p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel(), flags,
+                          keys.setdefault((gi, int(t) + 1), len(keys)))
+    if carry is not None:
+        total, scratch = carry
+        k, s = total.numel(), scratch.data_ptr()
+        if not keys:
+            keys[(None, 1)] = 0
+        _TENSOR.pack_into(table, (n - 1) * _TENSOR.size, s, total.data_ptr(), s + 4 * k, s + 8 * k, k, _lib.OPT_T_STEP, 0)
+    tensors = C.cast((C.c_char * len(table)).from_buffer(table), C.POINTER(_lib.GmpeOptimTensor))
+    hyper = (_lib.GmpeOptimHyper * max(len(keys), 1))()
+    for (gi, t), k in keys.items():
+        h = hyper[k]
+        h.lr, h.beta1, h.beta2, h.eps, h.weight_decay = _NO_GROUP if gi is None else hypers[gi]
+        h.t = t
+    plan = _lib.GmpeOptimPlan()
+    plan.n_tensors, plan.n_hypers, plan.tensors, plan.hypers = n, len(keys), tensors, hyper
+    plan.flags = (_lib.OPT_CLIP if clip else 0) | (_lib.OPT_STEP if step else 0)
+    plan.max_norm = max_grad_norm if clip else 0.0
+    return plan, (table, tensors, hyper), steps
+
+
+def _outputs(plan, workspace, dev):
+    """the plan's outputs and workspace -> (grad_norm, what the plan points to)"""
+    out = torch.empty((2,), dtype=torch.float64, device=dev)
+    grad_norm = torch.empty((), dtype=torch.float32, device=dev)
+    plan.out, plan.grad_norm_f32 = out.data_ptr(), grad_norm.data_ptr()
+    plan.workspace, plan.workspace_bytes = workspace.data_ptr(), workspace.numel()
+    return grad_norm, out
+
+
+def _count(steps, rows):
+    if steps and all(isinstance(t, torch.Tensor) for t in steps):
+        torch._foreach_add_(steps, 1)                   # torch's own way over its host-side step counts: one call
+    else:
+        for _, _, _, st in rows:
+            if st is not None:
+                st["step"] += 1
+
+
+def _too_many(n):
+    if n > _lib.OPT_MAX_PLAN_TENSORS:
+        raise ValueError("%d tensors with gradients: one call takes at most %d" % (n, _lib.OPT_MAX_PLAN_TENSORS))
+
+
 @torch.no_grad()
-def clip_and_step(optimizer, max_grad_norm=None, *, parameters=None, step=True, workspace=None):
+def clip_and_step(optimizer, max_grad_norm=None, *, parameters=None, step=True, workspace=None, shards=None, extra=None):
     """nn.utils.clip_grad_norm_(parameters, max_grad_norm) followed by optimizer.step(), two launches per 64 tensors -> grad_norm, the total 2-norm as a
     0-dim float32 device tensor (formed in double, rounded once).
       optimizer: the caller's torch.optim.Adam, read through param_groups at this call (a changed lr is honoured; every group has its own lr, betas, eps,
@@ -165,57 +245,125 @@ def clip_and_step(optimizer, max_grad_norm=None, *, parameters=None, step=True, 
         `parameters` is stepped with its gradient unscaled, a tensor of `parameters` alone is scaled only.
       step: False clips only; no state is created and no step is counted.
       workspace: an optional uint8 device tensor of workspace_bytes(optimizer, parameters) to reuse between calls.
+      shards: None, or the exchange of a data-parallel learner (gmpe.learner_shards): the gradients are this rank's contribution — the backward of
+        ppo_losses(..., shards=shards, reduce="sum") — and the clip and the step work on the SUM over the ranks: clip_and_step_begin,
+        shards.exchange(.local), clip_and_step_finish, which see. extra (with shards only): clip_and_step_begin's; the call then returns
+        (grad_norm, extra_sum).
     Only tensors that have a gradient take part, as in torch. Missing state is created as torch creates it (exp_avg and exp_avg_sq zeros_like, `step` the
     CPU float32 torch.tensor(0.) of a non-capturable, non-fused Adam) and `step` is incremented on the host. The arithmetic is the numeric contract of
     include/gmpe.h; the bits are a function of the shapes, the sets and the data. Nothing here waits for the device, and with a workspace nothing is
     allocated per call beyond the outputs."""
-    clip = max_grad_norm is not None
-    if clip:
-        max_grad_norm = float(max_grad_norm)
-        if not max_grad_norm > 0.0:
-            raise ValueError("max_grad_norm must be positive (or None: the norm is only reported), not %r" % (max_grad_norm,))
+    if shards is not None:
+        from . import learner_shards
+        world = learner_shards.check_shards(shards)
+        h = clip_and_step_begin(optimizer, max_grad_norm, parameters=parameters, step=step, workspace=workspace, extra=extra)
+        if h.local.numel() == 0:                        # no tensor has a gradient, on any rank: nothing is exchanged
+            return clip_and_step_finish(h, h.local.new_empty((world, 0)))
+        return clip_and_step_finish(h, learner_shards.gather(shards, h.local, "clip_and_step", torch.float32))
+    if extra is not None:
+        raise ValueError("extra rides on the exchange of shards: without shards there is none")
+    clip, max_grad_norm = _max_norm(max_grad_norm)
     step = bool(step)
     hypers, rows, dev = _table(optimizer, parameters, step)
-    if len(rows) > _lib.OPT_MAX_PLAN_TENSORS:
-        raise ValueError("%d tensors with gradients: one call takes at most %d" % (len(rows), _lib.OPT_MAX_PLAN_TENSORS))
+    _too_many(len(rows))
     if not rows:                                        # nothing has a gradient: clip_grad_norm_ of nothing
         return torch.zeros((), dtype=torch.float32, device=dev)
-    n = len(rows)
-    table = bytearray(n * _TENSOR.size)                 # gmpe_optim_tensor[n], one pack per tensor: field by field through ctypes costs several times that
-    keys, steps = {}, []
-    for i, (p, flags, gi, st) in enumerate(rows):
-        if st is None:
-            _TENSOR.pack_into(table, i * _TENSOR.size, 0, p.grad.data_ptr(), 0, 0, p.numel(), flags, 0)
-            continue
-        if not st:
-            _new_state(st, p)
-        t = st["step"]
-        steps.append(t)
-        _TENSOR.pack_into(table, i * _TENSOR.size, p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel(), flags,
-                          keys.setdefault((gi, int(t) + 1), len(keys)))
-    tensors = C.cast((C.c_char * len(table)).from_buffer(table), C.POINTER(_lib.GmpeOptimTensor))
-    hyper = (_lib.GmpeOptimHyper * max(len(keys), 1))()
-    for (gi, t), k in keys.items():
-        h = hyper[k]
-        h.lr, h.beta1, h.beta2, h.eps, h.weight_decay = hypers[gi]
-        h.t = t
-    plan = _lib.GmpeOptimPlan()
-    plan.n_tensors, plan.n_hypers, plan.tensors, plan.hypers = n, len(keys), tensors, hyper
-    plan.flags = (_lib.OPT_CLIP if clip else 0) | (_lib.OPT_STEP if step else 0)
-    plan.max_norm = max_grad_norm if clip else 0.0
+    plan, keep, steps = _bind(hypers, rows, clip, max_grad_norm, step)
     lib = _lib.load()
     need = C.c_size_t()
     _lib.check(lib.gmpe_optim_workspace_bytes(C.byref(plan), C.byref(need)), "gmpe_optim_workspace_bytes")
-    workspace = _workspace(int(need.value), workspace, dev)
-    out = torch.empty((2,), dtype=torch.float64, device=dev)
-    grad_norm = torch.empty((), dtype=torch.float32, device=dev)
-    plan.out, plan.grad_norm_f32 = out.data_ptr(), grad_norm.data_ptr()
-    plan.workspace, plan.workspace_bytes = workspace.data_ptr(), workspace.numel()
+    grad_norm, out = _outputs(plan, _workspace(int(need.value), workspace, dev), dev)
     _lib.check(lib.gmpe_optim_step(_ordinal(dev), C.byref(plan), _stream_of(dev)), "gmpe_optim_step")
-    if steps and all(isinstance(t, torch.Tensor) for t in steps):
-        torch._foreach_add_(steps, 1)                   # torch's own way over its host-side step counts: one call
-    else:
-        for _, _, _, st in rows:
-            if st is not None:
-                st["step"] += 1
+    _count(steps, rows)
     return grad_norm
+
+
+MAX_EXTRA = 16
+
+
+class ClipAndStepShard(object):
+    """What clip_and_step_begin leaves for clip_and_step_finish: `.local`, float32 [n + k] on the device (valid once the stream reaches it) — this rank's
+    gradients packed back to back in table order, then the k elements of `extra` — and the call's table with the tensors it points to."""
+
+    def __init__(self, optimizer, hypers, rows, dev, clip, max_grad_norm, step, carry, workspace, local):
+        self.optimizer, self.hypers, self.rows, self.dev, self.clip, self.max_grad_norm, self.step = optimizer, hypers, rows, dev, clip, max_grad_norm, step
+        self.carry, self.workspace, self.local, self.done = carry, workspace, local, False
+        self.grads = [p.grad for p, _, _, _ in rows]    # the tensors LOCAL read: APPLY writes the sums to the same ones
+
+
+def _shard_plan(plan, phase, world, local, all_, n):
+    sp = _lib.GmpeOptimShardPlan()
+    sp.base = plan
+    sp.phase, sp.world, sp.local, sp.all, sp.local_elems = phase, world, local, all_, n
+    return sp
+
+
+@torch.no_grad()
+def clip_and_step_begin(optimizer, max_grad_norm=None, *, parameters=None, step=True, workspace=None, extra=None):
+    """The first phase of clip_and_step over one shard of a data-parallel learner (gmpe_optim_step_shard, GMPE_SHARD_LOCAL), same arguments: one launch
+    per 64 tensors packs the gradients of every tensor of the call, clipped or stepped, into the handle's `.local`. Every refusal of clip_and_step
+    happens here; no state is created, no step is counted and no gradient is changed. -> ClipAndStepShard
+      extra: None, or a float32 tensor of at most 16 elements on the gradients' device. It rides behind the gradients in `.local` and comes back from
+        clip_and_step_finish as the sum over the ranks by the gradients' own rule — global scalars out of the collective that is paid for anyway.
+    The tables of all ranks must be equal — the same tensors with gradients, in the same order — and so must `extra`'s length: what is exchanged is
+    positions, not names. Between begin and finish the gradients must stay the tensors they are. A call in which no tensor has a gradient and no extra
+    is given leaves an empty `.local`: there is nothing to exchange, provided all ranks are in that state together."""
+    clip, max_grad_norm = _max_norm(max_grad_norm)
+    step = bool(step)
+    if extra is not None:
+        if not isinstance(extra, torch.Tensor) or extra.dtype != torch.float32:
+            raise ValueError("extra must be a float32 tensor")
+        if extra.numel() > MAX_EXTRA:
+            raise ValueError("extra must have at most %d elements, not %d" % (MAX_EXTRA, extra.numel()))
+    hypers, rows, dev = _table(optimizer, parameters, step)
+    _too_many(len(rows) + (extra is not None))
+    carry = None
+    if extra is not None:
+        if extra.device != dev:
+            raise ValueError("extra is on %s: it must be on %s (the device of the gradients)" % (extra.device, dev))
+        k = extra.numel()
+        carry = (extra.detach().reshape(-1).clone(), torch.zeros((3 * k,), dtype=torch.float32, device=dev))
+    local = torch.empty((0,), dtype=torch.float32, device=dev)
+    if rows or (carry is not None and carry[0].numel()):
+        plan, keep, _ = _bind(hypers, rows, clip, max_grad_norm, step, create=False, carry=carry)
+        lib = _lib.load()
+        n, need = C.c_int64(), C.c_size_t()
+        _lib.check(lib.gmpe_optim_shard_elems(C.byref(plan), C.byref(n)), "gmpe_optim_shard_elems")
+        _lib.check(lib.gmpe_optim_workspace_bytes(C.byref(plan), C.byref(need)), "gmpe_optim_workspace_bytes")
+        workspace = _workspace(int(need.value), workspace, dev)
+        if n.value:
+            local = torch.empty((n.value,), dtype=torch.float32, device=dev)
+            sp = _shard_plan(plan, _lib.SHARD_LOCAL, 1, local.data_ptr(), None, n.value)
+            _lib.check(lib.gmpe_optim_step_shard(_ordinal(dev), C.byref(sp), _stream_of(dev)), "gmpe_optim_step_shard")
+    return ClipAndStepShard(optimizer, hypers, rows, dev, clip, max_grad_norm, step, carry, workspace, local)
+
+
+@torch.no_grad()
+def clip_and_step_finish(handle, all):
+    """The second phase (GMPE_SHARD_APPLY), two launches per 64 tensors: all float32 [world, n + k], contiguous, on the handle's device, row r = rank r's
+    `.local` (torch.stack in one process, an all-gather across ranks). Every element becomes the sum of its column in rank order, in double, rounded
+    once — a sum, not a mean: the ranks' gradients of ppo_losses(..., reduce="sum") add up to the whole minibatch's. The sums are written to the
+    gradients (p.grad holds the global gradient afterwards, as under DDP), then clip_and_step's norm, clip and Adam step run on them; state is created
+    and `step` counted here. Every rank computes the same bits from the same rows, so the replicas' parameters, Adam state and norm stay bit-identical.
+    `all` is checked before any launch (a wrong row length — unequal tables — is caught here). Once per handle.
+    -> grad_norm, or (grad_norm, extra_sum [k]) when begin was given `extra`."""
+    from . import learner_shards
+    if not isinstance(handle, ClipAndStepShard):
+        raise TypeError("handle must come from clip_and_step_begin")
+    if handle.done:
+        raise RuntimeError("clip_and_step_finish was already called on this handle (it would step twice)")
+    h, dev = handle, handle.dev
+    world = learner_shards.check_all_stats(all, h.local, "clip_and_step_finish", torch.float32)
+    if any(p.grad is not g for (p, _, _, _), g in zip(h.rows, h.grads)):
+        raise RuntimeError("a gradient was replaced between clip_and_step_begin and clip_and_step_finish")
+    n = int(h.local.numel())
+    if n == 0:
+        grad_norm = torch.zeros((), dtype=torch.float32, device=dev)
+    else:
+        plan, keep, steps = _bind(h.hypers, h.rows, h.clip, h.max_grad_norm, h.step, carry=h.carry)
+        grad_norm, out = _outputs(plan, h.workspace, dev)
+        sp = _shard_plan(plan, _lib.SHARD_APPLY, world, None, all.data_ptr(), n)
+        _lib.check(_lib.load().gmpe_optim_step_shard(_ordinal(dev), C.byref(sp), _stream_of(dev)), "gmpe_optim_step_shard")
+        _count(steps, h.rows)
+    h.done = True
+    return grad_norm if h.carry is None else (grad_norm, h.carry[0])

@@ -90,12 +90,35 @@ PPOUpdate = collections.namedtuple("PPOUpdate", ["value_loss", "critic_grad_norm
 TRAIN_INFO = ("value_loss", "policy_loss", "dist_entropy", "actor_grad_norm", "critic_grad_norm", "ratio")      # graph_mappo.py:309-314
 
 
-def _no_accumulation(fn, accumulation_steps, shards=None):
+def _refusals(fn, accumulation_steps, shards):
+    """what ppo_update and train refuse, before anything else is read"""
+    if shards is not None and not (callable(getattr(shards, "exchange", None)) and hasattr(shards, "world") and hasattr(shards, "rank")):
+        raise NotImplementedError("shards: %s takes the exchange of a data-parallel learner — an object with exchange(local), world and rank "
+                                  "(gmpe.learner_shards.ProcessGroupExchange); anything else is not supported" % fn)
     if accumulation_steps != 1:
         raise NotImplementedError("accumulation_steps = %r: %s steps at every minibatch (gradient accumulation is not supported)" % (accumulation_steps, fn))
-    if shards is not None:
-        raise NotImplementedError("shards: %s clips and steps one learner's gradients; the gradient all-reduce of a data-parallel learner stays "
-                                  "DistributedDataParallel's (a norm across ranks is not supported)" % fn)
+
+
+def _ppo_update(actor, critic, actor_optimizer, critic_optimizer, sample, args, value_normalizer, update_actor, install, workspace, shards):
+    """ppo_update -> (PPOUpdate, ratio); ratio: with shards the whole minibatch's imp_weights.mean(), else None (it is u.imp_weights.mean())"""
+    res = minibatch_losses(actor, critic, sample, args, value_normalizer, install=install, workspace=workspace, shards=shards)
+    max_norm = getattr(args, "max_grad_norm", 10.0) if getattr(args, "use_max_grad_norm", True) else None
+    actor_optimizer.zero_grad()
+    if update_actor:
+        res.actor_loss.backward()
+    actor_grad_norm = clip_and_step(actor_optimizer, max_norm, parameters=actor.parameters(), step=bool(update_actor), shards=shards)
+    critic_optimizer.zero_grad()
+    (res.value_loss * getattr(args, "value_loss_coef", 1)).backward()
+    scalars = (res.value_loss.detach(), res.policy_loss.detach(), res.dist_entropy.detach(), res.ratio_mean.detach())
+    imp_weights = res.imp_weights.detach()
+    if shards is None:
+        critic_grad_norm, ratio = clip_and_step(critic_optimizer, max_norm, parameters=critic.parameters()), None
+    else:                                               # the ranks' contributions, and the sum and the count of imp_weights, ride on the critic's exchange
+        extra = torch.stack(scalars + (imp_weights.sum(), imp_weights.new_full((), float(imp_weights.numel()))))
+        critic_grad_norm, total = clip_and_step(critic_optimizer, max_norm, parameters=critic.parameters(), shards=shards, extra=extra)
+        scalars, ratio = tuple(total[:4].unbind()), total[4] / total[5]
+    value_loss, policy_loss, dist_entropy, ratio_mean = scalars
+    return PPOUpdate(value_loss, critic_grad_norm, policy_loss, dist_entropy, actor_grad_norm, ratio_mean, imp_weights), ratio
 
 
 def ppo_update(actor, critic, actor_optimizer, critic_optimizer, sample, args, value_normalizer=None, update_actor=True, install="replace", workspace=None,
@@ -108,24 +131,21 @@ def ppo_update(actor, critic, actor_optimizer, critic_optimizer, sample, args, v
     install="replace" the critic holds new v_out Parameters, which have no gradient, and the optimiser the old ones, which are stepped unclipped.
     Returns PPOUpdate(value_loss, critic_grad_norm, policy_loss, dist_entropy, actor_grad_norm, ratio_mean, imp_weights): detached device scalars and
     the [rows, 1] importance weights; actor_grad_norm is 0 without update_actor. workspace: minibatch_losses' own.
+    shards: None, or the exchange of a data-parallel learner (gmpe.learner_shards; no DistributedDataParallel around the networks): `sample` is this
+    rank's rows of a minibatch whose other rows lie on the other ranks, with equal parameters everywhere. minibatch_losses(..., shards=shards) gives
+    the rank's contributions (reduce="sum"), the two clip_and_step(..., shards=shards) sum the ranks' gradients in rank order and step every replica
+    alike, and the rank's value_loss, policy_loss, dist_entropy and ratio_mean ride as `extra` on the critic's exchange (which always happens), so the
+    PPOUpdate holds the WHOLE minibatch's scalars and norms, the same bits on every rank; imp_weights stays the rank's own rows. All ranks must make
+    the same calls with the same update_actor. args.use_popart with shards is refused by ppo_losses_popart, in its words.
     The reference's GradScaler is not reproduced: with float32 losses it changes no value unless a gradient overflows, and its step() waits for the
-    device. accumulation_steps != 1 and shards raise NotImplementedError. Nothing here waits for the device."""
-    _no_accumulation("ppo_update", accumulation_steps, shards)
-    res = minibatch_losses(actor, critic, sample, args, value_normalizer, install=install, workspace=workspace)
-    max_norm = getattr(args, "max_grad_norm", 10.0) if getattr(args, "use_max_grad_norm", True) else None
-    actor_optimizer.zero_grad()
-    if update_actor:
-        res.actor_loss.backward()
-    actor_grad_norm = clip_and_step(actor_optimizer, max_norm, parameters=actor.parameters(), step=bool(update_actor))
-    critic_optimizer.zero_grad()
-    (res.value_loss * getattr(args, "value_loss_coef", 1)).backward()
-    critic_grad_norm = clip_and_step(critic_optimizer, max_norm, parameters=critic.parameters())
-    return PPOUpdate(res.value_loss.detach(), critic_grad_norm, res.policy_loss.detach(), res.dist_entropy.detach(), actor_grad_norm,
-                     res.ratio_mean.detach(), res.imp_weights.detach())
+    device. accumulation_steps != 1 and a `shards` that is no such exchange raise NotImplementedError, before anything else is read. Nothing here
+    waits for the device (the exchange is the caller's)."""
+    _refusals("ppo_update", accumulation_steps, shards)
+    return _ppo_update(actor, critic, actor_optimizer, critic_optimizer, sample, args, value_normalizer, update_actor, install, workspace, shards)[0]
 
 
 def train(actor, critic, actor_optimizer, critic_optimizer, buffer, args, value_normalizer=None, update_actor=True, perms=None, *, install="replace",
-          accumulation_steps=1):
+          accumulation_steps=1, shards=None):
     """GR_MAPPO.train (graph_mappo.py:294-359) over a DeviceRolloutBuffer: buffer.normalized_advantages(value_normalizer), then args.ppo_epoch (15) passes
     of the generator the reference chooses — recurrent_generator with args.data_chunk_length (10) under args.use_recurrent_policy (True), else
     naive_recurrent_generator under args.use_naive_recurrent_policy, else feed_forward_generator, each with args.num_mini_batch (1) — and ppo_update
@@ -133,12 +153,16 @@ def train(actor, critic, actor_optimizer, critic_optimizer, buffer, args, value_
     memory; "device": drawn on the device; an int64 tensor is range-checked by the generator, which reads it back: the one wait on this path).
     Returns the reference's train_info: the six sums as float32 device adds in its order (value_loss, policy_loss, dist_entropy, actor_grad_norm,
     critic_grad_norm, ratio = imp_weights.mean()), each divided by ppo_epoch * num_mini_batch — a dict of 0-dim device tensors where the reference
-    calls .item() three times per minibatch. Between call and return nothing is copied to the host (a tensor in perms excepted, see above)."""
-    _no_accumulation("train", accumulation_steps)
+    calls .item() three times per minibatch. Between call and return nothing is copied to the host (a tensor in perms excepted, see above).
+    shards: None, or the exchange of a data-parallel learner: `buffer` is this rank's own, the advantages are normalised with the statistics of all
+    ranks' buffers (normalized_advantages(value_normalizer, shards=shards)), every minibatch is ppo_update(..., shards=shards), and ratio is the sum
+    of all ranks' imp_weights over their count. Every rank must produce the same number of minibatches (the same ppo_epoch and num_mini_batch over
+    buffers that yield as many samples): a rank that stops early leaves the others waiting in the exchange. Each rank draws its own permutation."""
+    _refusals("train", accumulation_steps, shards)
     ppo_epoch, num_mini_batch = int(getattr(args, "ppo_epoch", 15)), int(getattr(args, "num_mini_batch", 1))
     if perms is not None and len(perms) != ppo_epoch:
         raise ValueError("perms must hold one permutation per epoch: %d, not %d" % (ppo_epoch, len(perms)))
-    advantages = buffer.normalized_advantages(value_normalizer)
+    advantages = buffer.normalized_advantages(value_normalizer) if shards is None else buffer.normalized_advantages(value_normalizer, shards=shards)
     info = None
     for epoch in range(ppo_epoch):
         perm = None if perms is None else perms[epoch]
@@ -149,8 +173,8 @@ def train(actor, critic, actor_optimizer, critic_optimizer, buffer, args, value_
         else:
             generator = buffer.feed_forward_generator(advantages, num_mini_batch, perm=perm)
         for sample in generator:
-            u = ppo_update(actor, critic, actor_optimizer, critic_optimizer, sample, args, value_normalizer, update_actor, install)
-            terms = (u.value_loss, u.policy_loss, u.dist_entropy, u.actor_grad_norm, u.critic_grad_norm, u.imp_weights.mean())
+            u, ratio = _ppo_update(actor, critic, actor_optimizer, critic_optimizer, sample, args, value_normalizer, update_actor, install, None, shards)
+            terms = (u.value_loss, u.policy_loss, u.dist_entropy, u.actor_grad_norm, u.critic_grad_norm, u.imp_weights.mean() if ratio is None else ratio)
             info = terms if info is None else tuple(a + b for a, b in zip(info, terms))
     if info is None:
         raise ValueError("train needs at least one minibatch: ppo_epoch = %d" % ppo_epoch)

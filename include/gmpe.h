@@ -751,6 +751,39 @@ typedef struct gmpe_optim_plan {
 int gmpe_optim_workspace_bytes(const gmpe_optim_plan* plan, size_t* bytes_out);
 int gmpe_optim_step(int device, const gmpe_optim_plan* plan, void* stream);
 
+/* The same call for a learner whose minibatch lies in `world` shards (see gmpe_compute_returns_shard, gmpe_ppo_loss_shard): every shard has run its own
+ * backward over its own rows, and the clip and the step work on the SUM over the shards of their gradients — a sum, not a mean: it pairs with
+ * gmpe_ppo_loss_shard, whose shards' gradients add up to the gradient of the whole minibatch. Two phases around one exchange the caller makes, an
+ * all-gather of `local` into `all` (row r = shard r). The tables of all shards must be equal: the same tensors with numel > 0, in the same order.
+ *   GMPE_SHARD_LOCAL  k_opt_pack, one launch per group: the gradients of every tensor of the table, GMPE_OPT_T_IN_NORM or GMPE_OPT_T_STEP, copied back to
+ *                     back in table order into local[0 .. n), n = gmpe_optim_shard_elems(&base). It reads the geometry and the `grad` pointers of
+ *                     `base` and nothing else (param, exp_avg, exp_avg_sq, hypers' values, out, workspace may still be unset), and writes only `local`.
+ *   GMPE_SHARD_APPLY  two launches per group, every group's k_opt_reduce before any group's k_opt_step:
+ *     k_opt_reduce    in place of k_opt_norm. Per element e of the packed order
+ *                         g = (float)( ((double)all[0 * n + e] + (double)all[1 * n + e]) + ... + (double)all[(world - 1) * n + e] )
+ *                     a left fold in shard order that starts at shard 0's value, in double, rounded once (the loads of up to 8 shards are issued before
+ *                     their adds). g is written to the tensor's own grad, so the gradients hold the global gradient afterwards, on every shard the
+ *                     same bits; part[c] = the sum over chunk c of (double)g * (double)g over the GMPE_OPT_T_IN_NORM elements, in k_opt_norm's layout
+ *                     and order.
+ *     k_opt_step      as in gmpe_optim_step, line by line: the norm, the coefficient, the clip of the summed gradient, and Adam on it.
+ *                     APPLY checks `base` as gmpe_optim_step does.
+ * With world = 1 and all == local, LOCAL then APPLY is gmpe_optim_step bit for bit. Because every shard adds the same rows in the same order, parameters,
+ * Adam state and the norm stay bit-identical across replicas; an all-reduce, whose order belongs to its backend, would not promise that. Non-finite
+ * values propagate: a NaN in one shard's gradient is a NaN in every shard's sum. Neither phase allocates, uses atomics or waits for the device.
+ * Refused before any device call, beyond what `base` is refused for: a null plan, an unknown phase, world outside 1 .. GMPE_SHARD_MAX_WORLD, a missing
+ * or misaligned `local` (LOCAL) or `all` (APPLY), local_elems != gmpe_optim_shard_elems(&base), world * local_elems > 2^31 - 1. */
+typedef struct gmpe_optim_shard_plan {
+    gmpe_optim_plan base;               /* as for gmpe_optim_step                                                                      */
+    int32_t phase;                      /* GMPE_SHARD_LOCAL or GMPE_SHARD_APPLY                                                        */
+    int32_t world;                      /* shards, 1 .. GMPE_SHARD_MAX_WORLD                                                           */
+    float* local;                       /* f32 [local_elems] device, 4-byte aligned: written by LOCAL (not read by APPLY)              */
+    const float* all;                   /* f32 [world, local_elems] device, 4-byte aligned: read by APPLY (not read by LOCAL)          */
+    int64_t local_elems;                /* gmpe_optim_shard_elems(&base)                                                               */
+} gmpe_optim_shard_plan;
+/* the elements of `local`: the sum of the tensors' numel; reads what gmpe_optim_workspace_bytes reads */
+int gmpe_optim_shard_elems(const gmpe_optim_plan* plan, int64_t* elems_out);
+int gmpe_optim_step_shard(int device, const gmpe_optim_shard_plan* plan, void* stream);
+
 /* ---- The policy's masked GRU layer (handle-less): RNNLayer.forward (onpolicy/algorithms/utils/rnn.py:23-79) with recurrent_N == 1 ----
  * The layer in front of the action head (GR_Actor) and of the value head (GR_Critic): nn.GRU(D, H) driven step by step with the state multiplied by
  * the step's mask, then nn.LayerNorm(H). All arrays float32, contiguous. For every row k of `rows` independently, t = 0 .. steps-1 (x, masks, features
