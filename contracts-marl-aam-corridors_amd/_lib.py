@@ -199,7 +199,7 @@ class GmpeHeadPlan(C.Structure):
                 ("grad_weight", C.c_void_p), ("grad_bias", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
-GRU_ROW_TILE = 32        # GMPE_GRU_ROW_TILE of include/gmpe.h; tests/gru_lib.py TILE is the third copy — tests/test_gru_host.py compiles against the header and ties the three together
+GRU_ROW_TILE = 32        # GMPE_GRU_ROW_TILE of include/gmpe.h; tests/gru_lib.py TILE is the third copy — tests/test_abi_host.py compiles against the header, tests/test_gru_host.py ties the three together
 
 
 class GmpeGruPlan(C.Structure):
@@ -212,7 +212,7 @@ class GmpeGruPlan(C.Structure):
                 ("grad_ln_weight", C.c_void_p), ("grad_ln_bias", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
-MLP_ROW_TILE, MLP_MAX_PARTS, MLP_MAX_IN, MLP_MAX_LAYERS = 32, 4, 256, 3      # GMPE_MLP_* of include/gmpe.h; tests/test_mlp_host.py compiles against the header
+MLP_ROW_TILE, MLP_MAX_PARTS, MLP_MAX_IN, MLP_MAX_LAYERS = 32, 4, 256, 3      # GMPE_MLP_* of include/gmpe.h; tests/test_abi_host.py compiles against the header
 MLP_RELU, MLP_TANH = 0, 1
 
 
@@ -231,7 +231,7 @@ class GmpeMlpPlan(C.Structure):
                 ("grad_features", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
-# GMPE_GNN_* of include/gmpe.h; tests/test_gnn_host.py compiles against the header
+# GMPE_GNN_* of include/gmpe.h; tests/test_abi_host.py compiles against the header
 GNN_HIDDEN, GNN_MAX_NODES, GNN_MAX_HEADS, GNN_MAX_CONVS, GNN_MAX_EMBED_LAYERS = 16, 64, 4, 3, 2
 GNN_MAX_FEATS, GNN_MAX_EMBEDDINGS, GNN_MAX_EMBEDDING_SIZE = 16, 16, 8
 GNN_RELU, GNN_TANH = 0, 1
@@ -258,7 +258,7 @@ class GmpeGnnPlan(C.Structure):
         ("workspace_bytes", C.c_size_t)]
 
 
-# GMPE_OPT_* of include/gmpe.h; tests/test_optim_host.py compiles against the header
+# GMPE_OPT_* of include/gmpe.h; tests/test_abi_host.py compiles against the header
 OPT_MAX_TENSORS, OPT_MAX_HYPERS, OPT_CHUNK, OPT_MAX_PLAN_TENSORS, OPT_MAX_NUMEL = 64, 8, 1024, 4096, 1 << 30
 OPT_CLIP, OPT_STEP = 1, 2
 OPT_T_IN_NORM, OPT_T_STEP = 1, 2

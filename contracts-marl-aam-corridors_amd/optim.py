@@ -21,7 +21,7 @@ from . import _lib
 from .engine import _need_cuda, _ordinal, _stream_of, _workspace
 
 CHUNK = _lib.OPT_CHUNK
-_TENSOR = struct.Struct("@PPPPqii")                 # gmpe_optim_tensor; tests/test_optim_host.py holds its size and _lib's layout to the header
+_TENSOR = struct.Struct("@PPPPqii")                 # gmpe_optim_tensor; tests/test_optim_host.py holds its size, tests/test_abi_host.py _lib's layout to the header
 _UNSUPPORTED = ("amsgrad", "maximize", "capturable", "differentiable", "decoupled_weight_decay")
 
 

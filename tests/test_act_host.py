@@ -7,13 +7,12 @@
 (e) the action stream's draws are not the env stream's."""
 import ctypes as C
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import abi_lib
 import gmpe
 import act_lib as AL
 import oracle_lib as ol
@@ -68,28 +67,17 @@ def test_fixture_covers_the_action_counts_availability_and_stop_rows():
 # ---------------------------------------------------------------------------------------------- (b)
 def test_symbol_is_exported_and_the_plan_matches_the_header():
     lib = _lib.load()
-    assert "gmpe_act_sample" in _lib.SYMBOLS and hasattr(lib, "gmpe_act_sample")
-    hdr = open(os.path.join(ROOT, "include", "gmpe.h")).read()
-    body = hdr[hdr.index("typedef struct gmpe_act_plan {"):hdr.index("} gmpe_act_plan;")]
-    names = []
-    for line in body.splitlines()[1:]:
-        line = line.split("/*")[0].strip()
-        if line:
-            names += [n.strip(" *") for n in re.sub(r"^(const\s+)?\w+\*?\s+", "", line.rstrip(";")).split(",")]
-    assert names == [f[0] for f in _lib.GmpeActPlan._fields_]
+    assert "gmpe_act_sample" in _lib.SYMBOLS and "gmpe_act_sample" in abi_lib.exported()
+    assert abi_lib.layout(_lib.GmpeActPlan) == abi_lib.mirror_layout(_lib.GmpeActPlan)      # every field by its header name, at the header's offset
     assert C.sizeof(_lib.GmpeActPlan) == 8 + 6 * 4 + 3 * 8 + 8 * 8
-    assert "#define GMPE_ABI_VERSION 3" in hdr and lib.gmpe_abi_version() == 3
-    assert "int gmpe_act_sample(int device, const gmpe_act_plan* plan, void* stream);" in hdr
+    assert abi_lib.constant("GMPE_ABI_VERSION") == 3 and lib.gmpe_abi_version() == 3
+    assert ("int", "gmpe_act_sample", ["int", "const gmpe_act_plan*", "void*"]) in abi_lib.prototypes()
     assert gmpe.sample_actions is gmpe.act.sample_actions
 
 
 def test_new_kernels_use_no_scratch():
-    csrc = os.path.join(ROOT, "contracts-marl-aam-corridors_amd", "csrc")
-    subprocess.run(["make", "-s", "-C", csrc, "build/ru_act.txt"], check=True, capture_output=True, timeout=600)
-    txt = open(os.path.join(csrc, "build", "ru_act.txt")).read()
-    names = re.findall(r"Function Name: (\S*k_act\S*)", txt)
-    scratch = re.findall(r"Function Name: \S*k_act\S*.*?ScratchSize \[bytes/lane\]: (\d+)", txt, flags=re.S)
-    assert len(names) == 3 and len(scratch) == 3 and set(scratch) == {"0"}        # the 16-byte and the 4-byte row kernel, the counter's one thread
+    scratch = abi_lib.scratch("act", "k_act")
+    assert len(scratch) == 3 and set(scratch.values()) == {0}                     # the 16-byte and the 4-byte row kernel, the counter's one thread
 
 
 def _plan(**over):

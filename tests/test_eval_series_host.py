@@ -4,9 +4,7 @@ NumPy restatement (tests/eval_series_lib.py) against six cheap wrong variants on
 and time-limit episode ends on the CPU oracle."""
 import ctypes as C
 import os
-import subprocess
 import sys
-import tempfile
 import types
 
 import numpy as np
@@ -17,6 +15,7 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
 
+import abi_lib  # noqa: E402
 import eval_lib as EL  # noqa: E402
 import eval_series_lib as SL  # noqa: E402
 import gmpe  # noqa: E402
@@ -29,31 +28,18 @@ FIELDS = ["num_envs", "num_agents", "num_steps", "num_episodes", "n_actions", "r
 
 
 def test_symbol_is_exported_and_bound():
-    lib = _lib.load()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH]).decode()
-    assert "gmpe_episode_record_series" in _lib.SYMBOLS and hasattr(lib, "gmpe_episode_record_series")
-    assert " T gmpe_episode_record_series" in out
-    assert lib.gmpe_abi_version() == 3 and gmpe.config.ABI_VERSION == 3          # an added entry point: the ABI version stays
+    assert "gmpe_episode_record_series" in _lib.SYMBOLS and "gmpe_episode_record_series" in abi_lib.exported()
+    assert _lib.load().gmpe_abi_version() == 3 and gmpe.config.ABI_VERSION == 3  # an added entry point: the ABI version stays
 
 
 def test_plan_layout_matches_the_c_header():
     P = _lib.GmpeEpisodeSeriesPlan
     assert [f for f, _ in P._fields_] == FIELDS
-    src = "#include <stdio.h>\n#include <stddef.h>\n#include \"gmpe.h\"\nint main(void) {\n  printf(\"%zu\\n\", sizeof(gmpe_episode_series_plan));\n"
-    src += "".join("  printf(\"%%zu %%zu\\n\", offsetof(gmpe_episode_series_plan, %s), sizeof(((gmpe_episode_series_plan*)0)->%s));\n" % (f, f)
-                   for f in FIELDS)
-    src += "  return 0; }\n"
-    with tempfile.TemporaryDirectory() as d:
-        open(os.path.join(d, "l.c"), "w").write(src)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", os.path.join(d, "l"), os.path.join(d, "l.c")])
-        out = [int(x) for x in subprocess.check_output([os.path.join(d, "l")]).split()]
-    assert out[0] == C.sizeof(P) == 6 * 4 + 12 * 8
-    for i, f in enumerate(FIELDS):
-        d = getattr(P, f)
-        assert out[1 + 2 * i:3 + 2 * i] == [d.offset, d.size], f
+    size, fields = abi_lib.layout(P)
+    assert (size, fields) == abi_lib.mirror_layout(P) and size == 6 * 4 + 12 * 8
     # the existing record plan is untouched
-    R = _lib.GmpeEpisodeRecordPlan
-    assert C.sizeof(R) == 6 * 4 + 10 * 8 and R.reward.offset == 24 and R.rnn_states.offset == 24 + 9 * 8
+    size, fields = abi_lib.layout(_lib.GmpeEpisodeRecordPlan)
+    assert size == 6 * 4 + 10 * 8 and fields["reward"][0] == 24 and fields["rnn_states"][0] == 24 + 9 * 8
 
 
 FAKE = 0x1000      # an aligned non-null address: every plan below is refused before it could be used

@@ -7,14 +7,13 @@
 import ctypes as C
 import os
 import re
-import subprocess
-import tempfile
 import types
 
 import numpy as np
 import pytest
 import torch
 
+import abi_lib
 import gmpe
 import gnn_lib as G
 from gmpe import _lib
@@ -155,36 +154,17 @@ def test_the_restatement_against_the_references_gnnbase():
 
 
 # ---------------------------------------------------------------------------------------------- (b)
-def _probe(struct, fields, extra=""):
-    src = "#include <stdio.h>\n#include <stddef.h>\n#include \"gmpe.h\"\nint main(void) {\n  printf(\"%%zu\\n\", sizeof(%s));\n" % struct
-    src += "".join("  printf(\"%%zu %%zu\\n\", offsetof(%s, %s), sizeof(((%s*)0)->%s));\n" % (struct, f, struct, f) for f in fields)
-    src += extra + "  return 0; }\n"
-    with tempfile.TemporaryDirectory() as t:
-        open(os.path.join(t, "l.c"), "w").write(src)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", os.path.join(t, "l"), os.path.join(t, "l.c")])
-        return [int(x) for x in subprocess.check_output([os.path.join(t, "l")]).split()]
-
-
 CONSTS = ("HIDDEN", "MAX_NODES", "MAX_HEADS", "MAX_CONVS", "MAX_EMBED_LAYERS", "MAX_FEATS", "MAX_EMBEDDINGS", "MAX_EMBEDDING_SIZE", "RELU", "TANH", "NODE", "MEAN",
           "MAX", "ADD")
 
 
 def test_symbols_are_exported_and_the_plan_matches_the_header():
     lib = _lib.load()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH]).decode()
-    for s in ("gmpe_gnn_workspace_bytes", "gmpe_gnn_forward", "gmpe_gnn_backward"):
-        assert s in _lib.SYMBOLS and hasattr(lib, s) and " T %s\n" % s in out
+    assert {"gmpe_gnn_workspace_bytes", "gmpe_gnn_forward", "gmpe_gnn_backward"} <= set(_lib.SYMBOLS) & abi_lib.exported()
     assert lib.gmpe_abi_version() == 3 and gmpe.config.ABI_VERSION == 3          # added entry points: the ABI version stays
-    consts = "  printf(\"%s\\n\", %s);\n" % (" ".join(["%d"] * len(CONSTS)), ", ".join("GMPE_GNN_" + c for c in CONSTS))
-    for name, T, extra in (("gmpe_gnn_conv", _lib.GmpeGnnConv, ""), ("gmpe_gnn_plan", _lib.GmpeGnnPlan, consts)):
-        fields = [f for f, _ in T._fields_]
-        got = _probe(name, fields, extra)
-        assert got[0] == C.sizeof(T), name
-        for i, f in enumerate(fields):
-            fd = getattr(T, f)
-            assert got[1 + 2 * i:3 + 2 * i] == [fd.offset, fd.size], (name, f)
-        if extra:
-            assert got[-len(CONSTS):] == [getattr(_lib, "GNN_" + c) for c in CONSTS]
+    for T in (_lib.GmpeGnnConv, _lib.GmpeGnnPlan):
+        assert abi_lib.layout(T) == abi_lib.mirror_layout(T), T
+    assert [abi_lib.constant("GMPE_GNN_" + c) for c in CONSTS] == [getattr(_lib, "GNN_" + c) for c in CONSTS]
     assert C.sizeof(_lib.GmpeGnnConv) == 18 * 8 and C.sizeof(_lib.GmpeGnnPlan) == 8 + 16 * 4 + 2 * 8 + 8 * 8 + 4 * 8 + 5 * 8 + 4 * 8 + 3 * 144 + 4 * 8
     assert gmpe.gnn_base is gmpe.gnn.gnn_base and gmpe.gnn_workspace_bytes is gmpe.gnn.gnn_workspace_bytes
 
@@ -419,11 +399,8 @@ def test_python_layer_refuses_what_it_does_not_support():
 
 # ---------------------------------------------------------------------------------------------- (c)
 def test_no_kernel_of_the_file_uses_scratch_memory():
-    subprocess.run(["make", "-s", "-C", CSRC, "build/ru_gnn.txt"], check=True, capture_output=True, timeout=600)
-    txt = open(os.path.join(CSRC, "build", "ru_gnn.txt")).read()
-    names = re.findall(r"Function Name: (\S+)", txt)
-    scratch = re.findall(r"Function Name: \S*k_gnn\S*.*?ScratchSize \[bytes/lane\]: (\d+)", txt, flags=re.S)
-    assert len(names) == len(scratch) == 4 and all(s == "0" for s in scratch), (names, scratch)     # forward, the two backward halves, finish
+    assert "gnn" in abi_lib.ru_objects()                                                            # `make resource-usage` holds it
+    names, scratch = list(abi_lib.kernels("gnn")), list(abi_lib.scratch("gnn", "k_gnn").values())
+    assert len(names) == len(scratch) == 4 and all(s == 0 for s in scratch), (names, scratch)       # forward, the two backward halves, finish
     for k in ("k_gnn_fwd", "k_gnn_bwd_conv", "k_gnn_bwd_embed", "k_gnn_finish"):
         assert any(k in n for n in names), k
-    assert "$(B)/ru_gnn.txt" in open(os.path.join(CSRC, "Makefile")).read().split("RUFILES =")[1].split("\n")[0]      # and `make resource-usage` holds it

@@ -5,15 +5,13 @@
 (c) the compiler's resource report of csrc/gmpe_gru.hip shows no scratch memory."""
 import ctypes as C
 import os
-import re
-import subprocess
-import tempfile
 import types
 
 import numpy as np
 import pytest
 import torch
 
+import abi_lib
 import gmpe
 import gru_lib as G
 from gmpe import _lib
@@ -89,24 +87,11 @@ def test_backward64_is_the_derivative_of_forward64():
 # ---------------------------------------------------------------------------------------------- (b)
 def test_symbols_are_exported_and_the_plan_matches_the_header():
     lib = _lib.load()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH]).decode()
-    for s in ("gmpe_gru_workspace_bytes", "gmpe_gru_forward", "gmpe_gru_backward"):
-        assert s in _lib.SYMBOLS and hasattr(lib, s) and " T %s\n" % s in out
-    assert lib.gmpe_abi_version() == 3 and gmpe.config.ABI_VERSION == 3          # added entry points: the ABI version stays
-    assert re.search(r"#define\s+GMPE_ABI_VERSION\s+3\b", open(os.path.join(ROOT, "include", "gmpe.h")).read())
+    assert {"gmpe_gru_workspace_bytes", "gmpe_gru_forward", "gmpe_gru_backward"} <= set(_lib.SYMBOLS) & abi_lib.exported()
+    assert lib.gmpe_abi_version() == 3 and gmpe.config.ABI_VERSION == 3 == abi_lib.constant("GMPE_ABI_VERSION")   # added entry points: the ABI version stays
     PP = _lib.GmpeGruPlan
-    fields = [f for f, _ in PP._fields_]
-    src = "#include <stdio.h>\n#include <stddef.h>\n#include \"gmpe.h\"\nint main(void) {\n  printf(\"%zu %d\\n\", sizeof(gmpe_gru_plan), GMPE_GRU_ROW_TILE);\n"
-    src += "".join("  printf(\"%%zu %%zu\\n\", offsetof(gmpe_gru_plan, %s), sizeof(((gmpe_gru_plan*)0)->%s));\n" % (f, f) for f in fields)
-    src += "  return 0; }\n"
-    with tempfile.TemporaryDirectory() as t:
-        open(os.path.join(t, "l.c"), "w").write(src)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", os.path.join(t, "l"), os.path.join(t, "l.c")])
-        got = [int(x) for x in subprocess.check_output([os.path.join(t, "l")]).split()]
-    assert got[0] == C.sizeof(PP) == 2 * 8 + 2 * 4 + 8 + 22 * 8 + 8 and got[1] == _lib.GRU_ROW_TILE
-    for i, f in enumerate(fields):
-        fd = getattr(PP, f)
-        assert got[2 + 2 * i:4 + 2 * i] == [fd.offset, fd.size], f
+    assert abi_lib.layout(PP) == abi_lib.mirror_layout(PP) and C.sizeof(PP) == 2 * 8 + 2 * 4 + 8 + 22 * 8 + 8
+    assert abi_lib.constant("GMPE_GRU_ROW_TILE") == _lib.GRU_ROW_TILE
 
 
 def test_workspace_bytes():
@@ -252,11 +237,7 @@ def test_python_layer_refuses_what_it_does_not_support():
 
 # ---------------------------------------------------------------------------------------------- (c)
 def test_no_kernel_of_the_file_uses_scratch_memory():
-    csrc = os.path.join(ROOT, "contracts-marl-aam-corridors_amd", "csrc")
-    subprocess.run(["make", "-s", "-C", csrc, "build/ru_gru.txt"], check=True, capture_output=True, timeout=600)
-    txt = open(os.path.join(csrc, "build", "ru_gru.txt")).read()
-    names = re.findall(r"Function Name: (\S+)", txt)
-    scratch = re.findall(r"Function Name: \S*k_gru\S*.*?ScratchSize \[bytes/lane\]: (\d+)", txt, flags=re.S)
-    assert len(names) == len(scratch) == 5 and all(s == "0" for s in scratch), (names, scratch)     # forward (two plans), bptt, wgrad, finish
+    names, scratch = list(abi_lib.kernels("gru")), list(abi_lib.scratch("gru", "k_gru").values())
+    assert len(names) == len(scratch) == 5 and all(s == 0 for s in scratch), (names, scratch)       # forward (two plans), bptt, wgrad, finish
     for k in ("k_gru_fwd", "k_gru_bptt", "k_gru_wgrad", "k_gru_finish"):
         assert any(k in n for n in names), k

@@ -5,22 +5,17 @@ gmpe.policy), no GPU:
 (b) the exported symbols, the plan's layout against the C header, the workspace size against the restated geometry, the refusals of both layers;
 (c) the compiler's resource report of csrc/gmpe_head.hip shows no scratch memory."""
 import ctypes as C
-import os
-import re
-import subprocess
-import tempfile
 import types
 
 import numpy as np
 import pytest
 import torch
 
+import abi_lib
 import gmpe
 import head_lib as HL
 from gmpe import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "contracts-marl-aam-corridors_amd", "csrc")
 MB = 1 << 20
 
 
@@ -68,31 +63,13 @@ def test_the_parameter_reader_reads_the_three_forms():
 
 
 # ---------------------------------------------------------------------------------------------- (b)
-def _probe(struct, fields):
-    src = "#include <stdio.h>\n#include <stddef.h>\n#include \"gmpe.h\"\nint main(void) {\n  printf(\"%%zu\\n\", sizeof(%s));\n" % struct
-    src += "".join("  printf(\"%%zu %%zu\\n\", offsetof(%s, %s), sizeof(((%s*)0)->%s));\n" % (struct, f, struct, f) for f in fields)
-    src += "  printf(\"%d %d\\n\", GMPE_PPO_MAX_ACTIONS, GMPE_ABI_VERSION);\n  return 0; }\n"
-    with tempfile.TemporaryDirectory() as t:
-        open(os.path.join(t, "l.c"), "w").write(src)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", os.path.join(t, "l"), os.path.join(t, "l.c")])
-        return [int(x) for x in subprocess.check_output([os.path.join(t, "l")]).split()]
-
-
 def test_symbols_are_exported_and_the_plan_matches_the_header():
     lib = _lib.load()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH]).decode()
-    for s in ("gmpe_head_workspace_bytes", "gmpe_head_forward", "gmpe_head_backward", "gmpe_act_head"):
-        assert s in _lib.SYMBOLS and hasattr(lib, s) and " T %s\n" % s in out
+    assert {"gmpe_head_workspace_bytes", "gmpe_head_forward", "gmpe_head_backward", "gmpe_act_head"} <= set(_lib.SYMBOLS) & abi_lib.exported()
     assert lib.gmpe_abi_version() == 3 and gmpe.config.ABI_VERSION == 3          # added entry points: the ABI version stays
-    fields = [f for f, _ in _lib.GmpeHeadPlan._fields_]
-    got = _probe("gmpe_head_plan", fields)
-    assert got[0] == C.sizeof(_lib.GmpeHeadPlan) == 8 + 2 * 4 + 10 * 8
-    for i, f in enumerate(fields):
-        fd = getattr(_lib.GmpeHeadPlan, f)
-        assert got[1 + 2 * i:3 + 2 * i] == [fd.offset, fd.size], f
-    assert got[-2:] == [64, 3] and gmpe.head.MAX_ACTIONS == 64 and gmpe.head.HIDDEN == 64
-    hdr = open(os.path.join(ROOT, "include", "gmpe.h")).read()
-    assert "int gmpe_act_head(int device, const gmpe_act_plan* act_plan, const gmpe_head_plan* head_plan, void* stream);" in hdr
+    assert abi_lib.layout(_lib.GmpeHeadPlan) == abi_lib.mirror_layout(_lib.GmpeHeadPlan) and C.sizeof(_lib.GmpeHeadPlan) == 8 + 2 * 4 + 10 * 8
+    assert [abi_lib.constant("GMPE_PPO_MAX_ACTIONS"), abi_lib.constant("GMPE_ABI_VERSION")] == [64, 3] and gmpe.head.MAX_ACTIONS == 64 and gmpe.head.HIDDEN == 64
+    assert ("int", "gmpe_act_head", ["int", "const gmpe_act_plan*", "const gmpe_head_plan*", "void*"]) in abi_lib.prototypes()
     assert gmpe.action_logits is gmpe.head.action_logits and gmpe.act_head is gmpe.head.act_head
     assert gmpe.head_workspace_bytes is gmpe.head.head_workspace_bytes
     for name in ("actor_forward", "critic_forward", "minibatch_losses", "evaluator_act"):
@@ -269,11 +246,8 @@ def test_python_layer_refuses_what_it_does_not_support():
 
 # ---------------------------------------------------------------------------------------------- (c)
 def test_no_kernel_of_the_file_uses_scratch_memory():
-    subprocess.run(["make", "-s", "-C", CSRC, "build/ru_head.txt"], check=True, capture_output=True, timeout=600)
-    txt = open(os.path.join(CSRC, "build", "ru_head.txt")).read()
-    names = re.findall(r"Function Name: (\S+)", txt)
-    scratch = re.findall(r"Function Name: \S*k_head\S*.*?ScratchSize \[bytes/lane\]: (\d+)", txt, flags=re.S)
-    assert len(names) == len(scratch) == 5 and all(s == "0" for s in scratch), (names, scratch)     # forward, the fused rollout form, backward's three
+    assert "head" in abi_lib.ru_objects()                                                           # `make resource-usage` holds it
+    names, scratch = list(abi_lib.kernels("head")), list(abi_lib.scratch("head", "k_head").values())
+    assert len(names) == len(scratch) == 5 and all(s == 0 for s in scratch), (names, scratch)       # forward, the fused rollout form, backward's three
     for k in ("k_head_fwd", "k_head_act", "k_head_bwd_rows", "k_head_wgrad", "k_head_finish"):
         assert any(k in n for n in names), k
-    assert "$(B)/ru_head.txt" in open(os.path.join(CSRC, "Makefile")).read().split("RUFILES =")[1].split("\n")[0]      # and `make resource-usage` holds it

@@ -1,27 +1,20 @@
-"""CPU-side tests: C-ABI surface, config POD layout, host mirrors of the reference interface,
-sharding + gather (gloo, world_size 2), oracle self-consistency. No GPU compute."""
+"""CPU-side tests: the C entry points' refusals, host mirrors of the reference interface, sharding + gather (gloo, world_size 2), oracle
+self-consistency, the fused kernel's scratch allow-list. No GPU compute. (The C-ABI surface and the struct layouts: tests/test_abi_host.py.)"""
 import ctypes as C
 import os
 import re
 import subprocess
 import sys
-import tempfile
 
 import numpy as np
 import pytest
 
+import abi_lib
 import gmpe
 from gmpe import config as gcfg
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HDR = os.path.join(ROOT, "include", "gmpe.h")
 SO = os.path.join(ROOT, "contracts-marl-aam-corridors_amd", "libgmpe.so")
-
-
-def _declared_functions():
-    txt = open(HDR).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(gmpe_[a-z_0-9]+)\s*\(", txt)))
 
 
 def _load_so():
@@ -32,50 +25,11 @@ def _load_so():
     return C.CDLL(SO)
 
 
-def test_library_exports_every_declared_symbol():
-    lib = _load_so()
-    fns = _declared_functions()
-    assert len(fns) >= 15
-    for f in fns:
-        assert hasattr(lib, f), "libgmpe.so does not export %s declared in include/gmpe.h" % f
-    assert lib.gmpe_abi_version() == gcfg.ABI_VERSION
-
-
-def test_binding_symbol_list_matches_header():
-    from gmpe import _lib
-    assert sorted(_lib.SYMBOLS) == _declared_functions()
-
-
 def test_config_pod_layout_matches_c_header():
-    src = r'''
-    #include <stdio.h>
-    #include <stddef.h>
-    #include "gmpe.h"
-    int main(void) {
-      printf("%zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(gmpe_config), offsetof(gmpe_config, seed),
-             offsetof(gmpe_config, world_size), offsetof(gmpe_config, dt), offsetof(gmpe_config, ang_rate_opt),
-             offsetof(gmpe_config, sensitivity), offsetof(gmpe_config, walls), sizeof(gmpe_outputs));
-      printf("%d %d\n", (int)GMPE_F_ERROR_FLAGS, (int)GMPE_F_COUNT);
-      printf("%zu %zu %zu %zu %zu\n", offsetof(gmpe_config, graph_feat_type), offsetof(gmpe_config, agent_size), offsetof(gmpe_config, action_force_scale),
-             sizeof(gmpe_rollout), sizeof(gmpe_tuning));
-      printf("%zu\n", offsetof(gmpe_config, formation_type));
-      return 0; }'''
-    with tempfile.TemporaryDirectory() as td:
-        cpath = os.path.join(td, "t.c")
-        open(cpath, "w").write(src)
-        exe = os.path.join(td, "t")
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", exe, cpath])
-        out = subprocess.check_output([exe]).decode().split()
-    G = gcfg.GmpeConfig
-    from gmpe._lib import GmpeOutputs
-    assert [int(x) for x in out[:8]] == [C.sizeof(G), G.seed.offset, G.world_size.offset, G.dt.offset,
-                                         G.ang_rate_opt.offset, G.sensitivity.offset, G.walls.offset,
-                                         C.sizeof(GmpeOutputs)]
-    assert int(out[8]) == gcfg.FIELDS["error_flags"][0] and int(out[9]) == len(gcfg.FIELDS)
-    from gmpe._lib import GmpeRollout, GmpeTuning
-    assert [int(x) for x in out[10:15]] == [G.graph_feat_type.offset, G.agent_size.offset, G.action_force_scale.offset,
-                                            C.sizeof(GmpeRollout), C.sizeof(GmpeTuning)]
-    assert int(out[15]) == G.formation_type.offset                       # ABI 3
+    from gmpe._lib import GmpeOutputs, GmpeRollout, GmpeTuning
+    for cls in (gcfg.GmpeWall, gcfg.GmpeConfig, GmpeOutputs, GmpeRollout, GmpeTuning):      # the engine's own PODs, every field
+        assert abi_lib.layout(cls) == abi_lib.mirror_layout(cls), cls
+    assert abi_lib.constant("GMPE_F_ERROR_FLAGS") == gcfg.FIELDS["error_flags"][0] and abi_lib.constant("GMPE_F_COUNT") == len(gcfg.FIELDS)
 
 
 def test_create_without_gpu_fails_loudly():
@@ -587,25 +541,12 @@ def test_oracle_under_sanitizers():
     assert out.stdout.count("checksum") == 5 and "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr
 
 
-_RU = []
-
-
-def _resource_usage():
-    """`make resource-usage`: the compiler's register / scratch report of every kernel instantiation (made once per session)."""
-    if not _RU:
-        out = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "contracts-marl-aam-corridors_amd", "csrc"), "resource-usage"],
-                             capture_output=True, text=True, timeout=600)
-        _RU.append(out.stdout + out.stderr)
-    return _RU[0]
-
-
 def test_kernels_do_not_spill():
     """Every instantiation of the fused kernel must fit the register file (a spill costs 3x on this kernel:
     the inlined per-agent code is large and a non-inlined closure silently moves its state to scratch)."""
-    txt = _resource_usage()
-    names = re.findall(r"Function Name: (\S*k_env\S*)", txt)
-    scratch = re.findall(r"Function Name: \S*k_env\S*.*?ScratchSize \[bytes/lane\]: (\d+)", txt, flags=re.S)
-    assert len(names) >= 96 and len(scratch) == len(names)      # 6 scenario variants x (3 tile shapes x 3 exact sizes + the steady-state one + 3 rollout ones)
+    kenv = [nx for o in abi_lib.ru_objects() for nx in abi_lib.scratch(o, "k_env").items()]
+    names, scratch = [n for n, _ in kenv], [x for _, x in kenv]
+    assert len(names) >= 96                                     # 6 scenario variants x (3 tile shapes x 3 exact sizes + the steady-state one + 3 rollout ones)
     # Zero everywhere except two exact-size instantiations that sit at their 128-VGPR cap with a few dwords in cold paths and were
     # measured FASTER on one box than their spill-free alternatives (profiles/README.md): the July step kernels (3 dwords; c3 closed
     # loop 26.27 us vs 26.95 run-time sizes / 27.05 at three waves per SIMD) and navigation_graph's rollout kernel (5 dwords; c2
@@ -624,7 +565,7 @@ def test_every_instantiation_has_a_variant_row():
     scenario variant: the tube scenarios (SC 2..5) replay the reference's own rollouts through it, navigation_graph (SC 0, 1 with walls: no
     reference rollout exists) is compared with the oracle through it. A new instantiation without a row fails here."""
     import test_gpu_reference_variants as V
-    inst = sorted({tuple(int(q) for q in m) for m in re.findall(r"k_envILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)E", _resource_usage())})
+    inst = sorted({tuple(int(q) for q in m) for m in re.findall(r"k_envILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)E", " ".join(n for ks in abi_lib.resource_usage().values() for n in ks))})
     assert len(inst) == 96, len(inst)                       # 6 scenario variants x 16
     for sc in range(6):
         rows = sorted((b, ap, fl, gc) for b, ap, sc2, fl, gc in inst if sc2 == sc)
@@ -713,7 +654,7 @@ def test_bench_dump_outputs_is_bounded_typed_and_reproducible(tmp_path):
 
 
 def test_plain_c_consumer_of_the_abi_compiles_and_links(tmp_path):
-    """examples/c_abi_consumer.c — a consumer that is neither Python nor torch — builds with gcc -std=c11 -Wall -Werror against include/gmpe.h and links against
+    """examples/c_abi_consumer.c — a consumer that is neither Python nor torch — builds as strict C11 (tests/c_consumer_build.py) against include/gmpe.h and links against
     libgmpe.so + the HIP runtime (it RUNS in tests/test_gpu_c_consumer.py)."""
     from c_consumer_build import build_c_consumer
     exe = build_c_consumer(str(tmp_path))

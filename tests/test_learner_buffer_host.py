@@ -5,14 +5,13 @@ import argparse
 import ctypes as C
 import glob
 import os
-import subprocess
-import tempfile
 import types
 
 import numpy as np
 import pytest
 import torch
 
+import abi_lib
 import gmpe
 from gmpe import _lib
 from gmpe.rollout import LEARNER_FIELDS, DeviceRolloutBuffer, learner_storage_spec
@@ -111,28 +110,13 @@ def test_insert_keywords_refuse_fields_the_buffer_does_not_keep():
 
 
 def test_new_symbol_is_exported_and_bound():
-    lib = _lib.load()
-    assert "gmpe_insert_learner" in _lib.SYMBOLS and hasattr(lib, "gmpe_insert_learner")
-    out = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH]).decode()
-    assert " T gmpe_insert_learner" in out
+    assert "gmpe_insert_learner" in _lib.SYMBOLS and "gmpe_insert_learner" in abi_lib.exported()      # bound: tests/test_abi_host.py, for every symbol
 
 
 def test_learner_plan_layout_matches_c_header():
-    fields = [f[0] for f in _lib.GmpeLearnerPlan._fields_]
-    src = "#include <stdio.h>\n#include <stddef.h>\n#include \"gmpe.h\"\nint main(void) {\n  printf(\"%zu\\n\", sizeof(gmpe_learner_plan));\n"
-    src += "".join("  printf(\"%%zu\\n\", offsetof(gmpe_learner_plan, %s));\n" % f for f in fields)
-    src += "  printf(\"%d\\n\", GMPE_ABI_VERSION);\n  return 0; }\n"
-    with tempfile.TemporaryDirectory() as td:
-        cpath, exe = os.path.join(td, "t.c"), os.path.join(td, "t")
-        open(cpath, "w").write(src)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", exe, cpath])
-        out = [int(x) for x in subprocess.check_output([exe]).decode().split()]
-    P = _lib.GmpeLearnerPlan
-    assert out[0] == C.sizeof(P)
-    assert out[1:-1] == [getattr(P, f).offset for f in fields]
-    assert out[-1] == 3                                                                    # additive: the ABI version is unchanged
+    assert abi_lib.layout(_lib.GmpeLearnerPlan) == abi_lib.mirror_layout(_lib.GmpeLearnerPlan)
     from gmpe.config import ABI_VERSION
-    assert ABI_VERSION == 3
+    assert abi_lib.constant("GMPE_ABI_VERSION") == 3 == ABI_VERSION                          # additive: the ABI version is unchanged
 
 
 def _plan(**kw):

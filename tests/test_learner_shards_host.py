@@ -7,7 +7,6 @@ gmpe.ppo_losses_begin / _finish, gmpe.learner_shards), no GPU:
 (d) every argument error of the two-step wrappers, raised before anything is launched."""
 import ctypes as C
 import os
-import subprocess
 import tempfile
 import types
 
@@ -15,49 +14,31 @@ import numpy as np
 import pytest
 import torch
 
+import abi_lib
 import gmpe
 import learner_shards_lib as LS
 import ppo_loss_lib as P
 import returns_lib as R
 from gmpe import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
 
 # ---------------------------------------------------------------------------------------------- (a)
-def _layout(struct, fields, extra=()):
-    src = "#include <stdio.h>\n#include <stddef.h>\n#include \"gmpe.h\"\nint main(void) {\n  printf(\"%%zu\\n\", sizeof(%s));\n" % struct
-    src += "".join("  printf(\"%%zu %%zu\\n\", offsetof(%s, %s), sizeof(((%s*)0)->%s));\n" % (struct, f, struct, f) for f in fields)
-    src += "".join("  printf(\"%%ld\\n\", (long)(%s));\n" % e for e in extra) + "  return 0; }\n"
-    with tempfile.TemporaryDirectory() as t:
-        open(os.path.join(t, "l.c"), "w").write(src)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", os.path.join(t, "l"), os.path.join(t, "l.c")])
-        return [int(x) for x in subprocess.check_output([os.path.join(t, "l")]).split()]
-
-
 @pytest.mark.parametrize("cname,plan,base", [("gmpe_returns_shard_plan", "GmpeReturnsShardPlan", "GmpeReturnsPlan"),
                                              ("gmpe_ppo_loss_shard_plan", "GmpePpoLossShardPlan", "GmpePpoLossPlan")])
 def test_shard_plans_match_the_header(cname, plan, base):
     PP, BP = getattr(_lib, plan), getattr(_lib, base)
-    fields = [f for f, _ in PP._fields_]
-    assert fields == ["base", "phase", "world", "local", "all"]
-    got = _layout(cname, fields, ("sizeof(%s)" % cname.replace("_shard", ""), "GMPE_SHARD_LOCAL", "GMPE_SHARD_APPLY", "GMPE_SHARD_MAX_WORLD",
-                                  "GMPE_RETURNS_SHARD_STATS", "GMPE_PPO_SHARD_STATS", "GMPE_ABI_VERSION"))
-    assert got[0] == C.sizeof(PP) == C.sizeof(BP) + 4 + 4 + 8 + 8                 # the existing plan by value, then the four new fields
-    for i, f in enumerate(fields):
-        fd = getattr(PP, f)
-        assert got[1 + 2 * i:3 + 2 * i] == [fd.offset, fd.size], f
-    assert got[-7] == C.sizeof(BP)                                                # the existing plan is untouched
-    assert got[-6:] == [_lib.SHARD_LOCAL, _lib.SHARD_APPLY, _lib.SHARD_MAX_WORLD, _lib.RETURNS_SHARD_STATS, _lib.PPO_SHARD_STATS, 3]
+    assert abi_lib.c_name(PP) == cname and [f for f, _ in PP._fields_] == ["base", "phase", "world", "local", "all"]
+    assert abi_lib.layout(PP) == abi_lib.mirror_layout(PP)
+    assert abi_lib.layout(PP)[0] == C.sizeof(BP) + 4 + 4 + 8 + 8                  # the existing plan by value, then the four new fields
+    assert abi_lib.layout(BP)[0] == C.sizeof(BP)                                  # the existing plan is untouched
+    assert [abi_lib.constant("GMPE_" + k) for k in ("SHARD_LOCAL", "SHARD_APPLY", "SHARD_MAX_WORLD", "RETURNS_SHARD_STATS", "PPO_SHARD_STATS", "ABI_VERSION")] == [
+        _lib.SHARD_LOCAL, _lib.SHARD_APPLY, _lib.SHARD_MAX_WORLD, _lib.RETURNS_SHARD_STATS, _lib.PPO_SHARD_STATS, 3]
     assert gmpe.learner_shards.MAX_WORLD == _lib.SHARD_MAX_WORLD
 
 
 def test_symbols_are_exported_and_the_abi_version_stays():
-    lib = _lib.load()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH]).decode()
-    for s in ("gmpe_compute_returns_shard", "gmpe_ppo_loss_shard"):
-        assert s in _lib.SYMBOLS and hasattr(lib, s) and " T %s\n" % s in out
-    assert lib.gmpe_abi_version() == 3 and gmpe.config.ABI_VERSION == 3
+    assert {"gmpe_compute_returns_shard", "gmpe_ppo_loss_shard"} <= set(_lib.SYMBOLS) & abi_lib.exported()
+    assert _lib.load().gmpe_abi_version() == 3 and gmpe.config.ABI_VERSION == 3
 
 
 def _returns_shard_plan(**over):

@@ -5,13 +5,12 @@ restatement (gather_bytes) against the shaped one on the same yields, and the ca
 restatement from the right one, and what the cases cover."""
 import ctypes as C
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 import torch
 
+import abi_lib
 import gmpe
 from gmpe import _lib
 import minibatch_lib as M
@@ -21,34 +20,14 @@ GOLD = os.path.join(ROOT, "tests", "golden", "minibatch_generators.npz")
 
 
 def test_symbol_is_exported_and_bound():
-    lib = _lib.load()
-    assert "gmpe_minibatch_gather" in _lib.SYMBOLS and hasattr(lib, "gmpe_minibatch_gather")
+    assert "gmpe_minibatch_gather" in _lib.SYMBOLS and "gmpe_minibatch_gather" in abi_lib.exported()
 
 
 def test_plan_struct_layout_matches_c_header():
-    src = r'''
-    #include <stdio.h>
-    #include <stddef.h>
-    #include "gmpe.h"
-    int main(void) {
-      printf("%zu %zu %zu %zu %zu\n", sizeof(gmpe_mb_field), offsetof(gmpe_mb_field, slot_stride), offsetof(gmpe_mb_field, src),
-             offsetof(gmpe_mb_field, dst), offsetof(gmpe_mb_field, row_bytes));
-      printf("%zu %zu %zu %zu %zu %zu %zu\n", sizeof(gmpe_minibatch_plan), offsetof(gmpe_minibatch_plan, L), offsetof(gmpe_minibatch_plan, perm),
-             offsetof(gmpe_minibatch_plan, perm_len), offsetof(gmpe_minibatch_plan, offset), offsetof(gmpe_minibatch_plan, rows),
-             offsetof(gmpe_minibatch_plan, fields));
-      printf("%d %d %d %d %d %d %d %d\n", GMPE_MB_FEED_FORWARD, GMPE_MB_RECURRENT, GMPE_MB_ROW, GMPE_MB_ENV_ROW, GMPE_MB_CHUNK_HEAD, GMPE_MB_TABLE_NODE,
-             GMPE_MB_TABLE_ADJ, GMPE_MB_MAX_FIELDS);
-      return 0; }'''
-    with tempfile.TemporaryDirectory() as td:
-        cpath, exe = os.path.join(td, "t.c"), os.path.join(td, "t")
-        open(cpath, "w").write(src)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", exe, cpath])
-        out = [int(x) for x in subprocess.check_output([exe]).decode().split()]
-    Fd, P = _lib.GmpeMbField, _lib.GmpeMinibatchPlan
-    assert out[:5] == [C.sizeof(Fd), Fd.slot_stride.offset, Fd.src.offset, Fd.dst.offset, Fd.row_bytes.offset]
-    assert out[5:12] == [C.sizeof(P), P.L.offset, P.perm.offset, P.perm_len.offset, P.offset.offset, P.rows.offset, P.fields.offset]
-    assert out[12:] == [_lib.MB_FEED_FORWARD, _lib.MB_RECURRENT, _lib.MB_ROW, _lib.MB_ENV_ROW, _lib.MB_CHUNK_HEAD, _lib.MB_TABLE_NODE, _lib.MB_TABLE_ADJ,
-                        _lib.MB_MAX_FIELDS]
+    for P in (_lib.GmpeMbField, _lib.GmpeMinibatchPlan):
+        assert abi_lib.layout(P) == abi_lib.mirror_layout(P)
+    names = ("FEED_FORWARD", "RECURRENT", "ROW", "ENV_ROW", "CHUNK_HEAD", "TABLE_NODE", "TABLE_ADJ", "MAX_FIELDS")
+    assert [abi_lib.constant("GMPE_MB_" + k) for k in names] == [getattr(_lib, "MB_" + k) for k in names]
 
 
 def _plan(**kw):

@@ -6,15 +6,13 @@
 (c) the compiler's resource report of csrc/gmpe_mlp.hip shows no scratch memory."""
 import ctypes as C
 import os
-import re
-import subprocess
-import tempfile
 import types
 
 import numpy as np
 import pytest
 import torch
 
+import abi_lib
 import gmpe
 import mlp_lib as M
 from gmpe import _lib
@@ -82,33 +80,14 @@ def test_backward64_is_the_derivative_of_forward64(case):
 
 
 # ---------------------------------------------------------------------------------------------- (b)
-def _probe(struct, fields, extra=""):
-    src = "#include <stdio.h>\n#include <stddef.h>\n#include \"gmpe.h\"\nint main(void) {\n  printf(\"%%zu\\n\", sizeof(%s));\n" % struct
-    src += "".join("  printf(\"%%zu %%zu\\n\", offsetof(%s, %s), sizeof(((%s*)0)->%s));\n" % (struct, f, struct, f) for f in fields)
-    src += extra + "  return 0; }\n"
-    with tempfile.TemporaryDirectory() as t:
-        open(os.path.join(t, "l.c"), "w").write(src)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", os.path.join(t, "l"), os.path.join(t, "l.c")])
-        return [int(x) for x in subprocess.check_output([os.path.join(t, "l")]).split()]
-
-
 def test_symbols_are_exported_and_the_plan_matches_the_header():
     lib = _lib.load()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH]).decode()
-    for s in ("gmpe_mlp_workspace_bytes", "gmpe_mlp_forward", "gmpe_mlp_backward"):
-        assert s in _lib.SYMBOLS and hasattr(lib, s) and " T %s\n" % s in out
-    assert lib.gmpe_abi_version() == 3 and gmpe.config.ABI_VERSION == 3          # added entry points: the ABI version stays
-    assert re.search(r"#define\s+GMPE_ABI_VERSION\s+3\b", open(os.path.join(ROOT, "include", "gmpe.h")).read())
-    consts = "  printf(\"%d %d %d %d %d %d\\n\", GMPE_MLP_ROW_TILE, GMPE_MLP_MAX_PARTS, GMPE_MLP_MAX_IN, GMPE_MLP_MAX_LAYERS, GMPE_MLP_RELU, GMPE_MLP_TANH);\n"
-    for name, T, extra in (("gmpe_mlp_layer", _lib.GmpeMlpLayer, ""), ("gmpe_mlp_plan", _lib.GmpeMlpPlan, consts)):
-        fields = [f for f, _ in T._fields_]
-        got = _probe(name, fields, extra)
-        assert got[0] == C.sizeof(T), name
-        for i, f in enumerate(fields):
-            fd = getattr(T, f)
-            assert got[1 + 2 * i:3 + 2 * i] == [fd.offset, fd.size], (name, f)
-        if extra:
-            assert got[-6:] == [_lib.MLP_ROW_TILE, _lib.MLP_MAX_PARTS, _lib.MLP_MAX_IN, _lib.MLP_MAX_LAYERS, _lib.MLP_RELU, _lib.MLP_TANH]
+    assert {"gmpe_mlp_workspace_bytes", "gmpe_mlp_forward", "gmpe_mlp_backward"} <= set(_lib.SYMBOLS) & abi_lib.exported()
+    assert lib.gmpe_abi_version() == 3 and gmpe.config.ABI_VERSION == 3 == abi_lib.constant("GMPE_ABI_VERSION")   # added entry points: the ABI version stays
+    for T in (_lib.GmpeMlpLayer, _lib.GmpeMlpPlan):
+        assert abi_lib.layout(T) == abi_lib.mirror_layout(T), T
+    names = ("ROW_TILE", "MAX_PARTS", "MAX_IN", "MAX_LAYERS", "RELU", "TANH")
+    assert [abi_lib.constant("GMPE_MLP_" + k) for k in names] == [getattr(_lib, "MLP_" + k) for k in names]
     assert C.sizeof(_lib.GmpeMlpLayer) == 9 * 8 and C.sizeof(_lib.GmpeMlpPlan) == 8 + 6 * 4 + 4 * 8 + 4 * 4 + 4 * 8 + 5 * 8 + 3 * 72 + 4 * 8
 
 
@@ -307,12 +286,8 @@ def test_python_layer_refuses_what_it_does_not_support():
 
 # ---------------------------------------------------------------------------------------------- (c)
 def test_no_kernel_of_the_file_uses_scratch_memory():
-    csrc = os.path.join(ROOT, "contracts-marl-aam-corridors_amd", "csrc")
-    subprocess.run(["make", "-s", "-C", csrc, "build/ru_mlp.txt"], check=True, capture_output=True, timeout=600)
-    txt = open(os.path.join(csrc, "build", "ru_mlp.txt")).read()
-    names = re.findall(r"Function Name: (\S+)", txt)
-    scratch = re.findall(r"Function Name: \S*k_mlp\S*.*?ScratchSize \[bytes/lane\]: (\d+)", txt, flags=re.S)
-    assert len(names) == len(scratch) == 4 and all(s == "0" for s in scratch), (names, scratch)     # forward, bprop, wgrad, finish
+    assert "mlp" in abi_lib.ru_objects()                                                            # `make resource-usage` holds it
+    names, scratch = list(abi_lib.kernels("mlp")), list(abi_lib.scratch("mlp", "k_mlp").values())
+    assert len(names) == len(scratch) == 4 and all(s == 0 for s in scratch), (names, scratch)       # forward, bprop, wgrad, finish
     for k in ("k_mlp_fwd", "k_mlp_bprop", "k_mlp_wgrad", "k_mlp_finish"):
         assert any(k in n for n in names), k
-    assert "$(B)/ru_mlp.txt" in open(os.path.join(csrc, "Makefile")).read().split("RUFILES =")[1].split("\n")[0]      # and `make resource-usage` holds it

@@ -5,21 +5,16 @@
     every one before any device call (where there is no device, a call that got that far fails with a HIP error instead);
 (c) the compiler's resource report of csrc/gmpe_optim.hip shows no scratch memory."""
 import ctypes as C
-import os
-import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 import torch
 
+import abi_lib
 import gmpe
 import optim_lib as OL
 from gmpe import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "contracts-marl-aam-corridors_amd", "csrc")
 MB = 1 << 20
 
 
@@ -54,41 +49,17 @@ def test_the_metric_is_relative_to_the_arrays_own_size():
 
 
 # ---------------------------------------------------------------------------------------------- (b)
-STRUCTS = (("gmpe_optim_tensor", _lib.GmpeOptimTensor), ("gmpe_optim_hyper", _lib.GmpeOptimHyper), ("gmpe_optim_plan", _lib.GmpeOptimPlan))
-
-
-def _probe():
-    src = "#include <stdio.h>\n#include <stddef.h>\n#include \"gmpe.h\"\nint main(void) {\n"
-    for name, cls in STRUCTS:
-        src += "  printf(\"%%zu\\n\", sizeof(%s));\n" % name
-        src += "".join("  printf(\"%%zu %%zu\\n\", offsetof(%s, %s), sizeof(((%s*)0)->%s));\n" % (name, f, name, f) for f, _ in cls._fields_)
-    src += ("  printf(\"%d %d %d %d %lld %d %d %d %d %d\\n\", GMPE_OPT_MAX_TENSORS, GMPE_OPT_MAX_HYPERS, GMPE_OPT_CHUNK, GMPE_OPT_MAX_PLAN_TENSORS,\n"
-            "         (long long)GMPE_OPT_MAX_NUMEL, GMPE_OPT_CLIP, GMPE_OPT_STEP, GMPE_OPT_T_IN_NORM, GMPE_OPT_T_STEP, GMPE_ABI_VERSION);\n  return 0; }\n")
-    with tempfile.TemporaryDirectory() as t:
-        open(os.path.join(t, "l.c"), "w").write(src)
-        subprocess.check_call(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-o", os.path.join(t, "l"), os.path.join(t, "l.c")])
-        return [int(x) for x in subprocess.check_output([os.path.join(t, "l")]).split()]
-
-
 def test_symbols_are_exported_and_the_structs_match_the_header():
     lib = _lib.load()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH]).decode()
-    for s in ("gmpe_optim_workspace_bytes", "gmpe_optim_step"):
-        assert s in _lib.SYMBOLS and hasattr(lib, s) and " T %s\n" % s in out
+    assert {"gmpe_optim_workspace_bytes", "gmpe_optim_step"} <= set(_lib.SYMBOLS) & abi_lib.exported()
     assert lib.gmpe_abi_version() == 3 and gmpe.config.ABI_VERSION == 3          # added entry points: the ABI version stays
-    got = _probe()
-    i = 0
-    for name, cls in STRUCTS:
-        assert got[i] == C.sizeof(cls), name
-        i += 1
-        for f, _ in cls._fields_:
-            fd = getattr(cls, f)
-            assert got[i:i + 2] == [fd.offset, fd.size], (name, f)
-            i += 2
+    for cls in (_lib.GmpeOptimTensor, _lib.GmpeOptimHyper, _lib.GmpeOptimPlan):
+        assert abi_lib.layout(cls) == abi_lib.mirror_layout(cls), cls
     assert C.sizeof(_lib.GmpeOptimTensor) == 48 and C.sizeof(_lib.GmpeOptimHyper) == 48
-    assert got[i:] == [64, 8, 1024, 4096, 1 << 30, 1, 2, 1, 2, 3]
-    assert got[i:i + 9] == [_lib.OPT_MAX_TENSORS, _lib.OPT_MAX_HYPERS, _lib.OPT_CHUNK, _lib.OPT_MAX_PLAN_TENSORS, _lib.OPT_MAX_NUMEL, _lib.OPT_CLIP,
-                            _lib.OPT_STEP, _lib.OPT_T_IN_NORM, _lib.OPT_T_STEP]
+    names = ("MAX_TENSORS", "MAX_HYPERS", "CHUNK", "MAX_PLAN_TENSORS", "MAX_NUMEL", "CLIP", "STEP", "T_IN_NORM", "T_STEP")
+    got = [abi_lib.constant("GMPE_OPT_" + k) for k in names]
+    assert got + [abi_lib.constant("GMPE_ABI_VERSION")] == [64, 8, 1024, 4096, 1 << 30, 1, 2, 1, 2, 3]
+    assert got == [getattr(_lib, "OPT_" + k) for k in names]
     assert (OL.CHUNK, OL.MAX_TENSORS, OL.MAX_HYPERS, OL.IN_NORM, OL.STEP) == (1024, 64, 8, 1, 2) and gmpe.optim.CHUNK == 1024
     # 64 descriptors of 40 bytes and 8 hyper-parameter sets of 28 bytes travel as kernel arguments: under 4 KB with everything else
     assert 64 * 40 + 8 * 28 + 8 + 64 <= 4096
@@ -309,8 +280,6 @@ def test_ppo_update_and_train_refuse_what_they_do_not_do():
 
 # ---------------------------------------------------------------------------------------------- (c)
 def test_the_kernels_use_no_scratch():
-    subprocess.check_call(["make", "-s", "-C", CSRC, "build/ru_optim.txt"])
-    txt = open(os.path.join(CSRC, "build", "ru_optim.txt")).read()
-    found = dict(re.findall(r"Function Name: (\S+).*?ScratchSize \[bytes/lane\]: (\d+)", txt, flags=re.S))
-    assert len(found) == 2 and all(int(v) == 0 for v in found.values()), found
+    found = abi_lib.scratch("optim")
+    assert len(found) == 2 and all(v == 0 for v in found.values()), found
     assert any("k_opt_norm" in k for k in found) and any("k_opt_step" in k for k in found)

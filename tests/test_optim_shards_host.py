@@ -3,21 +3,18 @@ _finish, shards= of gmpe.clip_and_step, gmpe.policy.ppo_update and gmpe.policy.t
 refusal of both layers before any device call (where there is no device, a call that got that far fails with a HIP error instead), the length of `local`
 against the restated geometry, the restated combination rule on rows that tell rank orders apart, and the compiler's scratch report of the new kernels."""
 import ctypes as C
-import os
-import re
-import subprocess
-import tempfile
 import types
 
 import numpy as np
 import pytest
 import torch
 
+import abi_lib
 import gmpe
 import optim_lib as OL
 import optim_shards_lib as SL
 from gmpe import _lib, learner_shards, policy
-from test_optim_host import CSRC, ROOT, _adam, _plan
+from test_optim_host import _adam, _plan
 
 FIELDS = ["base", "phase", "world", "local", "all", "local_elems"]
 
@@ -25,23 +22,12 @@ FIELDS = ["base", "phase", "world", "local", "all", "local_elems"]
 def test_the_shard_plan_matches_the_header_and_the_symbols_are_exported():
     PP = _lib.GmpeOptimShardPlan
     assert [f for f, _ in PP._fields_] == FIELDS
-    src = "#include <stdio.h>\n#include <stddef.h>\n#include \"gmpe.h\"\nint main(void) {\n  printf(\"%zu %zu\\n\", sizeof(gmpe_optim_shard_plan), sizeof(gmpe_optim_plan));\n"
-    src += "".join("  printf(\"%%zu %%zu\\n\", offsetof(gmpe_optim_shard_plan, %s), sizeof(((gmpe_optim_shard_plan*)0)->%s));\n" % (f, f) for f in FIELDS)
-    src += "  printf(\"%d %d %d %d\\n\", GMPE_SHARD_LOCAL, GMPE_SHARD_APPLY, GMPE_SHARD_MAX_WORLD, GMPE_ABI_VERSION);\n  return 0; }\n"
-    with tempfile.TemporaryDirectory() as t:
-        open(os.path.join(t, "l.c"), "w").write(src)
-        subprocess.check_call(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-o", os.path.join(t, "l"), os.path.join(t, "l.c")])
-        got = [int(x) for x in subprocess.check_output([os.path.join(t, "l")]).split()]
-    assert got[0] == C.sizeof(PP) == C.sizeof(_lib.GmpeOptimPlan) + 4 + 4 + 8 + 8 + 8 and got[1] == C.sizeof(_lib.GmpeOptimPlan)
-    for i, f in enumerate(FIELDS):
-        fd = getattr(PP, f)
-        assert got[2 + 2 * i:4 + 2 * i] == [fd.offset, fd.size], f
-    assert got[-4:] == [_lib.SHARD_LOCAL, _lib.SHARD_APPLY, _lib.SHARD_MAX_WORLD, 3] == [0, 1, 4096, 3]
-    lib = _lib.load()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH]).decode()
-    for s in ("gmpe_optim_shard_elems", "gmpe_optim_step_shard"):
-        assert s in _lib.SYMBOLS and hasattr(lib, s) and " T %s\n" % s in out
-    assert lib.gmpe_abi_version() == 3 and gmpe.config.ABI_VERSION == 3          # added entry points: the ABI version stays
+    assert abi_lib.layout(PP) == abi_lib.mirror_layout(PP)
+    assert abi_lib.layout(PP)[0] == C.sizeof(_lib.GmpeOptimPlan) + 4 + 4 + 8 + 8 + 8 and abi_lib.layout(_lib.GmpeOptimPlan)[0] == C.sizeof(_lib.GmpeOptimPlan)
+    assert [abi_lib.constant("GMPE_" + k) for k in ("SHARD_LOCAL", "SHARD_APPLY", "SHARD_MAX_WORLD", "ABI_VERSION")] == [
+        _lib.SHARD_LOCAL, _lib.SHARD_APPLY, _lib.SHARD_MAX_WORLD, 3] == [0, 1, 4096, 3]
+    assert {"gmpe_optim_shard_elems", "gmpe_optim_step_shard"} <= set(_lib.SYMBOLS) & abi_lib.exported()
+    assert _lib.load().gmpe_abi_version() == 3 and gmpe.config.ABI_VERSION == 3          # added entry points: the ABI version stays
     assert gmpe.clip_and_step_begin is gmpe.optim.clip_and_step_begin and gmpe.clip_and_step_finish is gmpe.optim.clip_and_step_finish
     assert gmpe.optim.MAX_EXTRA == SL.MAX_EXTRA == 16
 
@@ -228,9 +214,7 @@ def test_the_lockstep_exchange_stacks_in_rank_order_and_a_failure_ends_the_other
 
 
 def test_the_new_kernels_use_no_scratch():
-    subprocess.check_call(["make", "-s", "-C", CSRC, "build/ru_optimshard.txt"])
-    txt = open(os.path.join(CSRC, "build", "ru_optimshard.txt")).read()
-    found = dict(re.findall(r"Function Name: (\S+).*?ScratchSize \[bytes/lane\]: (\d+)", txt, flags=re.S))
-    assert len(found) == 2 and all(int(v) == 0 for v in found.values()), found
+    assert "optimshard" in abi_lib.ru_objects()                                   # `make resource-usage` holds it
+    found = abi_lib.scratch("optimshard")
+    assert len(found) == 2 and all(v == 0 for v in found.values()), found
     assert any("k_opt_pack" in k for k in found) and any("k_opt_reduce" in k for k in found)
-    assert "$(B)/ru_optimshard.txt" in open(os.path.join(CSRC, "Makefile")).read().split("RUFILES =")[1].split("\n")[0]      # and `make resource-usage` holds it

@@ -11,14 +11,13 @@ the sum, and values are compared with the dot-product bound while everything aft
 again. The six PopArt tensors never depend on the values and are bit for bit in all three minibatches."""
 import ctypes as C
 import os
-import subprocess
-import tempfile
 import types
 
 import numpy as np
 import pytest
 import torch
 
+import abi_lib
 import gmpe
 import popart_lib as PL
 import ppo_loss_lib as P
@@ -180,24 +179,12 @@ def test_the_run_tells_the_truth_from_a_wrong_variant(variant):
 # ---------------------------------------------------------------------------------------------- (c)
 def test_symbols_are_exported_and_the_plan_matches_the_header():
     lib = _lib.load()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH]).decode()
-    for s in ("gmpe_ppo_loss_popart", "gmpe_ppo_loss_popart_workspace_bytes"):
-        assert s in _lib.SYMBOLS and hasattr(lib, s) and " T %s\n" % s in out
+    assert {"gmpe_ppo_loss_popart", "gmpe_ppo_loss_popart_workspace_bytes"} <= set(_lib.SYMBOLS) & abi_lib.exported()
     assert lib.gmpe_abi_version() == 3 and gmpe.config.ABI_VERSION == 3          # an added entry point: the ABI version stays
     PP = _lib.GmpePopartLossPlan
-    fields = [f for f, _ in PP._fields_]
-    src = "#include <stdio.h>\n#include <stddef.h>\n#include \"gmpe.h\"\nint main(void) {\n  printf(\"%zu %d\\n\", sizeof(gmpe_popart_loss_plan), GMPE_POPART_MAX_HIDDEN);\n"
-    src += "".join("  printf(\"%%zu %%zu\\n\", offsetof(gmpe_popart_loss_plan, %s), sizeof(((gmpe_popart_loss_plan*)0)->%s));\n" % (f, f) for f in fields)
-    src += "  printf(\"%zu\\n\", sizeof(gmpe_ppo_loss_plan));\n  return 0; }\n"
-    with tempfile.TemporaryDirectory() as t:
-        open(os.path.join(t, "l.c"), "w").write(src)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", os.path.join(t, "l"), os.path.join(t, "l.c")])
-        got = [int(x) for x in subprocess.check_output([os.path.join(t, "l")]).split()]
-    assert got[0] == C.sizeof(PP) == 8 + 4 * 4 + 5 * 8 + 28 * 8 and got[1] == _lib.POPART_MAX_HIDDEN == 1024
-    for i, f in enumerate(fields):
-        fd = getattr(PP, f)
-        assert got[2 + 2 * i:4 + 2 * i] == [fd.offset, fd.size], f
-    assert got[-1] == C.sizeof(_lib.GmpePpoLossPlan)                              # the existing plan is untouched
+    assert abi_lib.layout(PP) == abi_lib.mirror_layout(PP) and C.sizeof(PP) == 8 + 4 * 4 + 5 * 8 + 28 * 8
+    assert abi_lib.constant("GMPE_POPART_MAX_HIDDEN") == _lib.POPART_MAX_HIDDEN == 1024
+    assert abi_lib.layout(_lib.GmpePpoLossPlan)[0] == C.sizeof(_lib.GmpePpoLossPlan)   # the existing plan is untouched
     n = C.c_size_t()
     assert lib.gmpe_ppo_loss_popart_workspace_bytes(1000, 64, C.byref(n)) == 0 and n.value >= 4 * (8 + 64) * 8 and n.value % 8 == 0
     for rows, hidden in ((0, 64), (10, 0), (10, 1025)):

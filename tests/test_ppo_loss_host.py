@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_lib
 import gmpe
 import ppo_loss_lib as P
 from gmpe import _lib
@@ -136,20 +137,11 @@ def test_inputs_tell_the_truth_from_a_wrong_variant(variant, case):
 # ---------------------------------------------------------------------------------------------- (d)
 def test_symbols_are_exported_and_the_plan_matches_the_header():
     lib = _lib.load()
-    for s in ("gmpe_ppo_loss", "gmpe_ppo_loss_workspace_bytes"):
-        assert s in _lib.SYMBOLS and hasattr(lib, s)
-    hdr = open(os.path.join(ROOT, "include", "gmpe.h")).read()
-    body = hdr[hdr.index("typedef struct gmpe_ppo_loss_plan {"):hdr.index("} gmpe_ppo_loss_plan;")]
-    import re
-    names = []
-    for line in body.splitlines()[1:]:
-        line = line.split("/*")[0].strip()
-        if line:
-            names += [n.strip(" *") for n in re.sub(r"^(const\s+)?\w+\*?\s+", "", line.rstrip(";")).split(",")]
-    assert names == [f[0] for f in _lib.GmpePpoLossPlan._fields_]
-    assert _lib.PPO_MAX_ACTIONS >= 64 and "#define GMPE_PPO_MAX_ACTIONS %d" % _lib.PPO_MAX_ACTIONS in hdr
-    assert "#define GMPE_PPO_NUM_OUT %d" % _lib.PPO_NUM_OUT in hdr and len(_lib.PPO_OUT) == _lib.PPO_NUM_OUT
-    assert "#define GMPE_ABI_VERSION 3" in hdr
+    assert {"gmpe_ppo_loss", "gmpe_ppo_loss_workspace_bytes"} <= set(_lib.SYMBOLS) & abi_lib.exported()
+    assert abi_lib.layout(_lib.GmpePpoLossPlan) == abi_lib.mirror_layout(_lib.GmpePpoLossPlan)      # every field by its header name, at the header's offset
+    assert _lib.PPO_MAX_ACTIONS >= 64 and abi_lib.constant("GMPE_PPO_MAX_ACTIONS") == _lib.PPO_MAX_ACTIONS
+    assert abi_lib.constant("GMPE_PPO_NUM_OUT") == _lib.PPO_NUM_OUT == len(_lib.PPO_OUT)
+    assert abi_lib.constant("GMPE_ABI_VERSION") == 3
     n = C.c_size_t()
     assert lib.gmpe_ppo_loss_workspace_bytes(1000, C.byref(n)) == 0 and n.value >= 4 * 7 * 8 and n.value % 8 == 0
     assert lib.gmpe_ppo_loss_workspace_bytes(0, C.byref(n)) == -1

@@ -3,14 +3,13 @@ struct layouts, argument checks of the Python wrappers before any launch, the op
 restatement the GPU tests compare with (tests/returns_lib.py) against the reference's own vectors."""
 import ctypes as C
 import os
-import subprocess
-import tempfile
 import types
 
 import numpy as np
 import pytest
 import torch
 
+import abi_lib
 import gmpe
 from gmpe import _lib
 import returns_lib as R
@@ -21,33 +20,14 @@ NEW = ("gmpe_returns_workspace_bytes", "gmpe_compute_returns", "gmpe_available_a
 
 
 def test_new_symbols_are_exported_and_bound():
-    lib = _lib.load()
-    for f in NEW:
-        assert f in _lib.SYMBOLS
-        assert hasattr(lib, f), f
+    assert set(NEW) <= set(_lib.SYMBOLS) & abi_lib.exported()                  # bound: tests/test_abi_host.py, for every symbol
 
 
 def test_plan_struct_layouts_match_c_header():
-    src = r'''
-    #include <stdio.h>
-    #include <stddef.h>
-    #include "gmpe.h"
-    int main(void) {
-      printf("%zu %zu %zu %zu %zu %zu\n", sizeof(gmpe_returns_plan), offsetof(gmpe_returns_plan, gamma), offsetof(gmpe_returns_plan, rewards),
-             offsetof(gmpe_returns_plan, denorm_std), offsetof(gmpe_returns_plan, workspace), offsetof(gmpe_returns_plan, workspace_bytes));
-      printf("%zu %zu %zu %zu\n", sizeof(gmpe_avail_plan), offsetof(gmpe_avail_plan, n_actions), offsetof(gmpe_avail_plan, count),
-             offsetof(gmpe_avail_plan, stride_out));
-      printf("%d %d %d\n", GMPE_RETURNS_GAE, GMPE_RETURNS_PROPER_TIME_LIMITS, GMPE_RETURNS_ADVANTAGES_ONLY);
-      return 0; }'''
-    with tempfile.TemporaryDirectory() as td:
-        cpath, exe = os.path.join(td, "t.c"), os.path.join(td, "t")
-        open(cpath, "w").write(src)
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", exe, cpath])
-        out = [int(x) for x in subprocess.check_output([exe]).decode().split()]
-    P, Q = _lib.GmpeReturnsPlan, _lib.GmpeAvailPlan
-    assert out[:6] == [C.sizeof(P), P.gamma.offset, P.rewards.offset, P.denorm_std.offset, P.workspace.offset, P.workspace_bytes.offset]
-    assert out[6:10] == [C.sizeof(Q), Q.n_actions.offset, Q.count.offset, Q.stride_out.offset]
-    assert out[10:] == [_lib.RETURNS_GAE, _lib.RETURNS_PROPER_TIME_LIMITS, _lib.RETURNS_ADVANTAGES_ONLY]
+    for P in (_lib.GmpeReturnsPlan, _lib.GmpeAvailPlan):
+        assert abi_lib.layout(P) == abi_lib.mirror_layout(P)
+    assert [abi_lib.constant("GMPE_RETURNS_" + k) for k in ("GAE", "PROPER_TIME_LIMITS", "ADVANTAGES_ONLY")] == [
+        _lib.RETURNS_GAE, _lib.RETURNS_PROPER_TIME_LIMITS, _lib.RETURNS_ADVANTAGES_ONLY] == [1, 2, 4]
 
 
 def test_workspace_query_and_c_side_validation():
