@@ -327,3 +327,78 @@ def test_the_c_entry_on_a_side_stream_whatever_the_workspace_held():
         for i in range(3):
             assert same(p[i], want[0]["param"][i]) and same(g[i], want[0]["grad"][i]) and same(m[i], want[0]["exp_avg"][i])
             assert same(v[i], want[0]["exp_avg_sq"][i])
+
+
+# ---------------------------------------------------------------------------------------------- 10
+def _steps_on(where, params, groups, grads_per_step, max_norm):
+    """the steps of one optimiser over `groups(ps)` on `where`: torch's own clip and step on the CPU, clip_and_step on the device -> (snapshot, ps, opt)"""
+    ps = OL.torch_params(params, device=where)
+    opt = torch.optim.Adam(groups(ps), lr=OL.LR, eps=OL.EPS)
+    for grads in grads_per_step:
+        OL.set_grads(ps, grads)
+        if where == "cpu":
+            norm = torch.nn.utils.clip_grad_norm_(ps, max_norm)
+            opt.step()
+        else:
+            norm = gmpe.clip_and_step(opt, max_norm)
+    return OL.snapshot(ps, opt, norm), ps, opt
+
+
+def _restated(params, grads_per_step, max_norm, **per_tensor):
+    r = OL.Restated(params)
+    for grads in grads_per_step:
+        norm, g = r.step(grads, max_norm, **per_tensor)
+    return {"param": r.p, "grad": g, "exp_avg": r.m, "exp_avg_sq": r.v, "norm": norm}, r
+
+
+def test_a_ninth_hyper_parameter_set_opens_a_launch_group():
+    """ten param groups, each with its own lr, eps and weight_decay, in one call: a launch carries eight sets, so the ninth group's tensor opens a second
+    launch whose slots 0 and 1 hold the plan's sets 8 and 9"""
+    shapes = OL.SHAPES
+    n = len(shapes)
+    lr, eps, wd = [1e-3 * (i + 1) for i in range(n)], [1e-5 * 3 ** i for i in range(n)], [1e-2 * i for i in range(n)]
+    assert n == 10 and OL.MAX_HYPERS == 8
+    assert [g[0] for g in OL.geometry([(int(np.prod(s)), OL.IN_NORM | OL.STEP, i) for i, s in enumerate(shapes)])] == [8, 2]
+    params = OL.parameters(shapes, seed=10)
+    grads = [OL.gradients(shapes, k, 10) for k in range(3)]
+    groups = lambda ps: [dict(params=[p], lr=lr[i], eps=eps[i], weight_decay=wd[i]) for i, p in enumerate(ps)]
+    truth, _ = _restated(params, grads, OL.MAX_NORM, lr=lr, eps=eps, weight_decay=wd)
+    holds(_steps_on(DEV, params, groups, grads, OL.MAX_NORM)[0], _steps_on("cpu", params, groups, grads, OL.MAX_NORM)[0], truth, "ten groups")
+
+
+def test_a_second_launch_group_whose_first_slot_is_the_plans_second_set():
+    """70 tensors in two param groups, the last six in the second: they are the second launch, where the plan's set 1 lies in slot 0"""
+    n, cut = 70, OL.MAX_TENSORS
+    shapes = ((3,),) * n
+    assert [g[0] for g in OL.geometry([(3, OL.IN_NORM | OL.STEP, int(i >= cut)) for i in range(n)])] == [cut, n - cut]
+    params = OL.parameters(shapes, seed=11)
+    grads = [OL.gradients(shapes, k, 11) for k in range(3)]
+    groups = lambda ps: [dict(params=ps[:cut]), dict(params=ps[cut:], lr=3e-3, eps=1e-3, weight_decay=5e-2)]
+    per = lambda a, b: [a] * cut + [b] * (n - cut)
+    MN = 0.01                                           # under the first tensor's norm alone
+    truth, _ = _restated(params, grads, MN, lr=per(OL.LR, 3e-3), eps=per(OL.EPS, 1e-3), weight_decay=per(0.0, 5e-2))
+    assert truth["norm"] > MN
+    holds(_steps_on(DEV, params, groups, grads, MN)[0], _steps_on("cpu", params, groups, grads, MN)[0], truth, "70 tensors, two groups")
+
+
+def test_a_tensor_whose_gradient_came_late_has_its_own_step_count_and_bias_correction():
+    """one param group; tensor 2 has no gradient in the first two of four steps, so its bias corrections are those of steps 1 and 2 while its
+    neighbours' are those of steps 3 and 4"""
+    shapes, late = OL.SHAPES[:6], 2
+    params = OL.parameters(shapes, seed=12)
+    grads = [OL.gradients(shapes, k, 12) for k in range(4)]
+    for k in (0, 1):
+        grads[k][late] = None
+    groups = lambda ps: [dict(params=ps, weight_decay=1e-2)]
+    truth, r = _restated(params, grads, OL.MAX_NORM, weight_decay=1e-2)
+    assert r.t == [4, 4, 2, 4, 4, 4]
+    dev, ps, opt = _steps_on(DEV, params, groups, grads, OL.MAX_NORM)
+    ref, _, _ = _steps_on("cpu", params, groups, grads, OL.MAX_NORM)
+    assert [float(opt.state[p]["step"]) for p in ps] == [4, 4, 2, 4, 4, 4]
+    holds(dev, ref, truth, "a late gradient")
+    # with its neighbours' step count the late tensor would be far off: its own was used
+    wrong = OL.Restated(params)
+    for k in range(4):
+        wrong.step(grads[k], OL.MAX_NORM, weight_decay=1e-2)
+        wrong.t[late] = k + 1
+    assert OL.err(dev["param"][late], wrong.p[late]) > 1e-4
