@@ -26,6 +26,7 @@ SYMBOLS = ["gmpe_abi_version", "gmpe_last_error", "gmpe_obs_dim", "gmpe_node_fea
            "gmpe_mlp_workspace_bytes", "gmpe_mlp_forward", "gmpe_mlp_backward",
            "gmpe_gnn_workspace_bytes", "gmpe_gnn_forward", "gmpe_gnn_backward",
            "gmpe_head_workspace_bytes", "gmpe_head_forward", "gmpe_head_backward", "gmpe_act_head",
+           "gmpe_value_workspace_bytes", "gmpe_value_forward", "gmpe_value_backward",
            "gmpe_optim_workspace_bytes", "gmpe_optim_step", "gmpe_optim_shard_elems", "gmpe_optim_step_shard"]
 
 
@@ -199,6 +200,13 @@ class GmpeHeadPlan(C.Structure):
                 ("grad_weight", C.c_void_p), ("grad_bias", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
+class GmpeValuePlan(C.Structure):
+    """gmpe_value_plan (include/gmpe.h): the critic's value head v_out, forward and backward."""
+    _fields_ = [("rows", C.c_int64), ("hidden", C.c_int32), ("reserved", C.c_int32), ("features", C.c_void_p), ("weight", C.c_void_p),
+                ("bias", C.c_void_p), ("values_out", C.c_void_p), ("grad_values", C.c_void_p), ("grad_features", C.c_void_p),
+                ("grad_weight", C.c_void_p), ("grad_bias", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
 GRU_ROW_TILE = 32        # GMPE_GRU_ROW_TILE of include/gmpe.h; tests/gru_lib.py TILE is the third copy — tests/test_abi_host.py compiles against the header, tests/test_gru_host.py ties the three together
 
 
@@ -367,6 +375,9 @@ def load():
     lib.gmpe_head_forward.argtypes = [I, C.POINTER(GmpeHeadPlan), P]
     lib.gmpe_head_backward.argtypes = [I, C.POINTER(GmpeHeadPlan), P]
     lib.gmpe_act_head.argtypes = [I, C.POINTER(GmpeActPlan), C.POINTER(GmpeHeadPlan), P]
+    lib.gmpe_value_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.POINTER(C.c_size_t)]
+    lib.gmpe_value_forward.argtypes = [I, C.POINTER(GmpeValuePlan), P]
+    lib.gmpe_value_backward.argtypes = [I, C.POINTER(GmpeValuePlan), P]
     lib.gmpe_optim_workspace_bytes.argtypes = [C.POINTER(GmpeOptimPlan), C.POINTER(C.c_size_t)]
     lib.gmpe_optim_step.argtypes = [I, C.POINTER(GmpeOptimPlan), P]
     lib.gmpe_optim_shard_elems.argtypes = [C.POINTER(GmpeOptimPlan), C.POINTER(C.c_int64)]

@@ -2,7 +2,7 @@
 //   * every file: the library's error text and the one HIP-check macro;
 //   * the two sharded entry points (gmpe_compute_returns_shard, gmpe_ppo_loss_shard): the checks of their phase, world, `local` and `all`;
 //   * every file whose kernels take more than the default 48 KiB of dynamic LDS: the once-per-device raise of that limit;
-//   * the layer files (gmpe_gru.hip, gmpe_mlp.hip, gmpe_gnn.hip, gmpe_head.hip): the grid of resident workgroups, what a valid plan pointer and a valid
+//   * the layer files (gmpe_gru.hip, gmpe_mlp.hip, gmpe_gnn.hip, gmpe_head.hip, gmpe_value.hip): the grid of resident workgroups, what a valid plan pointer and a valid
 //     workspace are, the prologue of their *_workspace_bytes entries, the carving of a workspace, and the launch-and-check macro;
 //   * the entry points over gmpe_ppo_rows.h (gmpe_ppo_loss, gmpe_ppo_loss_popart, gmpe_act_sample, and gmpe_head.hip's three): the tile geometry the host
 //     fills and the row kernels read, and the checks and the float hyper-parameters the two loss entry points have in common.
@@ -49,7 +49,7 @@ static int raise_dynamic_lds_once(const void* fn, int device, int slot, size_t b
     return GMPE_OK;
 }
 
-// ---- the layer files: gmpe_gru.hip, gmpe_mlp.hip, gmpe_gnn.hip, gmpe_head.hip
+// ---- the layer files: gmpe_gru.hip, gmpe_mlp.hip, gmpe_gnn.hip, gmpe_head.hip, gmpe_value.hip
 
 constexpr int MAX_CU = 256, LDS_CU = 160 * 1024;        // the CUs a grid is sized for, and the LDS of one of them in bytes
 

@@ -1,4 +1,5 @@
-// gmpe_wgrad.h — the parameter-gradient machinery the layer files share (gmpe_gru.hip, gmpe_mlp.hip; internal, nothing here has external linkage):
+// gmpe_wgrad.h — the parameter-gradient machinery the layer files share (gmpe_gru.hip, gmpe_mlp.hip, gmpe_head.hip, gmpe_value.hip; internal, nothing here has
+// external linkage):
 // gradients of 64-wide matrices and of per-column vectors as double sums in a fixed order, rounded to float32 once, without atomics.
 //   weights: the M rows of a call are cut into P = min(128, ceil(M / 32)) contiguous parts of ceil(M / P) rows (partition). One workgroup adds a part's
 //     exact double products a(m, j) * b(m, d) in ascending row order into a [64][64] block of doubles (part_products); the finish kernel adds the parts

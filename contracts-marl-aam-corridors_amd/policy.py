@@ -2,6 +2,10 @@
 
     GR_Actor.forward      ->  actor_forward(actor, ...)    = gnn_base -> mlp_base((obs, nbd)) -> rnn_layer -> act_head
     GR_Critic.forward     ->  critic_forward(critic, ...)  = gnn_base -> mlp_base((cent_obs, nbd)) -> rnn_layer -> F.linear(v_out)
+    GR_MAPPOPolicy.get_actions / get_values               ->  get_actions(actor, critic, ...) / get_values(critic, ...): the critic chain ends in value_head
+    GMPERunner.collect / collect_with_mask + insert       ->  collect_step(actor, critic, buffer)
+    GMPERunner.compute                                    ->  compute(critic, buffer, value_normalizer)
+    run()'s loop over one episode, and one whole iteration  ->  rollout(actor, critic, buffer, ...), iteration(actor, critic, ..., buffer, args, ...)
     evaluate_actions + the loss arithmetic of ppo_update  ->  minibatch_losses(actor, critic, sample, args, ...)
     GR_MAPPO.ppo_update                                   ->  ppo_update(actor, critic, actor_optimizer, critic_optimizer, sample, args, ...)
     GR_MAPPO.train                                        ->  train(actor, critic, actor_optimizer, critic_optimizer, buffer, args, ...)
@@ -9,8 +13,9 @@
 
 The modules are the caller's unchanged GR_Actor / GR_Critic (onpolicy/algorithms/graph_actor_critic.py), read by their attribute names (.gnn_base, .base,
 .rnn, .act, .v_out, .args); the parameters stay where they are, so the optimisers and the checkpoints do not change. Everything a layer refuses is
-refused here by that layer, in its words. v_out stays torch's F.linear on the caller's weight and bias (with --use_popart in training, ppo_losses_popart
-evaluates it). There is no torch fallback: the arrays must be on a HIP device.
+refused here by that layer, in its words. In a rollout v_out is value_head, the dot product ppo_losses_popart evaluates in training with --use_popart, so
+the stored value_preds are what that loss recomputes; critic_forward and, by default, the learner entries keep torch's F.linear on the caller's weight
+and bias for a plain nn.Linear v_out (value_head="device" takes value_head there too). There is no torch fallback: the arrays must be on a HIP device.
 """
 import collections
 
@@ -23,6 +28,7 @@ from .head import act_head, action_logits
 from .mlp import mlp_base
 from .optim import clip_and_step
 from .ppo_loss import ppo_losses, ppo_losses_popart
+from . import value as _value
 
 
 def _recurrent(net):
@@ -67,11 +73,20 @@ def critic_forward(critic, cent_obs, node_obs, adj, agent_id, rnn_states_critic,
     return F.linear(features, critic.v_out.weight, critic.v_out.bias), rnn_states_critic
 
 
-def minibatch_losses(actor, critic, sample, args, value_normalizer=None, install="replace", workspace=None, shards=None):
+def _value_head_kind(fn, value_head):
+    if value_head not in ("torch", "device"):
+        raise ValueError("value_head = %r: %s takes \"torch\" (F.linear) or \"device\" (gmpe.value_head)" % (value_head, fn))
+    return value_head == "device"
+
+
+def minibatch_losses(actor, critic, sample, args, value_normalizer=None, install="replace", workspace=None, shards=None, *, value_head="torch"):
     """evaluate_actions and the loss arithmetic of GR_MAPPO.ppo_update (graph_mappo.py:147-245) for the generators' 16-tuple `sample`: the actor chain up to
     action_logits, the critic chain up to its values — up to its features with args.use_popart —, then ppo_losses (value_normalizer, shards) or
     ppo_losses_popart (critic.v_out, install). Returns their result object unchanged; backward() of its two losses reaches every parameter of the actor
-    and of the critic. workspace: the loss call's (ppo_loss.workspace_bytes / popart_workspace_bytes)."""
+    and of the critic. workspace: the loss call's (ppo_loss.workspace_bytes / popart_workspace_bytes). value_head: "torch" — v_out as F.linear — or
+    "device" — a plain nn.Linear v_out through gmpe.value_head, forward and backward; with args.use_popart it changes nothing (ppo_losses_popart
+    evaluates v_out itself)."""
+    device_value = _value_head_kind("minibatch_losses", value_head)
     if not isinstance(sample, (tuple, list)) or len(sample) != 16:
         raise ValueError("sample must be the generators' 16-tuple")
     share_obs, obs, node_obs, adj, agent_id, share_agent_id, rnn_states, rnn_states_critic = sample[:8]
@@ -81,7 +96,10 @@ def minibatch_losses(actor, critic, sample, args, value_normalizer=None, install
     critic_features, _ = _features(critic, _cent(critic, share_obs), node_obs, adj, share_agent_id, rnn_states_critic, masks)
     if getattr(args, "use_popart", False):
         return ppo_losses_popart(logits, critic_features, sample, args, critic.v_out, install=install, workspace=workspace, shards=shards)
-    values = F.linear(critic_features, critic.v_out.weight, critic.v_out.bias)
+    if device_value:
+        values = _value.value_head(critic_features, critic.v_out)
+    else:
+        values = F.linear(critic_features, critic.v_out.weight, critic.v_out.bias)
     return ppo_losses(logits, values, sample, args, value_normalizer, workspace=workspace, shards=shards)
 
 
@@ -99,9 +117,10 @@ def _refusals(fn, accumulation_steps, shards):
         raise NotImplementedError("accumulation_steps = %r: %s steps at every minibatch (gradient accumulation is not supported)" % (accumulation_steps, fn))
 
 
-def _ppo_update(actor, critic, actor_optimizer, critic_optimizer, sample, args, value_normalizer, update_actor, install, workspace, shards):
+def _ppo_update(actor, critic, actor_optimizer, critic_optimizer, sample, args, value_normalizer, update_actor, install, workspace, shards,
+                value_head="torch"):
     """ppo_update -> (PPOUpdate, ratio); ratio: with shards the whole minibatch's imp_weights.mean(), else None (it is u.imp_weights.mean())"""
-    res = minibatch_losses(actor, critic, sample, args, value_normalizer, install=install, workspace=workspace, shards=shards)
+    res = minibatch_losses(actor, critic, sample, args, value_normalizer, install=install, workspace=workspace, shards=shards, value_head=value_head)
     max_norm = getattr(args, "max_grad_norm", 10.0) if getattr(args, "use_max_grad_norm", True) else None
     actor_optimizer.zero_grad()
     if update_actor:
@@ -122,7 +141,7 @@ def _ppo_update(actor, critic, actor_optimizer, critic_optimizer, sample, args, 
 
 
 def ppo_update(actor, critic, actor_optimizer, critic_optimizer, sample, args, value_normalizer=None, update_actor=True, install="replace", workspace=None,
-               *, accumulation_steps=1, shards=None):
+               *, accumulation_steps=1, shards=None, value_head="torch"):
     """GR_MAPPO.ppo_update (graph_mappo.py:147-278) in the reference's order: minibatch_losses; actor_optimizer.zero_grad(); with update_actor the actor
     loss's backward(); clip_and_step over actor.parameters() (step only with update_actor); critic_optimizer.zero_grad(); (value_loss *
     args.value_loss_coef).backward(); clip_and_step over critic.parameters(). With args.use_max_grad_norm (default True) the gradients are clipped to
@@ -139,13 +158,15 @@ def ppo_update(actor, critic, actor_optimizer, critic_optimizer, sample, args, v
     the same calls with the same update_actor. args.use_popart with shards is refused by ppo_losses_popart, in its words.
     The reference's GradScaler is not reproduced: with float32 losses it changes no value unless a gradient overflows, and its step() waits for the
     device. accumulation_steps != 1 and a `shards` that is no such exchange raise NotImplementedError, before anything else is read. Nothing here
-    waits for the device (the exchange is the caller's)."""
+    waits for the device (the exchange is the caller's). value_head: minibatch_losses'."""
     _refusals("ppo_update", accumulation_steps, shards)
-    return _ppo_update(actor, critic, actor_optimizer, critic_optimizer, sample, args, value_normalizer, update_actor, install, workspace, shards)[0]
+    _value_head_kind("ppo_update", value_head)
+    return _ppo_update(actor, critic, actor_optimizer, critic_optimizer, sample, args, value_normalizer, update_actor, install, workspace, shards,
+                       value_head)[0]
 
 
 def train(actor, critic, actor_optimizer, critic_optimizer, buffer, args, value_normalizer=None, update_actor=True, perms=None, *, install="replace",
-          accumulation_steps=1, shards=None):
+          accumulation_steps=1, shards=None, value_head="torch"):
     """GR_MAPPO.train (graph_mappo.py:294-359) over a DeviceRolloutBuffer: buffer.normalized_advantages(value_normalizer), then args.ppo_epoch (15) passes
     of the generator the reference chooses — recurrent_generator with args.data_chunk_length (10) under args.use_recurrent_policy (True), else
     naive_recurrent_generator under args.use_naive_recurrent_policy, else feed_forward_generator, each with args.num_mini_batch (1) — and ppo_update
@@ -157,8 +178,10 @@ def train(actor, critic, actor_optimizer, critic_optimizer, buffer, args, value_
     shards: None, or the exchange of a data-parallel learner: `buffer` is this rank's own, the advantages are normalised with the statistics of all
     ranks' buffers (normalized_advantages(value_normalizer, shards=shards)), every minibatch is ppo_update(..., shards=shards), and ratio is the sum
     of all ranks' imp_weights over their count. Every rank must produce the same number of minibatches (the same ppo_epoch and num_mini_batch over
-    buffers that yield as many samples): a rank that stops early leaves the others waiting in the exchange. Each rank draws its own permutation."""
+    buffers that yield as many samples): a rank that stops early leaves the others waiting in the exchange. Each rank draws its own permutation.
+    value_head: minibatch_losses'."""
     _refusals("train", accumulation_steps, shards)
+    _value_head_kind("train", value_head)
     ppo_epoch, num_mini_batch = int(getattr(args, "ppo_epoch", 15)), int(getattr(args, "num_mini_batch", 1))
     if perms is not None and len(perms) != ppo_epoch:
         raise ValueError("perms must hold one permutation per epoch: %d, not %d" % (ppo_epoch, len(perms)))
@@ -173,13 +196,136 @@ def train(actor, critic, actor_optimizer, critic_optimizer, buffer, args, value_
         else:
             generator = buffer.feed_forward_generator(advantages, num_mini_batch, perm=perm)
         for sample in generator:
-            u, ratio = _ppo_update(actor, critic, actor_optimizer, critic_optimizer, sample, args, value_normalizer, update_actor, install, None, shards)
+            u, ratio = _ppo_update(actor, critic, actor_optimizer, critic_optimizer, sample, args, value_normalizer, update_actor, install, None, shards,
+                                   value_head)
             terms = (u.value_loss, u.policy_loss, u.dist_entropy, u.actor_grad_norm, u.critic_grad_norm, u.imp_weights.mean() if ratio is None else ratio)
             info = terms if info is None else tuple(a + b for a, b in zip(info, terms))
     if info is None:
         raise ValueError("train needs at least one minibatch: ppo_epoch = %d" % ppo_epoch)
     num_updates = ppo_epoch * num_mini_batch
     return {k: v / num_updates for k, v in zip(TRAIN_INFO, info)}
+
+
+# ---------------------------------------------------------------------------------------------- the rollout half
+def get_values(critic, share_obs, node_obs, adj, share_agent_id, rnn_states_critic, masks, out=None):
+    """GR_MAPPOPolicy.get_values (graphMAPPOPolicy.py) -> values [rows, 1], under torch.no_grad(): the critic chain of critic_forward with value_head
+    as v_out. out: value_head's — a float32 device tensor of `rows` elements written in place, e.g. a buffer's value_preds[t]."""
+    with torch.no_grad():
+        features, _ = _features(critic, _cent(critic, share_obs), node_obs, adj, share_agent_id, rnn_states_critic, masks)
+        return _value.value_head(features, critic.v_out, out=out)
+
+
+def _split_out(fn, out):
+    """get_actions' `out` -> (act_head's `out`, the tensor for the values or None)"""
+    if out is None:
+        return None, None
+    if not isinstance(out, dict):
+        raise ValueError("out must be a dict: %s takes act_head's entries and \"values\"" % fn)
+    out = dict(out)
+    return out, out.pop("values", None)
+
+
+def get_actions(actor, critic, share_obs, obs, node_obs, adj, agent_id, share_agent_id, rnn_states, rnn_states_critic, masks, available_actions=None,
+                deterministic=False, *, dones_prev=None, seed, env_id_base=0, num_agents, draw, draw_dev=None, out=None):
+    """GR_MAPPOPolicy.get_actions (graphMAPPOPolicy.py) -> (values, actions, action_log_probs, rnn_states, rnn_states_critic), the reference's order,
+    under torch.no_grad() on the current stream: actor_forward (its chain ends in act_head), then the critic chain ending in value_head.
+    The arrays and available_actions / dones_prev, seed, env_id_base, num_agents, draw, draw_dev: as for actor_forward and critic_forward.
+    out: actor_forward's dict, which may also hold "values" (value_head's out: float32, `rows` elements, written in place). The states come back
+    unchanged from a network without an RNN."""
+    act_out, values_out = _split_out("get_actions", out)
+    actions, logp, rnn_states = actor_forward(actor, obs, node_obs, adj, agent_id, rnn_states, masks, available_actions, deterministic,
+                                              dones_prev=dones_prev, seed=seed, env_id_base=env_id_base, num_agents=num_agents, draw=draw,
+                                              draw_dev=draw_dev, out=act_out)
+    with torch.no_grad():
+        features, rnn_states_critic = _features(critic, _cent(critic, share_obs), node_obs, adj, share_agent_id, rnn_states_critic, masks)
+        values = _value.value_head(features, critic.v_out, out=values_out)
+    return values, actions, logp, rnn_states, rnn_states_critic
+
+
+def _rollout_buffer(fn, actor, critic, buffer, returns=False):
+    """what the rollout entries need of a DeviceRolloutBuffer, checked before the device is touched"""
+    for name in ("engine", "step", "T", "value_preds", "act_outputs", "act_finish"):
+        if not hasattr(buffer, name):
+            raise ValueError("buffer must be a DeviceRolloutBuffer: %s reads buffer.%s" % (fn, name))
+    if buffer.value_preds is None or (returns and buffer.returns is None):
+        raise ValueError("%s needs a buffer with value_preds%s (policy_fields)" % (fn, " and returns" if returns else ""))
+    if getattr(buffer, "_node_obs", None) is None:
+        raise ValueError("%s reads node_obs rows: the buffer's engine must keep them (node_form 'rows' or 'both')" % fn)
+    if getattr(buffer, "_adj", None) is None:
+        raise ValueError("%s reads an adjacency: the buffer's engine must keep one (adj_form not 'none')" % fn)
+    for net, field in ((actor, "rnn_states"), (critic, "rnn_states_critic")):
+        if net is not None and _recurrent(net) and getattr(buffer, field, None) is None:
+            raise ValueError("the %s has an RNN: %s needs a buffer with %s (learner_fields)" % ("actor" if field == "rnn_states" else "critic", fn, field))
+
+
+def _slot_rows(buffer, t):
+    """slot t of the buffer's arrays as the networks take them: [N, A, ...] flattened to rows"""
+    e = buffer.engine
+    rows, E = e.N * e.A, int(buffer._node_obs.shape[-2])
+    flat = lambda x: None if x is None else x[t].reshape((rows,) + tuple(x.shape[3:]))
+    return dict(share_obs=flat(buffer.share_obs), obs=flat(buffer.obs), node_obs=flat(buffer._node_obs), adj=buffer._adj[t].reshape(-1, E, E),
+                agent_id=flat(buffer.agent_id), share_agent_id=flat(buffer.share_agent_id), rnn_states=flat(buffer.rnn_states),
+                rnn_states_critic=flat(buffer.rnn_states_critic), masks=flat(buffer.masks))
+
+
+def collect_step(actor, critic, buffer, deterministic=False):
+    """One step of run()'s loop (graph_mpe_runner.py:57-103: collect or collect_with_mask, envs.step, insert) on a DeviceRolloutBuffer built with
+    policy_fields and learner_fields: get_actions on slot buffer.step — the availability taken from dones[step - 1], everything available at step 0,
+    the draw keyed by buffer.act_draw, the values written into value_preds[step], the action and its log-prob into their slots —, then the env step,
+    the masks and the RNN states of slot step + 1 with the done rows zeroed, as DeviceRolloutBuffer.act_step does them. Bit for bit what
+    act_step(action_logits(...), value_head(...), rnn_states=..., rnn_states_critic=...) stores from the same layer calls. Nothing is copied to the
+    host and nothing waits for the device. Returns the engine's outputs of the step."""
+    _rollout_buffer("collect_step", actor, critic, buffer)
+    t, e = buffer.step, buffer.engine
+    c, rows = e.cfg, e.N * e.A
+    s = _slot_rows(buffer, t)
+    out = buffer.act_outputs()
+    out["values"] = buffer.value_preds[t]
+    buffer.available_actions_for(t)
+    _, _, _, h, hc = get_actions(actor, critic, s["share_obs"], s["obs"], s["node_obs"], s["adj"], s["agent_id"], s["share_agent_id"], s["rnn_states"],
+                                 s["rnn_states_critic"], s["masks"], None, deterministic, dones_prev=buffer.dones[t - 1].view(rows) if t else None,
+                                 seed=c.seed, env_id_base=c.env_id_base, num_agents=e.A, draw=buffer.act_draw, out=out)
+    learner = buffer._learner_inputs(None, None, None, h if _recurrent(actor) else None, hc if _recurrent(critic) else None, "collect_step")
+    return buffer.act_finish(learner)
+
+
+def compute(critic, buffer, value_normalizer=None):
+    """GMPERunner.compute (graph_mpe_runner.py:431-443): get_values on the last slot, then buffer.compute_returns(next_values, value_normalizer)
+    (with args.use_popart the normaliser is critic.v_out, as in the reference's trainer). Returns buffer.returns."""
+    _rollout_buffer("compute", None, critic, buffer, returns=True)
+    _, use_norm = buffer._flags("compute")
+    if use_norm and value_normalizer is None:
+        raise ValueError("compute: args.use_valuenorm / use_popart is set, so a value_normalizer is required")
+    e = buffer.engine
+    s = _slot_rows(buffer, buffer.T)
+    next_values = get_values(critic, s["share_obs"], s["node_obs"], s["adj"], s["share_agent_id"], s["rnn_states_critic"], s["masks"])
+    return buffer.compute_returns(next_values.view(e.N, e.A, 1), value_normalizer)
+
+
+def rollout(actor, critic, buffer, value_normalizer=None, deterministic=False):
+    """One episode of run()'s loop from buffer.step == 0 (after warmup() or after_update()): buffer.T calls of collect_step, then compute.
+    Returns buffer.returns."""
+    _rollout_buffer("rollout", actor, critic, buffer, returns=True)
+    if buffer.step != 0:
+        raise ValueError("rollout starts at buffer.step == 0, not %d (warmup() or after_update() first)" % buffer.step)
+    for _ in range(buffer.T):
+        collect_step(actor, critic, buffer, deterministic)
+    return compute(critic, buffer, value_normalizer)
+
+
+def iteration(actor, critic, actor_optimizer, critic_optimizer, buffer, args, value_normalizer=None, update_actor=True, perms=None, *,
+              deterministic=False, install="replace", accumulation_steps=1, shards=None, value_head="torch"):
+    """One iteration of run() (graph_mpe_runner.py:57-129): rollout, train, buffer.after_update(). Returns train's dict plus
+    average_episode_rewards = buffer.rewards.mean() * buffer.T (graph_mpe_runner.py:117), a 0-dim device tensor like the others.
+    update_actor, perms, install, accumulation_steps, shards, value_head: train's; deterministic: collect_step's."""
+    _refusals("iteration", accumulation_steps, shards)
+    _value_head_kind("iteration", value_head)
+    rollout(actor, critic, buffer, value_normalizer, deterministic)
+    info = train(actor, critic, actor_optimizer, critic_optimizer, buffer, args, value_normalizer, update_actor, perms, install=install,
+                 accumulation_steps=accumulation_steps, shards=shards, value_head=value_head)
+    info["average_episode_rewards"] = buffer.rewards.mean() * buffer.T
+    buffer.after_update()
+    return info
 
 
 def evaluator_act(actor, evaluator, deterministic=True, seed=0, draw0=0):

@@ -238,6 +238,17 @@ class DeviceRolloutBuffer(object):
         learner = self._learner_inputs(values, None, None, rnn_states, rnn_states_critic, "act_step")
         if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or tuple(logits.shape) != (rows, c.n_actions):
             raise ValueError("logits must be a tensor of shape (%d, %d)" % (rows, c.n_actions))
+        out = self.act_outputs()
+        self.available_actions_for(t)
+        sample_actions(logits, dones_prev=self.dones[t - 1] if t else None, stop_action=c.n_actions // 2 if t else None, seed=c.seed,
+                       env_id_base=c.env_id_base, num_agents=e.A, draw=self.act_draw, deterministic=deterministic, out=out)
+        return self.act_finish(learner)
+
+    def act_outputs(self):
+        """The `out` of the sampling launch of step `self.step` (act.sample_actions, head.act_head): actions[step] and action_log_probs[step] in place
+        where the buffer keeps them, the log-probs else into scratch the buffer owns, and the int32 action the env step then reads. What act_step
+        hands its own launch; gmpe.policy.collect_step hands it to the actor's."""
+        t, e = self.step, self.engine
         out = {}
         for name, key in (("actions", "actions_f32"), ("action_log_probs", "action_log_probs")):
             buf = getattr(self, name)
@@ -250,12 +261,15 @@ class DeviceRolloutBuffer(object):
             self._act_idx = torch.zeros((e.N, e.A), dtype=torch.int32, device=e.device)
         if "action_log_probs" not in out:
             if self._act_logp is None:
-                self._act_logp = torch.zeros((rows, 1), dtype=torch.float32, device=e.device)
+                self._act_logp = torch.zeros((e.N * e.A, 1), dtype=torch.float32, device=e.device)
             out["action_log_probs"] = self._act_logp
         out["action_idx"] = self._act_idx
-        self.available_actions_for(t)
-        sample_actions(logits, dones_prev=self.dones[t - 1] if t else None, stop_action=c.n_actions // 2 if t else None, seed=c.seed,
-                       env_id_base=c.env_id_base, num_agents=e.A, draw=self.act_draw, deterministic=deterministic, out=out)
+        return out
+
+    def act_finish(self, learner=None):
+        """What follows the sampling launch of step `self.step`: the env step on the action act_outputs() received, the masks, one gmpe_insert_learner
+        launch for `learner` (_learner_inputs' dict, or None), and the two counters."""
+        t, e = self.step, self.engine
         self._bind(t + 1)
         e.step(self._act_idx)
         e.masks_from_dones(self.dones[t], self.masks[t + 1], self.active_masks[t + 1])

@@ -1,0 +1,109 @@
+"""The reference runner's whole iteration (onpolicy/runner/shared/graph_mpe_runner.py:57-129) with the policy in the loop, on the device:
+
+    for episode in range(episodes):
+        for step in range(episode_length):
+            collect / collect_with_mask, envs.step, insert      ->  gmpe.policy.collect_step(actor, critic, buffer)
+        compute()                                               ->  gmpe.policy.compute(critic, buffer, value_normalizer)
+        train()                                                 ->  gmpe.policy.train(actor, critic, actor_optimizer, critic_optimizer, buffer, args, ...)
+        buffer.after_update()
+
+written out once (`by_pieces`) and as the one call that does the same (`gmpe.policy.iteration`). The networks are the caller's GR_Actor / GR_Critic,
+read by their attribute names; here they are stand-ins with those names (tests/test_gpu_policy.py's mirror modules with the shipped GNN and head
+weights), because the reference's modules need torch_geometric. Nothing between warmup() and the printed scalars is copied to the host.
+
+    python examples/policy_loop.py --envs 64 --agents 3 --episodes 3 [--popart]
+"""
+import argparse
+import os
+import sys
+import time
+import types
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))        # the stand-in networks
+import gmpe  # noqa: E402
+
+
+def runner_args(popart, episode_length):
+    """what the buffer, the losses and train read of the runner's args, with the reference's defaults"""
+    return types.SimpleNamespace(
+        gamma=0.99, gae_lambda=0.95, use_gae=True, use_proper_time_limits=False, use_popart=popart, use_valuenorm=not popart, clip_param=0.2,
+        huber_delta=10.0, entropy_coef=0.01, use_policy_active_masks=True, use_value_active_masks=True, use_clipped_value_loss=True, use_huber_loss=True,
+        use_max_grad_norm=True, max_grad_norm=10.0, value_loss_coef=1.0, use_recurrent_policy=True, use_naive_recurrent_policy=False, ppo_epoch=2,
+        num_mini_batch=1, data_chunk_length=10 if episode_length % 10 == 0 else episode_length, recurrent_N=1, hidden_size=64)
+
+
+def networks(cfg, eng, popart, dev):
+    import torch
+    import gnn_lib as G
+    import head_lib as HL
+    import trainer_lib as TL
+    from test_gpu_policy import _Net
+    key = G.ACTOR if int(cfg.node_feats) == 7 else G.ROTATE
+    actor = _Net(key, eng.D, "act").to(dev)
+    critic = _Net(key, eng.D, "popart" if popart else "v_out", seed=12).to(dev)
+    if popart:
+        class PopArt(HL.PopArt):                        # the reference's PopArt has debiased_mean_var (popart.py:85-89); the stand-in needs it too
+            def debiased_mean_var(self):
+                mean = self.mean / self.debiasing_term.clamp(min=self.epsilon)
+                return mean, (self.mean_sq / self.debiasing_term.clamp(min=self.epsilon) - mean ** 2).clamp(min=1e-2)
+        normalizer = critic.v_out = PopArt(dev)         # graph_mappo.py:63-64: the value normaliser IS the critic's output layer
+        params = list(critic.parameters()) + [critic.v_out.weight, critic.v_out.bias]
+    else:
+        class ValueNorm(TL.ValueNorm):
+            def running_mean_var(self):                 # valuenorm.py:48-55
+                mean = self.running_mean / self.debiasing_term.clamp(min=self.epsilon)
+                return mean, (self.running_mean_sq / self.debiasing_term.clamp(min=self.epsilon) - mean ** 2).clamp(min=1e-2)
+        normalizer, params = ValueNorm(dev), list(critic.parameters())
+    adam = lambda ps: torch.optim.Adam(ps, lr=7e-4, eps=1e-5, weight_decay=0)
+    return actor, critic, adam(list(actor.parameters())), adam(params), normalizer
+
+
+def by_pieces(actor, critic, aopt, copt, buf, args, normalizer):
+    """one iteration, call by call"""
+    from gmpe import policy
+    for _ in range(buf.T):
+        policy.collect_step(actor, critic, buf)         # get_actions on slot buf.step, the env step, the masks, the learner fields
+    policy.compute(critic, buf, normalizer)             # get_values on the last slot, then compute_returns
+    info = policy.train(actor, critic, aopt, copt, buf, args, normalizer, value_head="device")
+    info["average_episode_rewards"] = buf.rewards.mean() * buf.T
+    buf.after_update()
+    return info
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=64)
+    ap.add_argument("--agents", type=int, default=3)
+    ap.add_argument("--episode-length", type=int, default=20)
+    ap.add_argument("--episodes", type=int, default=3)
+    ap.add_argument("--popart", action="store_true", help="--use_popart: the critic's v_out is the value normaliser")
+    o = ap.parse_args()
+    import torch
+    from gmpe import policy
+    from gmpe.engine import GmpeEngine
+    from gmpe.rollout import DeviceRolloutBuffer
+    if not torch.cuda.is_available():
+        raise SystemExit("no GPU: the kernels have no CPU fallback")
+    dev = "cuda:0"
+    cfg = gmpe.make_config(num_envs=o.envs, num_agents=o.agents, episode_length=o.episode_length, seed=1)
+    eng = GmpeEngine(cfg, device=0)
+    args = runner_args(o.popart, o.episode_length)
+    actor, critic, aopt, copt, normalizer = networks(cfg, eng, o.popart, dev)
+    buf = DeviceRolloutBuffer(eng, o.episode_length, use_centralized_V=False, policy_fields="all", learner_fields="all", args=args)
+    buf.warmup()
+    for ep in range(o.episodes):
+        t0 = time.perf_counter()
+        if ep % 2 == 0:
+            info = by_pieces(actor, critic, aopt, copt, buf, args, normalizer)
+        else:
+            info = policy.iteration(actor, critic, aopt, copt, buf, args, normalizer, value_head="device")
+        line = {k: round(float(v), 5) for k, v in info.items()}             # the one read-back of the iteration
+        print("episode %d (%s) %.0f ms: %s" % (ep, "by pieces" if ep % 2 == 0 else "policy.iteration", (time.perf_counter() - t0) * 1e3, line))
+    eng.check_errors()
+    eng.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -674,6 +674,46 @@ int gmpe_head_forward(int device, const gmpe_head_plan* plan, void* stream);
 int gmpe_head_backward(int device, const gmpe_head_plan* plan, void* stream);
 int gmpe_act_head(int device, const gmpe_act_plan* act_plan, const gmpe_head_plan* head_plan, void* stream);
 
+/* ---- The critic's value head (handle-less): v_out of GR_Critic, an nn.Linear(64, 1) or a PopArt(64, 1) read as one ----
+ * values = features W^T + b (onpolicy/algorithms/graph_actor_critic.py:395) with weight [1, hidden], bias [1], float32, contiguous, hidden == 64;
+ * everything else is GMPE_ERR_INVALID_ARG with the function and the field in gmpe_last_error, before any launch. No allocation, no atomics, no host
+ * synchronisation; every launch on `stream`; capturable.
+ *
+ * gmpe_value_forward, ONE launch:
+ *   values_out[r] = the dot product gmpe_ppo_loss_popart evaluates at hidden == 64, bit for bit: a row is held by 16 lanes, lane c holding columns
+ *   4c .. 4c+3; acc = 0.0f, then acc = acc + features[r, 4c + i] * weight[4c + i] for i = 0 .. 3, multiply and add each rounded on its own; the 16 lanes
+ *   by an xor tree over offsets 1, 2, 4, 8 with the lower lane as the left operand; then + bias. A row's bits are a function of that row and the
+ *   parameters alone: not of rows, not of the row's place in the call, not of the width of the loads (16-byte units where features is 16-byte aligned,
+ *   4-byte units otherwise). So the value_preds a rollout stores are what gmpe_ppo_loss_popart recomputes on a minibatch of any other size.
+ * gmpe_value_backward, at most TWO launches, from grad_values [rows] (features and weight as in forward; bias and values_out are not read):
+ *   grad_features[r, j] = grad_values[r] * weight[j], one float32 product;
+ *   grad_weight[j]      = sum over r of grad_values[r] * features[r, j], grad_bias = sum over r of grad_values[r], of exact double products: within a
+ *                         tile of 256 rows, wave w (rows 64w .. 64w+63) adds the rows 4p + s of each s = 0 .. 3 over p = 0 .. 15 ascending, the four s by
+ *                         an xor tree (s ^ 1, then s ^ 2; the lower the left operand), the four waves in wave order; the tiles as 16 interleaved slices
+ *                         (slice q: tiles q, q + 16, ... ascending), the slices in slice order; rounded to float32 once.
+ *   So the order is a function of rows alone and two calls give the same bits. Each of the three outputs may be NULL and is then not formed.
+ * Workspace (backward only; gmpe_value_workspace_bytes is the single source of its size; its contents before the call do not matter):
+ *   f64 [ceil(rows / 256)][80] the tiles' column sums (64 weight columns, the bias column, padding). A forward-only plan needs none. */
+typedef struct gmpe_value_plan {
+    int64_t rows;                       /* >= 1                                                                                       */
+    int32_t hidden;                     /* 64                                                                                         */
+    int32_t reserved;
+    const float* features;              /* [rows, 64] the critic features                                                             */
+    const float* weight;                /* [1, 64]                                                                                    */
+    const float* bias;                  /* [1]; forward only                                                                          */
+    float* values_out;                  /* [rows]; forward: required, may point into the buffer's value_preds[t]; backward: not read  */
+    const float* grad_values;           /* [rows]; backward only                                                                      */
+    float* grad_features;               /* [rows, 64] or NULL; backward only                                                          */
+    float* grad_weight;                 /* [1, 64] or NULL; backward only                                                             */
+    float* grad_bias;                   /* [1] or NULL; backward only                                                                 */
+    void* workspace;                    /* gmpe_value_workspace_bytes(rows, 1) bytes, 8-byte aligned; backward only                   */
+    size_t workspace_bytes;
+} gmpe_value_plan;
+/* want_backward == 0: 0 bytes. */
+int gmpe_value_workspace_bytes(int64_t rows, int32_t want_backward, size_t* bytes_out);
+int gmpe_value_forward(int device, const gmpe_value_plan* plan, void* stream);
+int gmpe_value_backward(int device, const gmpe_value_plan* plan, void* stream);
+
 /* ---- The gradient clip and the Adam step of GR_MAPPO.ppo_update (handle-less) ----
  * nn.utils.clip_grad_norm_ followed by torch.optim.Adam.step (onpolicy/algorithms/graph_mappo.py:212-227 and :254-265) over a table of float32 tensors:
  * the 2-norm of the gradients flagged GMPE_OPT_T_IN_NORM, those gradients scaled by the clip coefficient, and torch's single-tensor Adam on the tensors
