@@ -27,7 +27,8 @@ SYMBOLS = ["gmpe_abi_version", "gmpe_last_error", "gmpe_obs_dim", "gmpe_node_fea
            "gmpe_gnn_workspace_bytes", "gmpe_gnn_forward", "gmpe_gnn_backward",
            "gmpe_head_workspace_bytes", "gmpe_head_forward", "gmpe_head_backward", "gmpe_act_head",
            "gmpe_value_workspace_bytes", "gmpe_value_forward", "gmpe_value_backward",
-           "gmpe_optim_workspace_bytes", "gmpe_optim_step", "gmpe_optim_shard_elems", "gmpe_optim_step_shard"]
+           "gmpe_optim_workspace_bytes", "gmpe_optim_step", "gmpe_optim_shard_elems", "gmpe_optim_step_shard",
+           "gmpe_optim_schedule_bytes", "gmpe_optim_schedule_fill", "gmpe_optim_step_scheduled"]
 
 
 class GmpeOutputs(C.Structure):
@@ -270,6 +271,7 @@ class GmpeGnnPlan(C.Structure):
 OPT_MAX_TENSORS, OPT_MAX_HYPERS, OPT_CHUNK, OPT_MAX_PLAN_TENSORS, OPT_MAX_NUMEL = 64, 8, 1024, 4096, 1 << 30
 OPT_CLIP, OPT_STEP = 1, 2
 OPT_T_IN_NORM, OPT_T_STEP = 1, 2
+OPT_HYPER_FLOATS, OPT_MAX_SCHEDULE_ROWS = 7, 1 << 20
 
 
 class GmpeOptimTensor(C.Structure):
@@ -294,6 +296,12 @@ class GmpeOptimShardPlan(C.Structure):
     """gmpe_optim_shard_plan (include/gmpe.h): gmpe_optim_plan in two phases around an all-gather of the shards' packed gradients."""
     _fields_ = [("base", GmpeOptimPlan), ("phase", C.c_int32), ("world", C.c_int32), ("local", C.c_void_p), ("all", C.c_void_p),
                 ("local_elems", C.c_int64)]
+
+
+class GmpeOptimSchedPlan(C.Structure):
+    """gmpe_optim_sched_plan (include/gmpe.h): gmpe_optim_plan with Adam's step count on the device — the Hyper sets of `rows` steps and a counter."""
+    _fields_ = [("base", GmpeOptimPlan), ("schedule", C.c_void_p), ("counter", C.c_void_p), ("status", C.c_void_p), ("rows", C.c_int32),
+                ("reserved", C.c_int32)]
 
 
 class GmpeError(RuntimeError):
@@ -382,6 +390,9 @@ def load():
     lib.gmpe_optim_step.argtypes = [I, C.POINTER(GmpeOptimPlan), P]
     lib.gmpe_optim_shard_elems.argtypes = [C.POINTER(GmpeOptimPlan), C.POINTER(C.c_int64)]
     lib.gmpe_optim_step_shard.argtypes = [I, C.POINTER(GmpeOptimShardPlan), P]
+    lib.gmpe_optim_schedule_bytes.argtypes = [C.POINTER(GmpeOptimPlan), C.c_int32, C.POINTER(C.c_size_t)]
+    lib.gmpe_optim_schedule_fill.argtypes = [C.POINTER(GmpeOptimPlan), C.c_int32, P]
+    lib.gmpe_optim_step_scheduled.argtypes = [I, C.POINTER(GmpeOptimSchedPlan), P]
     from .config import ABI_VERSION
     if lib.gmpe_abi_version() != ABI_VERSION:
         raise GmpeError("libgmpe.so ABI version mismatch")

@@ -6,8 +6,9 @@
 // The table is a kernel argument (64 descriptors of 40 bytes + 8 hyper-parameter sets of 28 bytes: under the 4 KB of a kernel's arguments), so a call
 // uploads nothing, allocates nothing and waits for nothing. Sizes are tiny (about 41 000 elements for the shipped actor): the job is few launches, not
 // bandwidth, which is why a lane finds its tensor by a binary search over the prefix sums rather than through a precomputed map in device memory.
-// The table, the search and the workgroup sum are gmpe_optim_table.h's, shared with gmpe_optim_shard.hip (gmpe_optim_step_shard), which launches this file's
-// k_opt_step through launch_steps() behind its own sum kernel.
+// The table, the search, the workgroup sum and k_opt_step itself (a template, instantiated here with the sets in the kernel arguments) are
+// gmpe_optim_table.h's, shared with gmpe_optim_shard.hip (gmpe_optim_step_shard), which launches this file's k_opt_step through launch_steps() behind its
+// own sum kernel, and with gmpe_optim_sched.hip (gmpe_optim_step_scheduled), which instantiates it over a schedule in device memory.
 #include <math.h>
 
 #include "gmpe_optim_table.h"
@@ -31,52 +32,6 @@ __global__ __launch_bounds__(BLOCK) void k_opt_norm(const Table tb, double* __re
     }
     const double tot = block_sum(s, red);
     if (threadIdx.x == 0) part[blockIdx.x] = tot;
-}
-
-struct StepArgs {
-    const double* part;            // the chunks' sums of ALL groups
-    int32_t n_parts;
-    int32_t clip, step, first;     // plan flags; first: this launch's workgroup 0 writes out
-    double max_norm;
-    double* out;
-    float* norm_f32;
-};
-
-__global__ __launch_bounds__(BLOCK) void k_opt_step(const Table tb, const StepArgs a) {
-    __shared__ double red[BLOCK];
-    double s = 0.0;
-    for (int j = threadIdx.x; j < a.n_parts; j += BLOCK) s += a.part[j];
-    const double norm = sqrt(block_sum(s, red));
-    float coef = 1.0f;
-    if (a.clip) {
-        const double c = a.max_norm / (norm + 1e-6);
-        coef = (float)(c > 1.0 ? 1.0 : c);                           // NaN stays NaN, as torch.clamp keeps it
-    }
-    if (a.first && blockIdx.x == 0 && threadIdx.x == 0) {
-        a.out[0] = norm; a.out[1] = (double)coef;
-        if (a.norm_f32) a.norm_f32[0] = (float)norm;
-    }
-    const uint32_t e0 = blockIdx.x * (uint32_t)CHUNK + threadIdx.x;
-    for (int k = 0; k < PER_THREAD; ++k) {
-        const uint32_t e = e0 + (uint32_t)k * BLOCK;
-        if (e >= tb.total) break;
-        const Desc& d = tb.d[find_tensor(tb, e)];
-        const uint32_t o = e - d.start;
-        const bool scale = a.clip && (d.flags & GMPE_OPT_T_IN_NORM), step = a.step && (d.flags & GMPE_OPT_T_STEP);
-        if (!scale && !step) continue;
-        float g = d.g[o];
-        if (scale) { g = g * coef; d.g[o] = g; }
-        if (step) {
-            const Hyper& h = tb.h[d.hyper];
-            float p = d.p[o], m = d.m[o], v = d.v[o];
-            if (h.wd != 0.0f) g = g + h.wd * p;
-            m = m + (g - m) * h.w1;
-            v = h.b2 * v + (h.w2 * g) * g;
-            const float denom = sqrtf(v) / h.s2 + h.eps;
-            p = p - h.a * (m / denom);
-            d.m[o] = m; d.v[o] = v; d.p[o] = p;
-        }
-    }
 }
 
 using gmpe::fail;
@@ -103,9 +58,10 @@ int check_geometry(const char* fn, const gmpe_optim_plan* pl) {
 // The launch groups of a checked plan, filled as far as `depth` says: the geometry alone, with the pointers (GRADS), or with the pointers and the float32
 // hyper-parameters (STEP).
 void layout(const gmpe_optim_plan* pl, Depth depth, Layout& y) {
-    int slot_of[MAXH];             // the plan's hyper index in each of the current group's slots
     int n_slots = 0;
     y.groups.emplace_back();
+    y.slot_hyper.assign(MAXH, -1);
+    int* slot_of = &y.slot_hyper[0];                                 // the plan's hyper index in each of the current group's slots
     Table* tb = &y.groups.back();
     tb->total = 0; tb->n = 0;
     for (int i = 0; i < pl->n_tensors; ++i) {
@@ -116,17 +72,14 @@ void layout(const gmpe_optim_plan* pl, Depth depth, Layout& y) {
         if (steps) for (slot = 0; slot < n_slots && slot_of[slot] != t.hyper; ++slot) {}
         if (tb->n == MAXT || (steps && slot == MAXH) || (uint64_t)tb->total + (uint64_t)t.numel > GROUP_LIMIT) {
             y.groups.emplace_back();
+            y.slot_hyper.resize(y.groups.size() * MAXH, -1);
+            slot_of = &y.slot_hyper[(y.groups.size() - 1) * MAXH];
             tb = &y.groups.back();
             tb->total = 0; tb->n = 0; n_slots = 0; slot = 0;
         }
         if (steps && slot == n_slots) {
             slot_of[n_slots++] = t.hyper;
-            if (depth == STEP) {
-                const gmpe_optim_hyper& h = pl->hypers[t.hyper];
-                const double bc1 = 1.0 - pow(h.beta1, (double)h.t), bc2 = 1.0 - pow(h.beta2, (double)h.t);
-                tb->h[slot] = Hyper{(float)h.weight_decay, (float)(1.0 - h.beta1), (float)h.beta2, (float)(1.0 - h.beta2), (float)(h.lr / bc1),
-                                    (float)sqrt(bc2), (float)h.eps};
-            }
+            if (depth == STEP) tb->h[slot] = make_hyper(pl->hypers[t.hyper], pl->hypers[t.hyper].t);
         }
         Desc& d = tb->d[tb->n++];
         d.start = tb->total; d.flags = (uint16_t)t.flags; d.hyper = (uint16_t)slot;
@@ -154,16 +107,7 @@ int gmpe_opt::prepare(const char* fn, const gmpe_optim_plan* pl, Depth depth, La
         if (pl->flags & ~(GMPE_OPT_CLIP | GMPE_OPT_STEP)) return fail(fn, "flags must be GMPE_OPT_CLIP, GMPE_OPT_STEP, both or 0");
         if (pl->reserved != 0) return fail(fn, "reserved must be 0");
         const bool clip = pl->flags & GMPE_OPT_CLIP, step = pl->flags & GMPE_OPT_STEP;
-        for (int i = 0; i < pl->n_hypers; ++i) {
-            const gmpe_optim_hyper& h = pl->hypers[i];
-            const std::string at = "hypers[" + std::to_string(i) + "].";
-            if (!(h.lr >= 0.0)) return fail(fn, at + "lr must be >= 0");
-            if (!(h.beta1 >= 0.0 && h.beta1 < 1.0)) return fail(fn, at + "beta1 must be in [0, 1)");
-            if (!(h.beta2 >= 0.0 && h.beta2 < 1.0)) return fail(fn, at + "beta2 must be in [0, 1)");
-            if (!(h.eps >= 0.0)) return fail(fn, at + "eps must be >= 0");
-            if (!(h.weight_decay >= 0.0)) return fail(fn, at + "weight_decay must be >= 0");
-            if (h.t < 1) return fail(fn, at + "t must be >= 1");
-        }
+        if (int rc = check_hypers(fn, pl)) return rc;
         if (clip && !(pl->max_norm > 0.0)) return fail(fn, "max_norm must be > 0 with GMPE_OPT_CLIP");
         for (int i = 0; i < pl->n_tensors; ++i) {
             const gmpe_optim_tensor& t = pl->tensors[i];
@@ -182,15 +126,40 @@ int gmpe_opt::prepare(const char* fn, const gmpe_optim_plan* pl, Depth depth, La
     return GMPE_OK;
 }
 
-int gmpe_opt::launch_steps(const gmpe_optim_plan* pl, const Layout& y, hipStream_t st) {
-    StepArgs a = {static_cast<const double*>(pl->workspace), (int32_t)y.n_chunks, (pl->flags & GMPE_OPT_CLIP) != 0, (pl->flags & GMPE_OPT_STEP) != 0, 0,
-                  pl->max_norm, pl->out, pl->grad_norm_f32};
-    for (size_t g = 0; g < y.groups.size(); ++g) {
-        a.first = g == 0;
-        const int64_t grid = y.chunks[g] > 0 ? y.chunks[g] : (g == 0 ? 1 : 0);
-        if (grid > 0) GMPE_LAUNCH(k_opt_step, dim3((unsigned)grid), dim3(BLOCK), 0, st, y.groups[g], a);
+int gmpe_opt::check_hypers(const char* fn, const gmpe_optim_plan* pl) {
+    for (int i = 0; i < pl->n_hypers; ++i) {
+        const gmpe_optim_hyper& h = pl->hypers[i];
+        const std::string at = "hypers[" + std::to_string(i) + "].";
+        if (!(h.lr >= 0.0)) return fail(fn, at + "lr must be >= 0");
+        if (!(h.beta1 >= 0.0 && h.beta1 < 1.0)) return fail(fn, at + "beta1 must be in [0, 1)");
+        if (!(h.beta2 >= 0.0 && h.beta2 < 1.0)) return fail(fn, at + "beta2 must be in [0, 1)");
+        if (!(h.eps >= 0.0)) return fail(fn, at + "eps must be >= 0");
+        if (!(h.weight_decay >= 0.0)) return fail(fn, at + "weight_decay must be >= 0");
+        if (h.t < 1) return fail(fn, at + "t must be >= 1");
     }
     return GMPE_OK;
+}
+
+int gmpe_opt::launch_norms(const gmpe_optim_plan* pl, const Layout& y, hipStream_t st) {
+    double* part = static_cast<double*>(pl->workspace);
+    int64_t base = 0;
+    for (size_t g = 0; g < y.groups.size(); ++g) {
+        if (y.chunks[g] > 0) GMPE_LAUNCH(k_opt_norm, dim3((unsigned)y.chunks[g]), dim3(BLOCK), 0, st, y.groups[g], part + base);
+        base += y.chunks[g];
+    }
+    return GMPE_OK;
+}
+
+gmpe_opt::StepArgs gmpe_opt::step_args(const gmpe_optim_plan* pl, const Layout& y) {
+    return StepArgs{static_cast<const double*>(pl->workspace), (int32_t)y.n_chunks, (pl->flags & GMPE_OPT_CLIP) != 0, (pl->flags & GMPE_OPT_STEP) != 0, 0,
+                    pl->max_norm, pl->out, pl->grad_norm_f32, nullptr, nullptr, nullptr, 0, 0, 0};
+}
+
+int gmpe_opt::launch_steps(const gmpe_optim_plan* pl, const Layout& y, hipStream_t st) { return launch_step_groups<false>(y, step_args(pl, y), st); }
+
+gmpe_opt::Hyper gmpe_opt::make_hyper(const gmpe_optim_hyper& h, int64_t t) {
+    const double bc1 = 1.0 - pow(h.beta1, (double)t), bc2 = 1.0 - pow(h.beta2, (double)t);
+    return Hyper{(float)h.weight_decay, (float)(1.0 - h.beta1), (float)h.beta2, (float)(1.0 - h.beta2), (float)(h.lr / bc1), (float)sqrt(bc2), (float)h.eps};
 }
 
 extern "C" {
@@ -209,12 +178,7 @@ int gmpe_optim_step(int device, const gmpe_optim_plan* pl, void* stream) {
     if (int rc = prepare("gmpe_optim_step", pl, STEP, y)) return rc;
     GMPE_HIP_CHECK(hipSetDevice(device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    double* part = static_cast<double*>(pl->workspace);
-    int64_t base = 0;
-    for (size_t g = 0; g < y.groups.size(); ++g) {
-        if (y.chunks[g] > 0) GMPE_LAUNCH(k_opt_norm, dim3((unsigned)y.chunks[g]), dim3(BLOCK), 0, st, y.groups[g], part + base);
-        base += y.chunks[g];
-    }
+    if (int rc = launch_norms(pl, y, st)) return rc;
     return launch_steps(pl, y, st);
 }
 

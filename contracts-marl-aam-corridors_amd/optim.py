@@ -8,6 +8,10 @@ For a data-parallel learner (include/gmpe.h gmpe_optim_step_shard) the same call
 rank order in double and rounded once — clip_and_step_begin, x.exchange(.local), clip_and_step_finish: one launch per 64 tensors before the all-gather
 and two after it. No DistributedDataParallel is involved, and the replicas stay bit-identical.
 
+For a captured graph of the step (include/gmpe.h gmpe_optim_step_scheduled) ScheduledStep is the same call over a table built once, with Adam's step count
+in device memory: .step() has the same kernel arguments at every call, so torch.cuda.graph can replay it; gmpe.policy.CapturedUpdate replays a whole
+ppo_update on it.
+
 The optimiser stays the caller's unchanged torch.optim.Adam: its param_groups are read at every call, its state holds torch's own keys, so
 optimizer.state_dict(), load_state_dict and a later optimizer.step() by torch keep working, in either order. There is no torch fallback: the tensors must
 be on a HIP device.
@@ -276,6 +280,138 @@ def clip_and_step(optimizer, max_grad_norm=None, *, parameters=None, step=True, 
     _lib.check(lib.gmpe_optim_step(_ordinal(dev), C.byref(plan), _stream_of(dev)), "gmpe_optim_step")
     _count(steps, rows)
     return grad_norm
+
+
+STEPS_AHEAD = 1024
+
+
+class _Budget(object):
+    """The host's count of a schedule's rows: `issued` steps launched from the host, `advanced` steps the host-side step counts were moved by (a replayed
+    graph launches nothing from here, so its steps are only ever advanced). The device counter stands at the larger of the two."""
+
+    def __init__(self, rows):
+        self.rows, self.issued, self.advanced = int(rows), 0, 0
+
+    @property
+    def remaining(self):
+        return self.rows - max(self.issued, self.advanced)
+
+    def need(self, fn, n=1):
+        if self.remaining < n:
+            raise RuntimeError("%s: the schedule holds %d steps and %d are used: %d more would run past it (refill() first, or build it with a larger "
+                               "steps_ahead)" % (fn, self.rows, self.rows - self.remaining, n))
+
+
+class ScheduledStep(object):
+    """clip_and_step over a table that is built once, with Adam's step count on the device (include/gmpe.h gmpe_optim_step_scheduled): the float32
+    hyper-parameter sets of the next `steps_ahead` step counts lie in device memory, a device counter picks the row and the call's last launch advances
+    it. The kernel arguments are the same at every call, so .step() may be captured in a torch.cuda.graph and replayed; its bits are clip_and_step's.
+
+        sched = gmpe.optim.ScheduledStep(optimizer, max_grad_norm, parameters=net.parameters())      # after a backward: the gradients exist
+        grad_norm = sched.step(); sched.advance_host()                                                 # == clip_and_step(optimizer, max_grad_norm, ...)
+
+      optimizer, max_grad_norm, parameters, workspace: clip_and_step's, with its refusals, all at construction. The table holds the tensors that have a
+        gradient NOW; missing Adam state is created as torch creates it. The gradients must stay these tensors (write new values into them: backward
+        into a kept .grad, or copy_): .step() raises RuntimeError when a .grad was replaced. shards= is not offered (no collective inside a graph).
+      steps_ahead: rows of the schedule. .remaining counts the unused ones on the host; .step() raises RuntimeError instead of launching past the last
+        (a raw C caller gets the device-side status, .status, set to 1 and nothing touched).
+      .step() -> grad_norm, ONE static 0-dim float32 device tensor that every call overwrites. It does not move the host-side step counts:
+      .advance_host(n) adds n to state["step"] of every stepped tensor — after n steps or replays optimizer.state_dict() is what n clip_and_step calls
+        leave, and torch's step() or clip_and_step can take over.
+      .refill() re-reads param_groups (a decayed lr) and the host step counts, rewrites the schedule and zeroes the counter with copies on the current
+        stream, nothing waits. A graph captured before stays valid: the addresses do not change."""
+
+    def __init__(self, optimizer, max_grad_norm=None, *, parameters=None, steps_ahead=STEPS_AHEAD, workspace=None):
+        self.clip, self.max_grad_norm = _max_norm(max_grad_norm)
+        steps_ahead = int(steps_ahead)
+        if not 1 <= steps_ahead <= _lib.OPT_MAX_SCHEDULE_ROWS:
+            raise ValueError("steps_ahead must be in 1 .. %d, not %d" % (_lib.OPT_MAX_SCHEDULE_ROWS, steps_ahead))
+        self.optimizer = optimizer
+        with torch.no_grad():
+            hypers, rows, dev = _table(optimizer, parameters, True)
+            _too_many(len(rows))
+            if not rows:
+                raise ValueError("no tensor has a gradient: ScheduledStep builds its table from the gradients there are (run a backward first)")
+            self.rows, self.dev = rows, dev
+            self.grads = [p.grad for p, _, _, _ in rows]
+            self._bind(hypers)
+            lib = _lib.load()
+            need = C.c_size_t()
+            _lib.check(lib.gmpe_optim_workspace_bytes(C.byref(self.plan.base), C.byref(need)), "gmpe_optim_workspace_bytes")
+            self.workspace = _workspace(int(need.value), workspace, dev)
+            self.grad_norm, self.out = _outputs(self.plan.base, self.workspace, dev)
+            _lib.check(lib.gmpe_optim_schedule_bytes(C.byref(self.plan.base), steps_ahead, C.byref(need)), "gmpe_optim_schedule_bytes")
+            self.schedule = torch.zeros((int(need.value) // 4,), dtype=torch.float32, device=dev)
+            self.counter = torch.zeros((1,), dtype=torch.int32, device=dev)
+            self.status = torch.zeros((1,), dtype=torch.int32, device=dev)
+            self.plan.schedule, self.plan.counter, self.plan.status = self.schedule.data_ptr(), self.counter.data_ptr(), self.status.data_ptr()
+            self.plan.rows = steps_ahead
+            self._upload()
+
+    def _bind(self, hypers):
+        base, self._keep, self.steps = _bind(hypers, self.rows, self.clip, self.max_grad_norm, True)
+        plan = getattr(self, "plan", None)
+        if plan is None:
+            self.plan = plan = _lib.GmpeOptimSchedPlan()
+        else:                                               # refill: the table must be the one the schedule's slots were laid out for
+            if bytes(self._keep[0]) != self._table_bytes:
+                raise RuntimeError("the table changed (a parameter, its state or its step count no longer matches): build a new ScheduledStep")
+            base.out, base.grad_norm_f32, base.workspace, base.workspace_bytes = plan.base.out, plan.base.grad_norm_f32, plan.base.workspace, \
+                plan.base.workspace_bytes
+        plan.base = base
+        self._table_bytes, self.hypers = bytes(self._keep[0]), hypers
+
+    def _upload(self):
+        host = torch.empty((self.schedule.numel(),), dtype=torch.float32, pin_memory=True)
+        _lib.check(_lib.load().gmpe_optim_schedule_fill(C.byref(self.plan.base), self.plan.rows, host.data_ptr()), "gmpe_optim_schedule_fill")
+        self.schedule.copy_(host, non_blocking=True)
+        self.counter.zero_()
+        self._budget = _Budget(self.plan.rows)
+
+    @property
+    def remaining(self):
+        return self._budget.remaining
+
+    def check_grads(self):
+        if any(p.grad is not g for (p, _, _, _), g in zip(self.rows, self.grads)):
+            raise RuntimeError("a gradient was replaced since the ScheduledStep was built: its table holds the tensors that were .grad then "
+                               "(write into them, e.g. zero_grad(set_to_none=False))")
+
+    def stale(self):
+        """whether param_groups no longer hold the hyper-parameters the schedule was filled with"""
+        return _groups(self.optimizer) != self.hypers
+
+    @torch.no_grad()
+    def step(self):
+        capturing = torch.cuda.is_current_stream_capturing()
+        if not capturing:
+            self._budget.need("ScheduledStep.step")
+        self.check_grads()
+        _lib.check(_lib.load().gmpe_optim_step_scheduled(_ordinal(self.dev), C.byref(self.plan), _stream_of(self.dev)), "gmpe_optim_step_scheduled")
+        if not capturing:
+            self._budget.issued += 1
+        return self.grad_norm
+
+    def advance_host(self, n=1):
+        n = int(n)
+        if n < 0:
+            raise ValueError("n must be >= 0")
+        if self.steps and all(isinstance(t, torch.Tensor) for t in self.steps):
+            torch._foreach_add_(self.steps, n)
+        else:
+            for _, _, _, st in self.rows:
+                if st is not None:
+                    st["step"] += n
+        self._budget.advanced += n
+
+    @torch.no_grad()
+    def refill(self):
+        if self._budget.issued > self._budget.advanced:
+            raise RuntimeError("ScheduledStep.refill: %d steps were issued and the host step counts advanced by %d: advance_host() first, the new "
+                               "schedule starts at the host's counts" % (self._budget.issued, self._budget.advanced))
+        self.check_grads()
+        self._bind(_groups(self.optimizer))
+        self._upload()
 
 
 MAX_EXTRA = 16

@@ -26,6 +26,7 @@ from .gnn import gnn_base
 from .gru import rnn_layer
 from .head import act_head, action_logits
 from .mlp import mlp_base
+from . import optim as _optim
 from .optim import clip_and_step
 from .ppo_loss import ppo_losses, ppo_losses_popart
 from . import value as _value
@@ -204,6 +205,208 @@ def train(actor, critic, actor_optimizer, critic_optimizer, buffer, args, value_
         raise ValueError("train needs at least one minibatch: ppo_epoch = %d" % ppo_epoch)
     num_updates = ppo_epoch * num_mini_batch
     return {k: v / num_updates for k, v in zip(TRAIN_INFO, info)}
+
+
+# ---------------------------------------------------------------------------------------------- one update as a captured graph
+_NORM_TENSORS = ("running_mean", "running_mean_sq", "debiasing_term", "weight", "bias", "stddev", "mean", "mean_sq")      # ValueNorm's and PopArt's
+
+
+def _same_sample(fn, static, sample):
+    """`sample` must be the 16-tuple the graph was captured for: the same entries, shapes, dtypes and device"""
+    if not isinstance(sample, (tuple, list)) or len(sample) != 16:
+        raise ValueError("sample must be the generators' 16-tuple")
+    for i, (a, b) in enumerate(zip(static, sample)):
+        if (a is None) != (b is None):
+            raise ValueError("%s: sample[%d] is %s, and the captured graph was built %s it" % (fn, i, "None" if b is None else "given",
+                                                                                             "without" if a is None else "with"))
+        if a is not None and (not isinstance(b, torch.Tensor) or b.shape != a.shape or b.dtype != a.dtype or b.device != a.device):
+            raise ValueError("%s: sample[%d] must be %s %s on %s as at capture, not %s %s on %s — a captured graph is fixed to its shapes (the minibatch "
+                             "rows follow from T, N, A, data_chunk_length and num_mini_batch)"
+                             % (fn, i, tuple(a.shape), a.dtype, a.device, tuple(getattr(b, "shape", ())), getattr(b, "dtype", type(b).__name__),
+                                getattr(b, "device", "the host")))
+
+
+def _unique(tensors):
+    seen, out = set(), []
+    for t in tensors:
+        if isinstance(t, torch.Tensor) and id(t) not in seen:
+            seen.add(id(t))
+            out.append(t)
+    return out
+
+
+class CapturedUpdate(object):
+    """ppo_update(..., install="in_place") captured once as a torch.cuda.CUDAGraph and replayed: the same kernels on the same inputs in the same order, so
+    the same bits, with one host call per minibatch where ppo_update issues about a hundred. The two clip_and_step calls are
+    gmpe.optim.ScheduledStep.step(), whose Adam step count lives on the device.
+
+        cap = gmpe.policy.CapturedUpdate(actor, critic, actor_optimizer, critic_optimizer, sample, args, value_normalizer)
+        u = cap.update(sample)        # or: train_info = cap.train(buffer)
+
+      sample: a 16-tuple of the generator the updates will come from; only its shapes, dtypes and device matter, and every later sample must have them.
+      args, value_normalizer, update_actor, value_head: ppo_update's, fixed at construction. install: "in_place" only — with args.use_popart,
+        "replace" creates new Parameters at every update, whose addresses a captured graph cannot follow, and is refused.
+      steps_ahead: rows of the two schedules (gmpe.optim.ScheduledStep); update raises RuntimeError before it would run past them, refill() starts
+        them again from the optimisers' current param_groups (a decayed lr) and step counts, and train() refills by itself when it has to.
+    Construction runs the update twice on a side stream (the warm-up torch.cuda.graph asks for) and once under capture, then puts every tensor the
+    update writes back bit for bit: parameters, Adam moments, the ValueNorm / PopArt tensors and the gradients are as before (missing Adam state is
+    created as torch creates it: zeros, step 0). Afterwards the .grad of every parameter the losses reach is a fixed tensor that each update overwrites
+    (a parameter that had none gets one, zero-filled; replace one and update raises); a parameter they do not reach keeps the .grad it had.
+    update(sample) -> the static PPOUpdate: device scalars and imp_weights that the NEXT update overwrites. It copies `sample` into the captured
+    tensors, replays and moves the host-side step counts; nothing waits for the device. Everything runs on the current stream, as one linear graph."""
+
+    def __init__(self, actor, critic, actor_optimizer, critic_optimizer, sample, args, value_normalizer=None, update_actor=True, *, install="in_place",
+                 value_head="torch", steps_ahead=None):
+        if install != "in_place":
+            raise NotImplementedError("install = %r: a captured update takes \"in_place\" only — \"replace\" creates new Parameters at every update, "
+                                      "whose addresses a captured graph cannot follow (not supported under capture)" % (install,))
+        _value_head_kind("CapturedUpdate", value_head)
+        _optim._groups(actor_optimizer)
+        _optim._groups(critic_optimizer)
+        if not isinstance(sample, (tuple, list)) or len(sample) != 16:
+            raise ValueError("sample must be the generators' 16-tuple")
+        dev = sample[1].device
+        if dev.type != "cuda":
+            raise ValueError("the arrays must be CUDA (HIP) device tensors: these kernels have no CPU fallback")
+        self.actor, self.critic, self.actor_optimizer, self.critic_optimizer = actor, critic, actor_optimizer, critic_optimizer
+        self.args, self.value_normalizer, self.update_actor, self.value_head = args, value_normalizer, bool(update_actor), value_head
+        self.max_norm = getattr(args, "max_grad_norm", 10.0) if getattr(args, "use_max_grad_norm", True) else None
+        steps_ahead = _optim.STEPS_AHEAD if steps_ahead is None else steps_ahead
+        self.sample = tuple(None if t is None else t.detach().clone() for t in sample)
+        self._a_all = _unique([p for g in actor_optimizer.param_groups for p in g["params"]] + list(actor.parameters()))
+        self._c_all = _unique([p for g in critic_optimizer.param_groups for p in g["params"]] + list(critic.parameters()))
+        params = self._a_all + self._c_all
+        # everything the update writes, as it is now
+        norms = [getattr(o, k, None) for o in (value_normalizer, getattr(critic, "v_out", None)) if o is not None for k in _NORM_TENSORS]
+        moments = [st[k] for opt in (actor_optimizer, critic_optimizer) for st in opt.state.values() for k in ("exp_avg", "exp_avg_sq") if k in st]
+        old_grads = [p.grad for p in params]
+        kept = _unique(params + norms + moments + old_grads)
+        with torch.no_grad():
+            saved = [t.detach().clone() for t in kept]
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            # the first run finds the tensors the losses reach: their gradients become the fixed ones, the tensor that was .grad before where there was one
+            self._backwards(self._losses(), None, None)
+            fixed = []
+            for p, old in zip(params, old_grads):
+                if p.grad is not None and old is not None and old.shape == p.grad.shape and old.dtype == p.grad.dtype and old.device == p.grad.device:
+                    p.grad = old
+                fixed.append(p.grad)
+            self._a_rows = [(p, p.grad) for p in self._a_all if p.grad is not None]
+            self._c_rows = [(p, p.grad) for p in self._c_all if p.grad is not None]
+            self.actor_step = _optim.ScheduledStep(actor_optimizer, self.max_norm, parameters=actor.parameters(), steps_ahead=steps_ahead) \
+                if self.update_actor and self._a_rows else None
+            self.critic_step = _optim.ScheduledStep(critic_optimizer, self.max_norm, parameters=critic.parameters(), steps_ahead=steps_ahead)
+            self._zero = torch.zeros((), dtype=torch.float32, device=dev)
+            self._body()                                # the second run: the captured sequence itself, eagerly
+        torch.cuda.current_stream(dev).wait_stream(side)
+        created = _unique([st[k] for opt in (actor_optimizer, critic_optimizer) for st in opt.state.values() for k in ("exp_avg", "exp_avg_sq") if k in st])
+        have = set(id(t) for t in kept)
+        with torch.no_grad():
+            for t, v in zip(kept, saved):
+                t.copy_(v)
+            for t in created + [g for g in fixed if g is not None]:
+                if id(t) not in have:
+                    t.zero_()
+        for s in self._steps():
+            s._upload()                                 # row 0 again: the warm-up advanced the counter, not the host's step counts
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            self.result = self._body()
+        for p, old, g in zip(params, old_grads, fixed):
+            if g is None:
+                p.grad = old                            # not reached by the losses: the .grad it had
+
+    def _steps(self):
+        return [s for s in (self.actor_step, self.critic_step) if s is not None]
+
+    def _losses(self):
+        return minibatch_losses(self.actor, self.critic, self.sample, self.args, self.value_normalizer, install="in_place", value_head=self.value_head)
+
+    def _backwards(self, res, a_rows, c_rows):
+        """ppo_update's two backward passes from gradients that are None, as zero_grad() leaves them; with rows, each new gradient is then copied into
+        its fixed tensor, which becomes .grad again, and the step runs -> (actor_grad_norm, critic_grad_norm) (None without rows)"""
+        norms = []
+        for which, (every, rows, sched) in enumerate(((self._a_all, a_rows, getattr(self, "actor_step", None)),
+                                                      (self._c_all, c_rows, getattr(self, "critic_step", None)))):
+            for p in every:
+                p.grad = None
+            if which == 1:
+                (res.value_loss * getattr(self.args, "value_loss_coef", 1)).backward()
+            elif self.update_actor:
+                res.actor_loss.backward()
+            if rows is None:
+                continue
+            if sched is None:                           # the actor without update_actor: clip_grad_norm_ of nothing
+                norms.append(self._zero)
+                continue
+            new = [p.grad for p, _ in rows]
+            if any(g is None for g in new):
+                raise RuntimeError("a parameter that had a gradient at construction received none in the captured update")
+            with torch.no_grad():
+                torch._foreach_copy_([g for _, g in rows], new)
+            for p, g in rows:
+                p.grad = g
+            norms.append(sched.step())
+        return norms
+
+    def _body(self):
+        res = self._losses()
+        actor_grad_norm, critic_grad_norm = self._backwards(res, self._a_rows, self._c_rows)
+        return PPOUpdate(res.value_loss.detach(), critic_grad_norm, res.policy_loss.detach(), res.dist_entropy.detach(), actor_grad_norm,
+                         res.ratio_mean.detach(), res.imp_weights.detach())
+
+    @property
+    def remaining(self):
+        return min(s.remaining for s in self._steps())
+
+    def update(self, sample):
+        _same_sample("CapturedUpdate.update", self.sample, sample)
+        for s in self._steps():
+            s._budget.need("CapturedUpdate.update")
+            s.check_grads()
+        with torch.no_grad():
+            for dst, src in zip(self.sample, sample):
+                if dst is not None:
+                    dst.copy_(src)
+        self.graph.replay()
+        for s in self._steps():
+            s.advance_host(1)
+        return self.result
+
+    def refill(self):
+        for s in self._steps():
+            s.refill()
+
+    def train(self, buffer, perms=None):
+        """train(..., install="in_place") with every minibatch through update(): its loop, its generators and its train_info, bit for bit.
+        normalized_advantages and the generator run eagerly. The schedules are refilled first when param_groups changed since they were filled or when
+        fewer than ppo_epoch * num_mini_batch rows are left."""
+        args = self.args
+        ppo_epoch, num_mini_batch = int(getattr(args, "ppo_epoch", 15)), int(getattr(args, "num_mini_batch", 1))
+        if perms is not None and len(perms) != ppo_epoch:
+            raise ValueError("perms must hold one permutation per epoch: %d, not %d" % (ppo_epoch, len(perms)))
+        if self.remaining < ppo_epoch * num_mini_batch or any(s.stale() for s in self._steps()):
+            self.refill()
+        advantages = buffer.normalized_advantages(self.value_normalizer)
+        info = None
+        for epoch in range(ppo_epoch):
+            perm = None if perms is None else perms[epoch]
+            if getattr(args, "use_recurrent_policy", True):
+                generator = buffer.recurrent_generator(advantages, num_mini_batch, int(getattr(args, "data_chunk_length", 10)), perm=perm)
+            elif getattr(args, "use_naive_recurrent_policy", False):
+                generator = buffer.naive_recurrent_generator(advantages, num_mini_batch)
+            else:
+                generator = buffer.feed_forward_generator(advantages, num_mini_batch, perm=perm)
+            for sample in generator:
+                u = self.update(sample)
+                terms = (u.value_loss, u.policy_loss, u.dist_entropy, u.actor_grad_norm, u.critic_grad_norm, u.imp_weights.mean())
+                info = tuple(t.clone() for t in terms) if info is None else tuple(a + b for a, b in zip(info, terms))      # the next replay overwrites u
+        if info is None:
+            raise ValueError("train needs at least one minibatch: ppo_epoch = %d" % ppo_epoch)
+        num_updates = ppo_epoch * num_mini_batch
+        return {k: v / num_updates for k, v in zip(TRAIN_INFO, info)}
 
 
 # ---------------------------------------------------------------------------------------------- the rollout half

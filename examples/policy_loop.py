@@ -11,7 +11,9 @@ written out once (`by_pieces`) and as the one call that does the same (`gmpe.pol
 read by their attribute names; here they are stand-ins with those names (tests/test_gpu_policy.py's mirror modules with the shipped GNN and head
 weights), because the reference's modules need torch_geometric. Nothing between warmup() and the printed scalars is copied to the host.
 
-    python examples/policy_loop.py --envs 64 --agents 3 --episodes 3 [--popart]
+    python examples/policy_loop.py --envs 64 --agents 3 --episodes 3 [--popart] [--captured]
+
+With --captured the train() of every iteration is gmpe.policy.CapturedUpdate.train: one ppo_update captured as a graph, replayed per minibatch.
 """
 import argparse
 import os
@@ -72,6 +74,20 @@ def by_pieces(actor, critic, aopt, copt, buf, args, normalizer):
     return info
 
 
+def captured(cap, actor, critic, aopt, copt, buf, args, normalizer):
+    """one iteration whose updates are replays of one captured graph (gmpe.policy.CapturedUpdate, built at the first call from a minibatch of the first
+    rollout: the graph is fixed to that minibatch's shapes) -> (info, the CapturedUpdate)"""
+    from gmpe import policy
+    policy.rollout(actor, critic, buf, normalizer)
+    if cap is None:
+        sample = next(iter(buf.recurrent_generator(buf.normalized_advantages(normalizer), args.num_mini_batch, args.data_chunk_length)))
+        cap = policy.CapturedUpdate(actor, critic, aopt, copt, sample, args, normalizer, value_head="device")
+    info = cap.train(buf)
+    info["average_episode_rewards"] = buf.rewards.mean() * buf.T
+    buf.after_update()
+    return info, cap
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=64)
@@ -79,6 +95,8 @@ def main():
     ap.add_argument("--episode-length", type=int, default=20)
     ap.add_argument("--episodes", type=int, default=3)
     ap.add_argument("--popart", action="store_true", help="--use_popart: the critic's v_out is the value normaliser")
+    ap.add_argument("--captured", action="store_true", help="every update is a replay of one captured graph (gmpe.policy.CapturedUpdate.train; with "
+                    "--popart the rescaled layer is written in place, install=\"in_place\")")
     o = ap.parse_args()
     import torch
     from gmpe import policy
@@ -93,14 +111,17 @@ def main():
     actor, critic, aopt, copt, normalizer = networks(cfg, eng, o.popart, dev)
     buf = DeviceRolloutBuffer(eng, o.episode_length, use_centralized_V=False, policy_fields="all", learner_fields="all", args=args)
     buf.warmup()
+    cap = None
     for ep in range(o.episodes):
         t0 = time.perf_counter()
-        if ep % 2 == 0:
-            info = by_pieces(actor, critic, aopt, copt, buf, args, normalizer)
+        if o.captured:
+            (info, cap), how = captured(cap, actor, critic, aopt, copt, buf, args, normalizer), "captured updates"
+        elif ep % 2 == 0:
+            info, how = by_pieces(actor, critic, aopt, copt, buf, args, normalizer), "by pieces"
         else:
-            info = policy.iteration(actor, critic, aopt, copt, buf, args, normalizer, value_head="device")
+            info, how = policy.iteration(actor, critic, aopt, copt, buf, args, normalizer, value_head="device"), "policy.iteration"
         line = {k: round(float(v), 5) for k, v in info.items()}             # the one read-back of the iteration
-        print("episode %d (%s) %.0f ms: %s" % (ep, "by pieces" if ep % 2 == 0 else "policy.iteration", (time.perf_counter() - t0) * 1e3, line))
+        print("episode %d (%s) %.0f ms: %s" % (ep, how, (time.perf_counter() - t0) * 1e3, line))
     eng.check_errors()
     eng.close()
 

@@ -824,6 +824,43 @@ typedef struct gmpe_optim_shard_plan {
 int gmpe_optim_shard_elems(const gmpe_optim_plan* plan, int64_t* elems_out);
 int gmpe_optim_step_shard(int device, const gmpe_optim_shard_plan* plan, void* stream);
 
+/* The same call with Adam's step count in device memory, so that a captured graph (hipGraph) of it can be replayed: gmpe_optim_step forms a = lr /
+ * (1 - beta1^t) and s2 = sqrt(1 - beta2^t) on the host from hypers[i].t and passes them as kernel arguments, which a replay would repeat for ever. Here
+ * the float32 sets of `rows` consecutive step counts lie in device memory (the schedule), a device counter says which row the next call uses, and the
+ * call's last launch advances it.
+ *
+ * The schedule. base's tensors are cut into launch groups as for gmpe_optim_step; a group's distinct `hyper` indices take its slots 0, 1, ... in the
+ * order in which its GMPE_OPT_T_STEP tensors first name them. A slot is GMPE_OPT_HYPER_FLOATS float32: wd, w1, b2, w2, a, s2, eps of gmpe_optim_step's
+ * formulas. A row is n_groups * GMPE_OPT_MAX_HYPERS slots — the row stride is n_groups * GMPE_OPT_MAX_HYPERS * GMPE_OPT_HYPER_FLOATS floats —, slot s
+ * of group g at float (g * GMPE_OPT_MAX_HYPERS + s) * GMPE_OPT_HYPER_FLOATS of its row; slots not in use are 0. Row k holds every slot's set for the
+ * step count hypers[i].t + k, so row 0 is what gmpe_optim_step would use for the same plan: one host function rounds the doubles for both, which makes
+ * a scheduled step's bits gmpe_optim_step's. gmpe_optim_schedule_bytes gives rows * row stride * 4; gmpe_optim_schedule_fill writes the rows into HOST
+ * memory (the caller uploads them; neither makes a device call; they read base's geometry, and fill the hypers' values, checked as gmpe_optim_step
+ * checks them, and no pointer into device memory).
+ *
+ * gmpe_optim_step_scheduled launches on `stream`: every group's k_opt_norm as in gmpe_optim_step; every group's k_opt_step, which reads row = *counter
+ * and takes its sets from schedule[row] instead of the kernel arguments, line by line the same arithmetic; then k_opt_advance, one thread, ++*counter.
+ * Ordering: all on the one stream and the advance last, so every kernel of a call reads the counter before that call writes it, and the next call (or
+ * the next replay) reads it after. hypers[i].t of `base` is not read by the launches (it is checked, >= 1): the device counter alone selects the row,
+ * and the kernel arguments are the same at every call, which is what makes the call capturable.
+ * Exhaustion: with *counter outside 0 .. rows - 1 no parameter, moment or gradient is touched (the clip included), *status becomes 1 and stays so
+ * (nothing here ever clears it), the counter does not advance, and out and grad_norm_f32 still receive the norm and the coefficient.
+ * No allocation, no atomics, no wait. Refused before any device call, beyond what `base` is refused for by gmpe_optim_step: a null plan, rows outside
+ * 1 .. GMPE_OPT_MAX_SCHEDULE_ROWS, reserved != 0, GMPE_OPT_STEP without a schedule, a misaligned schedule, a missing or misaligned counter or status. */
+#define GMPE_OPT_HYPER_FLOATS 7               /* float32 per schedule slot: wd, w1, b2, w2, a, s2, eps                                  */
+#define GMPE_OPT_MAX_SCHEDULE_ROWS (1 << 20)  /* rows per schedule                                                                    */
+typedef struct gmpe_optim_sched_plan {
+    gmpe_optim_plan base;               /* as for gmpe_optim_step                                                                      */
+    const float* schedule;              /* f32 [rows][row stride] device, 4-byte aligned: gmpe_optim_schedule_fill's rows; required with GMPE_OPT_STEP */
+    int32_t* counter;                   /* i32 [1] device: the row the next call uses; read by every k_opt_step, advanced by the last launch */
+    int32_t* status;                    /* i32 [1] device, sticky: set to 1 by a call past the schedule, never cleared                 */
+    int32_t rows;                       /* 1 .. GMPE_OPT_MAX_SCHEDULE_ROWS                                                             */
+    int32_t reserved;                   /* 0                                                                                           */
+} gmpe_optim_sched_plan;
+int gmpe_optim_schedule_bytes(const gmpe_optim_plan* plan, int32_t rows, size_t* bytes_out);
+int gmpe_optim_schedule_fill(const gmpe_optim_plan* plan, int32_t rows, void* host_dst);
+int gmpe_optim_step_scheduled(int device, const gmpe_optim_sched_plan* plan, void* stream);
+
 /* ---- The policy's masked GRU layer (handle-less): RNNLayer.forward (onpolicy/algorithms/utils/rnn.py:23-79) with recurrent_N == 1 ----
  * The layer in front of the action head (GR_Actor) and of the value head (GR_Critic): nn.GRU(D, H) driven step by step with the state multiplied by
  * the step's mask, then nn.LayerNorm(H). All arrays float32, contiguous. For every row k of `rows` independently, t = 0 .. steps-1 (x, masks, features
