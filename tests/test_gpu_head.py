@@ -184,25 +184,27 @@ def untouched(buf, n, off=0, fill=NAN):
 
 
 def c_call(case, off=0, fill=0, stream=None, backward=True):
-    """gmpe_head_forward (+ gmpe_head_backward, twice) through ctypes with caller-owned buffers at `off` floats past an aligned base"""
+    """gmpe_head_forward (+ gmpe_head_backward, twice) through ctypes with caller-owned buffers at `off` floats past an aligned base: one offset for every
+    pointer, or a dict {plan field: offset} with the fields it does not name at 0"""
     lib = _lib.load()
     rows, K, source = case
     f, w, b, g, _, _ = HL.truth(case)
-    fd, wd, bd, gd = offset(f, off), offset(w, off), offset(b, off), offset(g, off)
+    o = (lambda k: off.get(k, 0)) if isinstance(off, dict) else (lambda k: off)
+    fd, wd, bd, gd = offset(f, o("features")), offset(w, o("weight")), offset(b, o("bias")), offset(g, o("grad_logits"))
     st = C.c_void_p((stream or torch.cuda.current_stream(torch.device(DEV))).cuda_stream)
     p = _lib.GmpeHeadPlan()
     p.rows, p.n_actions, p.hidden = rows, K, 64
     p.features, p.weight, p.bias = fd.data_ptr(), wd.data_ptr(), bd.data_ptr()
-    lbuf, lg = guarded(rows * K, off=off)
+    lbuf, lg = guarded(rows * K, off=o("logits_out"))
     p.logits_out = lg.data_ptr()
     _lib.check(lib.gmpe_head_forward(0, C.byref(p), st), "gmpe_head_forward")
     torch.cuda.synchronize()
-    assert untouched(lbuf, rows * K, off), "logits_out: written outside"
+    assert untouched(lbuf, rows * K, o("logits_out")), "logits_out: written outside"
     res = {"logits": lg.cpu().numpy().reshape(rows, K)}
     if backward:
         nbytes = gmpe.head_workspace_bytes(rows, K)
         ws = torch.full((nbytes + GUARD,), fill, dtype=torch.uint8, device=DEV)
-        outs = {"grad_features": guarded(rows * 64, off=off), "grad_weight": guarded(K * 64, off=off), "grad_bias": guarded(K, off=off)}
+        outs = {k: guarded(n, off=o(k)) for k, n in (("grad_features", rows * 64), ("grad_weight", K * 64), ("grad_bias", K))}
         p.logits_out, p.bias, p.grad_logits = None, None, gd.data_ptr()                # backward reads neither
         for k, (_, v) in outs.items():
             setattr(p, k, v.data_ptr())
@@ -218,7 +220,7 @@ def c_call(case, off=0, fill=0, stream=None, backward=True):
                 torch.cuda.synchronize()
         assert bool((ws[nbytes:] == fill).all()), "bytes past the workspace were written"
         for k, (buf, v) in outs.items():
-            assert untouched(buf, v.numel(), off), k + ": written outside"
+            assert untouched(buf, v.numel(), o(k)), k + ": written outside"
             assert same(v.cpu().numpy(), first[k].cpu().numpy()), "the second backward call differs: " + k
             res[k] = v.cpu().numpy().reshape(dict(grad_features=(rows, 64), grad_weight=(K, 64), grad_bias=(K,))[k])
     return res
@@ -228,6 +230,19 @@ def c_call(case, off=0, fill=0, stream=None, backward=True):
 def test_the_c_entries_give_the_wrappers_bits_aligned_or_not_and_stay_inside_their_outputs(case):
     a = device_run(case)
     for off in (0, 1):
+        b = c_call(case, off=off)
+        assert sorted(a) == sorted(b)
+        for k in a:
+            assert same(a[k], b[k]), (off, k)
+
+
+def test_each_alignment_flag_alone_gives_the_same_bits():
+    """gmpe_head.hip chooses 16-byte or 4-byte units per array — features, weight, grad_features, and the [rows, K] array of the call (logits_out forward,
+    grad_logits backward) — where one offset for all pointers only ever runs all four together: each one off on its own, and features aligned while both
+    of backward's other row arrays are off"""
+    case = (257, 25, "actor")
+    a = device_run(case)
+    for off in ({"features": 1}, {"weight": 1}, {"grad_features": 1}, {"logits_out": 1, "grad_logits": 1}, {"grad_features": 1, "grad_logits": 1}):
         b = c_call(case, off=off)
         assert sorted(a) == sorted(b)
         for k in a:

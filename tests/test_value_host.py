@@ -2,6 +2,8 @@
 gmpe.value_head, gmpe.policy.get_actions / get_values / collect_step / compute / rollout / iteration), no GPU:
 (a) tests/value_lib.py's float32 emulation of the forward's fixed order against a float64 dot product, within 64 * 2^-24 * sum|f * w| per row: 4 + 4 + 1
     roundings of at most 2^-24 relative each lie on a row's path, each on a partial sum that sum|f * w| bounds (times 1 + a few 2^-24), so 64 is generous;
+    and its float64 emulation of the backward's fixed order against float32(math.fsum(exact products)) on signed g, up to 34 tiles, with inputs on which
+    each level of that order shows;
 (b) the exported symbols, the plan against the C header, the workspace size against the restated geometry, the C entries' refusals;
 (c) every refusal and argument error of value_head and of the new policy functions, raised on CPU tensors before any device call;
 (d) the compiler's resource report of csrc/gmpe_value.hip shows no scratch memory."""
@@ -49,6 +51,52 @@ def test_the_emulation_keeps_the_stated_order():
     f[:] = 0.0
     f[0, [0, 8, 12, 4]] = [2.0 ** 24, 1.0, 1.0, -2.0 ** 24]      # lanes 0, 1 hold +-2^24: they cancel first, the ones survive
     assert VL.emulate(f, w, np.zeros(1, np.float32))[0] == 2.0
+
+
+@pytest.mark.parametrize("rows", VL.ROWS + VL.MANY_ROWS)
+def test_the_backward_emulation_is_the_once_rounded_sum(rows):
+    """signed g, so the sums cancel: the emulation's order of double adds must still land on float32(the exact sum) or its float32 neighbour in every
+    column and in the bias. With these seeds it is exact in all 64 columns and in the bias at every row count, the smallest |sum| / sum|terms| of a
+    column being 1.7e-4 (256 rows): the neighbour is slack the reference does not use."""
+    f, _, _, g = VL.inputs(rows)
+    assert (g < 0).any() and (g > 0).any() or rows == 1
+    gw, gb = VL.emulate_backward(f, g)
+    assert gw.dtype == gb.dtype == np.float32 and gw.shape == (1, 64) and gb.shape == (1,)
+    products = g.astype(np.float64) * f.astype(np.float64)                  # exact: float32 x float32 fits a double
+    want_w, want_b = VL.once_rounded(products), VL.once_rounded(g.astype(np.float64))
+    ratio = np.abs(products.sum(0)) / np.abs(products).sum(0)
+    print("rows %d: the emulation is exact in %d of 64 columns, min |sum| / sum|terms| %.3g; bias exact: %s"
+          % (rows, int((gw.reshape(-1) == want_w).sum()), float(ratio.min()), bool(gb[0] == want_b[0])))
+    assert (VL.neighbours(want_w) == gw.reshape(1, 64)).any(0).all(), (gw, want_w)
+    assert (VL.neighbours(want_b) == gb.reshape(1, 1)).any(), (gb, want_b)
+    if rows in VL.MANY_ROWS:                                                # the inputs can see a finish that loses tile 16
+        lost_w, lost_b = VL.emulate_backward(f, g, skip_tiles=(16,))
+        assert not np.array_equal(VL.bits(lost_w), VL.bits(gw)) and VL.bits(lost_b)[0] != VL.bits(gb)[0]
+
+
+def _spike(rows, at):
+    """grad_weight[0, 0] and grad_bias of `rows` rows with g = 1 and column 0 holding 2^60, 1, 1, -2^60 in the rows `at`, zeros elsewhere: 2 where the
+    order lets the two 2^60 cancel first, 0 where a 1 is added to 2^60 (whose double ulp is 256) and lost"""
+    f = np.zeros((rows, 64), np.float32)
+    f[list(at), 0] = [2.0 ** 60, 1.0, 1.0, -2.0 ** 60]
+    gw, gb = VL.emulate_backward(f, np.ones((rows, 1), np.float32))
+    assert gb[0] == rows and not gw[0, 1:].any()
+    return float(gw[0, 0])
+
+
+def test_the_backward_emulation_keeps_the_stated_order():
+    assert _spike(13, (0, 4, 8, 12)) == 0.0             # one lane's passes 0 .. 3, ascending: ((2^60 + 1) + 1) - 2^60
+    assert _spike(13, (0, 8, 12, 4)) == 2.0             # ... 2^60 - 2^60 in passes 0 and 1, then the ones
+    assert _spike(4, (0, 2, 3, 1)) == 2.0               # the four row groups of pass 0: (2^60 - 2^60) + (1 + 1)
+    assert _spike(4, (0, 1, 3, 2)) == 0.0               # ... (2^60 + 1) + (-2^60 + 1)
+    assert _spike(4, (0, 1, 2, 3)) == 0.0               # ... (2^60 + 1) + (1 - 2^60)
+    assert _spike(193, (0, 64, 128, 192)) == 0.0        # the four waves in wave order
+    assert _spike(193, (0, 128, 192, 64)) == 2.0        # ... waves 0 and 1 hold the two 2^60: ((2^60 - 2^60) + 1) + 1
+    assert _spike(4097, (0, 256, 512, 4096)) == 2.0     # tiles 0 and 16 share slice 0 and cancel there; an ascending sum over the tiles would give 0
+    assert _spike(4097, (0, 4096, 512, 256)) == 1.0     # ... slice 0 = 2^60 + 1 loses tile 16's 1, then slice 1 = -2^60 and slice 2 = 1; ascending tiles: 2
+    one = np.random.RandomState(3).randn(1, 64).astype(np.float32)
+    gw, gb = VL.emulate_backward(one, np.float32([[-1.5]]))
+    assert np.array_equal(VL.bits(gw), VL.bits(np.float32(-1.5) * one)) and gb[0] == -1.5       # one row: one exact product, rounded once
 
 
 # ---------------------------------------------------------------------------------------------- (b)
