@@ -13,7 +13,7 @@ __all__ = ["config", "make_config", "config_from_args"]
 
 def __getattr__(name):
     # torch / HIP-dependent modules are imported on first use
-    if name in ("engine", "vec_env", "spaces", "_lib", "sharding", "rollout", "minibatch", "evaluate", "ppo_loss", "act", "learner_shards", "gru", "mlp", "gnn", "head", "value", "policy", "optim"):
+    if name in ("engine", "vec_env", "spaces", "_lib", "sharding", "rollout", "minibatch", "evaluate", "ppo_loss", "act", "learner_shards", "gru", "mlp", "gnn", "head", "value", "policy", "optim", "infos"):
         import importlib
         return importlib.import_module("." + name, __name__)
     if name in ("BatchedGraphMPEVecEnv", "MultiDeviceGraphMPEVecEnv", "GraphMPEEnv", "make_train_env", "make_eval_env"):
@@ -46,6 +46,9 @@ def __getattr__(name):
     if name in ("clip_and_step", "clip_and_step_begin", "clip_and_step_finish"):
         from . import optim
         return getattr(optim, name)
+    if name in ("env_infos", "eval_step", "eval_mean"):
+        from . import infos
+        return getattr(infos, name)
     if name in ("GmpeEngine", "compute_returns_begin", "compute_returns_finish"):
         from . import engine
         return getattr(engine, name)

@@ -28,7 +28,8 @@ SYMBOLS = ["gmpe_abi_version", "gmpe_last_error", "gmpe_obs_dim", "gmpe_node_fea
            "gmpe_head_workspace_bytes", "gmpe_head_forward", "gmpe_head_backward", "gmpe_act_head",
            "gmpe_value_workspace_bytes", "gmpe_value_forward", "gmpe_value_backward",
            "gmpe_optim_workspace_bytes", "gmpe_optim_step", "gmpe_optim_shard_elems", "gmpe_optim_step_shard",
-           "gmpe_optim_schedule_bytes", "gmpe_optim_schedule_fill", "gmpe_optim_step_scheduled"]
+           "gmpe_optim_schedule_bytes", "gmpe_optim_schedule_fill", "gmpe_optim_step_scheduled",
+           "gmpe_env_infos", "gmpe_eval_step", "gmpe_eval_mean"]
 
 
 class GmpeOutputs(C.Structure):
@@ -118,6 +119,24 @@ class GmpeEpisodeSummaryPlan(C.Structure):
 
 
 EVAL_INFO_WIDTH, EVAL_NUM_COLUMNS, EVAL_NUM_STATS = 18, 16, 7
+INFOS_CHUNK, INFOS_LEAF = 8192, 128      # GMPE_INFOS_* of include/gmpe.h: NumPy's reduce buffer and pairwise_sum's block
+
+
+class GmpeEnvInfosPlan(C.Structure):
+    """gmpe_env_infos_plan (include/gmpe.h): np.mean over envs of every info column per agent, process_infos + log_env."""
+    _fields_ = [("num_envs", C.c_int32), ("num_agents", C.c_int32), ("episode_length", C.c_int32), ("reserved", C.c_int32), ("dt", C.c_double),
+                ("info", C.c_void_p), ("out", C.c_void_p)]
+
+
+class GmpeEvalStepPlan(C.Structure):
+    """gmpe_eval_step_plan (include/gmpe.h): one step of GMPERunner.eval's bookkeeping — reward sums, per-env masks, zeroed RNN rows."""
+    _fields_ = [("num_envs", C.c_int32), ("num_agents", C.c_int32), ("rnn_row", C.c_int32), ("first", C.c_int32), ("reward", C.c_void_p),
+                ("done", C.c_void_p), ("sums", C.c_void_p), ("masks", C.c_void_p), ("rnn_states", C.c_void_p)]
+
+
+class GmpeEvalMeanPlan(C.Structure):
+    """gmpe_eval_mean_plan (include/gmpe.h): np.mean of contiguous float64 values in NumPy's order."""
+    _fields_ = [("count", C.c_int64), ("values", C.c_void_p), ("out", C.c_void_p)]
 
 
 MB_FEED_FORWARD, MB_RECURRENT = 0, 1
@@ -393,6 +412,9 @@ def load():
     lib.gmpe_optim_schedule_bytes.argtypes = [C.POINTER(GmpeOptimPlan), C.c_int32, C.POINTER(C.c_size_t)]
     lib.gmpe_optim_schedule_fill.argtypes = [C.POINTER(GmpeOptimPlan), C.c_int32, P]
     lib.gmpe_optim_step_scheduled.argtypes = [I, C.POINTER(GmpeOptimSchedPlan), P]
+    lib.gmpe_env_infos.argtypes = [I, C.POINTER(GmpeEnvInfosPlan), P]
+    lib.gmpe_eval_step.argtypes = [I, C.POINTER(GmpeEvalStepPlan), P]
+    lib.gmpe_eval_mean.argtypes = [I, C.POINTER(GmpeEvalMeanPlan), P]
     from .config import ABI_VERSION
     if lib.gmpe_abi_version() != ABI_VERSION:
         raise GmpeError("libgmpe.so ABI version mismatch")

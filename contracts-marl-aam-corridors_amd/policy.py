@@ -6,6 +6,8 @@
     GMPERunner.collect / collect_with_mask + insert       ->  collect_step(actor, critic, buffer)
     GMPERunner.compute                                    ->  compute(critic, buffer, value_normalizer)
     run()'s loop over one episode, and one whole iteration  ->  rollout(actor, critic, buffer, ...), iteration(actor, critic, ..., buffer, args, ...)
+    GMPERunner.eval                                       ->  eval_episode(actor, eval_engine, args)
+    GMPERunner.run                                        ->  run(actor, critic, actor_optimizer, critic_optimizer, buffer, args, ..., on_log=, on_eval=, on_save=)
     evaluate_actions + the loss arithmetic of ppo_update  ->  minibatch_losses(actor, critic, sample, args, ...)
     GR_MAPPO.ppo_update                                   ->  ppo_update(actor, critic, actor_optimizer, critic_optimizer, sample, args, ...)
     GR_MAPPO.train                                        ->  train(actor, critic, actor_optimizer, critic_optimizer, buffer, args, ...)
@@ -26,6 +28,7 @@ from .gnn import gnn_base
 from .gru import rnn_layer
 from .head import act_head, action_logits
 from .mlp import mlp_base
+from . import infos as _infos
 from . import optim as _optim
 from .optim import clip_and_step
 from .ppo_loss import ppo_losses, ppo_losses_popart
@@ -529,6 +532,109 @@ def iteration(actor, critic, actor_optimizer, critic_optimizer, buffer, args, va
     info["average_episode_rewards"] = buffer.rewards.mean() * buffer.T
     buffer.after_update()
     return info
+
+
+# ---------------------------------------------------------------------------------------------- run(): the periodic eval, and the loop itself
+def eval_episode(actor, eval_engine, args=None, *, episode_length=None, seed=0):
+    """GMPERunner.eval (graph_mpe_runner.py:445-516): one deterministic episode on the eval envs, under torch.no_grad(). eval_engine: a GmpeEngine (or a
+    vec env's .engine) of its own, with node rows and an adjacency. A reset, then episode_length (keyword, else args.episode_length, else the engine's
+    cfg.episode_length) times: actor_forward(..., deterministic=True, available_actions=None) on the engine's outputs with this function's own
+    [N, A, recurrent_N, hidden_size] states (args' sizes, default 1 and 64) and [N, A, 1] masks, the env step, and one launch of gmpe_eval_step: the
+    reward sums, and masks and RNN states reset per ENV — zero where every agent of the env is done — as the reference does; there are no stop-action
+    rows and a finished env is not frozen (the engine's auto-reset plays on, as the reference's eval envs do).
+    Returns {'eval_average_episode_rewards': float64 [N, A] sums over the steps, 'mean': 0-dim float64, log_env's np.mean of them}: device tensors,
+    bit for bit the reference's NumPy on the same rewards. Nothing is copied to the host and nothing waits for the device."""
+    eng = eval_engine if hasattr(eval_engine, "out") else getattr(eval_engine, "engine", None)
+    if eng is None or not hasattr(eng, "out") or not hasattr(eng, "cfg"):
+        raise ValueError("eval_episode: eval_engine must be a GmpeEngine (or a BatchedGraphMPEVecEnv's .engine), not %s" % type(eval_engine).__name__)
+    if eng.out.node_obs is None:
+        raise ValueError("eval_episode reads node_obs rows: eval_engine must keep them (node_form 'rows' or 'both')")
+    if eng.out.adj is None:
+        raise ValueError("eval_episode reads an adjacency: eval_engine must keep one (adj_form not 'none')")
+    cfg = eng.cfg
+    T = episode_length if episode_length is not None else getattr(args, "episode_length", None)
+    T = int(cfg.episode_length if T is None else T)
+    if T < 1:
+        raise ValueError("eval_episode: episode_length must be >= 1, not %d" % T)
+    N, A = eng.N, eng.A
+    rows, dev = N * A, eng.device
+    R, H = int(getattr(args, "recurrent_N", 1)), int(getattr(args, "hidden_size", 64))
+    with torch.no_grad():
+        o = eng.reset()
+        E = int(o.node_obs.shape[-2])
+        rnn_states = torch.zeros((N, A, R, H), dtype=torch.float32, device=dev)
+        masks = torch.ones((N, A, 1), dtype=torch.float32, device=dev)
+        sums = torch.empty((N, A), dtype=torch.float64, device=dev)
+        flat_h = rnn_states.view(rows, R, H)
+        for t in range(T):
+            idx, _, h = actor_forward(actor, o.obs.reshape(rows, -1), o.node_obs.reshape(rows, E, -1), o.adj.reshape(-1, E, E), o.agent_id.reshape(rows),
+                                      flat_h, masks.view(rows, 1), None, True, seed=seed, env_id_base=int(cfg.env_id_base), num_agents=A, draw=t, out={})
+            if h is not flat_h:
+                flat_h.copy_(h.reshape(flat_h.shape))
+            o = eng.step(idx.view(N, A))
+            _infos.eval_step(o.reward, o.done, sums, masks, rnn_states, first=t == 0)
+        mean = _infos.eval_mean(sums)
+    return {"eval_average_episode_rewards": sums, "mean": mean}
+
+
+def linear_lr(initial_lr, episode, episodes):
+    """update_linear_schedule's learning rate (onpolicy/utils/util.py:18-22), in its arithmetic"""
+    return initial_lr - (initial_lr * (episode / float(episodes)))
+
+
+def run(actor, critic, actor_optimizer, critic_optimizer, buffer, args, value_normalizer=None, *, episodes=None, eval_engine=None, on_log=None,
+        on_eval=None, on_save=None, eval_seed=0, **iteration_keywords):
+    """GMPERunner.run (graph_mpe_runner.py:40-207) over a DeviceRolloutBuffer: buffer.warmup(), then `episodes` iterations (default
+    int(args.num_env_steps) // episode_length // n_rollout_threads; episode_length is args.episode_length, else buffer.T; n_rollout_threads is
+    args.n_rollout_threads, else the engine's N). Per episode, in the reference's order:
+      with args.use_linear_lr_decay, GR_MAPPOPolicy.lr_decay: every param_group of actor_optimizer gets linear_lr(args.lr, episode, episodes), of
+        critic_optimizer linear_lr(args.critic_lr, episode, episodes);
+      iteration(actor, critic, actor_optimizer, critic_optimizer, buffer, args, value_normalizer, **iteration_keywords);
+      total_num_steps = (episode + 1) * episode_length * n_rollout_threads;
+      on_save(episode) when episode % args.save_interval == 0 or on the last episode;
+      on_log(total_num_steps, train_infos, env_infos) when episode % args.log_interval == 0: iteration's dict (average_episode_rewards included) and
+        gmpe.env_infos(buffer, args) of the rollout's last step;
+      on_eval(total_num_steps, eval_infos) when episode % args.eval_interval == 0 and args.use_eval: eval_episode(actor, eval_engine, args, seed=eval_seed).
+    After the loop on_save(episodes - 1) once more: the reference's final forced save. The intervals default to the reference's 1, 5 and 25. A callback
+    that is None is skipped, and what only it would receive is not computed. Every payload is device tensors: run itself never waits for the device,
+    a callback that reads a value does. args.increase_fairness is refused: the engine's reward weights are fixed at creation. args.use_eval without
+    eval_engine raises ValueError. Returns the last iteration's train_infos (None with no episode)."""
+    if getattr(args, "increase_fairness", False):
+        raise NotImplementedError("args.increase_fairness: run() cannot raise fair_rew mid-training — the engine's reward weights are fixed at "
+                                  "creation (not supported)")
+    use_eval = bool(getattr(args, "use_eval", False))
+    if use_eval and eval_engine is None:
+        raise ValueError("args.use_eval is set: run needs eval_engine (a GmpeEngine of its own for the eval episodes)")
+    episode_length = int(getattr(args, "episode_length", None) or buffer.T)
+    threads = int(getattr(args, "n_rollout_threads", None) or buffer.engine.N)
+    if episodes is None:
+        if getattr(args, "num_env_steps", None) is None:
+            raise ValueError("run needs episodes= or args.num_env_steps")
+        episodes = int(args.num_env_steps) // episode_length // threads
+    episodes = int(episodes)
+    save_interval, log_interval = int(getattr(args, "save_interval", 1)), int(getattr(args, "log_interval", 5))
+    eval_interval = int(getattr(args, "eval_interval", 25))
+    decay = bool(getattr(args, "use_linear_lr_decay", False))
+    if decay and (getattr(args, "lr", None) is None or getattr(args, "critic_lr", None) is None):
+        raise ValueError("args.use_linear_lr_decay is set: run needs args.lr and args.critic_lr, the rates the schedule starts from")
+    buffer.warmup()
+    train_infos = None
+    for episode in range(episodes):
+        if decay:
+            for optimizer, initial in ((actor_optimizer, args.lr), (critic_optimizer, args.critic_lr)):
+                for group in optimizer.param_groups:
+                    group["lr"] = linear_lr(initial, episode, episodes)
+        train_infos = iteration(actor, critic, actor_optimizer, critic_optimizer, buffer, args, value_normalizer, **iteration_keywords)
+        total_num_steps = (episode + 1) * episode_length * threads
+        if on_save is not None and (episode % save_interval == 0 or episode == episodes - 1):
+            on_save(episode)
+        if on_log is not None and episode % log_interval == 0:
+            on_log(total_num_steps, train_infos, _infos.env_infos(buffer, args))
+        if on_eval is not None and use_eval and episode % eval_interval == 0:
+            on_eval(total_num_steps, eval_episode(actor, eval_engine, args, seed=eval_seed))
+    if on_save is not None:
+        on_save(episodes - 1)
+    return train_infos
 
 
 def evaluator_act(actor, evaluator, deterministic=True, seed=0, draw0=0):

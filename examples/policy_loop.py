@@ -11,9 +11,12 @@ written out once (`by_pieces`) and as the one call that does the same (`gmpe.pol
 read by their attribute names; here they are stand-ins with those names (tests/test_gpu_policy.py's mirror modules with the shipped GNN and head
 weights), because the reference's modules need torch_geometric. Nothing between warmup() and the printed scalars is copied to the host.
 
-    python examples/policy_loop.py --envs 64 --agents 3 --episodes 3 [--popart] [--captured]
+    python examples/policy_loop.py --envs 64 --agents 3 --episodes 3 [--popart] [--captured] [--run]
 
 With --captured the train() of every iteration is gmpe.policy.CapturedUpdate.train: one ppo_update captured as a graph, replayed per minibatch.
+With --run the same training is the reference's whole run() loop as one call, gmpe.policy.run, with three printing callbacks: the linear lr decay, the
+iterations, the `agent{i}/...` means of process_infos + log_env at the log interval (gmpe.env_infos), the deterministic eval episode on a second
+engine at the eval interval (gmpe.policy.eval_episode) and the saves. Only the callbacks read values back.
 """
 import argparse
 import os
@@ -88,6 +91,33 @@ def captured(cap, actor, critic, aopt, copt, buf, args, normalizer):
     return info, cap
 
 
+def run_whole(o, actor, critic, aopt, copt, buf, args, normalizer, cfg):
+    """GMPERunner.run as gmpe.policy.run plus the callbacks a training script still writes"""
+    from gmpe import policy
+    from gmpe.engine import GmpeEngine
+    args.episode_length, args.n_rollout_threads = o.episode_length, o.envs
+    args.save_interval, args.log_interval, args.eval_interval, args.use_eval = 2, 1, 2, True
+    args.use_linear_lr_decay, args.lr, args.critic_lr = True, 7e-4, 7e-4
+    eval_engine = GmpeEngine(gmpe.make_config(num_envs=o.envs, num_agents=o.agents, episode_length=o.episode_length, seed=2), device=0)
+
+    def on_log(total_num_steps, train_infos, env_infos):
+        print("steps %d train: %s" % (total_num_steps, {k: round(float(v), 5) for k, v in train_infos.items()}))
+        for a in range(o.agents):
+            keys = ["agent%d/%s" % (a, k) for k in ("individual_rewards", "dist_to_goal", "time_to_goal", "num_agent_collisions")]
+            print("steps %d %s" % (total_num_steps, "  ".join("%s %.4f" % (k, float(env_infos[k])) for k in keys)))
+
+    def on_eval(total_num_steps, eval_infos):
+        print("steps %d eval average episode rewards of agent: %.5f" % (total_num_steps, float(eval_infos["mean"])))
+
+    def on_save(episode):
+        print("episode %d: save (lr %.3g)" % (episode, aopt.param_groups[0]["lr"]))
+
+    policy.run(actor, critic, aopt, copt, buf, args, normalizer, episodes=o.episodes, eval_engine=eval_engine, on_log=on_log, on_eval=on_eval,
+               on_save=on_save, value_head="device")
+    eval_engine.check_errors()
+    eval_engine.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=64)
@@ -97,6 +127,7 @@ def main():
     ap.add_argument("--popart", action="store_true", help="--use_popart: the critic's v_out is the value normaliser")
     ap.add_argument("--captured", action="store_true", help="every update is a replay of one captured graph (gmpe.policy.CapturedUpdate.train; with "
                     "--popart the rescaled layer is written in place, install=\"in_place\")")
+    ap.add_argument("--run", action="store_true", help="the whole loop as one call: gmpe.policy.run with printing callbacks")
     o = ap.parse_args()
     import torch
     from gmpe import policy
@@ -110,6 +141,11 @@ def main():
     args = runner_args(o.popart, o.episode_length)
     actor, critic, aopt, copt, normalizer = networks(cfg, eng, o.popart, dev)
     buf = DeviceRolloutBuffer(eng, o.episode_length, use_centralized_V=False, policy_fields="all", learner_fields="all", args=args)
+    if o.run:
+        run_whole(o, actor, critic, aopt, copt, buf, args, normalizer, cfg)
+        eng.check_errors()
+        eng.close()
+        return
     buf.warmup()
     cap = None
     for ep in range(o.episodes):

@@ -1255,6 +1255,53 @@ typedef struct gmpe_episode_summary_plan {
 } gmpe_episode_summary_plan;
 int gmpe_episode_summary(int device, const gmpe_episode_summary_plan* plan, void* stream);
 
+/* ---- run()'s log and eval intervals on device data (handle-less): Runner.process_infos + log_env (base_runner.py:194-302) and the bookkeeping of
+ * GMPERunner.eval (graph_mpe_runner.py:445-516). No allocation, no workspace, no host synchronisation, every launch on `stream`.
+ *
+ * gmpe_env_infos: out[a, k] = np.mean of the N Python floats float(info[n, a, k]), n = 0 .. N-1, bit for bit: float64 NumPy's add.reduce takes
+ * the values in consecutive chunks of GMPE_INFOS_CHUNK, starts from +0.0 and adds each chunk's pairwise_sum in order (a piece of more than
+ * GMPE_INFOS_LEAF values splits at n2 = n/2 - (n/2) % 8; a smaller one is summed by eight accumulators, their tree, then the tail; fewer than 8
+ * values sequentially), then divides by N. In column Time_req_to_goal a value of exactly -1 counts as (double)episode_length * dt
+ * (base_runner.py:215-216). A NaN in a column gives that column NaN. */
+#define GMPE_INFOS_CHUNK 8192            /* NumPy's reduce buffer, in elements                                                          */
+#define GMPE_INFOS_LEAF 128              /* pairwise_sum's PW_BLOCKSIZE                                                                 */
+typedef struct gmpe_env_infos_plan {
+    int32_t num_envs;               /* N >= 1                                                                                       */
+    int32_t num_agents;             /* 1 .. GMPE_MAX_AGENTS                                                                         */
+    int32_t episode_length;         /* >= 1: all_args.episode_length                                                                */
+    int32_t reserved;               /* 0                                                                                            */
+    double dt;                      /* finite: the runner's dt                                                                      */
+    const float* info;              /* [N, A, GMPE_INFO_KEYS]                                                                       */
+    double* out;                    /* [A, GMPE_INFO_KEYS] out                                                                      */
+} gmpe_env_infos_plan;
+int gmpe_env_infos(int device, const gmpe_env_infos_plan* plan, void* stream);
+
+/* gmpe_eval_step, once behind each env step of the eval episode, same stream:
+ *   sums[n, a] = (first ? +0.0 : sums[n, a]) + double(reward[n, a]) — np.sum(np.array(eval_episode_rewards), axis=0): one add per step, in step order;
+ *   masks[n, a, 0] = 0 where every agent of env n is done, else 1 (:500-505; per env, not per agent);
+ *   rnn_states[n, :, :, :] = 0 where every agent of env n is done (:495-499); other rows are left as they are.
+ * first = 1 stores instead of adding, so `sums` needs no memset. */
+typedef struct gmpe_eval_step_plan {
+    int32_t num_envs;               /* N >= 1                                                                                       */
+    int32_t num_agents;             /* 1 .. GMPE_MAX_AGENTS                                                                         */
+    int32_t rnn_row;                /* recurrent_N * hidden_size, 1 .. 2^20 with rnn_states, else 0                                 */
+    int32_t first;                  /* 0 or 1                                                                                       */
+    const float* reward;            /* [N, A]                                                                                       */
+    const uint8_t* done;            /* [N, A]                                                                                       */
+    double* sums;                   /* [N, A] state                                                                                 */
+    float* masks;                   /* [N, A, 1] out                                                                                */
+    float* rnn_states;              /* [N, A, rnn_row] in place; may be NULL                                                        */
+} gmpe_eval_step_plan;
+int gmpe_eval_step(int device, const gmpe_eval_step_plan* plan, void* stream);
+
+/* gmpe_eval_mean: out[0] = np.mean of `count` contiguous float64 values, bit for bit, in gmpe_env_infos' order (log_env's mean of the [N, A] sums). */
+typedef struct gmpe_eval_mean_plan {
+    int64_t count;                  /* 1 .. 2^40                                                                                    */
+    const double* values;           /* [count]                                                                                      */
+    double* out;                    /* [1] out                                                                                      */
+} gmpe_eval_mean_plan;
+int gmpe_eval_mean(int device, const gmpe_eval_mean_plan* plan, void* stream);
+
 /* PPO minibatches from a rollout (GraphReplayBuffer.feed_forward_generator / recurrent_generator, onpolicy/utils/graph_buffer.py:368-758): one minibatch's rows
  * of every field gathered from the [T+1, N, ...] arrays through a device permutation, as exact byte copies (16-byte vectors where row size and alignment allow)
  * or, for the table kinds, expanded from the f64 entity table with the arithmetic of gmpe_expand_node_obs / gmpe_expand_adj (bit-identical to the engine).
