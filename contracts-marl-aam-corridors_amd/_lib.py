@@ -24,7 +24,7 @@ SYMBOLS = ["gmpe_abi_version", "gmpe_last_error", "gmpe_obs_dim", "gmpe_node_fea
            "gmpe_act_sample", "gmpe_compute_returns_shard", "gmpe_ppo_loss_shard",
            "gmpe_gru_workspace_bytes", "gmpe_gru_forward", "gmpe_gru_backward",
            "gmpe_mlp_workspace_bytes", "gmpe_mlp_forward", "gmpe_mlp_backward",
-           "gmpe_gnn_workspace_bytes", "gmpe_gnn_forward", "gmpe_gnn_backward",
+           "gmpe_gnn_workspace_bytes", "gmpe_gnn_forward", "gmpe_gnn_backward", "gmpe_gnn_forward_table", "gmpe_gnn_backward_table",
            "gmpe_head_workspace_bytes", "gmpe_head_forward", "gmpe_head_backward", "gmpe_act_head",
            "gmpe_value_workspace_bytes", "gmpe_value_forward", "gmpe_value_backward",
            "gmpe_optim_workspace_bytes", "gmpe_optim_step", "gmpe_optim_shard_elems", "gmpe_optim_step_shard",
@@ -286,6 +286,12 @@ class GmpeGnnPlan(C.Structure):
         ("workspace_bytes", C.c_size_t)]
 
 
+class GmpeGnnTablePlan(C.Structure):
+    """gmpe_gnn_table_plan (include/gmpe.h): the same GNNBase with a graph's rows and matrix rebuilt from an fp64 entity table."""
+    _fields_ = [("base", GmpeGnnPlan), ("cfg", C.POINTER(GmpeConfig)), ("table", C.c_void_p), ("table_rows", C.c_int64),
+                ("table_index", C.c_void_p), ("index64", C.c_int32), ("table_share", C.c_int32)]
+
+
 # GMPE_OPT_* of include/gmpe.h; tests/test_abi_host.py compiles against the header
 OPT_MAX_TENSORS, OPT_MAX_HYPERS, OPT_CHUNK, OPT_MAX_PLAN_TENSORS, OPT_MAX_NUMEL = 64, 8, 1024, 4096, 1 << 30
 OPT_CLIP, OPT_STEP = 1, 2
@@ -398,6 +404,8 @@ def load():
     lib.gmpe_gnn_workspace_bytes.argtypes = [C.POINTER(GmpeGnnPlan), C.c_int32, C.POINTER(C.c_size_t)]
     lib.gmpe_gnn_forward.argtypes = [I, C.POINTER(GmpeGnnPlan), P]
     lib.gmpe_gnn_backward.argtypes = [I, C.POINTER(GmpeGnnPlan), P]
+    lib.gmpe_gnn_forward_table.argtypes = [I, C.POINTER(GmpeGnnTablePlan), P]
+    lib.gmpe_gnn_backward_table.argtypes = [I, C.POINTER(GmpeGnnTablePlan), P]
     lib.gmpe_head_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]
     lib.gmpe_head_forward.argtypes = [I, C.POINTER(GmpeHeadPlan), P]
     lib.gmpe_head_backward.argtypes = [I, C.POINTER(GmpeHeadPlan), P]

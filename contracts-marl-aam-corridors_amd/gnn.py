@@ -4,6 +4,9 @@ three, whatever the number of graphs, of nodes and of edges. The dense adjacency
 
     nbd_features = gmpe.gnn_base(node_obs, adj, agent_id, self.gnn_base)        # was: self.gnn_base(node_obs, adj, agent_id)
 
+gnn_base_from_table is the same module straight from the fp64 entity table the rows and the adjacency are pure functions of (gmpe_gnn_forward_table /
+gmpe_gnn_backward_table): bit for bit gnn_base on the engine's own arrays, which are then never written.
+
 There is no torch fallback: the arrays must be on a HIP device.
 """
 import ctypes as C
@@ -118,7 +121,6 @@ def _base_params(base):
 
 def _check(node_obs, adj, agent_id, names, ps, meta):
     """Everything the host can see, before the device is touched -> (device, rows, E, F, adj_share, num_embeddings, embedding_size)"""
-    heads, gnn_n, embed_n, _, _, ln, _, aggregate, _ = meta
     for name, t in (("node_obs", node_obs), ("adj", adj), ("agent_id", agent_id)):
         if not isinstance(t, torch.Tensor):
             raise ValueError("%s must be a tensor" % name)
@@ -136,10 +138,24 @@ def _check(node_obs, adj, agent_id, names, ps, meta):
     if adj.dim() != 3 or adj.shape[1] != E or adj.shape[2] != E or adj.shape[0] < 1 or rows % int(adj.shape[0]):
         raise ValueError("adj must have shape (rows, E, E) or (rows / S, E, E) = (%d / S, %d, %d), not %s" % (rows, E, E, tuple(adj.shape)))
     share = rows // int(adj.shape[0])
+    _check_ids(agent_id, rows)
+    nemb, esz = _check_params(names, ps, meta, F)
+    dev = node_obs.device
+    _need_cuda(dev)
+    _layers.need_device(tensors + [("agent_id", agent_id)], dev, "node_obs")
+    return dev, rows, E, F, share, nemb, esz
+
+
+def _check_ids(agent_id, rows):
     if agent_id.dim() == 2 and agent_id.shape[0] == rows and agent_id.shape[1] > 1:
         raise NotImplementedError("agent_id has %d ids per row: gnn_base is built for one" % agent_id.shape[1])
     if tuple(agent_id.shape) not in ((rows,), (rows, 1)):
         raise ValueError("agent_id must have shape (rows,) or (rows, 1) = (%d,), not %s" % (rows, tuple(agent_id.shape)))
+
+
+def _check_params(names, ps, meta, F):
+    """the parameters' shapes for F node features -> (num_embeddings, embedding_size)"""
+    heads, gnn_n, embed_n, _, _, ln, _, aggregate, _ = meta
     table, w1 = ps[0], ps[1]
     if table.dim() != 2 or w1.dim() != 2:
         raise ValueError("base.gnn.embed_layer.entity_embed.weight and lin1.weight must be matrices")
@@ -159,10 +175,7 @@ def _check(node_obs, adj, agent_id, names, ps, meta):
     for name, t, s in zip(names, ps, shapes):
         if tuple(t.shape) != s:
             raise ValueError("base.gnn.%s must have shape %s (F = %d, %d heads of %d, averaged), not %s" % (name, s, F, heads, HIDDEN, tuple(t.shape)))
-    dev = node_obs.device
-    _need_cuda(dev)
-    _layers.need_device(tensors + [("agent_id", agent_id)], dev, "node_obs")
-    return dev, rows, E, F, share, nemb, esz
+    return nemb, esz
 
 
 def _shape_plan(rows, E, F, share, heads, gnn_n, embed_n, nemb, esz):
@@ -205,7 +218,9 @@ def _plan(shape, meta, node_obs, adj, agent_id, ps):
     rows, E, F, share, nemb, esz = shape
     p = _shape_plan(rows, E, F, share, heads, gnn_n, embed_n, nemb, esz)
     p.embed_activation, p.conv_activation, p.embed_layer_norm, p.aggregate, p.max_edge_dist, p.ln_eps = eact, cact, ln, aggregate, max_dist, ln_eps
-    p.node_obs, p.adj, p.agent_id = node_obs.data_ptr(), adj.data_ptr(), agent_id.data_ptr()
+    if node_obs is not None:                            # None: the base of a table plan, which reads neither
+        p.node_obs, p.adj = node_obs.data_ptr(), adj.data_ptr()
+    p.agent_id = agent_id.data_ptr()
     _fill(p, meta, ln, embed_n, gnn_n, ps, "")
     return p
 
@@ -240,6 +255,108 @@ class _Base(torch.autograd.Function):
         _fill(plan, ctx.meta, ctx.meta[5], ctx.meta[2], ctx.meta[1], grads, "grad_")
         _layers.run("gmpe_gnn_backward", dev, plan)
         return (None, None, None, None, None, None) + tuple(grads)
+
+
+def _table_plan(shape, meta, cfg, share, table, index, agent_id, ps):
+    """gmpe_gnn_table_plan around _plan's base: the table [table_rows, W], the index or the share"""
+    tp = _lib.GmpeGnnTablePlan()
+    tp.base = _plan(shape, meta, None, None, agent_id, ps)
+    tp.cfg, tp.table, tp.table_rows = C.pointer(cfg), table.data_ptr(), table.numel() // table.shape[-1]
+    if index is not None:
+        tp.table_index, tp.index64 = index.data_ptr(), int(index.dtype == torch.int64)
+    tp.table_share = share
+    return tp
+
+
+class _BaseTable(torch.autograd.Function):
+    """_Base with a graph's rows and matrix rebuilt from the entity table (gmpe_gnn_forward_table / _backward_table): the table, the index and the ids are
+    kept in place of node_obs and adj."""
+
+    @staticmethod
+    def forward(ctx, meta, shape, workspace, cfg, share, table, index, agent_id, *ps):
+        dev = table.device
+        cs = [t.detach().contiguous() for t in (agent_id,) + tuple(ps)]
+        features = torch.empty((shape[0], HIDDEN), dtype=torch.float32, device=dev)
+        tp = _table_plan(shape, meta, cfg, share, table, index, cs[0], cs[1:])
+        tp.base.features = features.data_ptr()
+        _layers.run("gmpe_gnn_forward_table", dev, tp)
+        if workspace is not None:
+            ctx.save_for_backward(*cs)
+            ctx.source = (cfg, share, table, index)
+        ctx.meta, ctx.shape, ctx.workspace = meta, shape, workspace
+        return features
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gf):
+        cs = list(ctx.saved_tensors)
+        cfg, share, table, index = ctx.source
+        gf = gf.contiguous()
+        grads = [torch.empty_like(t) for t in cs[1:]]
+        tp = _table_plan(ctx.shape, ctx.meta, cfg, share, table, index, cs[0], cs[1:])
+        tp.base.grad_features = gf.data_ptr()
+        tp.base.workspace, tp.base.workspace_bytes = ctx.workspace.data_ptr(), ctx.workspace.numel()
+        _fill(tp.base, ctx.meta, ctx.meta[5], ctx.meta[2], ctx.meta[1], grads, "grad_")
+        _layers.run("gmpe_gnn_backward_table", table.device, tp)
+        return (None,) * 8 + tuple(grads)
+
+
+def gnn_base_from_table(entity_table, table_index, agent_id, base, cfg, *, table_share=None, workspace=None):
+    """gnn_base(node_obs[table_index, agent_id], adj[table_index], agent_id, base) straight from the fp64 entity table those arrays are pure functions
+    of (gmpe_gnn_forward_table / _backward_table) -> nbd_features [rows, 16], bit for bit gnn_base's on the engine's own rows and adjacency, in the
+    output and in every parameter gradient (for equal `rows`: a parameter gradient's summation order is a function of (rows, E, configuration)).
+    Neither [rows, E, F] nor [rows, E, E] is ever written: a graph costs its index next to a table that is already there. It is NOT faster than
+    gnn_base on arrays that exist — the GNN's arithmetic dominates, and every graph rebuilds its own matrix —: its purpose is bytes.
+    entity_table: contiguous float64 device tensor [..., W], W = cfg.entity_table_width (an engine's out.entity_table, a DeviceRolloutBuffer's
+    entity_table); the leading dims are flattened to table rows. It is not copied: it must stay unchanged until backward has run.
+    table_index: int32 or int64 [rows], the table row of every graph (t * N + n for a buffer's [T+1, N, W]); or None with table_share = S, where
+    table row g // S serves graph g (a rollout step's [N, W] table with S = num_agents) and rows = table rows * S.
+    agent_id: gnn_base's, the ego whose view graph g is; needed whatever base's aggregate. An index outside the table and an id outside
+    [0, num_agents) are clamped: nothing is read out of bounds, and that row's value is unspecified.
+    base, workspace: gnn_base's, with its refusals; the node features and the entity count are cfg's. One autograd node over all parameters, nothing
+    saved under torch.no_grad()."""
+    names, ps, meta = _base_params(base)
+    if not isinstance(entity_table, torch.Tensor) or not isinstance(agent_id, torch.Tensor):
+        raise ValueError("entity_table and agent_id must be tensors")
+    if entity_table.dtype != torch.float64:
+        raise ValueError("entity_table must be float64, not %s" % entity_table.dtype)
+    W = int(cfg.entity_table_width)
+    if entity_table.dim() < 2 or int(entity_table.shape[-1]) != W or entity_table.numel() < W:
+        raise ValueError("entity_table must have shape (..., W) with W = cfg.entity_table_width = %d and at least one row, not %s"
+                         % (W, tuple(entity_table.shape)))
+    if not entity_table.is_contiguous():
+        raise ValueError("entity_table must be contiguous")
+    table_rows = entity_table.numel() // W
+    if table_index is not None:
+        if table_share is not None:
+            raise ValueError("table_share is for table_index = None: give one of them")
+        if not isinstance(table_index, torch.Tensor) or table_index.dtype not in (torch.int32, torch.int64):
+            raise ValueError("table_index must be an int32 or int64 tensor, or None with table_share")
+        if table_index.dim() != 1 or table_index.shape[0] < 1:
+            raise ValueError("table_index must have shape (rows,), not %s" % (tuple(table_index.shape),))
+        rows, share = int(table_index.shape[0]), 1
+    else:
+        if table_share is None or isinstance(table_share, bool) or int(table_share) != table_share or int(table_share) < 1:
+            raise ValueError("table_index is None: table_share must be an integer >= 1, not %r" % (table_share,))
+        share = int(table_share)
+        rows = table_rows * share
+    E, F = int(cfg.num_entities), int(cfg.node_feats)
+    if E > MAX_NODES:
+        raise NotImplementedError("E = %d nodes: gnn_base is built for at most %d" % (E, MAX_NODES))
+    _layers.need_float32("gnn_base_from_table", [("base.gnn." + n, t) for n, t in zip(names, ps)])
+    if agent_id.dtype not in (torch.int32, torch.int64, torch.float32):
+        raise ValueError("agent_id must be int32, int64 or float32, not %s" % agent_id.dtype)
+    _check_ids(agent_id, rows)
+    nemb, esz = _check_params(names, ps, meta, F)
+    dev = entity_table.device
+    _need_cuda(dev)
+    others = [("agent_id", agent_id)] + ([("table_index", table_index)] if table_index is not None else [])
+    _layers.need_device([("base.gnn." + n, t) for n, t in zip(names, ps)] + others, dev, "entity_table")
+    ids = agent_id.detach().reshape(rows).to(torch.int32)
+    index = None if table_index is None else table_index.detach().contiguous()
+    train = torch.is_grad_enabled() and any(t.requires_grad for t in ps)
+    workspace = _layers.backward_workspace(train, lambda: gnn_workspace_bytes(rows, E, F, meta[0], meta[1], meta[2], nemb, esz), workspace, dev)
+    return _BaseTable.apply(meta, (rows, E, F, 1, nemb, esz), workspace, cfg, share, entity_table.detach(), index, ids, *ps)
 
 
 def gnn_base(node_obs, adj, agent_id, base, workspace=None):

@@ -27,7 +27,11 @@ _ALIGN = 256
 # process_adj's result for one minibatch: edge_index [2, n] (row 0 sources, row 1 destinations; node ids graph * num_nodes + i), edge_attr [n, 1], and the
 # true edge count n_edges — an int in the exact mode, an int32 device tensor [1] with an explicit cap (then n = cap and only min(n_edges, cap) entries are edges)
 EdgeList = collections.namedtuple("EdgeList", ("edge_index", "edge_attr", "num_graphs", "num_nodes", "n_edges"))
-ADJ_MODES = ("matrix", "edges")
+# A minibatch's graphs addressed through the entity table the buffer already holds (adj="table"): `table` the buffer's own [T+1, N, W] tensor, not copied;
+# `index` int64 [rows], the table row t * N + n of every sample in the order the other entries are drawn; `cfg` the table's config. The ego of row r is
+# entry 4 (agent_id) or 5 (share_agent_id) of the same tuple. gmpe.gnn_base_from_table consumes it: no [rows, E, F] and no [rows, E, E] batch is written.
+TableRows = collections.namedtuple("TableRows", ("table", "index", "cfg"))
+ADJ_MODES = ("matrix", "edges", "table")
 
 
 def check_edge_args(adj, max_edge_dist, cap=None):
@@ -90,6 +94,18 @@ def edge_list(cfg, device, source, src, T, N, A, E, max_edge_dist, perm=None, of
     return EdgeList(ei, ea, graphs, E, ne)
 
 
+def table_index(units, T, N, A, data_chunk_length=None):
+    """The table row t * N + n of every output row of a minibatch over `units` (int64 tensor: its slice of the permutation), in the gather's row order —
+    sample_of's map (csrc/gmpe_mb_map.h) in torch's integer arithmetic, on the device `units` is on. Feed-forward (data_chunk_length None): unit u is
+    sample u of the [T, N, A] order, so t * N + n = u // A. Recurrent: unit k is chunk c; its sample l is entry c * L + l of the [N, A, T] order and
+    stands at output row l * len(units) + k."""
+    if data_chunk_length is None:
+        return units // A
+    L = int(data_chunk_length)
+    f = (units[None, :] * L + torch.arange(L, dtype=torch.int64, device=units.device)[:, None]).reshape(-1)
+    return (f % T) * N + f // (A * T)
+
+
 def _slot_array(name, t, lead, tail_dims, dtypes, device):
     """`t` must be a contiguous tensor [lead..., *tail] of one of `dtypes` on `device` (tail entries None: any size, at least 1), else ValueError."""
     shape_ok = isinstance(t, torch.Tensor) and t.dim() == len(lead) + len(tail_dims) and tuple(t.shape[:len(lead)]) == tuple(lead) and \
@@ -127,6 +143,8 @@ class Gather(object):
                 raise ValueError("arrays[%r] is required" % k)
         if adj == "edges" and "adj" not in arrays and "entity_table" not in arrays:
             raise ValueError('adj="edges" needs an adjacency form in the arrays: adj (materialised or compact) or the entity_table')
+        if adj == "table" and "entity_table" not in arrays:
+            raise ValueError('adj="table" needs the entity_table in the arrays (a buffer whose engine keeps tables: node_form "table" or "both")')
         obs = arrays["obs"]
         if not isinstance(obs, torch.Tensor) or obs.dim() != 4 or obs.shape[0] < 2:
             raise ValueError("obs must be a float32 tensor [T+1, N, A, D] with T >= 1")
@@ -161,6 +179,8 @@ class Gather(object):
         tab = arrays.get("entity_table")
         if tab is not None:
             chk("entity_table", (T1, N), (W,), (torch.float64,))
+        self._table = tab
+        nrows = len(fields)
         if "node_obs" in arrays:
             add("node_obs", _lib.MB_ROW, chk("node_obs", full, (E, F), f32), E * F * 4, torch.float32, (E, F))
         elif tab is not None:
@@ -184,6 +204,8 @@ class Gather(object):
         self.adj_mode = adj
         if adj == "edges":
             del fields[nfields:]                             # no [rows, E, E] batch: the minibatch's entry 3 is the EdgeList (edges)
+        elif adj == "table":
+            del fields[nrows:]                               # ... nor a [rows, E, F] one: entry 2 is None, entry 3 the TableRows (table_rows)
         ids = arrays["agent_id"]
         add("agent_id", _lib.MB_ROW, ids, 4, torch.int32, (1,))
         if use_centralized_V:
@@ -275,6 +297,14 @@ class Gather(object):
         return edge_list(self.cfg, self.device, source, src, self.T, self.N, self.A, self.cfg.num_entities, max_edge_dist, perm=perm, offset=offset, rows=rows,
                          data_chunk_length=self.L if self.recurrent else None, inclusive=inclusive, index64=index64, cap=cap)
 
+    def table_rows(self, perm, offset, rows):
+        """The TableRows of the minibatch perm[offset : offset + rows]: the buffer's own entity table and, per output row of __call__, its table row
+        t * N + n — sample_of's map (csrc/gmpe_mb_map.h) in torch's integer arithmetic on the device. Enqueued on the current stream; nothing is gathered."""
+        if self._table is None:
+            raise ValueError('table_rows needs the entity_table in the arrays (a buffer whose engine keeps tables: node_form "table" or "both")')
+        units = perm[int(offset):int(offset) + int(rows)]
+        return TableRows(self._table, table_index(units, self.T, self.N, self.A, self.L if self.recurrent else None), self.cfg)
+
     def tuple(self, out):
         """the reference's 16-tuple order (None where a field was not given)"""
         return tuple(out.get(k) for k in TUPLE)
@@ -337,7 +367,9 @@ def feed_forward_generator(cfg, arrays, advantages, num_mini_batch=None, mini_ba
                            max_edge_dist=None, inclusive=False):
     """GraphReplayBuffer.feed_forward_generator on the device: yields the reference's 16-tuple per minibatch (available_actions_batch None without
     available_actions). The arguments are checked here; the permutation is drawn at the first next(), as the reference's.
-    adj="edges": entry 3 of the tuple is the minibatch's EdgeList (process_adj with max_edge_dist; exact sizes) and no adj batch is written."""
+    adj="edges": entry 3 of the tuple is the minibatch's EdgeList (process_adj with max_edge_dist; exact sizes) and no adj batch is written.
+    adj="table" (the arrays must hold the entity_table): entry 2 is None and entry 3 the minibatch's TableRows — the table itself and one int64 per row —,
+    so neither the node rows nor the matrices are written; gmpe.policy's layers run gnn_base_from_table on it."""
     check_edge_args(adj, max_edge_dist)
     if advantages is None:
         raise ValueError("feed_forward_generator needs the advantages (the reference reshapes them unconditionally, graph_buffer.py:422)")
@@ -381,5 +413,7 @@ def _run(g, sampler, perm, max_edge_dist=None, inclusive=False):
             out = g(p, off, rows) if rows else _empty(g)
             if g.adj_mode == "edges":
                 out["adj"] = g.edges(p, off, rows, max_edge_dist, inclusive) if rows else _empty_edges(g)
+            elif g.adj_mode == "table":
+                out["adj"] = g.table_rows(p, off, rows)
             yield g.tuple(out)
     return gen()

@@ -24,9 +24,10 @@ import collections
 import torch
 import torch.nn.functional as F
 
-from .gnn import gnn_base
+from .gnn import gnn_base, gnn_base_from_table
 from .gru import rnn_layer
 from .head import act_head, action_logits
+from .minibatch import TableRows
 from .mlp import mlp_base
 from . import infos as _infos
 from . import optim as _optim
@@ -43,8 +44,14 @@ def _recurrent(net):
 
 
 def _features(net, own_obs, node_obs, adj, agent_id, rnn_states, masks):
-    """(features [rows, 64], rnn_states) of an actor or a critic in front of its head; own_obs None: the graph features alone enter the MLPBase"""
-    nbd = gnn_base(node_obs, adj, agent_id, net.gnn_base)
+    """(features [rows, 64], rnn_states) of an actor or a critic in front of its head; own_obs None: the graph features alone enter the MLPBase.
+    adj a gmpe.minibatch.TableRows (node_obs is then not read): the GNNBase runs straight from the entity table, graph r the view of ego agent_id[r] of
+    table row index[r] — or, without an index, of row r // num_agents: a rollout step's [N, W] table."""
+    if isinstance(adj, TableRows):
+        share = None if adj.index is not None else int(adj.cfg.num_agents)
+        nbd = gnn_base_from_table(adj.table, adj.index, agent_id, net.gnn_base, adj.cfg, table_share=share)
+    else:
+        nbd = gnn_base(node_obs, adj, agent_id, net.gnn_base)
     features = mlp_base(nbd if own_obs is None else (own_obs, nbd), net.base)
     if _recurrent(net):
         features, rnn_states = rnn_layer(features, rnn_states, masks, net.rnn)
@@ -112,6 +119,13 @@ PPOUpdate = collections.namedtuple("PPOUpdate", ["value_loss", "critic_grad_norm
 TRAIN_INFO = ("value_loss", "policy_loss", "dist_entropy", "actor_grad_norm", "critic_grad_norm", "ratio")      # graph_mappo.py:309-314
 
 
+def _graph_kind(fn, graph):
+    """train's `graph` -> the generators' adj"""
+    if graph not in ("rows", "table"):
+        raise ValueError("graph = %r: %s takes \"rows\" (node rows and matrices per minibatch) or \"table\" (the buffer's entity table)" % (graph, fn))
+    return "table" if graph == "table" else "matrix"
+
+
 def _refusals(fn, accumulation_steps, shards):
     """what ppo_update and train refuse, before anything else is read"""
     if shards is not None and not (callable(getattr(shards, "exchange", None)) and hasattr(shards, "world") and hasattr(shards, "rank")):
@@ -170,7 +184,7 @@ def ppo_update(actor, critic, actor_optimizer, critic_optimizer, sample, args, v
 
 
 def train(actor, critic, actor_optimizer, critic_optimizer, buffer, args, value_normalizer=None, update_actor=True, perms=None, *, install="replace",
-          accumulation_steps=1, shards=None, value_head="torch"):
+          accumulation_steps=1, shards=None, value_head="torch", graph="rows"):
     """GR_MAPPO.train (graph_mappo.py:294-359) over a DeviceRolloutBuffer: buffer.normalized_advantages(value_normalizer), then args.ppo_epoch (15) passes
     of the generator the reference chooses — recurrent_generator with args.data_chunk_length (10) under args.use_recurrent_policy (True), else
     naive_recurrent_generator under args.use_naive_recurrent_policy, else feed_forward_generator, each with args.num_mini_batch (1) — and ppo_update
@@ -183,22 +197,29 @@ def train(actor, critic, actor_optimizer, critic_optimizer, buffer, args, value_
     ranks' buffers (normalized_advantages(value_normalizer, shards=shards)), every minibatch is ppo_update(..., shards=shards), and ratio is the sum
     of all ranks' imp_weights over their count. Every rank must produce the same number of minibatches (the same ppo_epoch and num_mini_batch over
     buffers that yield as many samples): a rank that stops early leaves the others waiting in the exchange. Each rank draws its own permutation.
-    value_head: minibatch_losses'."""
+    value_head: minibatch_losses'.
+    graph: "rows" — every minibatch gathers its [rows, E, F] node rows and [rows, E, E] matrices — or "table": the generators run with adj="table" and
+    the GNNBase of actor and critic reads the buffer's entity table through one int64 per row (gnn_base_from_table), for a buffer that keeps tables
+    (node_form "table" or "both"). The same bits, parameters and train_info, and no faster; what it saves is the minibatch's bytes."""
     _refusals("train", accumulation_steps, shards)
     _value_head_kind("train", value_head)
+    adj = _graph_kind("train", graph)
     ppo_epoch, num_mini_batch = int(getattr(args, "ppo_epoch", 15)), int(getattr(args, "num_mini_batch", 1))
     if perms is not None and len(perms) != ppo_epoch:
         raise ValueError("perms must hold one permutation per epoch: %d, not %d" % (ppo_epoch, len(perms)))
     advantages = buffer.normalized_advantages(value_normalizer) if shards is None else buffer.normalized_advantages(value_normalizer, shards=shards)
     info = None
+    form = {} if adj == "matrix" else {"adj": adj}          # "rows": the generators are called as before, so any buffer with their signature still serves
     for epoch in range(ppo_epoch):
         perm = None if perms is None else perms[epoch]
         if getattr(args, "use_recurrent_policy", True):
-            generator = buffer.recurrent_generator(advantages, num_mini_batch, int(getattr(args, "data_chunk_length", 10)), perm=perm)
+            generator = buffer.recurrent_generator(advantages, num_mini_batch, int(getattr(args, "data_chunk_length", 10)), perm=perm, **form)
         elif getattr(args, "use_naive_recurrent_policy", False):
+            if form:
+                raise NotImplementedError("graph = \"table\": naive_recurrent_generator yields node rows and matrices only (not supported)")
             generator = buffer.naive_recurrent_generator(advantages, num_mini_batch)
         else:
-            generator = buffer.feed_forward_generator(advantages, num_mini_batch, perm=perm)
+            generator = buffer.feed_forward_generator(advantages, num_mini_batch, perm=perm, **form)
         for sample in generator:
             u, ratio = _ppo_update(actor, critic, actor_optimizer, critic_optimizer, sample, args, value_normalizer, update_actor, install, None, shards,
                                    value_head)
@@ -212,6 +233,12 @@ def train(actor, critic, actor_optimizer, critic_optimizer, buffer, args, value_
 
 # ---------------------------------------------------------------------------------------------- one update as a captured graph
 _NORM_TENSORS = ("running_mean", "running_mean_sq", "debiasing_term", "weight", "bias", "stddev", "mean", "mean_sq")      # ValueNorm's and PopArt's
+
+
+def _no_table_rows(fn, sample):
+    if any(isinstance(t, TableRows) for t in sample):
+        raise NotImplementedError("%s: the sample holds a TableRows (adj=\"table\"): a captured update takes node rows and matrices only — the table form "
+                                  "is not supported under capture" % fn)
 
 
 def _same_sample(fn, static, sample):
@@ -268,6 +295,7 @@ class CapturedUpdate(object):
         _optim._groups(critic_optimizer)
         if not isinstance(sample, (tuple, list)) or len(sample) != 16:
             raise ValueError("sample must be the generators' 16-tuple")
+        _no_table_rows("CapturedUpdate", sample)
         dev = sample[1].device
         if dev.type != "cuda":
             raise ValueError("the arrays must be CUDA (HIP) device tensors: these kernels have no CPU fallback")
@@ -365,6 +393,7 @@ class CapturedUpdate(object):
         return min(s.remaining for s in self._steps())
 
     def update(self, sample):
+        _no_table_rows("CapturedUpdate.update", sample)
         _same_sample("CapturedUpdate.update", self.sample, sample)
         for s in self._steps():
             s._budget.need("CapturedUpdate.update")
@@ -455,9 +484,10 @@ def _rollout_buffer(fn, actor, critic, buffer, returns=False):
             raise ValueError("buffer must be a DeviceRolloutBuffer: %s reads buffer.%s" % (fn, name))
     if buffer.value_preds is None or (returns and buffer.returns is None):
         raise ValueError("%s needs a buffer with value_preds%s (policy_fields)" % (fn, " and returns" if returns else ""))
-    if getattr(buffer, "_node_obs", None) is None:
+    table = getattr(buffer, "entity_table", None) is not None          # then a slot's graphs can come from its table (_slot_rows)
+    if getattr(buffer, "_node_obs", None) is None and not table:
         raise ValueError("%s reads node_obs rows: the buffer's engine must keep them (node_form 'rows' or 'both')" % fn)
-    if getattr(buffer, "_adj", None) is None:
+    if getattr(buffer, "_adj", None) is None and not table:
         raise ValueError("%s reads an adjacency: the buffer's engine must keep one (adj_form not 'none')" % fn)
     for net, field in ((actor, "rnn_states"), (critic, "rnn_states_critic")):
         if net is not None and _recurrent(net) and getattr(buffer, field, None) is None:
@@ -465,11 +495,16 @@ def _rollout_buffer(fn, actor, critic, buffer, returns=False):
 
 
 def _slot_rows(buffer, t):
-    """slot t of the buffer's arrays as the networks take them: [N, A, ...] flattened to rows"""
+    """slot t of the buffer's arrays as the networks take them: [N, A, ...] flattened to rows. A buffer that lacks the node rows or the adjacency gives
+    the slot's graphs as its [N, W] entity table instead (a TableRows without an index: table row r // A serves row r)"""
     e = buffer.engine
-    rows, E = e.N * e.A, int(buffer._node_obs.shape[-2])
+    rows, E = e.N * e.A, int(e.cfg.num_entities)
     flat = lambda x: None if x is None else x[t].reshape((rows,) + tuple(x.shape[3:]))
-    return dict(share_obs=flat(buffer.share_obs), obs=flat(buffer.obs), node_obs=flat(buffer._node_obs), adj=buffer._adj[t].reshape(-1, E, E),
+    if buffer._node_obs is None or buffer._adj is None:
+        node_obs, adj = None, TableRows(buffer.entity_table[t], None, e.cfg)
+    else:
+        node_obs, adj = flat(buffer._node_obs), buffer._adj[t].reshape(-1, E, E)
+    return dict(share_obs=flat(buffer.share_obs), obs=flat(buffer.obs), node_obs=node_obs, adj=adj,
                 agent_id=flat(buffer.agent_id), share_agent_id=flat(buffer.share_agent_id), rnn_states=flat(buffer.rnn_states),
                 rnn_states_critic=flat(buffer.rnn_states_critic), masks=flat(buffer.masks))
 
@@ -520,15 +555,16 @@ def rollout(actor, critic, buffer, value_normalizer=None, deterministic=False):
 
 
 def iteration(actor, critic, actor_optimizer, critic_optimizer, buffer, args, value_normalizer=None, update_actor=True, perms=None, *,
-              deterministic=False, install="replace", accumulation_steps=1, shards=None, value_head="torch"):
+              deterministic=False, install="replace", accumulation_steps=1, shards=None, value_head="torch", graph="rows"):
     """One iteration of run() (graph_mpe_runner.py:57-129): rollout, train, buffer.after_update(). Returns train's dict plus
     average_episode_rewards = buffer.rewards.mean() * buffer.T (graph_mpe_runner.py:117), a 0-dim device tensor like the others.
-    update_actor, perms, install, accumulation_steps, shards, value_head: train's; deterministic: collect_step's."""
+    update_actor, perms, install, accumulation_steps, shards, value_head, graph: train's; deterministic: collect_step's."""
     _refusals("iteration", accumulation_steps, shards)
     _value_head_kind("iteration", value_head)
+    _graph_kind("iteration", graph)
     rollout(actor, critic, buffer, value_normalizer, deterministic)
     info = train(actor, critic, actor_optimizer, critic_optimizer, buffer, args, value_normalizer, update_actor, perms, install=install,
-                 accumulation_steps=accumulation_steps, shards=shards, value_head=value_head)
+                 accumulation_steps=accumulation_steps, shards=shards, value_head=value_head, graph=graph)
     info["average_episode_rewards"] = buffer.rewards.mean() * buffer.T
     buffer.after_update()
     return info

@@ -427,10 +427,11 @@ class DeviceRolloutBuffer(object):
         return self.advantages
 
     # ------------------------------------------------------------------ PPO minibatches (GraphReplayBuffer's generators, gmpe_minibatch_gather)
-    def minibatch_arrays(self, learner=None):
+    def minibatch_arrays(self, learner=None, table=False):
         """The arrays a minibatch gathers from, in the storage form the buffer keeps (node rows or entity table; materialised, compact or no adjacency) plus the
         learner arrays (rnn_states / rnn_states_critic [T+1, N, A, R, H], actions / action_log_probs [T, N, A, k]): the buffer's own (learner_fields), each
-        overridden by an array of the same name in `learner`."""
+        overridden by an array of the same name in `learner`. table: the entity table too wherever the buffer keeps one (adj="table" addresses a minibatch
+        through it, whatever else is kept)."""
         e = self.engine
         N, A, T1 = e.N, e.A, self.T + 1
         arrays = dict(obs=self.obs, agent_id=self.agent_id, masks=self.masks, active_masks=self.active_masks, value_preds=self.value_preds,
@@ -442,6 +443,8 @@ class DeviceRolloutBuffer(object):
         if self._adj is not None:
             arrays["adj"] = self._adj
         elif self.entity_table is not None:
+            arrays["entity_table"] = self.entity_table
+        if table and self.entity_table is not None:
             arrays["entity_table"] = self.entity_table
         for name in LEARNER_FIELDS:
             if getattr(self, name, None) is not None:
@@ -472,9 +475,11 @@ class DeviceRolloutBuffer(object):
         unless the buffer or `learner` holds them), one gather launch per minibatch (two with the entity-table forms). perm: None draws torch.randperm on the CPU default
         generator as the reference does (a seeded run trains on the same minibatches) and uploads it once; "device" draws on the device; or an int64 tensor.
         adj="edges" (with max_edge_dist, inclusive): entry 3 is the minibatch's EdgeList — process_adj's result, computed once for actor and critic from the
-        adjacency form the buffer stores (gmpe_minibatch_edges) — and no [rows, E, E] batch is written."""
+        adjacency form the buffer stores (gmpe_minibatch_edges) — and no [rows, E, E] batch is written.
+        adj="table" (a buffer that keeps entity tables: node_form "table" or "both"): entry 2 is None and entry 3 the minibatch's gmpe.minibatch.TableRows —
+        this buffer's entity_table, not copied, and one int64 per row — for gmpe.gnn_base_from_table; neither the rows nor the matrices are written."""
         check_edge_args(adj, max_edge_dist)
-        return feed_forward_generator(self.engine.cfg, self.minibatch_arrays(learner), self._advantages(advantages), num_mini_batch, mini_batch_size,
+        return feed_forward_generator(self.engine.cfg, self.minibatch_arrays(learner, adj == "table"), self._advantages(advantages), num_mini_batch, mini_batch_size,
                                       perm=perm, use_centralized_V=self.use_centralized_V, adj=adj, max_edge_dist=max_edge_dist, inclusive=inclusive)
 
     def recurrent_generator(self, advantages, num_mini_batch, data_chunk_length, *, learner=None, perm=None, adj="matrix", max_edge_dist=None, inclusive=False):
@@ -482,7 +487,7 @@ class DeviceRolloutBuffer(object):
         l * chunks + k, rnn states [chunks, R, H] from each chunk's first sample. perm as feed_forward_generator (over the T*N*A // L chunks); adj,
         max_edge_dist, inclusive as feed_forward_generator."""
         check_edge_args(adj, max_edge_dist)
-        return recurrent_generator(self.engine.cfg, self.minibatch_arrays(learner), self._advantages(advantages), num_mini_batch, data_chunk_length,
+        return recurrent_generator(self.engine.cfg, self.minibatch_arrays(learner, adj == "table"), self._advantages(advantages), num_mini_batch, data_chunk_length,
                                    perm=perm, use_centralized_V=self.use_centralized_V, adj=adj, max_edge_dist=max_edge_dist, inclusive=inclusive)
 
     def step_edges(self, step, max_edge_dist, inclusive=False, index64=True, cap=None):

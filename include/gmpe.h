@@ -1133,6 +1133,34 @@ int gmpe_gnn_workspace_bytes(const gmpe_gnn_plan* plan, int32_t want_backward, s
 int gmpe_gnn_forward(int device, const gmpe_gnn_plan* plan, void* stream);
 int gmpe_gnn_backward(int device, const gmpe_gnn_plan* plan, void* stream);
 
+/* ---- The same GNNBase straight from the fp64 entity table (gmpe_outputs.entity_table): the policy as a consumer of the table form ----
+ * Graph g is the view of ego = agent_id[g] of table row idx: idx = table_index[g] with an index, g / table_share without one (a rollout step's [N, W]
+ * table serves its N * A rows with table_share = A). Nothing else changes: the plan wraps an unchanged gmpe_gnn_plan, and
+ *     features, gradients == gmpe_gnn_forward / _backward on node_obs[g] = the row gmpe_expand_node_obs gives for (idx, ego), adj[g] = the matrix
+ *     gmpe_expand_adj gives for idx, BIT FOR BIT
+ * for equal base.rows (a parameter gradient's summation order is a function of (rows, E, configuration), as above). The kernels rebuild entry (j, i) of
+ * the matrix and node `lane`'s row in the step that stages a graph's inputs in LDS, with the arithmetic those two entry points share, and everything
+ * behind that step is the code of gmpe_gnn_forward / _backward: ONE launch forward, THREE backward, the same workspace (gmpe_gnn_workspace_bytes of
+ * the base plan: the same function of the shapes), no atomics, no allocation, no host synchronisation, capturable. Neither [rows, E, F] nor [rows, E, E]
+ * exists in memory: a graph costs its 4- or 8-byte index next to a table that is already there.
+ * It is not faster: the GNN's arithmetic dominates, and every graph rebuilds its own E x E matrix (DESIGN.md 3.13 has the measured times). Its purpose is bytes.
+ * base.node_obs, base.adj and base.adj_share are not read. base.num_nodes and base.node_feats must be gmpe_num_entities(cfg) and gmpe_node_feats(cfg).
+ * base.agent_id is always required: the view needs its ego, whatever the aggregate. idx is clamped into [0, table_rows) and ego into [0, num_agents):
+ * nothing is read out of bounds, and such a row's value is unspecified. Refused before any device call, with the function and the field named: a null
+ * plan, cfg or table; num_nodes / node_feats that disagree with cfg; a table not 8-byte aligned; a table_index not 4-byte (index64 = 0) or 8-byte
+ * (index64 = 1) aligned; table_rows < 1; without an index, table_share < 1 or rows not a multiple of it; and everything gmpe_gnn_forward refuses. */
+typedef struct gmpe_gnn_table_plan {
+    gmpe_gnn_plan base;                 /* as for gmpe_gnn_forward / _backward; node_obs, adj and adj_share are not read                */
+    const gmpe_config* cfg;             /* host memory: the scenario, feature type and entity counts the table was written with          */
+    const double* table;                /* [table_rows, W] f64 device memory, W = gmpe_entity_table_width(cfg), 8-byte aligned          */
+    int64_t table_rows;                 /* >= 1                                                                                       */
+    const void* table_index;            /* [rows] int32 or int64 device memory, or NULL: idx = g / table_share                        */
+    int32_t index64;                    /* 0: table_index is int32; 1: int64                                                          */
+    int32_t table_share;                /* without table_index: >= 1, rows a multiple of it; ignored with one                         */
+} gmpe_gnn_table_plan;
+int gmpe_gnn_forward_table(int device, const gmpe_gnn_table_plan* plan, void* stream);
+int gmpe_gnn_backward_table(int device, const gmpe_gnn_table_plan* plan, void* stream);
+
 /* ---- Evaluation of a policy over a batch of episodes (handle-less): GMPERunner.render(get_metrics=True) as one episode per env ----
  * (onpolicy/runner/shared/graph_mpe_runner.py:526-1060, base_runner.py:194-574). Every env plays one episode from a reset; the caller's policy acts,
  * the engine steps, gmpe_episode_record books the step. No allocation, no host synchronisation, every launch on `stream`.
