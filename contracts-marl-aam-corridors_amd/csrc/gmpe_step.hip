@@ -889,7 +889,15 @@ static int launch(gmpe_handle* h, int mode, const int32_t* act, const float* one
     HIPCHK(hipSetDevice(h->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (h->timing && !h->capturing) {
+    // the per-launch event pairs are for eager launches: none inside the handle's own capture (gmpe_step_many_prepare), and none inside a caller's —
+    // the stream itself is asked, since h->capturing knows of the handle's own capture only (a stream that cannot be asked is timed as before)
+    bool timed = h->timing && !h->capturing;
+    if (timed) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(st, &cs) != hipSuccess) (void)hipGetLastError();
+        else if (cs != hipStreamCaptureStatusNone) timed = false;
+    }
+    if (timed) {
         if (h->ev_used + 2 > h->ev.size()) {
             for (int q = 0; q < 2; ++q) { hipEvent_t e; HIPCHK(hipEventCreate(&e)); h->ev.push_back(e); }
         }
@@ -904,7 +912,7 @@ static int launch(gmpe_handle* h, int mode, const int32_t* act, const float* one
         launch_env(h, false, st, p);
     }
     HIPCHK(hipGetLastError());
-    if (h->timing && !h->capturing) { HIPCHK(hipEventRecord(e1, st)); h->ev_used += 2; }
+    if (timed) { HIPCHK(hipEventRecord(e1, st)); h->ev_used += 2; }
     return GMPE_OK;
 }
 

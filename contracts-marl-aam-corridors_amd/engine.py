@@ -61,6 +61,7 @@ class GmpeEngine(object):
             info=torch.empty((N, A, len(INFO_KEYS)), dtype=torch.float32, device=dev) if with_info else None)
         self._tape = None
         self._ovr = None
+        self._timing = False
         self._o = self._pack(self.out)
 
     # ------------------------------------------------------------------ plumbing
@@ -362,6 +363,7 @@ class GmpeEngine(object):
     # ------------------------------------------------------------------ timing hooks
     def timing(self, enable):
         _lib.check(self.lib.gmpe_timing_enable(self.h, int(bool(enable))), "gmpe_timing_enable")
+        self._timing = bool(enable)                         # what a caller's graph capture asks before it records a step (gmpe.policy.CapturedRollout)
 
     def timing_read(self, reset=True):
         ms, n = C.c_double(), C.c_int64()

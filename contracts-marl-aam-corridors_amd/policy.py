@@ -11,6 +11,7 @@
     evaluate_actions + the loss arithmetic of ppo_update  ->  minibatch_losses(actor, critic, sample, args, ...)
     GR_MAPPO.ppo_update                                   ->  ppo_update(actor, critic, actor_optimizer, critic_optimizer, sample, args, ...)
     GR_MAPPO.train                                        ->  train(actor, critic, actor_optimizer, critic_optimizer, buffer, args, ...)
+    one update / one episode's rollout as a replayed graph ->  CapturedUpdate(...).update / .train, CapturedRollout(...).replay; run(..., captured=True)
     the evaluator's act callable                          ->  evaluator_act(actor, evaluator)
 
 The modules are the caller's unchanged GR_Actor / GR_Critic (onpolicy/algorithms/graph_actor_critic.py), read by their attribute names (.gnn_base, .base,
@@ -509,13 +510,15 @@ def _slot_rows(buffer, t):
                 rnn_states_critic=flat(buffer.rnn_states_critic), masks=flat(buffer.masks))
 
 
-def collect_step(actor, critic, buffer, deterministic=False):
+def collect_step(actor, critic, buffer, deterministic=False, *, draw_dev=None):
     """One step of run()'s loop (graph_mpe_runner.py:57-103: collect or collect_with_mask, envs.step, insert) on a DeviceRolloutBuffer built with
     policy_fields and learner_fields: get_actions on slot buffer.step — the availability taken from dones[step - 1], everything available at step 0,
     the draw keyed by buffer.act_draw, the values written into value_preds[step], the action and its log-prob into their slots —, then the env step,
     the masks and the RNN states of slot step + 1 with the done rows zeroed, as DeviceRolloutBuffer.act_step does them. Bit for bit what
     act_step(action_logits(...), value_head(...), rnn_states=..., rnn_states_critic=...) stores from the same layer calls. Nothing is copied to the
-    host and nothing waits for the device. Returns the engine's outputs of the step."""
+    host and nothing waits for the device. Returns the engine's outputs of the step.
+    draw_dev: None, or act_head's int64 [1] device counter (buffer.act_draw_counter()): the draw is then keyed by what the counter holds when the
+    launch runs, not by the host's buffer.act_draw, and the launch adds one to it — the form a captured step takes (CapturedRollout)."""
     _rollout_buffer("collect_step", actor, critic, buffer)
     t, e = buffer.step, buffer.engine
     c, rows = e.cfg, e.N * e.A
@@ -525,7 +528,8 @@ def collect_step(actor, critic, buffer, deterministic=False):
     buffer.available_actions_for(t)
     _, _, _, h, hc = get_actions(actor, critic, s["share_obs"], s["obs"], s["node_obs"], s["adj"], s["agent_id"], s["share_agent_id"], s["rnn_states"],
                                  s["rnn_states_critic"], s["masks"], None, deterministic, dones_prev=buffer.dones[t - 1].view(rows) if t else None,
-                                 seed=c.seed, env_id_base=c.env_id_base, num_agents=e.A, draw=buffer.act_draw, out=out)
+                                 seed=c.seed, env_id_base=c.env_id_base, num_agents=e.A, draw=buffer.act_draw if draw_dev is None else 0,
+                                 draw_dev=draw_dev, out=out)
     learner = buffer._learner_inputs(None, None, None, h if _recurrent(actor) else None, hc if _recurrent(critic) else None, "collect_step")
     return buffer.act_finish(learner)
 
@@ -552,6 +556,199 @@ def rollout(actor, critic, buffer, value_normalizer=None, deterministic=False):
     for _ in range(buffer.T):
         collect_step(actor, critic, buffer, deterministic)
     return compute(critic, buffer, value_normalizer)
+
+
+# ---------------------------------------------------------------------------------------------- one rollout as a captured graph
+def _buffer_arrays(buffer):
+    """every device tensor the buffer holds, named for a complaint: what a rollout writes lies among them, and a captured one has their addresses
+    in its nodes (the buffer enumerates its own: DeviceRolloutBuffer._arrays)"""
+    return [("buffer." + k, t) for k, t in buffer._arrays()]
+
+
+def _capturable_engine(fn, engine, path=True):
+    """what a captured rollout refuses of the buffer's engine, by name, from what the host knows; path: the handle's launch path too (fixed at creation)"""
+    if getattr(engine, "_timing", False):
+        raise NotImplementedError("%s: the engine's timing is enabled (GmpeEngine.timing(True)): its per-launch event pairs have no place in a captured "
+                                  "graph — timing(False) first (not supported under capture)" % fn)
+    if path and getattr(engine, "adj_form", None) == "full" and engine.tuning()["split"]:
+        raise NotImplementedError("%s: this handle runs the split big-E path with a dense adjacency, whose steps fork onto side streams; a captured "
+                                  "rollout is one chain on one stream — adj_compact=True or adj_form=\"none\" (not supported under capture)" % fn)
+
+
+class CapturedRollout(object):
+    """rollout(actor, critic, buffer, value_normalizer, deterministic) captured once as a torch.cuda.CUDAGraph and replayed: buffer.T collect_steps and
+    compute, unrolled — every step's slot addresses in its own nodes —, the same kernels on the same inputs in the same order, so the same bits, with
+    one host call per episode where rollout issues about twelve launches per step through Python.
+
+        cap = gmpe.policy.CapturedRollout(actor, critic, buffer, value_normalizer)
+        returns = cap.replay()        # == rollout(actor, critic, buffer, value_normalizer), bit for bit
+
+      buffer: rollout's, at buffer.step == 0 (after warmup() or after_update()); rows form or table-only. deterministic: collect_step's, fixed here.
+    The action draws come from the buffer's device counter (buffer.act_draw_counter()): every captured step keys its draw by the counter and adds one
+    to it; replay() first makes the counter equal buffer.act_draw — eager steps may have run since —, launches, adds T to buffer.act_draw, leaves
+    buffer.step at 0 and points the engine's current outputs at slot T, as rollout does. Nothing waits for the device.
+    Construction runs the rollout once on a side stream (the warm-up torch.cuda.graph asks for; it also gets every kernel's one-time attribute call
+    out of the way) and once under capture, which executes nothing, then puts back bit for bit what the warm-up wrote: the engine's state
+    (get_state / set_state, which wait for the device), every buffer array, act_draw, step and the engine's bound outputs.
+    The graph holds addresses: of every actor and critic parameter, of the value normaliser's tensors and of every buffer array. Values changed in
+    place are followed — an optimiser step (torch's Adam, clip_and_step), a ValueNorm update, PopArt with install="in_place" —; a tensor that moved
+    is not: replay() compares every data_ptr with the captured one and raises RuntimeError, naming the first that differs, before anything is
+    launched. The engine's RNG tape and control override are kernel parameters too: one installed or removed after capture is refused by name.
+    Everything runs on the current stream, as one linear graph."""
+
+    def __init__(self, actor, critic, buffer, value_normalizer=None, deterministic=False):
+        fn = "CapturedRollout"
+        _rollout_buffer(fn, actor, critic, buffer, returns=True)
+        _, use_norm = buffer._flags(fn)
+        if use_norm and value_normalizer is None:
+            raise ValueError("%s: args.use_valuenorm / use_popart is set, so a value_normalizer is required" % fn)
+        if buffer.step != 0:
+            raise ValueError("%s starts at buffer.step == 0, not %d (warmup() or after_update() first)" % (fn, buffer.step))
+        e = buffer.engine
+        _capturable_engine(fn, e)
+        dev = e.device
+        if dev.type != "cuda":
+            raise ValueError("the arrays must be CUDA (HIP) device tensors: these kernels have no CPU fallback")
+        self.actor, self.critic, self.buffer, self.engine = actor, critic, buffer, e
+        self.value_normalizer, self.deterministic = value_normalizer, bool(deterministic)
+        self._ovr, self._tape = e._ovr, e._tape
+        self.counter = buffer.act_draw_counter()
+        buffer.act_outputs()                                # the buffer's own action scratch exists before its arrays are listed
+        # everything a rollout writes, as it is now
+        state, out, act_draw = e.get_state(), e.out, buffer.act_draw
+        kept = _unique([t for _, t in _buffer_arrays(buffer)])
+        with torch.no_grad():
+            saved = [t.clone() for t in kept]
+
+        def put_back(device):
+            """the host's counters and the binding; device: what the warm-up wrote too (a capture moves only the host's side)"""
+            if device:
+                torch.cuda.current_stream(dev).wait_stream(side)
+                e.set_state(state)
+                with torch.no_grad():
+                    for t, v in zip(kept, saved):
+                        t.copy_(v)
+            buffer.act_draw, buffer.step = act_draw, 0
+            e.rebind(out)
+
+        buffer.sync_act_draw_counter()
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        try:
+            with torch.cuda.stream(side):
+                self._body()                                # the captured sequence itself, eagerly
+        finally:
+            put_back(True)                                  # also when a layer refused half-way: construction changes nothing the caller can see
+        self.graph = torch.cuda.CUDAGraph()
+        try:
+            with torch.cuda.graph(self.graph):
+                self.returns = self._body()
+        finally:
+            put_back(False)
+        self._addresses = [(name, t.data_ptr()) for name, t in self._tensors()]
+
+    def _body(self):
+        b = self.buffer
+        for _ in range(b.T):
+            collect_step(self.actor, self.critic, b, self.deterministic, draw_dev=self.counter)
+        return compute(self.critic, b, self.value_normalizer)
+
+    def _tensors(self):
+        """(name, tensor) of everything whose address the graph holds, as the modules and the buffer hold them NOW, in a fixed order"""
+        out = [("actor." + k, p) for k, p in self.actor.named_parameters()] + [("critic." + k, p) for k, p in self.critic.named_parameters()]
+        for tag, o in (("value_normalizer.", self.value_normalizer), ("critic.v_out.", getattr(self.critic, "v_out", None))):
+            if o is not None:
+                out += [(tag + k, getattr(o, k)) for k in _NORM_TENSORS if isinstance(getattr(o, k, None), torch.Tensor)]
+        return out + _buffer_arrays(self.buffer)
+
+    def replay(self):
+        fn = "CapturedRollout.replay"
+        b, e = self.buffer, self.engine
+        if b.step != 0:
+            raise ValueError("%s starts at buffer.step == 0, not %d (warmup() or after_update() first)" % (fn, b.step))
+        _capturable_engine(fn, e, path=False)
+        if e._ovr is not self._ovr:
+            raise NotImplementedError("%s: the engine's control override was set or removed after capture: it is a kernel parameter of every captured "
+                                      "step — build a new CapturedRollout (not supported under capture)" % fn)
+        if e._tape is not self._tape:
+            raise NotImplementedError("%s: the engine's RNG tape was set or removed after capture: it is a kernel parameter of every captured step — "
+                                      "build a new CapturedRollout (not supported under capture)" % fn)
+        now = self._tensors()
+        if len(now) != len(self._addresses):
+            raise RuntimeError("%s: the graph was captured over %d tensors and the modules and the buffer now hold %d" % (fn, len(self._addresses), len(now)))
+        for (name, t), (was, ptr) in zip(now, self._addresses):
+            if name != was or t.data_ptr() != ptr:
+                raise RuntimeError("%s: %s is not where it was captured (%s): the graph reads and writes the captured address — keep tensors in place "
+                                   "(torch's Adam, clip_and_step and PopArt's install=\"in_place\" do), or build a new CapturedRollout"
+                                   % (fn, was, "now %s" % name if name != was else "data_ptr 0x%x, captured 0x%x" % (t.data_ptr(), ptr)))
+        if not e.h:
+            raise RuntimeError("%s: the engine was closed" % fn)
+        b.sync_act_draw_counter()
+        self.graph.replay()
+        b.act_draw += b.T
+        b._bind(b.T)
+        return self.returns
+
+
+def _captured_refusals(fn, keywords):
+    """what run(..., captured=True) refuses of its iteration keywords, as CapturedUpdate refuses them -> the keywords with install filled in"""
+    kw = dict(keywords)
+    install = kw.setdefault("install", "in_place")
+    if install != "in_place":
+        raise NotImplementedError("install = %r: %s with captured=True takes \"in_place\" only — \"replace\" creates new Parameters at every update, "
+                                  "whose addresses a captured graph cannot follow (not supported under capture)" % (install, fn))
+    if kw.get("shards") is not None:
+        raise NotImplementedError("shards: %s with captured=True runs one unsharded learner — the exchange between the ranks is no part of a captured "
+                                  "update (not supported under capture)" % fn)
+    if kw.get("graph", "rows") != "rows":
+        raise NotImplementedError("graph = %r: %s with captured=True takes \"rows\" only — a captured update takes node rows and matrices, the table "
+                                  "form is not supported under capture" % (kw["graph"], fn))
+    return kw
+
+
+class _CapturedIteration(object):
+    """iteration(...) with both halves replayed: the rollout through a CapturedRollout built at the first call, train through a CapturedUpdate built
+    from the first minibatch of the first episode — drawn with the generator's own permutation and the CPU generator put back, so that train draws
+    the same one again. Bit for bit iteration(..., install="in_place")."""
+
+    def __init__(self, actor, critic, actor_optimizer, critic_optimizer, buffer, args, value_normalizer, update_actor=True, perms=None, *,
+                 deterministic=False, install="in_place", accumulation_steps=1, shards=None, value_head="torch", graph="rows"):
+        _refusals("run", accumulation_steps, shards)
+        _value_head_kind("run", value_head)
+        self.nets = (actor, critic, actor_optimizer, critic_optimizer)
+        self.buffer, self.args, self.value_normalizer = buffer, args, value_normalizer
+        self.update_actor, self.perms, self.deterministic, self.value_head = update_actor, perms, deterministic, value_head
+        self.rollout = self.update = None
+
+    def _first_sample(self):
+        buffer, args = self.buffer, self.args
+        num_mini_batch = int(getattr(args, "num_mini_batch", 1))
+        perm = None if self.perms is None else self.perms[0]
+        advantages = buffer.normalized_advantages(self.value_normalizer)
+        rng = torch.get_rng_state()
+        if getattr(args, "use_recurrent_policy", True):
+            generator = buffer.recurrent_generator(advantages, num_mini_batch, int(getattr(args, "data_chunk_length", 10)), perm=perm)
+        elif getattr(args, "use_naive_recurrent_policy", False):
+            generator = buffer.naive_recurrent_generator(advantages, num_mini_batch)
+        else:
+            generator = buffer.feed_forward_generator(advantages, num_mini_batch, perm=perm)
+        sample = next(iter(generator))
+        torch.set_rng_state(rng)
+        return sample
+
+    def __call__(self):
+        actor, critic = self.nets[:2]
+        buffer = self.buffer
+        if self.rollout is None:
+            self.rollout = CapturedRollout(actor, critic, buffer, self.value_normalizer, self.deterministic)
+        self.rollout.replay()
+        if self.update is None:
+            self.update = CapturedUpdate(*self.nets, self._first_sample(), self.args, self.value_normalizer, self.update_actor, install="in_place",
+                                         value_head=self.value_head)
+        info = self.update.train(buffer, self.perms)
+        info["average_episode_rewards"] = buffer.rewards.mean() * buffer.T
+        buffer.after_update()
+        return info
 
 
 def iteration(actor, critic, actor_optimizer, critic_optimizer, buffer, args, value_normalizer=None, update_actor=True, perms=None, *,
@@ -619,7 +816,7 @@ def linear_lr(initial_lr, episode, episodes):
 
 
 def run(actor, critic, actor_optimizer, critic_optimizer, buffer, args, value_normalizer=None, *, episodes=None, eval_engine=None, on_log=None,
-        on_eval=None, on_save=None, eval_seed=0, **iteration_keywords):
+        on_eval=None, on_save=None, eval_seed=0, captured=False, **iteration_keywords):
     """GMPERunner.run (graph_mpe_runner.py:40-207) over a DeviceRolloutBuffer: buffer.warmup(), then `episodes` iterations (default
     int(args.num_env_steps) // episode_length // n_rollout_threads; episode_length is args.episode_length, else buffer.T; n_rollout_threads is
     args.n_rollout_threads, else the engine's N). Per episode, in the reference's order:
@@ -634,7 +831,14 @@ def run(actor, critic, actor_optimizer, critic_optimizer, buffer, args, value_no
     After the loop on_save(episodes - 1) once more: the reference's final forced save. The intervals default to the reference's 1, 5 and 25. A callback
     that is None is skipped, and what only it would receive is not computed. Every payload is device tensors: run itself never waits for the device,
     a callback that reads a value does. args.increase_fairness is refused: the engine's reward weights are fixed at creation. args.use_eval without
-    eval_engine raises ValueError. Returns the last iteration's train_infos (None with no episode)."""
+    eval_engine raises ValueError. Returns the last iteration's train_infos (None with no episode).
+    captured=True: both halves of every iteration are replayed graphs — after warmup() a CapturedRollout is built and every episode's rollout is its
+    replay(); every train is CapturedUpdate.train, the CapturedUpdate built from the first minibatch of the first episode; the lr decay reaches the
+    update through the schedules' refill. Bit for bit run(..., install="in_place"), and install defaults to "in_place" then: any other install, shards
+    and graph="table" raise NotImplementedError, before anything else is read. Still nothing waits for the device but the two constructions, in
+    the first episode."""
+    if captured:
+        iteration_keywords = _captured_refusals("run", iteration_keywords)
     if getattr(args, "increase_fairness", False):
         raise NotImplementedError("args.increase_fairness: run() cannot raise fair_rew mid-training — the engine's reward weights are fixed at "
                                   "creation (not supported)")
@@ -653,6 +857,8 @@ def run(actor, critic, actor_optimizer, critic_optimizer, buffer, args, value_no
     decay = bool(getattr(args, "use_linear_lr_decay", False))
     if decay and (getattr(args, "lr", None) is None or getattr(args, "critic_lr", None) is None):
         raise ValueError("args.use_linear_lr_decay is set: run needs args.lr and args.critic_lr, the rates the schedule starts from")
+    replayed = _CapturedIteration(actor, critic, actor_optimizer, critic_optimizer, buffer, args, value_normalizer, **iteration_keywords) \
+        if captured else None
     buffer.warmup()
     train_infos = None
     for episode in range(episodes):
@@ -660,7 +866,10 @@ def run(actor, critic, actor_optimizer, critic_optimizer, buffer, args, value_no
             for optimizer, initial in ((actor_optimizer, args.lr), (critic_optimizer, args.critic_lr)):
                 for group in optimizer.param_groups:
                     group["lr"] = linear_lr(initial, episode, episodes)
-        train_infos = iteration(actor, critic, actor_optimizer, critic_optimizer, buffer, args, value_normalizer, **iteration_keywords)
+        if replayed is not None:
+            train_infos = replayed()
+        else:
+            train_infos = iteration(actor, critic, actor_optimizer, critic_optimizer, buffer, args, value_normalizer, **iteration_keywords)
         total_num_steps = (episode + 1) * episode_length * threads
         if on_save is not None and (episode % save_interval == 0 or episode == episodes - 1):
             on_save(episode)

@@ -221,7 +221,20 @@ class DeviceRolloutBuffer(object):
         return self.engine.out
 
     act_draw = 0            # the call counter of act_step's action stream: one value per act, carried by carry_from
-    _act_idx = _act_logp = None
+    _act_idx = _act_logp = _act_draw_dev = None
+
+    def act_draw_counter(self):
+        """act_draw as an int64 [1] device tensor, created on demand: what the steps of a captured rollout hand the sampling launch as draw_dev
+        (gmpe.policy.CapturedRollout), which advances it by one per step on the stream. The host's act_draw stays the truth: whoever launches such steps
+        first makes the counter equal to it (sync_act_draw_counter) and afterwards adds the steps to act_draw."""
+        if self._act_draw_dev is None:
+            self._act_draw_dev = torch.full((1,), int(self.act_draw), dtype=torch.int64, device=self.engine.device)
+        return self._act_draw_dev
+
+    def sync_act_draw_counter(self):
+        """counter = act_draw, one fill on the current stream (nothing where no counter was asked for); nothing waits for the device"""
+        if self._act_draw_dev is not None:
+            self._act_draw_dev.fill_(int(self.act_draw))
 
     def act_step(self, logits, values=None, *, rnn_states=None, rnn_states_critic=None, deterministic=False):
         """insert_step with the action head in the launch sequence: `logits` (the policy head's linear output of this step, [N*A, n_actions], before
@@ -368,6 +381,12 @@ class DeviceRolloutBuffer(object):
     def _carried(self):
         return [b for b in (self.obs, self._node_obs, self.entity_table, self._adj, self.agent_id, self.masks, self.active_masks,
                             self.bad_masks, self.available_actions, self.rnn_states, self.rnn_states_critic) if b is not None]
+
+    def _arrays(self):
+        """(name, tensor) of every device tensor the buffer holds as an attribute, by name: the arrays, the returns workspace, info, the action scratch
+        and the draw counter. Whoever must save, restore or guard all of a buffer's storage (gmpe.policy.CapturedRollout) asks here, so that an
+        array added later is included without being listed anywhere else."""
+        return [(k, v) for k, v in sorted(vars(self).items()) if isinstance(v, torch.Tensor)]
 
     # ------------------------------------------------------------------ policy side (opt-in: policy_fields)
     def available_actions_for(self, step):
@@ -527,4 +546,5 @@ class DeviceRolloutBuffer(object):
         for dst, src in zip(self._carried(), other._carried()):
             dst[0].copy_(src[-1])
         self.act_draw = other.act_draw
+        self.sync_act_draw_counter()
         self.step = 0

@@ -13,7 +13,9 @@ weights), because the reference's modules need torch_geometric. Nothing between 
 
     python examples/policy_loop.py --envs 64 --agents 3 --episodes 3 [--popart] [--captured] [--run]
 
-With --captured the train() of every iteration is gmpe.policy.CapturedUpdate.train: one ppo_update captured as a graph, replayed per minibatch.
+With --captured both halves of every iteration are replayed graphs: the rollout is gmpe.policy.CapturedRollout.replay — the episode's collect_steps and
+compute captured once, one launch per episode — and train() is gmpe.policy.CapturedUpdate.train: one ppo_update captured as a graph, replayed per
+minibatch. With --run --captured the same is gmpe.policy.run(..., captured=True).
 With --run the same training is the reference's whole run() loop as one call, gmpe.policy.run, with three printing callbacks: the linear lr decay, the
 iterations, the `agent{i}/...` means of process_infos + log_env at the log interval (gmpe.env_infos), the deterministic eval episode on a second
 engine at the eval interval (gmpe.policy.eval_episode) and the saves. Only the callbacks read values back.
@@ -77,18 +79,22 @@ def by_pieces(actor, critic, aopt, copt, buf, args, normalizer):
     return info
 
 
-def captured(cap, actor, critic, aopt, copt, buf, args, normalizer):
-    """one iteration whose updates are replays of one captured graph (gmpe.policy.CapturedUpdate, built at the first call from a minibatch of the first
-    rollout: the graph is fixed to that minibatch's shapes) -> (info, the CapturedUpdate)"""
+def captured(caps, actor, critic, aopt, copt, buf, args, normalizer):
+    """one iteration of two replayed graphs: the rollout (gmpe.policy.CapturedRollout, built at the first call on the warmed-up buffer: the graph is
+    fixed to the buffer's arrays and the networks' parameters, whose values it follows) and the updates (gmpe.policy.CapturedUpdate, built at the
+    first call from a minibatch of the first rollout: the graph is fixed to that minibatch's shapes) -> (info, (the CapturedRollout, the CapturedUpdate))"""
     from gmpe import policy
-    policy.rollout(actor, critic, buf, normalizer)
+    roll, cap = caps or (None, None)
+    if roll is None:
+        roll = policy.CapturedRollout(actor, critic, buf, normalizer)
+    roll.replay()
     if cap is None:
         sample = next(iter(buf.recurrent_generator(buf.normalized_advantages(normalizer), args.num_mini_batch, args.data_chunk_length)))
         cap = policy.CapturedUpdate(actor, critic, aopt, copt, sample, args, normalizer, value_head="device")
     info = cap.train(buf)
     info["average_episode_rewards"] = buf.rewards.mean() * buf.T
     buf.after_update()
-    return info, cap
+    return info, (roll, cap)
 
 
 def run_whole(o, actor, critic, aopt, copt, buf, args, normalizer, cfg):
@@ -113,7 +119,7 @@ def run_whole(o, actor, critic, aopt, copt, buf, args, normalizer, cfg):
         print("episode %d: save (lr %.3g)" % (episode, aopt.param_groups[0]["lr"]))
 
     policy.run(actor, critic, aopt, copt, buf, args, normalizer, episodes=o.episodes, eval_engine=eval_engine, on_log=on_log, on_eval=on_eval,
-               on_save=on_save, value_head="device")
+               on_save=on_save, value_head="device", captured=o.captured)
     eval_engine.check_errors()
     eval_engine.close()
 
@@ -125,8 +131,8 @@ def main():
     ap.add_argument("--episode-length", type=int, default=20)
     ap.add_argument("--episodes", type=int, default=3)
     ap.add_argument("--popart", action="store_true", help="--use_popart: the critic's v_out is the value normaliser")
-    ap.add_argument("--captured", action="store_true", help="every update is a replay of one captured graph (gmpe.policy.CapturedUpdate.train; with "
-                    "--popart the rescaled layer is written in place, install=\"in_place\")")
+    ap.add_argument("--captured", action="store_true", help="every rollout and every update is a replay of a captured graph (gmpe.policy.CapturedRollout.replay, "
+                    "gmpe.policy.CapturedUpdate.train; with --popart the rescaled layer is written in place, install=\"in_place\")")
     ap.add_argument("--run", action="store_true", help="the whole loop as one call: gmpe.policy.run with printing callbacks")
     o = ap.parse_args()
     import torch
@@ -151,7 +157,7 @@ def main():
     for ep in range(o.episodes):
         t0 = time.perf_counter()
         if o.captured:
-            (info, cap), how = captured(cap, actor, critic, aopt, copt, buf, args, normalizer), "captured updates"
+            (info, cap), how = captured(cap, actor, critic, aopt, copt, buf, args, normalizer), "captured rollout and updates"
         elif ep % 2 == 0:
             info, how = by_pieces(actor, critic, aopt, copt, buf, args, normalizer), "by pieces"
         else:
