@@ -29,7 +29,7 @@ SYMBOLS = ["gmpe_abi_version", "gmpe_last_error", "gmpe_obs_dim", "gmpe_node_fea
            "gmpe_value_workspace_bytes", "gmpe_value_forward", "gmpe_value_backward",
            "gmpe_optim_workspace_bytes", "gmpe_optim_step", "gmpe_optim_shard_elems", "gmpe_optim_step_shard",
            "gmpe_optim_schedule_bytes", "gmpe_optim_schedule_fill", "gmpe_optim_step_scheduled",
-           "gmpe_env_infos", "gmpe_eval_step", "gmpe_eval_mean"]
+           "gmpe_env_infos", "gmpe_eval_step", "gmpe_eval_mean", "gmpe_step_tail"]
 
 
 class GmpeOutputs(C.Structure):
@@ -87,6 +87,13 @@ class GmpeLearnerPlan(C.Structure):
                 ("rnn_states", C.c_void_p), ("rnn_states_critic", C.c_void_p), ("stride_dones", C.c_int64), ("stride_value_preds", C.c_int64),
                 ("stride_actions", C.c_int64), ("stride_action_log_probs", C.c_int64), ("stride_rnn_states", C.c_int64),
                 ("stride_rnn_states_critic", C.c_int64)]
+
+
+class GmpeStepTailPlan(C.Structure):
+    """gmpe_step_tail_plan (include/gmpe.h): gmpe_learner_plan with the step's masks, the stop rows of its position and the draw counter, one launch."""
+    _fields_ = [("learner", GmpeLearnerPlan), ("num_agents", C.c_int32), ("n_actions", C.c_int32), ("masks", C.c_void_p), ("active_masks", C.c_void_p),
+                ("available_actions", C.c_void_p), ("stride_masks", C.c_int64), ("stride_active_masks", C.c_int64),
+                ("stride_available_actions", C.c_int64), ("draw_dev", C.c_void_p), ("draw_inc", C.c_uint64)]
 
 
 class GmpeEpisodeRecordPlan(C.Structure):
@@ -384,6 +391,7 @@ def load():
     lib.gmpe_minibatch_edges.argtypes = [C.POINTER(GmpeConfig), I, C.POINTER(GmpeMbEdgesPlan), P]
     lib.gmpe_minibatch_edges_workspace_bytes.argtypes = [C.c_int64, C.POINTER(C.c_size_t)]
     lib.gmpe_insert_learner.argtypes = [I, C.POINTER(GmpeLearnerPlan), P]
+    lib.gmpe_step_tail.argtypes = [I, C.POINTER(GmpeStepTailPlan), P]
     lib.gmpe_episode_record.argtypes = [I, C.POINTER(GmpeEpisodeRecordPlan), P]
     lib.gmpe_episode_record_series.argtypes = [I, C.POINTER(GmpeEpisodeSeriesPlan), P]
     lib.gmpe_episode_metrics.argtypes = [I, C.POINTER(GmpeEpisodeMetricsPlan), P]

@@ -89,7 +89,7 @@ int gmpe_act_sample(int device, const gmpe_act_plan* pl, void* stream) {
         if (int rc = gmpe::raise_dynamic_lds_once(reinterpret_cast<const void*>(fn), device, vec, TILE * (GMPE_PPO_MAX_ACTIONS | 1) * sizeof(float)))
             return rc;
     GMPE_LAUNCH(fn, dim3((unsigned)num_tiles(pl->rows)), dim3(TILE), lds, st, a);
-    if (pl->draw_dev) return gmpe::act_advance(pl->draw_dev, pl->draw_inc, st);
+    if (pl->draw_dev && pl->draw_inc) return gmpe::act_advance(pl->draw_dev, pl->draw_inc, st);   // adding zero changes nothing: no launch
     return GMPE_OK;
 }
 

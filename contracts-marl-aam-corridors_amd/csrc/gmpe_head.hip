@@ -274,7 +274,7 @@ int gmpe_act_head(int device, const gmpe_act_plan* ap, const gmpe_head_plan* hp,
     HeadArgs h = bind(hp, y);
     h.vec_k = !(((uintptr_t)hp->logits_out | (uintptr_t)ap->available_actions) & 15);
     GMPE_LAUNCH(k_head_act, dim3((unsigned)y.ntiles), dim3(TILE), gmpe_head::lds_bytes(ap->n_actions), st, a, h);
-    if (ap->draw_dev) return gmpe::act_advance(ap->draw_dev, ap->draw_inc, st);
+    if (ap->draw_dev && ap->draw_inc) return gmpe::act_advance(ap->draw_dev, ap->draw_inc, st);   // adding zero changes nothing: no launch
     return GMPE_OK;
 }
 

@@ -631,16 +631,8 @@ def _slots(name, t, lead, tail_dim, dev):
     return tuple(int(x) for x in t.shape[1 + len(lead):])
 
 
-def insert_learner(step, dones, arrays, values=None, actions=None, action_log_probs=None, rnn_states=None, rnn_states_critic=None):
-    """GMPERunner.insert's learner fields of step `step` (graph_mpe_runner.py:384-392 + graph_buffer.py:229-234) as one launch on the current stream
-    (gmpe_insert_learner): value_preds[step] = values, actions[step] = float32(actions), action_log_probs[step] = action_log_probs, and
-    rnn_states[step + 1] / rnn_states_critic[step + 1] = the policy's states with the rows of every agent done at `step` (dones[step] != 0) zeroed.
-      dones: uint8 / bool [T, N, A] (each slot contiguous; slot `step` is read on the device, no host sync);
-      arrays: dict of the buffer's arrays, some of value_preds [T+1, N, A, 1], actions / action_log_probs [T, N, A, k],
-              rnn_states / rnn_states_critic [T+1, N, A, R, H] (float32; each slot contiguous, any stride(0) of at least one slot: views of a slab);
-      inputs: the policy's outputs as contiguous device tensors with N*A rows — values f32 [N*A, 1], actions int64 (what the policy returns) or f32
-              [N*A, k], action_log_probs f32 [N*A, k], rnn_states / rnn_states_critic f32 [N*A, R, H]. None skips a field.
-    Every argument is checked (ValueError) before the launch."""
+def _learner_plan(plan, step, dones, arrays, given):
+    """insert_learner's checks, shared with step_tail: fills the gmpe_learner_plan `plan` -> (the inputs to keep alive, device, T, lead dims, lanes)"""
     if not isinstance(dones, torch.Tensor) or dones.dtype not in (torch.uint8, torch.bool) or dones.dim() < 2 or not dones[0].is_contiguous():
         raise ValueError("dones must be a uint8 / bool tensor [T, ...] with contiguous slots")
     dev = dones.device
@@ -651,8 +643,6 @@ def insert_learner(step, dones, arrays, values=None, actions=None, action_log_pr
     unknown = set(arrays) - {v[0] for v in LEARNER_INPUTS.values()}
     if unknown:
         raise ValueError("unknown learner arrays: %s" % sorted(unknown))
-    given = dict(values=values, actions=actions, action_log_probs=action_log_probs, rnn_states=rnn_states, rnn_states_critic=rnn_states_critic)
-    plan = _lib.GmpeLearnerPlan()
     plan.lanes, plan.t, plan.num_steps = lanes, int(step), T
     plan.dones, plan.stride_dones = dones.data_ptr(), dones.stride(0)
     plan.recurrent_n, plan.hidden, plan.hidden_critic, plan.act_dim = 1, 1, 1, 1
@@ -687,11 +677,75 @@ def insert_learner(step, dones, arrays, values=None, actions=None, action_log_pr
         else:
             plan.rnn_critic_in, plan.rnn_states_critic, plan.stride_rnn_states_critic = x.data_ptr(), buf.data_ptr(), buf.stride(0)
             plan.recurrent_n, plan.hidden_critic = tail
-    if actions is not None and action_log_probs is not None and arrays["actions"].shape[-1] != arrays["action_log_probs"].shape[-1]:
+    if given["actions"] is not None and given["action_log_probs"] is not None and arrays["actions"].shape[-1] != arrays["action_log_probs"].shape[-1]:
         raise ValueError("actions and action_log_probs must have the same last dim")
-    if rnn_states is not None and rnn_states_critic is not None and arrays["rnn_states"].shape[-2] != arrays["rnn_states_critic"].shape[-2]:
+    if given["rnn_states"] is not None and given["rnn_states_critic"] is not None and \
+            arrays["rnn_states"].shape[-2] != arrays["rnn_states_critic"].shape[-2]:
         raise ValueError("rnn_states and rnn_states_critic must have the same recurrent_N")
+    return keep, dev, T, lead, lanes
+
+
+def insert_learner(step, dones, arrays, values=None, actions=None, action_log_probs=None, rnn_states=None, rnn_states_critic=None):
+    """GMPERunner.insert's learner fields of step `step` (graph_mpe_runner.py:384-392 + graph_buffer.py:229-234) as one launch on the current stream
+    (gmpe_insert_learner): value_preds[step] = values, actions[step] = float32(actions), action_log_probs[step] = action_log_probs, and
+    rnn_states[step + 1] / rnn_states_critic[step + 1] = the policy's states with the rows of every agent done at `step` (dones[step] != 0) zeroed.
+      dones: uint8 / bool [T, N, A] (each slot contiguous; slot `step` is read on the device, no host sync);
+      arrays: dict of the buffer's arrays, some of value_preds [T+1, N, A, 1], actions / action_log_probs [T, N, A, k],
+              rnn_states / rnn_states_critic [T+1, N, A, R, H] (float32; each slot contiguous, any stride(0) of at least one slot: views of a slab);
+      inputs: the policy's outputs as contiguous device tensors with N*A rows — values f32 [N*A, 1], actions int64 (what the policy returns) or f32
+              [N*A, k], action_log_probs f32 [N*A, k], rnn_states / rnn_states_critic f32 [N*A, R, H]. None skips a field.
+    Every argument is checked (ValueError) before the launch."""
+    given = dict(values=values, actions=actions, action_log_probs=action_log_probs, rnn_states=rnn_states, rnn_states_critic=rnn_states_critic)
+    plan = _lib.GmpeLearnerPlan()
+    keep, dev = _learner_plan(plan, step, dones, arrays, given)[:2]
     if not keep:
         return
     _need_cuda(dev)
     _lib.check(_lib.load().gmpe_insert_learner(dev.index, C.byref(plan), _stream_of(dev)), "gmpe_insert_learner")
+
+
+def step_tail(step, dones, arrays, *, num_agents, masks=None, active_masks=None, available_actions=None, draw_dev=None, draw_inc=0, values=None,
+              actions=None, action_log_probs=None, rnn_states=None, rnn_states_critic=None):
+    """Everything that follows the env step of step `step` as ONE launch on the current stream (gmpe_step_tail): insert_learner(step, dones, arrays, ...)
+    for whatever inputs are given (none is fine), masks[step + 1] / active_masks[step + 1] from dones[step] (masks_from_dones' rule, lane q of env
+    q // num_agents), the stop rows available_actions_from_dones writes for position `step` — available_actions[step + 1], from dones[step - 1], all
+    ones at step 0 —, and draw_dev += draw_inc. Bit for bit what the separate calls write; the launch is made also when only the masks are asked for.
+      dones, arrays and the inputs: as for insert_learner. masks / active_masks: float32 [T+1, ...lane dims(, 1)]; available_actions: float32
+      [T+1, ...lane dims, n_actions] (the buffer's whole array); each slot contiguous, any stride(0) of at least one slot. draw_dev: the int64 [1]
+      device counter of act_head / sample_actions, called with draw_inc=0 for this step, or None."""
+    given = dict(values=values, actions=actions, action_log_probs=action_log_probs, rnn_states=rnn_states, rnn_states_critic=rnn_states_critic)
+    tp = _lib.GmpeStepTailPlan()
+    keep, dev, T, lead, lanes = _learner_plan(tp.learner, step, dones, arrays, given)
+    if int(num_agents) < 1 or lanes % int(num_agents):
+        raise ValueError("need num_agents >= 1 dividing the %d lanes" % lanes)
+    tp.num_agents = int(num_agents)
+    for name, x in (("masks", masks), ("active_masks", active_masks), ("available_actions", available_actions)):
+        if x is None:
+            continue
+        avail = name == "available_actions"
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() < 1 + len(lead) + avail or x.shape[0] != T + 1 or \
+                tuple(x.shape[1:1 + len(lead)]) != lead or (not avail and x[0].numel() != lanes) or x.dim() > 2 + len(lead):
+            raise ValueError("%s must be a float32 tensor [%d, %s%s]" % (name, T + 1, ", ".join(map(str, lead)), ", n_actions" if avail else "(, 1)"))
+        if not x[0].is_contiguous() or x.stride(0) < x[0].numel():
+            raise ValueError("%s: every slot must be contiguous and the slots must not overlap" % name)
+        if x.device != dev:
+            raise ValueError("%s must be on %s (the device of the other arrays)" % (name, dev))
+        if avail:
+            n = int(x.shape[-1])
+            if not 1 <= n <= 64:
+                raise ValueError("available_actions: n_actions must be in 1 .. 64")
+            tp.n_actions, tp.available_actions, tp.stride_available_actions = n, x[1].data_ptr(), x.stride(0)
+        else:
+            setattr(tp, name, x.data_ptr())
+            setattr(tp, "stride_" + name, x.stride(0))
+    if int(draw_inc) < 0:
+        raise ValueError("draw_inc must be >= 0")
+    if draw_dev is not None:
+        if not isinstance(draw_dev, torch.Tensor) or draw_dev.dtype not in (torch.int64, torch.uint64) or draw_dev.numel() != 1 or \
+                not draw_dev.is_contiguous():
+            raise ValueError("draw_dev must be a contiguous int64 tensor with one element")
+        if draw_dev.device != dev:
+            raise ValueError("draw_dev must be on %s (the device of the other arrays)" % dev)
+        tp.draw_dev, tp.draw_inc = draw_dev.data_ptr(), int(draw_inc) & 0xFFFFFFFFFFFFFFFF
+    _need_cuda(dev)
+    _lib.check(_lib.load().gmpe_step_tail(dev.index, C.byref(tp), _stream_of(dev)), "gmpe_step_tail")

@@ -60,16 +60,16 @@ def _features(net, own_obs, node_obs, adj, agent_id, rnn_states, masks):
 
 
 def actor_forward(actor, obs, node_obs, adj, agent_id, rnn_states, masks, available_actions=None, deterministic=False, *, dones_prev=None, seed,
-                  env_id_base=0, num_agents, draw, draw_dev=None, out=None):
+                  env_id_base=0, num_agents, draw, draw_dev=None, draw_inc=1, out=None):
     """GR_Actor.forward (graph_actor_critic.py:162-173) -> (actions, action_log_probs, rnn_states), under torch.no_grad().
     obs [rows, obs_dim], node_obs [rows, E, F], adj [rows, E, E] or [rows / S, E, E], agent_id [rows] or [rows, 1], rnn_states [rows, 1, 64],
     masks [rows, 1]: float32 device tensors as the layers take them. available_actions / dones_prev, seed, env_id_base, num_agents, draw, draw_dev,
-    out: as for act_head (out may hold "logits"). actions is the int64 [rows, 1] tensor the reference returns; with `out` given and no "actions" in
+    draw_inc, out: as for act_head (out may hold "logits"). actions is the int64 [rows, 1] tensor the reference returns; with `out` given and no "actions" in
     it, it is the int32 action_idx [rows] instead (what GmpeEngine.step takes). rnn_states comes back unchanged when the actor has no RNN."""
     with torch.no_grad():
         features, rnn_states = _features(actor, obs, node_obs, adj, agent_id, rnn_states, masks)
         idx, actions, logp = act_head(features, actor.act, available_actions, dones_prev=dones_prev, seed=seed, env_id_base=env_id_base,
-                                      num_agents=num_agents, draw=draw, draw_dev=draw_dev, deterministic=deterministic, out=out)
+                                      num_agents=num_agents, draw=draw, draw_dev=draw_dev, draw_inc=draw_inc, deterministic=deterministic, out=out)
     return (idx if actions is None else actions), logp, rnn_states
 
 
@@ -462,16 +462,16 @@ def _split_out(fn, out):
 
 
 def get_actions(actor, critic, share_obs, obs, node_obs, adj, agent_id, share_agent_id, rnn_states, rnn_states_critic, masks, available_actions=None,
-                deterministic=False, *, dones_prev=None, seed, env_id_base=0, num_agents, draw, draw_dev=None, out=None):
+                deterministic=False, *, dones_prev=None, seed, env_id_base=0, num_agents, draw, draw_dev=None, draw_inc=1, out=None):
     """GR_MAPPOPolicy.get_actions (graphMAPPOPolicy.py) -> (values, actions, action_log_probs, rnn_states, rnn_states_critic), the reference's order,
     under torch.no_grad() on the current stream: actor_forward (its chain ends in act_head), then the critic chain ending in value_head.
-    The arrays and available_actions / dones_prev, seed, env_id_base, num_agents, draw, draw_dev: as for actor_forward and critic_forward.
+    The arrays and available_actions / dones_prev, seed, env_id_base, num_agents, draw, draw_dev, draw_inc: as for actor_forward and critic_forward.
     out: actor_forward's dict, which may also hold "values" (value_head's out: float32, `rows` elements, written in place). The states come back
     unchanged from a network without an RNN."""
     act_out, values_out = _split_out("get_actions", out)
     actions, logp, rnn_states = actor_forward(actor, obs, node_obs, adj, agent_id, rnn_states, masks, available_actions, deterministic,
                                               dones_prev=dones_prev, seed=seed, env_id_base=env_id_base, num_agents=num_agents, draw=draw,
-                                              draw_dev=draw_dev, out=act_out)
+                                              draw_dev=draw_dev, draw_inc=draw_inc, out=act_out)
     with torch.no_grad():
         features, rnn_states_critic = _features(critic, _cent(critic, share_obs), node_obs, adj, share_agent_id, rnn_states_critic, masks)
         values = _value.value_head(features, critic.v_out, out=values_out)
@@ -514,23 +514,25 @@ def collect_step(actor, critic, buffer, deterministic=False, *, draw_dev=None):
     """One step of run()'s loop (graph_mpe_runner.py:57-103: collect or collect_with_mask, envs.step, insert) on a DeviceRolloutBuffer built with
     policy_fields and learner_fields: get_actions on slot buffer.step — the availability taken from dones[step - 1], everything available at step 0,
     the draw keyed by buffer.act_draw, the values written into value_preds[step], the action and its log-prob into their slots —, then the env step,
-    the masks and the RNN states of slot step + 1 with the done rows zeroed, as DeviceRolloutBuffer.act_step does them. Bit for bit what
+    the masks, the step's stop rows and the RNN states of slot step + 1 with the done rows zeroed in one launch (gmpe_step_tail), as
+    DeviceRolloutBuffer.act_step does them: ten launches a step. Bit for bit what
     act_step(action_logits(...), value_head(...), rnn_states=..., rnn_states_critic=...) stores from the same layer calls. Nothing is copied to the
     host and nothing waits for the device. Returns the engine's outputs of the step.
     draw_dev: None, or act_head's int64 [1] device counter (buffer.act_draw_counter()): the draw is then keyed by what the counter holds when the
-    launch runs, not by the host's buffer.act_draw, and the launch adds one to it — the form a captured step takes (CapturedRollout)."""
+    launch runs, not by the host's buffer.act_draw, and the step's tail launch adds one to it (the sampling launch is given draw_inc = 0, which
+    spares its counter launch) — the form a captured step takes (CapturedRollout)."""
     _rollout_buffer("collect_step", actor, critic, buffer)
     t, e = buffer.step, buffer.engine
     c, rows = e.cfg, e.N * e.A
     s = _slot_rows(buffer, t)
     out = buffer.act_outputs()
     out["values"] = buffer.value_preds[t]
-    buffer.available_actions_for(t)
     _, _, _, h, hc = get_actions(actor, critic, s["share_obs"], s["obs"], s["node_obs"], s["adj"], s["agent_id"], s["share_agent_id"], s["rnn_states"],
                                  s["rnn_states_critic"], s["masks"], None, deterministic, dones_prev=buffer.dones[t - 1].view(rows) if t else None,
                                  seed=c.seed, env_id_base=c.env_id_base, num_agents=e.A, draw=buffer.act_draw if draw_dev is None else 0,
-                                 draw_dev=draw_dev, out=out)
+                                 draw_dev=draw_dev, draw_inc=0 if draw_dev is not None else 1, out=out)
     learner = buffer._learner_inputs(None, None, None, h if _recurrent(actor) else None, hc if _recurrent(critic) else None, "collect_step")
+    buffer._tail_draw_dev = draw_dev                        # act_finish's tail launch advances it
     return buffer.act_finish(learner)
 
 
@@ -578,7 +580,7 @@ def _capturable_engine(fn, engine, path=True):
 class CapturedRollout(object):
     """rollout(actor, critic, buffer, value_normalizer, deterministic) captured once as a torch.cuda.CUDAGraph and replayed: buffer.T collect_steps and
     compute, unrolled — every step's slot addresses in its own nodes —, the same kernels on the same inputs in the same order, so the same bits, with
-    one host call per episode where rollout issues about twelve launches per step through Python.
+    one host call per episode where rollout issues ten launches per step through Python.
 
         cap = gmpe.policy.CapturedRollout(actor, critic, buffer, value_normalizer)
         returns = cap.replay()        # == rollout(actor, critic, buffer, value_normalizer), bit for bit

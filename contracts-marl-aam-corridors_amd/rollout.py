@@ -10,8 +10,8 @@ Opt-in policy-side storage (policy_storage_spec): value_preds / returns / bad_ma
 with compute_returns / normalized_advantages (GraphReplayBuffer.compute_returns, GR_MAPPO.train's advantage lines) and the stop-action rows of
 available_actions (graph_mpe_runner.py:263-335) computed on the device.
 Opt-in learner-side storage (learner_storage_spec): rnn_states / rnn_states_critic [T+1, N, A, R, H] and actions / action_log_probs [T, N, A, k], written
-with value_preds by ONE launch per step from the policy's outputs (insert_step / insert_external keywords, gmpe_insert_learner: the runner's
-`rnn_states[dones] = 0` on the device, no host sync) and carried by after_update: with every field kept, the buffer is a whole device GraphReplayBuffer.
+with value_preds, the step's masks and its stop rows by ONE launch per step from the policy's outputs (insert_step / insert_external keywords,
+gmpe_step_tail: the runner's `rnn_states[dones] = 0` on the device, no host sync) and carried by after_update: with every field kept, the buffer is a whole device GraphReplayBuffer.
 act_step puts the action head itself into the step's launch sequence: the policy hands over its logits, one launch (gmpe_act_sample, act.py) masks them from
 the previous step's dones, draws the action and writes actions[t] / action_log_probs[t] in place, then the env steps.
 The open-loop collect(action_sets) and the sharded collectors (sharding.ShardedRolloutCollector, vec_env.MultiDeviceGraphMPEVecEnv) have no policy output
@@ -20,7 +20,7 @@ to store: they never write the learner fields.
 import torch
 
 from .config import NODE_FEATS
-from .engine import StepOutputs, available_actions_from_dones, compute_returns, denorm_scalars, insert_learner, returns_workspace_bytes
+from .engine import StepOutputs, available_actions_from_dones, compute_returns, denorm_scalars, returns_workspace_bytes, step_tail
 from . import _lib
 from .minibatch import LEARNER, EdgeList, check_edge_args, edge_list, feed_forward_generator, recurrent_generator
 
@@ -196,16 +196,14 @@ class DeviceRolloutBuffer(object):
         step, buffer with value_preds) go to value_preds[step] (graph_buffer.py:234); with available_actions the step's stop-action slot is written too.
         The learner keywords take the policy's own outputs of this step in its [N*A, ...] shapes — actions int64 [N*A, k], action_log_probs [N*A, k],
         rnn_states / rnn_states_critic [N*A, R, H] — each needing its buffer array (learner_fields). With any of them the env step runs first, then ONE launch
-        (gmpe_insert_learner) writes values, actions[step], action_log_probs[step] and the RNN states of slot step + 1 with the rows of the agents this
-        step made done zeroed (GMPERunner.insert, graph_mpe_runner.py:386-392)."""
+        (gmpe_step_tail) writes values, actions[step], action_log_probs[step] and the RNN states of slot step + 1 with the rows of the agents this
+        step made done zeroed (GMPERunner.insert, graph_mpe_runner.py:386-392), and with them the masks and the step's stop-action slot."""
         t = self.step
         learner = self._learner_inputs(values, actions, action_log_probs, rnn_states, rnn_states_critic, "insert_step")
         if learner is not None:
-            self.available_actions_for(t)
             self._bind(t + 1)
             self.engine.step(action_idx)
-            self.engine.masks_from_dones(self.dones[t], self.masks[t + 1], self.active_masks[t + 1])
-            insert_learner(t, self.dones, self._learner_arrays(), **learner)
+            self._step_tail(t, learner)
             self.step = (t + 1) % self.T
             return self.engine.out
         if values is not None:
@@ -222,6 +220,14 @@ class DeviceRolloutBuffer(object):
 
     act_draw = 0            # the call counter of act_step's action stream: one value per act, carried by carry_from
     _act_idx = _act_logp = _act_draw_dev = None
+    _tail_draw_dev = None   # set by gmpe.policy.collect_step for one act_finish: the counter its sampling launch read and left for the tail to advance
+
+    def _step_tail(self, t, learner, draw_dev=None):
+        """What follows the env step of step t, one launch (engine.step_tail, gmpe_step_tail): masks[t + 1] / active_masks[t + 1], the stop rows of
+        available_actions[t + 1] where the buffer keeps them — what available_actions_for(t) writes, which nothing reads before the step ends —, the
+        learner fields of `learner` (_learner_inputs' dict, or None) and, with draw_dev, the draw counter's advance by one."""
+        step_tail(t, self.dones, self._learner_arrays(), num_agents=self.engine.A, masks=self.masks, active_masks=self.active_masks,
+                  available_actions=self.available_actions, draw_dev=draw_dev, draw_inc=0 if draw_dev is None else 1, **(learner or {}))
 
     def act_draw_counter(self):
         """act_draw as an int64 [1] device tensor, created on demand: what the steps of a captured rollout hand the sampling launch as draw_dev
@@ -239,10 +245,10 @@ class DeviceRolloutBuffer(object):
     def act_step(self, logits, values=None, *, rnn_states=None, rnn_states_critic=None, deterministic=False):
         """insert_step with the action head in the launch sequence: `logits` (the policy head's linear output of this step, [N*A, n_actions], before
         masking) instead of an action. One launch (gmpe_act_sample, act.sample_actions) masks them with the availability of this step — taken from
-        dones[step - 1] directly, all available at step 0; the available_actions slot is still written when the buffer keeps that field —, draws the
-        action (or takes the mode with deterministic=True) and writes actions[step] and action_log_probs[step] into their slots in place (when the
-        buffer keeps them) and the int32 action into a tensor the buffer owns; then the env step, the masks, and one gmpe_insert_learner launch for
-        whatever else was given (values, rnn_states, rnn_states_critic, as insert_step's). The draw of a row is keyed by the engine's seed, the env's
+        dones[step - 1] directly, all available at step 0; the available_actions slot is still written, after the env step, when the buffer keeps that
+        field —, draws the action (or takes the mode with deterministic=True) and writes actions[step] and action_log_probs[step] into their slots in
+        place (when the buffer keeps them) and the int32 action into a tensor the buffer owns; then the env step and one gmpe_step_tail launch for the
+        masks, the stop rows and whatever else was given (values, rnn_states, rnn_states_critic, as insert_step's). The draw of a row is keyed by the engine's seed, the env's
         global id (cfg.env_id_base), the agent and `act_draw`, which advances by one per call: the same envs take the same actions however they are
         spread over buffers. The stored log-probs are bit for bit what ppo_losses recomputes from the same logits."""
         from .act import sample_actions
@@ -252,7 +258,6 @@ class DeviceRolloutBuffer(object):
         if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or tuple(logits.shape) != (rows, c.n_actions):
             raise ValueError("logits must be a tensor of shape (%d, %d)" % (rows, c.n_actions))
         out = self.act_outputs()
-        self.available_actions_for(t)
         sample_actions(logits, dones_prev=self.dones[t - 1] if t else None, stop_action=c.n_actions // 2 if t else None, seed=c.seed,
                        env_id_base=c.env_id_base, num_agents=e.A, draw=self.act_draw, deterministic=deterministic, out=out)
         return self.act_finish(learner)
@@ -280,14 +285,14 @@ class DeviceRolloutBuffer(object):
         return out
 
     def act_finish(self, learner=None):
-        """What follows the sampling launch of step `self.step`: the env step on the action act_outputs() received, the masks, one gmpe_insert_learner
-        launch for `learner` (_learner_inputs' dict, or None), and the two counters."""
+        """What follows the sampling launch of step `self.step`: the env step on the action act_outputs() received, one gmpe_step_tail launch for the
+        masks, the step's stop rows and `learner` (_learner_inputs' dict, or None) — and for the device draw counter, where collect_step left one in
+        _tail_draw_dev —, and the two host counters."""
         t, e = self.step, self.engine
+        draw_dev, self._tail_draw_dev = self._tail_draw_dev, None
         self._bind(t + 1)
         e.step(self._act_idx)
-        e.masks_from_dones(self.dones[t], self.masks[t + 1], self.active_masks[t + 1])
-        if learner is not None:
-            insert_learner(t, self.dones, self._learner_arrays(), **learner)
+        self._step_tail(t, learner, draw_dev)
         self.act_draw += 1
         self.step = (t + 1) % self.T
         return e.out
@@ -297,7 +302,7 @@ class DeviceRolloutBuffer(object):
         """GraphReplayBuffer.insert's env-side arguments for step outputs produced elsewhere (a replayed log, another engine):
         device or host tensors in the engine's shapes ([N,A,D], [N,A,1], [N,A,E,F], [N,E,E] or [N,A,E,E], [N,A], [N,A] bool/u8).
         Same slot placement and mask rules as insert_step (graph_buffer.py:223-251, graph_mpe_runner.py:395-405); the policy keywords as insert_step's,
-        written by one launch after the dones."""
+        written with the masks and the stop rows by one launch after the dones."""
         t, e = self.step, self.engine
         learner = self._learner_inputs(values, actions, action_log_probs, rnn_states, rnn_states_critic, "insert_external")
         dev = e.device
@@ -312,18 +317,15 @@ class DeviceRolloutBuffer(object):
             a = a[:, 0]                                   # the A per-agent matrices are one matrix (…_july.py:1625)
         elif not e.adj_compact and a.dim() == 3:
             a = a[:, None].expand(-1, e.A, -1, -1)
-        self.available_actions_for(t)
         put(self._adj[t + 1], a); put(self.rewards[t], rewards); put(self.dones[t], torch.as_tensor(dones).to(torch.uint8))
-        e.masks_from_dones(self.dones[t], self.masks[t + 1], self.active_masks[t + 1])
-        if learner is not None:
-            insert_learner(t, self.dones, self._learner_arrays(), **learner)
+        self._step_tail(t, learner)
         self.step = (t + 1) % self.T
 
     def _learner_arrays(self):
         return {k: getattr(self, k) for k in ("value_preds",) + LEARNER_FIELDS if getattr(self, k) is not None}
 
     def _learner_inputs(self, values, actions, action_log_probs, rnn_states, rnn_states_critic, what):
-        """The policy's outputs as device tensors for insert_learner (no copy when they already are: float32, int64 actions kept), or None when only
+        """The policy's outputs as device tensors for step_tail (no copy when they already are: float32, int64 actions kept), or None when only
         `values` (or nothing) is given to insert_step, which keeps its own path. A field the buffer does not keep raises ValueError."""
         given = dict(values=values, actions=actions, action_log_probs=action_log_probs, rnn_states=rnn_states, rnn_states_critic=rnn_states_critic)
         if all(given[k] is None for k in LEARNER_FIELDS) and (what == "insert_step" or values is None):

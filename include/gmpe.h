@@ -454,6 +454,29 @@ typedef struct gmpe_learner_plan {
 } gmpe_learner_plan;
 int gmpe_insert_learner(int device, const gmpe_learner_plan* plan, void* stream);
 
+/* Everything that follows the env step of rollout step t = learner.t and is a function of dones[t - 1], dones[t] and the policy's outputs alone (the
+ * "after the step" half of GMPERunner.insert, graph_mpe_runner.py:384-405, with collect_with_mask's stop rows), in ONE launch on `stream`:
+ *   the learner's fields, exactly as gmpe_insert_learner writes them for `learner` (its inputs are all optional here too);
+ *   masks[t + 1][q] = dones[t][q] ? 0 : 1;  active_masks[t + 1][q] = 0 where lane q is done and not every agent of its env is, else 1
+ *     (gmpe_masks_from_dones' rule; lane q belongs to env q / num_agents);
+ *   position t of available_actions (the buffer's slot t + 1), exactly as gmpe_available_actions_from_dones writes it with first = t, count = 1:
+ *     all ones at t = 0, else the one-hot row at n_actions / 2 for a lane with dones[t - 1] != 0 and ones for every other lane;
+ *   *draw_dev += draw_inc by one thread (gmpe_act_sample's counter: the step's sampling launch, given draw_inc = 0, has read it earlier on the stream).
+ * Any dones byte != 0 counts as done. An output left NULL is skipped. Plain stores, no atomics, no allocation, no host synchronisation: capturable.
+ * Every argument the host can see is checked before any device call; always exactly one launch, also when no learner input is given. */
+typedef struct gmpe_step_tail_plan {
+    gmpe_learner_plan learner;      /* as for gmpe_insert_learner; here `dones` is required (the masks read it)                      */
+    int32_t num_agents;             /* A >= 1; lanes % A == 0; an env's lanes are consecutive                                        */
+    int32_t n_actions;              /* with available_actions: 1 .. 64, stop row at n_actions / 2                                    */
+    float* masks;                   /* slot 0 of f32 [T+1][lanes], or NULL                                                           */
+    float* active_masks;            /* slot 0 of f32 [T+1][lanes], or NULL                                                           */
+    float* available_actions;       /* rows of position 0 (the buffer's slot 1), as gmpe_avail_plan's, or NULL                       */
+    int64_t stride_masks, stride_active_masks, stride_available_actions;   /* elements between slots, each at least one slot        */
+    uint64_t* draw_dev;             /* u64 [1], 8-byte aligned, or NULL                                                              */
+    uint64_t draw_inc;              /* added to *draw_dev                                                                            */
+} gmpe_step_tail_plan;
+int gmpe_step_tail(int device, const gmpe_step_tail_plan* plan, void* stream);
+
 /* The loss arithmetic of one PPO minibatch (GR_MAPPO.ppo_update, onpolicy/algorithms/graph_mappo.py:176-207 + cal_value_loss :89-117) between the policy
  * head's logits / the critic's values and the two scalars the reference calls .backward() on, with their gradients, in four launches on `stream`
  * (no atomics, no allocation, no host synchronisation; capturable):
@@ -602,7 +625,8 @@ int gmpe_ppo_loss_popart(int device, const gmpe_popart_loss_plan* plan, void* st
  *   first available j whose running float32 sum of probabilities c_j has (double)c_j > u, else the mode. An unavailable action is never returned.
  *   deterministic == 1 (FixedCategorical.mode): the first index of the largest masked logit.
  *   Counter: with draw_dev (u64 [1] on the device) the rows use *draw_dev + draw and a second one-thread launch then adds draw_inc to *draw_dev, so a
- *   captured graph draws fresh numbers at every replay; without it there is exactly one launch.
+ *   captured graph draws fresh numbers at every replay; without it, or with draw_inc == 0 (the caller advances the counter itself: gmpe_step_tail), there
+ *   is exactly one launch.
  * logits / available_actions are contiguous [rows, K], read in 16-byte units when both are 16-byte aligned, in 4-byte units otherwise. Every argument
  * the host can see is checked before any device call. */
 typedef struct gmpe_act_plan {
@@ -649,7 +673,7 @@ int gmpe_act_sample(int device, const gmpe_act_plan* plan, void* stream);
  *
  * gmpe_act_head, the rollout form: gmpe_act_sample with act_plan->logits == NULL (anything else is refused) and the logits formed in the launch from
  * head_plan->features, weight and bias (rows and n_actions of the two plans must agree; the head plan's gradient fields and workspace are not read).
- * Exactly ONE launch, plus gmpe_act_sample's one-thread counter launch when draw_dev is given. The logits are the dot product of gmpe_head_forward (one
+ * Exactly ONE launch, plus gmpe_act_sample's one-thread counter launch when draw_dev is given and draw_inc != 0. The logits are the dot product of gmpe_head_forward (one
  * device function) and the row's routine is gmpe_act_sample's (one device function): action_idx, log_probs, actions_f32, actions_i64 — and logits_out,
  * written when it is not NULL — are bit for bit what gmpe_head_forward followed by gmpe_act_sample gives. With gmpe_ppo_loss recomputing log_probs from
  * gmpe_head_forward's logits, an unchanged policy has importance weights of exactly 1 whatever the two batch shapes. */
