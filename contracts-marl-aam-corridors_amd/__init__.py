@@ -34,7 +34,7 @@ def __getattr__(name):
     if name in ("mlp_base", "mlp_workspace_bytes"):
         from . import mlp
         return getattr(mlp, name)
-    if name in ("gnn_base", "gnn_base_from_table", "gnn_workspace_bytes"):
+    if name in ("gnn_base", "gnn_base_from_table", "gnn_workspace_bytes", "gnn_base_wide", "gnn_base_wide_from_table"):
         from . import gnn
         return getattr(gnn, name)
     if name in ("action_logits", "act_head", "head_workspace_bytes"):

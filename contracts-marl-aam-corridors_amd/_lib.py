@@ -25,6 +25,7 @@ SYMBOLS = ["gmpe_abi_version", "gmpe_last_error", "gmpe_obs_dim", "gmpe_node_fea
            "gmpe_gru_workspace_bytes", "gmpe_gru_forward", "gmpe_gru_backward",
            "gmpe_mlp_workspace_bytes", "gmpe_mlp_forward", "gmpe_mlp_backward",
            "gmpe_gnn_workspace_bytes", "gmpe_gnn_forward", "gmpe_gnn_backward", "gmpe_gnn_forward_table", "gmpe_gnn_backward_table",
+           "gmpe_gnn_forward_wide", "gmpe_gnn_forward_wide_table", "gmpe_gnn_wide_geometry",
            "gmpe_head_workspace_bytes", "gmpe_head_forward", "gmpe_head_backward", "gmpe_act_head",
            "gmpe_value_workspace_bytes", "gmpe_value_forward", "gmpe_value_backward",
            "gmpe_optim_workspace_bytes", "gmpe_optim_step", "gmpe_optim_shard_elems", "gmpe_optim_step_shard",
@@ -269,6 +270,7 @@ class GmpeMlpPlan(C.Structure):
 # GMPE_GNN_* of include/gmpe.h; tests/test_abi_host.py compiles against the header
 GNN_HIDDEN, GNN_MAX_NODES, GNN_MAX_HEADS, GNN_MAX_CONVS, GNN_MAX_EMBED_LAYERS = 16, 64, 4, 3, 2
 GNN_MAX_FEATS, GNN_MAX_EMBEDDINGS, GNN_MAX_EMBEDDING_SIZE = 16, 16, 8
+GNN_WIDE_MAX_NODES = 128                # the forward-only entries gmpe_gnn_forward_wide / _wide_table
 GNN_RELU, GNN_TANH = 0, 1
 GNN_NODE, GNN_MEAN, GNN_MAX, GNN_ADD = 0, 1, 2, 3
 GNN_CONV_PARAMS = ("query_weight", "query_bias", "key_weight", "key_bias", "value_weight", "value_bias", "edge_weight", "skip_weight", "skip_bias")
@@ -414,6 +416,9 @@ def load():
     lib.gmpe_gnn_backward.argtypes = [I, C.POINTER(GmpeGnnPlan), P]
     lib.gmpe_gnn_forward_table.argtypes = [I, C.POINTER(GmpeGnnTablePlan), P]
     lib.gmpe_gnn_backward_table.argtypes = [I, C.POINTER(GmpeGnnTablePlan), P]
+    lib.gmpe_gnn_forward_wide.argtypes = [I, C.POINTER(GmpeGnnPlan), P]
+    lib.gmpe_gnn_forward_wide_table.argtypes = [I, C.POINTER(GmpeGnnTablePlan), P]
+    lib.gmpe_gnn_wide_geometry.argtypes = [C.POINTER(GmpeGnnPlan), C.POINTER(C.c_int64)]
     lib.gmpe_head_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]
     lib.gmpe_head_forward.argtypes = [I, C.POINTER(GmpeHeadPlan), P]
     lib.gmpe_head_backward.argtypes = [I, C.POINTER(GmpeHeadPlan), P]

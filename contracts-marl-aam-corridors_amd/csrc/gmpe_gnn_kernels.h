@@ -965,8 +965,9 @@ struct Layout {
     size_t lds_fwd, lds_bwd, dX, total;
 };
 
-// the checks of the shape and the configuration, which the workspace size depends on
-int check_shape(const char* fn, const gmpe_gnn_plan* pl, Layout& y) {
+// the checks of the shape and the configuration, which the workspace size depends on. maxe: the nodes the calling entry is built for; above MAXE
+// (gmpe_gnn_wide.hip's forward) only K1 and L are filled: the geometry below is the one-wave-per-graph kernels'.
+int check_shape(const char* fn, const gmpe_gnn_plan* pl, Layout& y, int maxe = MAXE) {
     const auto range = [&](const char* name, int64_t v, int64_t lo, int64_t hi) {
         if (v < lo || v > hi)
             return fail(fn, std::string("unsupported ") + name + " = " + std::to_string(v) + ": " + std::to_string(lo) + " .. " + std::to_string(hi) + " are built");
@@ -978,7 +979,7 @@ int check_shape(const char* fn, const gmpe_gnn_plan* pl, Layout& y) {
     if (pl->concat != 0) return fail(fn, "unsupported concat = " + std::to_string(pl->concat) + ": only averaged heads are built");
     if (pl->beta != 0) return fail(fn, "unsupported beta = " + std::to_string(pl->beta) + ": only beta = 0 is built");
     if (pl->edge_dim != 1) return fail(fn, "unsupported edge_dim = " + std::to_string(pl->edge_dim) + ": only 1 is built");
-    if (int rc = range("num_nodes", pl->num_nodes, 1, MAXE)) return rc;
+    if (int rc = range("num_nodes", pl->num_nodes, 1, maxe)) return rc;
     if (int rc = range("node_feats", pl->node_feats, 2, GMPE_GNN_MAX_FEATS)) return rc;
     if (int rc = range("heads", pl->heads, 1, MAXH)) return rc;
     if (int rc = range("gnn_layer_n", pl->gnn_layer_n, 0, MAXC - 1)) return rc;
@@ -990,6 +991,7 @@ int check_shape(const char* fn, const gmpe_gnn_plan* pl, Layout& y) {
     const int E = pl->num_nodes, nconv = pl->gnn_layer_n + 1;
     y.K1 = pl->node_feats - 1 + pl->embedding_size + 1;
     y.L = lay_of(pl->num_embeddings, pl->embedding_size, y.K1, pl->heads, nconv, pl->embed_layer_n);
+    if (E > MAXE) return GMPE_OK;
     const auto waves = [&](bool bwd, size_t& lds) {       // as many graphs side by side as the LDS holds next to the parameters
         const size_t per = (size_t)wlay_of(E, nconv, bwd).total * sizeof(float), fixed = (size_t)y.L.np * sizeof(float);
         int w = (int)((LDS_CU - fixed) / per);
@@ -1010,8 +1012,8 @@ int check_shape(const char* fn, const gmpe_gnn_plan* pl, Layout& y) {
 }
 
 // `table`: the plan is a gmpe_gnn_table_plan's base — node_obs and adj are not read, and agent_id is needed whatever the aggregate: the view needs its ego
-int check_plan(const char* fn, const gmpe_gnn_plan* pl, bool backward, Layout& y, bool table = false) {
-    if (int rc = check_shape(fn, pl, y)) return rc;
+int check_plan(const char* fn, const gmpe_gnn_plan* pl, bool backward, Layout& y, bool table = false, int maxe = MAXE) {
+    if (int rc = check_shape(fn, pl, y, maxe)) return rc;
     const auto act = [&](const char* name, int v) {
         return v == GMPE_GNN_RELU || v == GMPE_GNN_TANH ? (int)GMPE_OK : fail(fn, std::string(name) + " must be GMPE_GNN_RELU or GMPE_GNN_TANH");
     };

@@ -9,7 +9,7 @@
 namespace {
 
 // The table plan's own fields, before its base's checks -> base, the plan the shared checks and bind() read: adj_share is not the table plan's to give
-int check_table_plan(const char* fn, const gmpe_gnn_table_plan* tp, bool backward, Layout& y, gmpe_gnn_plan& base) {
+int check_table_plan(const char* fn, const gmpe_gnn_table_plan* tp, bool backward, Layout& y, gmpe_gnn_plan& base, int maxe = MAXE) {
     if (!tp) return fail(fn, "null plan");
     if (!tp->cfg) return fail(fn, "cfg is required");
     if (!tp->table) return fail(fn, "table is required");
@@ -30,7 +30,7 @@ int check_table_plan(const char* fn, const gmpe_gnn_table_plan* tp, bool backwar
     }
     base = tp->base;
     base.adj_share = 1;
-    return check_plan(fn, &base, backward, y, true);
+    return check_plan(fn, &base, backward, y, true, maxe);
 }
 
 GnnTableArgs bind_table(const gmpe_gnn_table_plan* tp, const gmpe_gnn_plan& base, const Layout& y, bool backward) {
@@ -47,6 +47,8 @@ GnnTableArgs bind_table(const gmpe_gnn_table_plan* tp, const gmpe_gnn_plan& base
 }
 
 }  // namespace
+
+#ifndef GMPE_GNN_WIDE           // gmpe_gnn_wide.hip includes this file for the table plan's checks and binding, with its own entry points
 
 extern "C" {
 
@@ -65,3 +67,5 @@ int gmpe_gnn_backward_table(int device, const gmpe_gnn_table_plan* tp, void* str
 }
 
 }  // extern "C"
+
+#endif  // GMPE_GNN_WIDE

@@ -7,6 +7,9 @@ three, whatever the number of graphs, of nodes and of edges. The dense adjacency
 gnn_base_from_table is the same module straight from the fp64 entity table the rows and the adjacency are pure functions of (gmpe_gnn_forward_table /
 gmpe_gnn_backward_table): bit for bit gnn_base on the engine's own arrays, which are then never written.
 
+gnn_base_wide / gnn_base_wide_from_table are the forward alone on graphs of up to 128 nodes (gmpe_gnn_forward_wide / _wide_table), for rollout and
+evaluation at more entities than gnn_base, and training, take: 64.
+
 There is no torch fallback: the arrays must be on a HIP device.
 """
 import ctypes as C
@@ -18,6 +21,7 @@ from .engine import _need_cuda
 
 HIDDEN = _lib.GNN_HIDDEN                                # embed_hidden_size and gnn_hidden_size the library is built for
 MAX_NODES, MAX_HEADS, MAX_GNN_LAYER_N, MAX_EMBED_LAYER_N = _lib.GNN_MAX_NODES, _lib.GNN_MAX_HEADS, _lib.GNN_MAX_CONVS - 1, _lib.GNN_MAX_EMBED_LAYERS
+WIDE_MAX_NODES = _lib.GNN_WIDE_MAX_NODES                # the forward-only gnn_base_wide / gnn_base_wide_from_table
 MAX_FEATS, MAX_EMBEDDINGS, MAX_EMBEDDING_SIZE = _lib.GNN_MAX_FEATS, _lib.GNN_MAX_EMBEDDINGS, _lib.GNN_MAX_EMBEDDING_SIZE
 _ACTIVATIONS = {"ReLU": _lib.GNN_RELU, "Tanh": _lib.GNN_TANH}
 _AGGREGATES = {"mean": _lib.GNN_MEAN, "max": _lib.GNN_MAX, "add": _lib.GNN_ADD}
@@ -119,20 +123,20 @@ def _base_params(base):
     return names, ps, (heads[0], gnn_n, embed_n, eact, cact, int(ln), ln_eps, aggregate, float(net.max_edge_dist))
 
 
-def _check(node_obs, adj, agent_id, names, ps, meta):
+def _check(node_obs, adj, agent_id, names, ps, meta, who="gnn_base", max_nodes=MAX_NODES):
     """Everything the host can see, before the device is touched -> (device, rows, E, F, adj_share, num_embeddings, embedding_size)"""
     for name, t in (("node_obs", node_obs), ("adj", adj), ("agent_id", agent_id)):
         if not isinstance(t, torch.Tensor):
             raise ValueError("%s must be a tensor" % name)
     tensors = [("node_obs", node_obs), ("adj", adj)] + [("base.gnn." + n, t) for n, t in zip(names, ps)]
-    _layers.need_float32("gnn_base", tensors)
+    _layers.need_float32(who, tensors)
     if agent_id.dtype not in (torch.int32, torch.int64, torch.float32):
         raise ValueError("agent_id must be int32, int64 or float32, not %s" % agent_id.dtype)
     if node_obs.dim() != 3 or min(node_obs.shape) < 1:
         raise ValueError("node_obs must have shape (rows, E, F), not %s" % (tuple(node_obs.shape),))
     rows, E, F = (int(v) for v in node_obs.shape)
-    if E > MAX_NODES:
-        raise NotImplementedError("E = %d nodes: gnn_base is built for at most %d" % (E, MAX_NODES))
+    if E > max_nodes:
+        raise NotImplementedError("E = %d nodes: %s is built for at most %d" % (E, who, max_nodes))
     if not 2 <= F <= MAX_FEATS:
         raise NotImplementedError("F = %d node features: gnn_base is built for 2 .. %d" % (F, MAX_FEATS))
     if adj.dim() != 3 or adj.shape[1] != E or adj.shape[2] != E or adj.shape[0] < 1 or rows % int(adj.shape[0]):
@@ -316,6 +320,16 @@ def gnn_base_from_table(entity_table, table_index, agent_id, base, cfg, *, table
     base, workspace: gnn_base's, with its refusals; the node features and the entity count are cfg's. One autograd node over all parameters, nothing
     saved under torch.no_grad()."""
     names, ps, meta = _base_params(base)
+    rows, share, E, F, nemb, esz, dev, ids, index = _check_table(entity_table, table_index, agent_id, (names, ps, meta), cfg, table_share)
+    train = torch.is_grad_enabled() and any(t.requires_grad for t in ps)
+    workspace = _layers.backward_workspace(train, lambda: gnn_workspace_bytes(rows, E, F, meta[0], meta[1], meta[2], nemb, esz), workspace, dev)
+    return _BaseTable.apply(meta, (rows, E, F, 1, nemb, esz), workspace, cfg, share, entity_table.detach(), index, ids, *ps)
+
+
+def _check_table(entity_table, table_index, agent_id, params, cfg, table_share, who="gnn_base", max_nodes=MAX_NODES):
+    """gnn_base_from_table's arguments, params = _base_params(base), before the device is touched -> (rows, table_share, E, F, num_embeddings,
+    embedding_size, device, the ids as int32 [rows], the index contiguous or None)"""
+    names, ps, meta = params
     if not isinstance(entity_table, torch.Tensor) or not isinstance(agent_id, torch.Tensor):
         raise ValueError("entity_table and agent_id must be tensors")
     if entity_table.dtype != torch.float64:
@@ -341,9 +355,9 @@ def gnn_base_from_table(entity_table, table_index, agent_id, base, cfg, *, table
         share = int(table_share)
         rows = table_rows * share
     E, F = int(cfg.num_entities), int(cfg.node_feats)
-    if E > MAX_NODES:
-        raise NotImplementedError("E = %d nodes: gnn_base is built for at most %d" % (E, MAX_NODES))
-    _layers.need_float32("gnn_base_from_table", [("base.gnn." + n, t) for n, t in zip(names, ps)])
+    if E > max_nodes:
+        raise NotImplementedError("E = %d nodes: %s is built for at most %d" % (E, who, max_nodes))
+    _layers.need_float32(who + "_from_table", [("base.gnn." + n, t) for n, t in zip(names, ps)])
     if agent_id.dtype not in (torch.int32, torch.int64, torch.float32):
         raise ValueError("agent_id must be int32, int64 or float32, not %s" % agent_id.dtype)
     _check_ids(agent_id, rows)
@@ -354,9 +368,7 @@ def gnn_base_from_table(entity_table, table_index, agent_id, base, cfg, *, table
     _layers.need_device([("base.gnn." + n, t) for n, t in zip(names, ps)] + others, dev, "entity_table")
     ids = agent_id.detach().reshape(rows).to(torch.int32)
     index = None if table_index is None else table_index.detach().contiguous()
-    train = torch.is_grad_enabled() and any(t.requires_grad for t in ps)
-    workspace = _layers.backward_workspace(train, lambda: gnn_workspace_bytes(rows, E, F, meta[0], meta[1], meta[2], nemb, esz), workspace, dev)
-    return _BaseTable.apply(meta, (rows, E, F, 1, nemb, esz), workspace, cfg, share, entity_table.detach(), index, ids, *ps)
+    return rows, share, E, F, nemb, esz, dev, ids, index
 
 
 def gnn_base(node_obs, adj, agent_id, base, workspace=None):
@@ -382,3 +394,54 @@ def gnn_base(node_obs, adj, agent_id, base, workspace=None):
     train = torch.is_grad_enabled() and any(t.requires_grad for t in ps)
     workspace = _layers.backward_workspace(train, lambda: gnn_workspace_bytes(rows, E, F, meta[0], meta[1], meta[2], nemb, esz), workspace, dev)
     return _Base.apply(meta, (rows, E, F, share, nemb, esz), workspace, node_obs, adj, ids, *ps)
+
+
+def _forward_only(ps):
+    if torch.is_grad_enabled() and any(t.requires_grad for t in ps):
+        raise NotImplementedError("a parameter of base requires a gradient and gradients are enabled, but gnn_base_wide is forward only: backward at "
+                                  "E > %d is not built (call it under torch.no_grad(), or train with gnn_base at E <= %d)" % (MAX_NODES, MAX_NODES))
+
+
+def gnn_base_wide(node_obs, adj, agent_id, base):
+    """gnn_base's forward on graphs of 1 <= E <= 128 nodes (gmpe_gnn_forward_wide) -> nbd_features [rows, 16]: rollout, evaluation and the value
+    bootstrap of a policy at more entities than it can be trained on here — the GNN's weights do not depend on E. The arguments, the checks and the
+    parameter reader are gnn_base's. Forward only, without an autograd node: with gradients enabled and a parameter of base requiring one it raises
+    NotImplementedError before any launch; under torch.no_grad(), or with frozen parameters, it runs.
+    E <= 64 runs gnn_base's own launch: its bits. E > 64 runs one launch in which a node belongs to a thread of a pair of waves; a graph's arithmetic
+    is the same function of E and the configuration, so a graph of <= 64 nodes padded with isolated nodes (type 0, adjacency entries 0 or >=
+    max_edge_dist) keeps gnn_base's bits in every original node. A graph's result does not depend on the other graphs of the call."""
+    names, ps, meta = _base_params(base)
+    _forward_only(ps)
+    dev, rows, E, F, share, nemb, esz = _check(node_obs, adj, agent_id, names, ps, meta, "gnn_base_wide", WIDE_MAX_NODES)
+    cs = [t.detach().contiguous() for t in (node_obs, adj, agent_id.detach().reshape(rows).to(torch.int32)) + tuple(ps)]
+    features = torch.empty((rows, HIDDEN), dtype=torch.float32, device=dev)
+    plan = _plan((rows, E, F, share, nemb, esz), meta, cs[0], cs[1], cs[2], cs[3:])
+    plan.features = features.data_ptr()
+    _layers.run("gmpe_gnn_forward_wide", dev, plan)
+    return features
+
+
+def gnn_base_wide_from_table(entity_table, table_index, agent_id, base, cfg, table_share=None):
+    """gnn_base_wide straight from the fp64 entity table (gmpe_gnn_forward_wide_table) -> nbd_features [rows, 16], bit for bit gnn_base_wide on the
+    engine's own rows and adjacency; cfg.num_entities may be up to 128. The arguments and the checks are gnn_base_from_table's; forward only, as
+    gnn_base_wide."""
+    names, ps, meta = _base_params(base)
+    _forward_only(ps)
+    rows, share, E, F, nemb, esz, dev, ids, index = _check_table(entity_table, table_index, agent_id, (names, ps, meta), cfg, table_share,
+                                                                 "gnn_base_wide", WIDE_MAX_NODES)
+    cs = [t.detach().contiguous() for t in (ids,) + tuple(ps)]
+    features = torch.empty((rows, HIDDEN), dtype=torch.float32, device=dev)
+    tp = _table_plan((rows, E, F, 1, nemb, esz), meta, cfg, share, entity_table.detach(), index, cs[0], cs[1:])
+    tp.base.features = features.data_ptr()
+    _layers.run("gmpe_gnn_forward_wide_table", dev, tp)
+    return features
+
+
+def wide_geometry(rows, num_nodes, node_feats, heads=3, gnn_layer_N=2, embed_layer_N=1, num_embeddings=4, embedding_size=2):
+    """(graphs side by side in a workgroup, dynamic LDS bytes, workgroups) of the launch gnn_base_wide makes for these shapes and counts
+    (gmpe_gnn_wide_geometry); no device is touched. Up to 64 nodes it is gnn_base's forward launch."""
+    out = (C.c_int64 * 3)()
+    plan = _shape_plan(int(rows), int(num_nodes), int(node_feats), 1, int(heads), int(gnn_layer_N), int(embed_layer_N), int(num_embeddings),
+                       int(embedding_size))
+    _lib.check(_lib.load().gmpe_gnn_wide_geometry(C.byref(plan), out), "gmpe_gnn_wide_geometry")
+    return int(out[0]), int(out[1]), int(out[2])

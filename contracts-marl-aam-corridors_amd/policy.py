@@ -25,7 +25,7 @@ import collections
 import torch
 import torch.nn.functional as F
 
-from .gnn import gnn_base, gnn_base_from_table
+from .gnn import MAX_NODES as GNN_MAX_NODES, gnn_base, gnn_base_from_table, gnn_base_wide, gnn_base_wide_from_table
 from .gru import rnn_layer
 from .head import act_head, action_logits
 from .minibatch import TableRows
@@ -47,10 +47,15 @@ def _recurrent(net):
 def _features(net, own_obs, node_obs, adj, agent_id, rnn_states, masks):
     """(features [rows, 64], rnn_states) of an actor or a critic in front of its head; own_obs None: the graph features alone enter the MLPBase.
     adj a gmpe.minibatch.TableRows (node_obs is then not read): the GNNBase runs straight from the entity table, graph r the view of ego agent_id[r] of
-    table row index[r] — or, without an index, of row r // num_agents: a rollout step's [N, W] table."""
+    table row index[r] — or, without an index, of row r // num_agents: a rollout step's [N, W] table. Graphs of more than 64 nodes (up to 128) go to the
+    forward-only gnn_base_wide / gnn_base_wide_from_table, which refuse a call that needs gradients by name: rollout and evaluation run there, training
+    does not."""
     if isinstance(adj, TableRows):
         share = None if adj.index is not None else int(adj.cfg.num_agents)
-        nbd = gnn_base_from_table(adj.table, adj.index, agent_id, net.gnn_base, adj.cfg, table_share=share)
+        table = gnn_base_wide_from_table if int(adj.cfg.num_entities) > GNN_MAX_NODES else gnn_base_from_table
+        nbd = table(adj.table, adj.index, agent_id, net.gnn_base, adj.cfg, table_share=share)
+    elif isinstance(node_obs, torch.Tensor) and node_obs.dim() == 3 and node_obs.shape[1] > GNN_MAX_NODES:
+        nbd = gnn_base_wide(node_obs, adj, agent_id, net.gnn_base)
     else:
         nbd = gnn_base(node_obs, adj, agent_id, net.gnn_base)
     features = mlp_base(nbd if own_obs is None else (own_obs, nbd), net.base)

@@ -1185,6 +1185,25 @@ typedef struct gmpe_gnn_table_plan {
 int gmpe_gnn_forward_table(int device, const gmpe_gnn_table_plan* plan, void* stream);
 int gmpe_gnn_backward_table(int device, const gmpe_gnn_table_plan* plan, void* stream);
 
+/* ---- The same GNNBase's forward on graphs of up to 128 nodes: rollout, evaluation and the value bootstrap at more entities than 64 ----
+ * gmpe_gnn_forward / gmpe_gnn_forward_table with num_nodes in 1 .. GMPE_GNN_WIDE_MAX_NODES (for the table form, cfg's entity count); every other
+ * field, check and refusal is theirs, under these entries' names. Forward only: the gradient pointers, workspace and workspace_bytes are not read,
+ * and there is no backward at num_nodes > 64 (gmpe_gnn_backward refuses it as before).
+ *   num_nodes <= 64: the narrow entry's own launch — the bits are gmpe_gnn_forward's by construction, so a caller need not branch.
+ *   num_nodes  > 64: one launch of a kernel in which a node belongs to a thread of a pair of waves, not to a lane of one wave. A workgroup of 256
+ *     threads owns tiles of W graphs, W = 2 where two graphs' state fits 160 KiB of LDS next to the parameters and 1 above; pair p owns graph p of the
+ *     tile, its thread t node t. The arithmetic of a graph is the one written above, a function of E and the configuration alone: every sum over a
+ *     node's edges runs ascending in the node's thread, heads are added ascending, a pool adds the nodes ascending in one thread per channel. So a
+ *     graph's row does not depend on rows, on its place in the call, on W, on adj_share or on the source, and appending isolated nodes (type 0, all
+ *     their adjacency entries 0 or >= max_edge_dist) to a graph of <= 64 nodes leaves every original node's row at gmpe_gnn_forward's bits.
+ * Every configuration gmpe_gnn_forward accepts fits at 128 nodes (162 816 B with 16 features, 4 heads, 3 convs, 2 embed layers, 16 x 8 embeddings).
+ * gmpe_gnn_wide_geometry: the launch of a plan's shape (no pointer is read) -> out[0] = W (for num_nodes <= 64 the narrow forward's), out[1] = the
+ * launch's dynamic LDS in bytes, out[2] = its workgroups. No atomics, no allocation, no host synchronisation; capturable. */
+#define GMPE_GNN_WIDE_MAX_NODES 128
+int gmpe_gnn_forward_wide(int device, const gmpe_gnn_plan* plan, void* stream);
+int gmpe_gnn_forward_wide_table(int device, const gmpe_gnn_table_plan* plan, void* stream);
+int gmpe_gnn_wide_geometry(const gmpe_gnn_plan* plan, int64_t* out);
+
 /* ---- Evaluation of a policy over a batch of episodes (handle-less): GMPERunner.render(get_metrics=True) as one episode per env ----
  * (onpolicy/runner/shared/graph_mpe_runner.py:526-1060, base_runner.py:194-574). Every env plays one episode from a reset; the caller's policy acts,
  * the engine steps, gmpe_episode_record books the step. No allocation, no host synchronisation, every launch on `stream`.
