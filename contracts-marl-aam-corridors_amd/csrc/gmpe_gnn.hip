@@ -1,21 +1,6 @@
 // gmpe_gnn.hip — the policy's GNNBase from node rows and a dense adjacency (include/gmpe.h gmpe_gnn_forward / gmpe_gnn_backward): the entry points, and
-// the kernels of gmpe_gnn_kernels.h instantiated over that source. The mapping, the arithmetic and the host checks are written there; the geometry here.
-// gmpe_gnn_table.hip includes this file with GMPE_GNN_TABLE defined: the same geometry and kernels, its own entry points in place of these.
-#include "gmpe_host.h"          // include/gmpe.h, for the sizes below
-
-namespace {
-
-constexpr int C = GMPE_GNN_HIDDEN, BLOCK = 256, NW = BLOCK / 64;
-constexpr int MAXE = GMPE_GNN_MAX_NODES, MAXH = GMPE_GNN_MAX_HEADS, MAXC = GMPE_GNN_MAX_CONVS, MAXL = GMPE_GNN_MAX_EMBED_LAYERS;
-constexpr int NINS = 32;                                // row stride of a node's lin1 input in LDS: F - 1 + embedding_size <= 23 columns, zeros behind
-constexpr int QDS = 40;                                 // backward's per-node row: q [16], the head's output gradient [16], max, -, 1 / sum and D (doubles), -
-constexpr int LIN = C * C + C;                          // a 16 x 16 Linear with its bias
-
-}  // namespace
-
+// the kernels of gmpe_gnn_kernels.h instantiated over that source. The geometry, the mapping, the arithmetic and the host checks are written there.
 #include "gmpe_gnn_kernels.h"
-
-#ifndef GMPE_GNN_TABLE
 
 extern "C" {
 
@@ -41,5 +26,3 @@ int gmpe_gnn_backward(int device, const gmpe_gnn_plan* pl, void* stream) {
 }
 
 }  // extern "C"
-
-#endif  // GMPE_GNN_TABLE

@@ -1,5 +1,7 @@
-// gmpe_gnn_kernels.h — the kernels and the host half of the two files that run the policy's GNNBase: gmpe_gnn.hip (a graph's inputs are node rows and an
-// adjacency: the <false> instantiations) and gmpe_gnn_table.hip (they are built from an entity table: the <true> ones). Everything here has internal linkage.
+// gmpe_gnn_kernels.h — the geometry, the kernels and the host half of the three files that run the policy's GNNBase: gmpe_gnn.hip (a graph's inputs are
+// node rows and an adjacency: the GnnArgs instantiations), gmpe_gnn_table.hip (they are built from an entity table: the GnnTableArgs ones) and
+// gmpe_gnn_wide.hip (the forward of both sources on graphs of 65 .. 128 nodes). Each of them includes this file alone and adds its kernel instantiations
+// and its extern "C" entries. Everything here has internal linkage.
 // The two sources are two translation units because both backward kernels use all 512 registers of a lane: with both sources in one kernel, or with the
 // table's fields as ordinary arguments next to the rows', they spill (DESIGN.md 3.13 has the counts).
 //
@@ -42,10 +44,17 @@
 
 namespace {
 
-// C, BLOCK, NW, MAXE, MAXH, MAXC, MAXL, NINS, QDS, LIN: the geometry, which gmpe_gnn.hip defines in front of its #include of this file (tests/gnn_lib.py
-// restates it from there); gmpe_gnn_table.hip gets both through gmpe_gnn.hip
+// the geometry (tests/gnn_lib.py restates it from here)
+constexpr int C = GMPE_GNN_HIDDEN, BLOCK = 256, NW = BLOCK / 64;
+constexpr int MAXE = GMPE_GNN_MAX_NODES, MAXH = GMPE_GNN_MAX_HEADS, MAXC = GMPE_GNN_MAX_CONVS, MAXL = GMPE_GNN_MAX_EMBED_LAYERS;
+constexpr int NINS = 32;                                // row stride of a node's lin1 input in LDS: F - 1 + embedding_size <= 23 columns, zeros behind
+constexpr int QDS = 40;                                 // backward's per-node row: q [16], the head's output gradient [16], max, -, 1 / sum and D (doubles), -
+constexpr int LIN = C * C + C;                          // a 16 x 16 Linear with its bias
+// the wide forward (gmpe_gnn_wide.hip): a node per thread of a pair of waves, a graph per pair
+constexpr int WIDE_MAXE = GMPE_GNN_WIDE_MAX_NODES, PAIR = 2 * 64, NPAIR = BLOCK / PAIR;
 using gmpe::LDS_CU;
 static_assert(C == 16 && NW == 4 && MAXH == 4 && MAXC == 3 && MAXL == 2, "16 channels, four waves");
+static_assert(WIDE_MAXE == PAIR && NPAIR == 2, "a node per thread of a wave pair, two pairs in a workgroup");
 static_assert(GMPE_GNN_MAX_FEATS - 1 + GMPE_GNN_MAX_EMBEDDING_SIZE <= NINS, "a node's lin1 input fits its LDS row");
 
 // 16 x 16 blocks of parameter gradients (one element per thread) and 16-wide vectors (thread t owns entry t % 16 of the groups g with g % 16 == t / 16)
@@ -304,55 +313,60 @@ __device__ __forceinline__ void load_params(const GnnArgs& p, const Lay& L, floa
         }
 }
 
-// What a graph's source gives: the masked matrix into ev (all lanes of an active wave) and, with `on`, the first F - 1 features of this lane's node into its
-// lin1 input row nin -> its type as the float the rows hold. From the rows and the adjacency:
-__device__ __forceinline__ float graph_source(const GnnArgs& p, float* ev, float* nin, int lane, int64_t g, bool on) {
+// The node mapping of the functions below: thread s of the ns that stage a graph's matrix; `node`, the node this thread owns, and `owner`, whether it
+// computes a node at all. A narrow kernel passes lane, 64, lane, true (a graph per wave); k_gnn_fwd_wide its thread of a pair of waves. `on`, this thread
+// owns a node of a graph, is formed from them in each function: handed down as a finished predicate it costs k_gnn_bwd_embed its last registers
+// (DESIGN.md 3.13a).
+//
+// What a graph's source gives: the masked matrix into ev (all staging threads of an active graph) and, with `on`, the first F - 1 features of this thread's
+// node into its lin1 input row nin -> its type as the float the rows hold. From the rows and the adjacency:
+__device__ __forceinline__ float graph_source(const GnnArgs& p, float* ev, float* nin, int s, int ns, int node, int64_t g, bool on) {
     const int E = p.E, es = E | 1;
     const float* a = p.adj + (g / p.S) * (int64_t)(E * E);
 #pragma unroll 1
-    for (int f = lane; f < E * E; f += 64) {
+    for (int f = s; f < E * E; f += ns) {
         const int j = f / E, i = f - j * E;
         const float v = a[f];
         ev[j * es + i] = (v > 0.0f && v < p.maxd) ? v : 0.0f;
     }
     if (!on) return 0.0f;
-    const float* xr = p.x + (g * E + lane) * p.F;
+    const float* xr = p.x + (g * E + node) * p.F;
 #pragma unroll 1
     for (int k = 0; k < p.F - 1; ++k) nin[k] = xr[k];
     return xr[p.F - 1];
 }
-// ... and from an entity table, with gmpe_expand.h's arithmetic (the engine's bits): entry (j, i) of the env-step's matrix, and the row of entity `lane` as
+// ... and from an entity table, with gmpe_expand.h's arithmetic (the engine's bits): entry (j, i) of the env-step's matrix, and the row of entity `node` as
 // ego id[g] sees it. The helpers write a whole row, the type last, into nin (16-byte aligned, as KIND 0's float4 stores need); the caller overwrites the
 // type's place with the embedding, as it does behind the copied rows.
-__device__ __forceinline__ float graph_source(const GnnTableArgs& p, float* ev, float* nin, int lane, int64_t g, bool on) {
+__device__ __forceinline__ float graph_source(const GnnTableArgs& p, float* ev, float* nin, int s, int ns, int node, int64_t g, bool on) {
     const int E = p.E, es = E | 1;
     int64_t idx = !p.tidx ? g / p.tshare : (p.idx64 ? static_cast<const int64_t*>(p.tidx)[g] : (int64_t) static_cast<const int32_t*>(p.tidx)[g]);
     idx = idx < 0 ? 0 : (idx > p.tlast ? p.tlast : idx);
     const double* T = p.tab + idx * p.TW;
 #pragma unroll 1
-    for (int f = lane; f < E * E; f += 64) {
+    for (int f = s; f < E * E; f += ns) {
         const int j = f / E, i = f - j * E;
         const float v = gmpe::adj_entry_from_table(T, E, p.TW, j, i);
         ev[j * es + i] = (v > 0.0f && v < p.maxd) ? v : 0.0f;
     }
     if (!on) return 0.0f;
     const int id = p.id[g], ego = id < 0 ? 0 : (id >= p.A ? p.A - 1 : id);
-    if (p.kind == 0) gmpe::node_row_from_table<0>(T, nin, p.A, p.NL, E, p.TW, p.two, ego, lane);
-    else if (p.kind == 1) gmpe::node_row_from_table<1>(T, nin, p.A, p.NL, E, p.TW, p.two, ego, lane);
-    else gmpe::node_row_from_table<2>(T, nin, p.A, p.NL, E, p.TW, p.two, ego, lane);
+    if (p.kind == 0) gmpe::node_row_from_table<0>(T, nin, p.A, p.NL, E, p.TW, p.two, ego, node);
+    else if (p.kind == 1) gmpe::node_row_from_table<1>(T, nin, p.A, p.NL, E, p.TW, p.two, ego, node);
+    else gmpe::node_row_from_table<2>(T, nin, p.A, p.NL, E, p.TW, p.two, ego, node);
     return nin[p.F - 1];
 }
 
-// A graph's inputs into the wave's LDS: the masked matrix, every node's lin1 input row and its part P of lin1. Every wave of the workgroup calls it
-// together (it ends in a workgroup barrier). -> P, this lane's node's part; type, its clamped entity type. ARGS: GnnArgs or GnnTableArgs, the source.
+// A graph's inputs into its LDS block wl: the masked matrix, every node's lin1 input row and its part P of lin1. Every wave of the workgroup calls it
+// together (it ends in a workgroup barrier). -> P, this thread's node's part; type, its clamped entity type. ARGS: GnnArgs or GnnTableArgs, the source.
 template <class ARGS>
-__device__ __forceinline__ void graph_inputs(const ARGS& p, const Lay& L, const WLay& WL, const float* Wt, float* wl, int lane, int64_t g, bool active,
-                                             float (&P)[C], int& type) {
+__device__ __forceinline__ void graph_inputs(const ARGS& p, const Lay& L, const WLay& WL, const float* Wt, float* wl, int s, int ns, int node, bool owner,
+                                             int64_t g, bool active, float (&P)[C], int& type) {
     const int E = p.E;
-    const bool on = active && lane < E;
-    float* nin = wl + WL.nin + lane * NINS;
+    const bool on = active && owner && node < E;
+    float* nin = wl + WL.nin + node * NINS;
     float tf = 0.0f;
-    if (active) tf = graph_source(p, wl + WL.ev, nin, lane, g, on);
+    if (active) tf = graph_source(p, wl + WL.ev, nin, s, ns, node, g, on);
     type = 0;
     if (on) {
         type = tf >= 1.0f ? (tf < (float)p.nemb ? (int)tf : p.nemb - 1) : 0;           // int() truncates; NaN and everything outside go to the ends
@@ -368,23 +382,23 @@ __device__ __forceinline__ void graph_inputs(const ARGS& p, const Lay& L, const 
 #pragma unroll
             for (int c = 0; c < C; ++c) P[c] = fmaf(Wt[L.w1 + c * p.K1 + k], v, P[c]);
         }
-        store16(wl + WL.P + lane * C, P);
+        store16(wl + WL.P + node * C, P);
     }
     __syncthreads();
 }
 
-// One graph's forward for a wave; every wave of the workgroup calls it together (it holds workgroup barriers). `on`: this lane owns a node of a graph.
-// -> x, the node's row of the last layer (also in the wave's xs[KEEP ? nconv : 0]).
+// One graph's forward for the threads of its block wl; every wave of the workgroup calls it together (it holds workgroup barriers).
+// -> x, the node's row of the last layer (also in the block's xs[KEEP ? nconv : 0]).
 template <bool KEEP, class ARGS>
-__device__ __forceinline__ void graph_forward(const ARGS& p, const Lay& L, const WLay& WL, const float* Wt, float* wl, int lane,
+__device__ __forceinline__ void graph_forward(const ARGS& p, const Lay& L, const WLay& WL, const float* Wt, float* wl, int s, int ns, int node, bool owner,
                                               int64_t g, bool active, float (&x)[C]) {
     const int E = p.E, es = E | 1, H = p.H;
-    const bool on = active && lane < E;
+    const bool on = active && owner && node < E;
     const float* ev = wl + WL.ev;
     {
         float P[C];
         int type;
-        graph_inputs(p, L, WL, Wt, wl, lane, g, active, P, type);
+        graph_inputs(p, L, WL, Wt, wl, s, ns, node, owner, g, active, P, type);
     }
     double xa[C];                                       // a node's sum over its incoming edges in double, rounded once
     zero16(xa);
@@ -395,7 +409,7 @@ __device__ __forceinline__ void graph_forward(const ARGS& p, const Lay& L, const
 #pragma unroll 1
         for (int j = 0; j < E; ++j) {
             reload();
-            const float e = ev[j * es + lane];
+            const float e = ev[j * es + node];
             if (e > 0.0f) {
                 float Pj[C], y[C];
                 load16(wl + WL.P + j * C, Pj);
@@ -410,11 +424,11 @@ __device__ __forceinline__ void graph_forward(const ARGS& p, const Lay& L, const
     const float Hf = (float)H;
     for (int cc = 0; cc < p.nconv; ++cc) {
         const float* Wc = Wt + L.conv + cc * L.cs;
-        float s[C], o[C];
+        float sk[C], o[C];
         zero16(o);
         if (on) {
-            if (KEEP) store16(wl + WL.xs + (cc * E + lane) * C, x);
-            lin16(Wc + cws(H), Wc + cbs(H), x, s);
+            if (KEEP) store16(wl + WL.xs + (cc * E + node) * C, x);
+            lin16(Wc + cws(H), Wc + cbs(H), x, sk);
         }
         for (int h = 0; h < H; ++h) {
             float q[C];
@@ -423,8 +437,8 @@ __device__ __forceinline__ void graph_forward(const ARGS& p, const Lay& L, const
                 lin16(Wc + cw(H, 0, h), Wc + cb(H, 0, h), x, q);
                 lin16(Wc + cw(H, 1, h), Wc + cb(H, 1, h), x, k);
                 lin16(Wc + cw(H, 2, h), Wc + cb(H, 2, h), x, v);
-                store16(wl + WL.kv + lane * 2 * C, k);
-                store16(wl + WL.kv + lane * 2 * C + C, v);
+                store16(wl + WL.kv + node * 2 * C, k);
+                store16(wl + WL.kv + node * 2 * C + C, v);
             }
             __syncthreads();
             if (on) {
@@ -434,7 +448,7 @@ __device__ __forceinline__ void graph_forward(const ARGS& p, const Lay& L, const
 #pragma unroll 1
                 for (int j = 0; j < E; ++j) {
                     reload();
-                    const float e = ev[j * es + lane];
+                    const float e = ev[j * es + node];
                     if (e > 0.0f) {
                         float k[C];
                         load16(wl + WL.kv + j * 2 * C, k);
@@ -447,7 +461,7 @@ __device__ __forceinline__ void graph_forward(const ARGS& p, const Lay& L, const
 #pragma unroll 1
                 for (int j = 0; j < E; ++j) {
                     reload();
-                    const float e = ev[j * es + lane];
+                    const float e = ev[j * es + node];
                     if (e > 0.0f) {
                         float k[C], v[C];
                         load16(wl + WL.kv + j * 2 * C, k);
@@ -467,10 +481,10 @@ __device__ __forceinline__ void graph_forward(const ARGS& p, const Lay& L, const
         }
         if (on) {
 #pragma unroll
-            for (int c = 0; c < C; ++c) x[c] = activate(p.cact, __fdiv_rn(o[c], Hf) + s[c]);
+            for (int c = 0; c < C; ++c) x[c] = activate(p.cact, __fdiv_rn(o[c], Hf) + sk[c]);
         }
     }
-    if (on) store16(wl + WL.xs + ((KEEP ? p.nconv : 0) * E + lane) * C, x);
+    if (on) store16(wl + WL.xs + ((KEEP ? p.nconv : 0) * E + node) * C, x);
     __syncthreads();
 }
 
@@ -479,12 +493,29 @@ __device__ __forceinline__ int ego_of(const GnnArgs& p, int64_t g) {
     return id < 0 ? 0 : (id >= p.E ? p.E - 1 : id);
 }
 
+// the gather or the pool of graph g over the rows xs that graph_forward<false> left: one thread per channel, the nodes ascending
+__device__ __forceinline__ void graph_output(const GnnArgs& p, const float* xs, int channel, int64_t g) {
+    float r;
+    if (p.aggr == GMPE_GNN_NODE) r = xs[ego_of(p, g) * C + channel];
+    else {
+        r = xs[channel];
+#pragma unroll 1
+        for (int i = 1; i < p.E; ++i) {
+            reload();
+            const float v = xs[i * C + channel];
+            r = p.aggr == GMPE_GNN_MAX ? (v > r ? v : r) : r + v;
+        }
+        if (p.aggr == GMPE_GNN_MEAN) r = __fdiv_rn(r, (float)p.E);
+    }
+    p.out[g * C + channel] = r;
+}
+
 template <class ARGS>
 __global__ __launch_bounds__(BLOCK) void k_gnn_fwd(ARGS p) {
     extern __shared__ __attribute__((aligned(16))) float sh[];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, E = p.E;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const Lay L = lay_of(p.nemb, p.esz, p.K1, p.H, p.nconv, p.nel);
-    const WLay WL = wlay_of(E, p.nconv, false);
+    const WLay WL = wlay_of(p.E, p.nconv, false);
     float* wl = sh + L.np + wv * WL.total;
     load_params(p, L, sh, tid);
     __syncthreads();
@@ -492,23 +523,8 @@ __global__ __launch_bounds__(BLOCK) void k_gnn_fwd(ARGS p) {
         const int64_t g = tile * p.W + wv;
         const bool active = wv < p.W && g < p.rows;
         float x[C];
-        graph_forward<false>(p, L, WL, sh, wl, lane, g, active, x);
-        if (active && lane < C) {
-            const float* xs = wl + WL.xs;
-            float r;
-            if (p.aggr == GMPE_GNN_NODE) r = xs[ego_of(p, g) * C + lane];
-            else {
-                r = xs[lane];
-#pragma unroll 1
-                for (int i = 1; i < E; ++i) {
-                    reload();
-                    const float v = xs[i * C + lane];
-                    r = p.aggr == GMPE_GNN_MAX ? (v > r ? v : r) : r + v;
-                }
-                if (p.aggr == GMPE_GNN_MEAN) r = __fdiv_rn(r, (float)E);
-            }
-            p.out[g * C + lane] = r;
-        }
+        graph_forward<false>(p, L, WL, sh, wl, lane, 64, lane, true, g, active, x);
+        if (active && lane < C) graph_output(p, wl + WL.xs, lane, g);
         __syncthreads();                                // the next tile overwrites the waves' state
     }
 }
@@ -574,7 +590,7 @@ __global__ __launch_bounds__(BLOCK) void k_gnn_bwd_conv(ARGS p) {
         const int nw = left < p.W ? (int)left : p.W;    // the graphs of this tile
         const bool active = wv < nw, on = active && lane < E;
         float x[C], dy[C];
-        graph_forward<true>(p, L, WL, Wt, wl, lane, g, active, x);
+        graph_forward<true>(p, L, WL, Wt, wl, lane, 64, lane, true, g, active, x);
         const float* ev = wl + WL.ev;
         float* st = wl + WL.st;
         float* qd = wl + WL.qd;
@@ -803,7 +819,7 @@ __global__ __launch_bounds__(BLOCK) void k_gnn_bwd_embed(ARGS p) {
         const bool active = wv < nw, on = active && lane < E;
         float P[C];
         int type;
-        graph_inputs(p, L, WL, Wt, wl, lane, g, active, P, type);
+        graph_inputs(p, L, WL, Wt, wl, lane, 64, lane, true, g, active, P, type);
         const float* ev = wl + WL.ev;
         float* st = wl + WL.st;
         float* qd = wl + WL.qd;
@@ -966,7 +982,7 @@ struct Layout {
 };
 
 // the checks of the shape and the configuration, which the workspace size depends on. maxe: the nodes the calling entry is built for; above MAXE
-// (gmpe_gnn_wide.hip's forward) only K1 and L are filled: the geometry below is the one-wave-per-graph kernels'.
+// (gmpe_gnn_wide.hip's forward) the forward geometry is a graph per pair of waves and backward's fields stay zero: there is no backward.
 int check_shape(const char* fn, const gmpe_gnn_plan* pl, Layout& y, int maxe = MAXE) {
     const auto range = [&](const char* name, int64_t v, int64_t lo, int64_t hi) {
         if (v < lo || v > hi)
@@ -989,22 +1005,25 @@ int check_shape(const char* fn, const gmpe_gnn_plan* pl, Layout& y, int maxe = M
     if (pl->adj_share < 1) return fail(fn, "adj_share must be >= 1");
     if (pl->rows % pl->adj_share) return fail(fn, "rows must be a multiple of adj_share");
     const int E = pl->num_nodes, nconv = pl->gnn_layer_n + 1;
+    y = {};
     y.K1 = pl->node_feats - 1 + pl->embedding_size + 1;
     y.L = lay_of(pl->num_embeddings, pl->embedding_size, y.K1, pl->heads, nconv, pl->embed_layer_n);
-    if (E > MAXE) return GMPE_OK;
+    const bool wide = E > MAXE;
     const auto waves = [&](bool bwd, size_t& lds) {       // as many graphs side by side as the LDS holds next to the parameters
         const size_t per = (size_t)wlay_of(E, nconv, bwd).total * sizeof(float), fixed = (size_t)y.L.np * sizeof(float);
+        const int cap = wide ? NPAIR : NW;
         int w = (int)((LDS_CU - fixed) / per);
-        w = w < 1 ? 1 : (w > NW ? NW : w);
+        w = w < 1 ? 1 : (w > cap ? cap : w);
         lds = fixed + w * per;
         return w;
     };
     y.W_fwd = waves(false, y.lds_fwd);
-    y.W_bwd = waves(true, y.lds_bwd);
+    if (!wide) y.W_bwd = waves(true, y.lds_bwd);
     if (y.lds_fwd > (size_t)LDS_CU || y.lds_bwd > (size_t)LDS_CU) return fail(fn, "internal: the LDS layout does not fit");
     y.ntiles_fwd = (pl->rows + y.W_fwd - 1) / y.W_fwd;
-    y.ntiles_bwd = (pl->rows + y.W_bwd - 1) / y.W_bwd;
     y.nblocks_fwd = gmpe::resident_grid(y.ntiles_fwd, y.lds_fwd, 4);
+    if (wide) return GMPE_OK;
+    y.ntiles_bwd = (pl->rows + y.W_bwd - 1) / y.W_bwd;
     y.nblocks_bwd = gmpe::resident_grid(y.ntiles_bwd, y.lds_bwd, 1);        // the backward kernels keep a thread's sums in registers: one wave per SIMD
     y.dX = (size_t)y.nblocks_bwd * y.L.np * sizeof(double);
     y.total = y.dX + (size_t)pl->rows * E * C * sizeof(float);
@@ -1079,6 +1098,44 @@ GnnArgs bind(const gmpe_gnn_plan* pl, const Layout& y, bool backward) {
     a.out = pl->features; a.gout = pl->grad_features;
     a.part = static_cast<double*>(pl->workspace);
     a.dX = gmpe::at<float>(pl->workspace, y.dX);
+    return a;
+}
+
+// The table plan's own fields, before its base's checks -> base, the plan the shared checks and bind() read: adj_share is not the table plan's to give
+int check_table_plan(const char* fn, const gmpe_gnn_table_plan* tp, bool backward, Layout& y, gmpe_gnn_plan& base, int maxe = MAXE) {
+    if (!tp) return fail(fn, "null plan");
+    if (!tp->cfg) return fail(fn, "cfg is required");
+    if (!tp->table) return fail(fn, "table is required");
+    const gmpe_config* cfg = tp->cfg;
+    if (cfg->abi_version != GMPE_ABI_VERSION) return fail(fn, "cfg.abi_version mismatch");
+    const int A = cfg->num_agents, L = cfg->num_landmarks, E = gmpe_num_entities(cfg);
+    if (A < 1 || A > GMPE_MAX_AGENTS || L < A || cfg->num_obstacles < 0 || E > GMPE_MAX_ENTITIES) return fail(fn, "cfg out of range");
+    if (tp->base.num_nodes != E) return fail(fn, "num_nodes = " + std::to_string(tp->base.num_nodes) + " but cfg has " + std::to_string(E) + " entities");
+    if (tp->base.node_feats != gmpe_node_feats(cfg))
+        return fail(fn, "node_feats = " + std::to_string(tp->base.node_feats) + " but cfg's node rows have " + std::to_string(gmpe_node_feats(cfg)));
+    if ((uintptr_t)tp->table & 7) return fail(fn, "table must be 8-byte aligned");
+    if (tp->index64 != 0 && tp->index64 != 1) return fail(fn, "index64 must be 0 or 1");
+    if ((uintptr_t)tp->table_index & (tp->index64 ? 7 : 3)) return fail(fn, tp->index64 ? "table_index must be 8-byte aligned" : "table_index must be 4-byte aligned");
+    if (tp->table_rows < 1) return fail(fn, "table_rows must be >= 1");
+    if (!tp->table_index) {
+        if (tp->table_share < 1) return fail(fn, "table_share must be >= 1 without a table_index");
+        if (tp->base.rows % tp->table_share) return fail(fn, "rows must be a multiple of table_share without a table_index");
+    }
+    base = tp->base;
+    base.adj_share = 1;
+    return check_plan(fn, &base, backward, y, true, maxe);
+}
+
+GnnTableArgs bind_table(const gmpe_gnn_table_plan* tp, const gmpe_gnn_plan& base, const Layout& y, bool backward) {
+    GnnTableArgs a = {};
+    static_cast<GnnArgs&>(a) = bind(&base, y, backward);
+    const gmpe_config* cfg = tp->cfg;
+    a.x = nullptr; a.adj = nullptr;
+    a.tab = tp->table; a.tidx = tp->table_index; a.tlast = tp->table_rows - 1;
+    a.idx64 = tp->index64; a.tshare = tp->table_index ? 1 : tp->table_share;
+    a.kind = cfg->graph_feat_type == 1 ? 2 : (cfg->scenario >= GMPE_SCENARIO_ROT_INV ? 1 : 0);      // as gmpe_expand_node_obs picks its row kernel
+    a.two = cfg->scenario == GMPE_SCENARIO_TWO_PHASE;
+    a.A = cfg->num_agents; a.NL = cfg->num_landmarks; a.TW = gmpe_entity_table_width(cfg);
     return a;
 }
 

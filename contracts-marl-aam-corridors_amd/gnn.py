@@ -229,18 +229,24 @@ def _plan(shape, meta, node_obs, adj, agent_id, ps):
     return p
 
 
+def _forward(name, meta, shape, node_obs, adj, agent_id, ps):
+    """the forward entry `name` over the rows and the adjacency -> (features, the contiguous inputs the plan points at)"""
+    dev = node_obs.device
+    cs = [t.detach().contiguous() for t in (node_obs, adj, agent_id) + tuple(ps)]
+    features = torch.empty((shape[0], HIDDEN), dtype=torch.float32, device=dev)
+    plan = _plan(shape, meta, cs[0], cs[1], cs[2], cs[3:])
+    plan.features = features.data_ptr()
+    _layers.run(name, dev, plan)
+    return features, cs
+
+
 class _Base(torch.autograd.Function):
     """features = base(node_obs, adj, agent_id) as one node over all parameters. gmpe_gnn_backward recomputes a graph's forward, so only the inputs are
     kept; changing any of them in place before backward is the caller's error, as with any saved tensor. The workspace is backward's own scratch."""
 
     @staticmethod
     def forward(ctx, meta, shape, workspace, node_obs, adj, agent_id, *ps):
-        dev = node_obs.device
-        cs = [t.detach().contiguous() for t in (node_obs, adj, agent_id) + tuple(ps)]
-        features = torch.empty((shape[0], HIDDEN), dtype=torch.float32, device=dev)
-        plan = _plan(shape, meta, cs[0], cs[1], cs[2], cs[3:])
-        plan.features = features.data_ptr()
-        _layers.run("gmpe_gnn_forward", dev, plan)
+        features, cs = _forward("gmpe_gnn_forward", meta, shape, node_obs, adj, agent_id, ps)
         if workspace is not None:
             ctx.save_for_backward(*cs)
         ctx.meta, ctx.shape, ctx.workspace = meta, shape, workspace
@@ -272,18 +278,24 @@ def _table_plan(shape, meta, cfg, share, table, index, agent_id, ps):
     return tp
 
 
+def _forward_table(name, meta, shape, cfg, share, table, index, agent_id, ps):
+    """the forward entry `name` over the entity table -> (features, the contiguous ids and parameters the plan points at)"""
+    dev = table.device
+    cs = [t.detach().contiguous() for t in (agent_id,) + tuple(ps)]
+    features = torch.empty((shape[0], HIDDEN), dtype=torch.float32, device=dev)
+    tp = _table_plan(shape, meta, cfg, share, table, index, cs[0], cs[1:])
+    tp.base.features = features.data_ptr()
+    _layers.run(name, dev, tp)
+    return features, cs
+
+
 class _BaseTable(torch.autograd.Function):
     """_Base with a graph's rows and matrix rebuilt from the entity table (gmpe_gnn_forward_table / _backward_table): the table, the index and the ids are
     kept in place of node_obs and adj."""
 
     @staticmethod
     def forward(ctx, meta, shape, workspace, cfg, share, table, index, agent_id, *ps):
-        dev = table.device
-        cs = [t.detach().contiguous() for t in (agent_id,) + tuple(ps)]
-        features = torch.empty((shape[0], HIDDEN), dtype=torch.float32, device=dev)
-        tp = _table_plan(shape, meta, cfg, share, table, index, cs[0], cs[1:])
-        tp.base.features = features.data_ptr()
-        _layers.run("gmpe_gnn_forward_table", dev, tp)
+        features, cs = _forward_table("gmpe_gnn_forward_table", meta, shape, cfg, share, table, index, agent_id, ps)
         if workspace is not None:
             ctx.save_for_backward(*cs)
             ctx.source = (cfg, share, table, index)
@@ -412,13 +424,9 @@ def gnn_base_wide(node_obs, adj, agent_id, base):
     max_edge_dist) keeps gnn_base's bits in every original node. A graph's result does not depend on the other graphs of the call."""
     names, ps, meta = _base_params(base)
     _forward_only(ps)
-    dev, rows, E, F, share, nemb, esz = _check(node_obs, adj, agent_id, names, ps, meta, "gnn_base_wide", WIDE_MAX_NODES)
-    cs = [t.detach().contiguous() for t in (node_obs, adj, agent_id.detach().reshape(rows).to(torch.int32)) + tuple(ps)]
-    features = torch.empty((rows, HIDDEN), dtype=torch.float32, device=dev)
-    plan = _plan((rows, E, F, share, nemb, esz), meta, cs[0], cs[1], cs[2], cs[3:])
-    plan.features = features.data_ptr()
-    _layers.run("gmpe_gnn_forward_wide", dev, plan)
-    return features
+    _, rows, E, F, share, nemb, esz = _check(node_obs, adj, agent_id, names, ps, meta, "gnn_base_wide", WIDE_MAX_NODES)
+    ids = agent_id.detach().reshape(rows).to(torch.int32)
+    return _forward("gmpe_gnn_forward_wide", meta, (rows, E, F, share, nemb, esz), node_obs, adj, ids, ps)[0]
 
 
 def gnn_base_wide_from_table(entity_table, table_index, agent_id, base, cfg, table_share=None):
@@ -427,14 +435,9 @@ def gnn_base_wide_from_table(entity_table, table_index, agent_id, base, cfg, tab
     gnn_base_wide."""
     names, ps, meta = _base_params(base)
     _forward_only(ps)
-    rows, share, E, F, nemb, esz, dev, ids, index = _check_table(entity_table, table_index, agent_id, (names, ps, meta), cfg, table_share,
-                                                                 "gnn_base_wide", WIDE_MAX_NODES)
-    cs = [t.detach().contiguous() for t in (ids,) + tuple(ps)]
-    features = torch.empty((rows, HIDDEN), dtype=torch.float32, device=dev)
-    tp = _table_plan((rows, E, F, 1, nemb, esz), meta, cfg, share, entity_table.detach(), index, cs[0], cs[1:])
-    tp.base.features = features.data_ptr()
-    _layers.run("gmpe_gnn_forward_wide_table", dev, tp)
-    return features
+    rows, share, E, F, nemb, esz, _, ids, index = _check_table(entity_table, table_index, agent_id, (names, ps, meta), cfg, table_share,
+                                                               "gnn_base_wide", WIDE_MAX_NODES)
+    return _forward_table("gmpe_gnn_forward_wide_table", meta, (rows, E, F, 1, nemb, esz), cfg, share, entity_table.detach(), index, ids, ps)[0]
 
 
 def wide_geometry(rows, num_nodes, node_feats, heads=3, gnn_layer_N=2, embed_layer_N=1, num_embeddings=4, embedding_size=2):

@@ -21,7 +21,7 @@ C = 16                          # GMPE_GNN_HIDDEN
 MARGIN = 1e-5                   # a ReLU graph is redrawn when its smallest |pre-activation| in the float64 truth is below this
 SIDE, MAX_EDGE_DIST = 2.4, 1.0
 
-# ---------------------------------------------------------------------------------------------- the launch geometry, restated (csrc/gmpe_gnn.hip)
+# ---------------------------------------------------------------------------------------------- the launch geometry, restated (csrc/gmpe_gnn_kernels.h)
 BLOCK, NW, NINS, QDS, LIN, MAX_CU, LDS_CU = 256, 4, 32, 40, C * C + C, 256, 160 * 1024
 
 

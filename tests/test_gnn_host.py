@@ -217,7 +217,7 @@ def test_workspace_bytes_and_the_restated_geometry():
 
 
 def test_the_restated_constants_are_the_sources():
-    text, host = (open(os.path.join(CSRC, f)).read() for f in ("gmpe_gnn.hip", "gmpe_host.h"))
+    text, host = (open(os.path.join(CSRC, f)).read() for f in ("gmpe_gnn_kernels.h", "gmpe_host.h"))
     for name, want in (("BLOCK", "256"), ("NW", "BLOCK / 64"), ("NINS", "32"), ("QDS", "40"), ("LIN", "C * C + C"), ("MAX_CU", "256"), ("LDS_CU", "160 * 1024")):
         m = re.search(r"\b%s\s*=\s*([^,;]+)[,;]" % name, host if name in ("MAX_CU", "LDS_CU") else text)
         assert m and m.group(1).strip() == want, (name, m and m.group(1))

@@ -1,6 +1,6 @@
 """Bit-for-bit A/B of two builds of libgmpe.so over the three entry points that share gmpe_ppo_rows.h: gmpe_ppo_loss, gmpe_ppo_loss_popart and
 gmpe_act_sample, over gmpe_compute_returns and the two sharded entry points, and over the nine entry points of the three layer kernels (gmpe_gru_*,
-gmpe_mlp_*, gmpe_gnn_*), called through their C plans on fixed inputs. The GPU suites bound the losses and the layers against float64, so they would
+gmpe_mlp_*, gmpe_gnn_*) and the two wide forwards (gmpe_gnn_forward_wide, _wide_table), called through their C plans on fixed inputs. The GPU suites bound the losses and the layers against float64, so they would
 not see a changed rounding or a changed order of the finish sums; this does.
 
     GMPE_LIB=/path/to/libgmpe_parent.so python tools/learner_ab_bits.py dump a.npz     # one process per build
@@ -26,6 +26,10 @@ of the size its *_workspace_bytes entry gives. gru/: tests/gru_lib.py's CASES x 
 8257- and 32801-row cases, at mlp_lib's seed 0. gnn/: tests/gnn_lib.py's CASES, and 5005 graphs of E = 6 (the 65 of the actor's case repeated: every
 workgroup of backward owns several tiles, the finish adds 256 partial rows) with a dense adjacency and with one matrix shared by five rows.
 Kept: features (and hxs_out) of both plans, every input gradient, every parameter gradient, the workspace size.
+gnnwide/: gmpe_gnn_forward_wide on tests/gnn_lib.py's inputs at E = 65 (W = 2), 87 | 88 (W = 2 | 1 at the shipped sizes) and 128 with the four
+aggregates and the largest configuration; 1, 2, 3 and 513 graphs of E = 65 (an idle pair; a workgroup with two tiles); one matrix serving three rows;
+gmpe_gnn_forward_wide_table on the tables of a stepped navigation_graph engine at E = 65 and 128 (tests/test_gpu_gnn_wide.py's), actor and critic, with
+an int32 index, an int64 index and a table_share. Kept: features. The GPU suite bounds nodes above 64 against float64 only.
 """
 import ctypes as C
 import itertools
@@ -357,6 +361,59 @@ def dump(path):
     X, A, I, W = (t.repeat((many // 65,) + (1,) * (t.dim() - 1)) for t in gnn_lib.inputs(65, 6, gnn_lib.ACTOR)[:4])
     gnn_case("%dx6_dense" % many, gnn_lib.ACTOR, X, A, I, W)
     gnn_case("%dx6_shared%d" % (many, share), gnn_lib.ACTOR, X, A[:many // share], I, W)
+
+    # ---- the forward at 65 .. 128 nodes, through gmpe_gnn_forward_wide and gmpe_gnn_forward_wide_table
+    def wide_params(key):
+        names, ps, meta = gnn._base_params(gnn_lib.build(gnn_lib.CONFIGS[key]).to(dev))
+        return [t.detach().contiguous() for t in ps], meta
+
+    def wide_case(tag, key, x, adj, ids):
+        ps, meta = wide_params(key)
+        x, adj, ids = x.to(dev).contiguous(), adj.to(dev).contiguous(), ids.to(device=dev, dtype=torch.int32)
+        (rows, E, F), (nemb, esz) = x.shape, ps[0].shape
+        out = zeros((rows, gnn_lib.C))
+        plan = gnn._plan((rows, E, F, rows // adj.shape[0], nemb, esz), meta, x, adj, ids, ps)
+        plan.features = ptr(out)
+        _lib.check(lib.gmpe_gnn_forward_wide(dev.index, C.byref(plan), stream), "gmpe_gnn_forward_wide")
+        save("gnnwide/rows/" + tag, features=out)
+
+    def wide_table_case(tag, key, cfg, table, index, share, ids):
+        ps, meta = wide_params(key)
+        ids = ids.to(device=dev, dtype=torch.int32)
+        rows, E, F, (nemb, esz) = ids.shape[0], cfg.num_entities, cfg.node_feats, ps[0].shape
+        out = zeros((rows, gnn_lib.C))
+        tp = gnn._table_plan((rows, E, F, 1, nemb, esz), meta, cfg, share, table, index, ids, ps)
+        tp.base.features = ptr(out)
+        _lib.check(lib.gmpe_gnn_forward_wide_table(dev.index, C.byref(tp), stream), "gmpe_gnn_forward_wide_table")
+        save("gnnwide/table/" + tag, features=out)
+
+    largest = gnn_lib.cfg_key(gnn_lib._RANDOM[-1])
+    for n, E, key in ((5, 65, gnn_lib.ACTOR), (4, 87, gnn_lib.ACTOR), (4, 88, gnn_lib.ACTOR), (9, 128, gnn_lib.ACTOR), (9, 128, gnn_lib.CRITIC),
+                      (9, 128, gnn_lib.ACTOR_MAX), (9, 128, gnn_lib.ACTOR_ADD), (3, 128, largest)):
+        wide_case("%dx%d_%s" % (n, E, key), key, *gnn_lib.inputs(n, E, key)[:3])
+    x, adj, ids = gnn_lib.inputs(9, 65, gnn_lib.ACTOR)[:3]
+    for rows in (1, 2, 3):                              # one pair idle; a full tile; a second tile with an idle pair
+        wide_case("%dx65" % rows, gnn_lib.ACTOR, x[:rows], adj[:rows], ids[:rows])
+    wide_case("513x65", gnn_lib.ACTOR, x.repeat(57, 1, 1), adj.repeat(57, 1, 1), ids.repeat(57))      # 257 tiles on 256 workgroups
+    envs, S = 2, 3
+    wide_case("compact_%dx%dx66" % (envs, S), gnn_lib.ACTOR, gnn_lib.inputs(envs * S, 66, gnn_lib.ACTOR)[0], gnn_lib.inputs(envs, 66, gnn_lib.ACTOR)[1],
+              torch.arange(S).repeat(envs))
+    from gmpe.engine import GmpeEngine
+    for tag, kw in (("nav65", dict(num_agents=30, num_obstacles=5, world_size=6.0, seed=96)), ("nav128", dict(num_agents=64, world_size=12.0, seed=97))):
+        cfg = gmpe.make_config(scenario_name="navigation_graph", num_envs=2, episode_length=4, graph_feat_type="global", **kw)
+        N, A = cfg.num_envs, cfg.num_agents
+        eng = GmpeEngine(cfg, node_form="both", adj_compact=True)
+        eng.reset()
+        rng = np.random.RandomState(7)
+        tabs = [eng.step(torch.as_tensor(rng.randint(0, cfg.n_actions, (N, A)).astype(np.int32))).entity_table.clone() for _ in range(6)]
+        eng.check_errors()
+        tabs = torch.stack(tabs).contiguous()            # [6, N, W]: past the time limit, so every env has reset
+        g = torch.Generator().manual_seed(cfg.num_entities)
+        index, ego = torch.randint(0, 6 * N, (11,), generator=g), torch.randint(0, A, (11,), generator=g)
+        for key in (gnn_lib.ACTOR, gnn_lib.CRITIC):
+            wide_table_case("%s_%s_index32" % (tag, key), key, cfg, tabs, index.to(device=dev, dtype=torch.int32), 1, ego)
+            wide_table_case("%s_%s_index64" % (tag, key), key, cfg, tabs, index.to(dev), 1, ego)
+            wide_table_case("%s_%s_share" % (tag, key), key, cfg, tabs[-1].contiguous(), None, A, torch.arange(A).repeat(N))
     np.savez(path, **kept)
     print("dump: %d arrays, %d elements (%d non-zero) from %s -> %s" % (len(kept), sum(a.size for a in kept.values()),
                                                                        sum(int(np.count_nonzero(a)) for a in kept.values()), _lib.LIB_PATH, path))
@@ -382,7 +439,7 @@ def compare(pa, pb):
         if d:
             print("%s: %d of %d elements differ" % (k, d, x.size))
             differing += d
-    per = {p: sum(1 for k in names if k.startswith(p)) for p in ("loss/", "popart_", "act/", "returns/", "shard/", "layers/")}
+    per = {p: sum(1 for k in names if k.startswith(p)) for p in ("loss/", "popart_", "act/", "returns/", "shard/", "layers/", "gnnwide/")}
     print("compare: %d arrays (%s), %d elements, %d differing" % (len(names), ", ".join("%s %d" % (p.rstrip("/_"), n) for p, n in per.items()), elements,
                                                                  differing))
     return 1 if differing or not names else 0
