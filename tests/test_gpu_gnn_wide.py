@@ -21,12 +21,24 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 R = G._RANDOM
 LARGEST, TANH_ADD, TANH_RELU = G.cfg_key(R[-1]), G.cfg_key(R[5]), G.cfg_key(R[6])
-# (graphs, E, configuration, special graphs): both sides of W = 2 | 1 (87 | 88 at the shipped sizes, 81 | 82 at the largest), E = 65 and 128, every
-# aggregate, the largest configuration gnn_base accepts, Tanh, and the written edge cases at E = 70
-CASES = ((5, 65, G.ACTOR, False), (5, 65, G.CRITIC, False), (5, 65, G.ROTATE, False), (4, 84, G.ACTOR, False), (4, 85, G.ACTOR, False),
+# (graphs, E, configuration, special graphs): E = 84 and 85 inside W = 2, both sides of W = 2 | 1 (87 | 88 at the shipped sizes, 81 | 82 at the largest
+# configuration: BOUNDARY below, the fullest LDS the kernel gets), E = 65 and 128, every aggregate, the largest configuration gnn_base accepts at W = 1
+# (E = 100, 128), Tanh, and the written edge cases at E = 70
+BOUNDARY = ((4, 87, G.ACTOR, False), (4, 88, G.ACTOR, False), (4, 81, LARGEST, False), (4, 82, LARGEST, False))
+CASES = ((5, 65, G.ACTOR, False), (5, 65, G.CRITIC, False), (5, 65, G.ROTATE, False), (4, 84, G.ACTOR, False), (4, 85, G.ACTOR, False)) + BOUNDARY + (
          (6, 96, G.ACTOR, False), (6, 96, G.CRITIC, False), (9, 128, G.ACTOR, False), (9, 128, G.CRITIC, False), (9, 128, G.ACTOR_MAX, False),
          (9, 128, G.ACTOR_ADD, False), (6, 100, LARGEST, False), (3, 128, LARGEST, False), (6, 90, TANH_ADD, False), (6, 90, TANH_RELU, False),
          (8, 70, G.ACTOR, True), (8, 70, G.CRITIC, True))
+
+
+def test_the_boundary_cases_lie_on_both_sides_of_two_graphs_per_workgroup():
+    """W = 2, 1, 2, 1, and the two W = 2 launches ask for the most LDS of any: 162 496 and 162 336 of 163 840 bytes"""
+    got = []
+    for n, E, key, _ in BOUNDARY:
+        c = G.CONFIGS[key]
+        got.append(W.wide_geometry(n, E, c["F"], c["heads"], c["gnn_n"], c["embed_n"], c["nemb"], c["esz"])[:2])
+    assert [g[0] for g in got] == [2, 1, 2, 1] and got[0][1] == 162496 and got[2][1] == 162336
+    assert all(lds <= 160 * 1024 for _, lds in got)
 
 
 @functools.lru_cache(maxsize=None)
@@ -82,7 +94,7 @@ def padded(x, adj, ids, E, spread):
 
 
 @pytest.mark.parametrize("spread", [False, True], ids=["appended", "spread"])
-@pytest.mark.parametrize("E0,E", [(6, 65), (20, 100), (64, 65), (64, 128), (44, 85)])
+@pytest.mark.parametrize("E0,E", [(6, 65), (20, 100), (64, 65), (64, 128), (44, 85), (64, 87)])
 def test_a_padded_graph_keeps_gnn_bases_bits(E0, E, spread):
     x, adj, ids = G.inputs(5, E0, G.ACTOR)[:3]
     X, A, I = padded(x, adj, ids, E, spread)
